@@ -15,10 +15,12 @@ it is one of the ranks.
 
 Workloads (BASELINE.json configs): N=1 -> configs[1] "1 000 synthetic 5 Mb genomes, k=31,
 scaled=1000"; N=8 -> configs[2] "10 000 genomes tiled across 8 MI355X"; N=2/4 use the same
-1 250 genomes per GPU as configs[2].  Rank 0 prints ONE JSON line.  At N=1 the line also carries,
-under "also", short runs of the other BASELINE configs (bottom-m mode, 10 000 genomes on one GPU,
-the mixed-length set, fastANI-style fragment ANI) and of the headline workload at k = 51, each with its
-own parity check.
+1 250 genomes per GPU as configs[2].  Rank 0 prints ONE JSON line.  A plain run sets up, warms up,
+times the K steps and prints the headline figure; `--dump-outputs DIR` also writes what the last timed
+step computed as .npy files.  With `--full` the line also carries the device-pow steps, the roofline,
+the CPU baseline, the PCIe-inclusive passes and, at N=1 under "also", short runs of the other BASELINE
+configs (bottom-m mode, 10 000 genomes on one GPU, the mixed-length set, fastANI-style fragment ANI)
+and of the headline workload at k = 51, each with its own parity check.
 """
 
 from __future__ import annotations
@@ -64,6 +66,13 @@ def parse_args(argv=None):
     ap.add_argument("--also-n", type=int, default=10000)
     ap.add_argument("--no-fresh-child", action="store_true", help="skip the fresh-process fragment-ANI call (a child started before this process touches the GPU)")
     ap.add_argument("--fresh-fragani-child", action="store_true", help=argparse.SUPPRESS)  # the child's own mode
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the device-pow steps, roofline and device-copy figures, the CPU baseline "
+                    "and its parity checks, the PCIe-inclusive passes, the extra BASELINE configs (--also), the fresh-process fragment-ANI "
+                    "call, the multi-GPU cross-check and one-GPU basis")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64/float32, "
+                    "at most 64 MB: a fixed seeded sample of rows and columns when the matrices are larger)")
     ap.add_argument("--dry-run-plan", action="store_true",
                     help="print, without touching a GPU (or importing torch), what every rank of `--gpus N` would hold and exchange: "
                     "shards, all-gather sizes, tile buffers, the strong_basis memory need")
@@ -949,6 +958,57 @@ def also_fragani(engine, arena, args, n_total, lengths) -> dict:
 
 
 # --------------------------------------------------------------------------- one rank
+DUMP_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SKETCH_GENOMES = 16  # sketches of this many seeded-sampled genomes ...
+DUMP_SKETCH_HASHES = 1 << 16  # ... each cut to its smallest hashes
+
+
+def dump_outputs(out_dir: str, matrices: dict, null: np.ndarray, sketches, col0: int) -> None:
+    """Write the last timed step's results as ``out_dir/<name>.npy``: the row x column matrices of this rank's tile
+    (float64), the NULL pairs as ``is_null`` (float32 0/1; every matrix holds 0 there instead of the NaN the
+    reference reports, so all files are finite), the sketch size of every genome, and the sorted sketch hashes of a
+    seeded sample of genomes split into high and low 32-bit halves (u64 hashes do not fit a float64).  When the
+    matrices would exceed the budget, the same seeded sample of rows and columns is taken from each of them;
+    ``rows.npy`` / ``cols.npy`` give the genome indices kept."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(20240601)
+    files = {}
+    sizes = sketches.sizes().astype(np.float64)
+    files["sketch_sizes"] = sizes
+    n = sketches.n
+    pick = np.sort(rng.choice(n, size=min(n, DUMP_SKETCH_GENOMES), replace=False))
+    off = sketches.offsets_host()
+    parts, lens = [], []
+    for g in pick:
+        a, b = int(off[g]), min(int(off[g + 1]), int(off[g]) + DUMP_SKETCH_HASHES)
+        parts.append(sketches.hashes[a:b].cpu().numpy().view(np.uint64))
+        lens.append(b - a)
+    h = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
+    files["sketch_sample_genomes"] = pick.astype(np.float64)
+    files["sketch_sample_lengths"] = np.asarray(lens, dtype=np.float64)
+    files["sketch_sample_hash_hi"] = (h >> np.uint64(32)).astype(np.float64)
+    files["sketch_sample_hash_lo"] = (h & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    nq, ns = next(iter(matrices.values())).shape
+    rows, cols = np.arange(nq), np.arange(ns)
+    left = DUMP_BYTES - sum(x.nbytes for x in files.values()) - 16 * (nq + ns) - 4096  # (.npy headers)
+    cell = 4 + 8 * len(matrices)
+    if nq * ns * cell > left:
+        f = (left / (nq * ns * cell)) ** 0.5
+        rows = np.sort(rng.choice(nq, size=max(1, int(nq * f)), replace=False))
+        cols = np.sort(rng.choice(ns, size=max(1, int(ns * f)), replace=False))
+    files["rows"] = rows.astype(np.float64)
+    files["cols"] = (cols + col0).astype(np.float64)
+    null = null[np.ix_(rows, cols)]
+    files["is_null"] = null.astype(np.float32)
+    for name, m in matrices.items():
+        files[name] = np.where(null, 0.0, m[np.ix_(rows, cols)].astype(np.float64))
+    for name, arr in files.items():
+        if not np.isfinite(arr).all():
+            raise SystemExit(f"bench.py: --dump-outputs: {name} holds non-finite values outside the NULL pairs")
+        np.save(out / f"{name}.npy", np.ascontiguousarray(arr))
+
+
 def run_rank(args, fresh_fragani: dict | None = None) -> None:
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1065,20 +1125,28 @@ def run_rank(args, fresh_fragani: dict | None = None) -> None:
         out = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        if bottom:  # a NULL pair is NaN in the Mash-ANI matrix (no shared or no denominator hashes)
+            ident = out[3].cpu().numpy()
+            matrices, nul = {"identity": ident, "counts": out[2].cpu().numpy()}, ~np.isfinite(ident)
+        else:
+            nul = h_null.view(np.bool_)
+            matrices = {"identity": h_ident.numpy(), "cov_query": h_cov.numpy(), "counts": h_counts.numpy().view(np.uint32)}
+        dump_outputs(args.dump_outputs, matrices, nul, out[1], c0)
     if dist_path:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=engine.device if backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
         # every rank cross-checks a block of its column tile with the independent merge kernel
         nq_chk, ns_chk = min(n_total, 256), min(c1 - c0, 64)
-        if not bottom:
+        if args.full and not bottom:
             chk = engine.pair_counts(out[1], (0, nq_chk), (c0, c0 + ns_chk), algo=_capi.PA_PAIRS_MERGE)
             if not torch.equal(chk, out[2][:nq_chk, :ns_chk]):
                 raise SystemExit(f"PARITY FAILURE on rank {rank}: bit-row and merge counts differ")
     prof = engine.prof_get()
     engine.prof_enable(False)
     t_dev_elapsed = None
-    if strict_out:  # the same K steps with the transform on the device (f64 pow, <= 1 ulp): matrices stay in HBM
+    if strict_out and args.full:  # the same K steps with the transform on the device (f64 pow, <= 1 ulp): matrices stay in HBM
         step(True)
         fence()
         t0 = time.perf_counter()
@@ -1131,7 +1199,7 @@ def run_rank(args, fresh_fragani: dict | None = None) -> None:
     # a device copy on the same box, so fractions can be read against the nominal
     # 8 TB/s and against what this GPU actually streams (1 GiB read + 1 GiB written per copy)
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         src = torch.empty(1 << 30, dtype=torch.uint8, device=engine.device)
         dst = torch.empty_like(src)
         dst.copy_(src)
@@ -1181,7 +1249,7 @@ def run_rank(args, fresh_fragani: dict | None = None) -> None:
                             "2-bit genomes resident in HBM -> f64 Mash-ANI matrix in HBM"),
             "value_clock_note": "inputs are resident when the clock starts, as the bench contract prescribes; the same step from packed "
             "genomes in pinned HOST memory (SURVEY.md 8d T_e2e, PCIe-bound: 1.25 GB per step) is value_e2e_strict, the step "
-            "with the transform left on the device (f64 pow, <= 1 ulp, matrices in HBM) is value_t_dev",
+            "with the transform left on the device (f64 pow, <= 1 ulp, matrices in HBM) is value_t_dev (both with --full)",
             "ani_transform_in_value": "host glibc pow (pa_ani_host), one pow per ordered pair: the reference's doubles" if strict_out else "device",
             "value_t_dev": (n_total * n_total * args.steps / t_dev_elapsed) if t_dev_elapsed else None,
             "ms_per_step_t_dev": (t_dev_elapsed / args.steps * 1e3) if t_dev_elapsed else None,
@@ -1229,8 +1297,11 @@ def run_rank(args, fresh_fragani: dict | None = None) -> None:
             "device": engine.device_info()["name"],
             "reference_tools": reference_tools_probe(),
         }
+        if not args.full:  # figures that take runs of their own (value_t_dev, the device copy) or come from outside this run
+            for key in ("value_t_dev", "ms_per_step_t_dev", "roofline", "reference_tools"):
+                del result[key]
         cb = None
-        if world == 1 and not dist_path and not args.no_cpu_baseline and not bottom:
+        if args.full and world == 1 and not dist_path and not args.no_cpu_baseline and not bottom:
             cb = cpu_baseline(engine, arena, sk, args, n_total, lengths)
             n_pair = cb.pop("_n_pair")
             cpu_counts = cb.pop("_cpu_counts")
@@ -1241,9 +1312,9 @@ def run_rank(args, fresh_fragani: dict | None = None) -> None:
             result["cpu_baseline"] = cb
             result["parity_checked"] = (f"sketches of {'all' if not cb['extrapolated'] else 'the sampled'} genomes and "
                                         f"{'all ' if not cb['extrapolated'] else 'a block of '}{n_pair}x{n_pair} pair counts equal the oracle")
-        else:
+        elif args.full:
             result["cpu_baseline"] = None
-        if world == 1 and not dist_path and not args.no_pcie:
+        if args.full and world == 1 and not dist_path and not args.no_pcie:
             # T_e2e (packed genomes in pinned host RAM -> f64 identity & cov_query in host RAM), reported
             # beside `value`, never inside it.  "plain": the whole arena (bases + mask bitmap) is copied, then the resident
             # step runs.  "streamed": the mask crosses as runs and the bases go up in chunks behind the hash kernel
@@ -1370,7 +1441,7 @@ def run_rank(args, fresh_fragani: dict | None = None) -> None:
                                  "value_over_cpu has the genomes resident in HBM when the clock starts, as the bench contract defines `value`",
                     }
             del h_packed, h_mask, e_ident, e_cov
-        if world == 1 and not dist_path and not args.no_also and not bottom and not args.mixed_lengths:
+        if args.full and world == 1 and not dist_path and not args.no_also and not bottom and not args.mixed_lengths:
             also = {}
             wanted = [x for x in args.also.split(",") if x]
 
@@ -1413,7 +1484,7 @@ def run_rank(args, fresh_fragani: dict | None = None) -> None:
                     result["config1_files"] = config1_files()
                 except (Exception, SystemExit) as err:  # noqa: BLE001 - never costs the headline line
                     result["config1_files"] = {"error": f"{type(err).__name__}: {err}", "matrices": "not compared"}
-    if rank == 0 and world > 1 and os.environ.get("PA_BENCH_NO_BASIS") != "1":
+    if args.full and rank == 0 and world > 1 and os.environ.get("PA_BENCH_NO_BASIS") != "1":
         # The same workload -- all n_total genomes -- on ONE GPU, measured here and now by rank 0 while the other ranks
         # wait at the barrier below: value / strong_basis.one_gpu_pairs_per_s is the speed-up of the N-GPU run over one
         # GPU on the SAME work.  (The per-N values of a SCALE run are not comparable with each other: the workload
@@ -1467,7 +1538,7 @@ def main():
         raise SystemExit(launch_ranks(args))
     # before this process imports torch or touches the GPU: the fragment-ANI call of a fresh process (also.fragment_ani.fresh_process)
     fresh = None
-    if (args.gpus == 1 and "RANK" not in os.environ and os.environ.get("PA_BENCH_FORCE_DIST") != "1" and not args.no_also and not args.no_fresh_child
+    if (args.full and args.gpus == 1 and "RANK" not in os.environ and os.environ.get("PA_BENCH_FORCE_DIST") != "1" and not args.no_also and not args.no_fresh_child
             and "fragani" in args.also.split(",") and args.sketch_mode == "scaled" and not args.mixed_lengths):
         fresh = run_fresh_fragani_child(args)
     run_rank(args, fresh)

@@ -51,7 +51,7 @@ def _run_bench(extra_env: dict, *argv: str) -> dict:
 
 
 def test_bench_launches_its_own_ranks_two_ranks_on_one_gpu():
-    res = _run_bench({"PA_BENCH_BACKEND": "gloo"}, "--gpus", "2", "--genomes", "64", "--length", "200000", "--steps", "2", "--warmup", "1")
+    res = _run_bench({"PA_BENCH_BACKEND": "gloo"}, "--gpus", "2", "--genomes", "64", "--length", "200000", "--steps", "2", "--warmup", "1", "--full")
     assert res["n_gpus"] == 2 and res["rccl_ranks"] == 2 and res["collective_backend"] == "gloo"
     assert res["config"]["genomes"] == 64 and res["config"]["genomes_per_gpu"] == 32
     assert res["value"] > 0 and res["scaling"] == "weak"
@@ -66,7 +66,7 @@ def test_bench_eight_ranks_on_one_gpu_with_the_one_gpu_basis():
     unequal sketch payloads, column tiles, rank 0's one-GPU basis while seven ranks wait in the barrier), with the eight
     ranks sharing this box's one device and the collectives on host copies (gloo).  No scaling figure comes out of this --
     eight ranks on one GPU -- only that the eight-rank path runs to its end and its line is consistent."""
-    res = _run_bench({"PA_BENCH_BACKEND": "gloo"}, "--gpus", "8", "--genomes", "72", "--length", "120000", "--steps", "2", "--warmup", "1")
+    res = _run_bench({"PA_BENCH_BACKEND": "gloo"}, "--gpus", "8", "--genomes", "72", "--length", "120000", "--steps", "2", "--warmup", "1", "--full")
     assert res["n_gpus"] == 8 and res["rccl_ranks"] == 8 and res["collective_backend"] == "gloo"
     assert res["config"]["genomes"] == 72 and res["config"]["genomes_per_gpu"] == 9
     assert res["value"] > 0 and res["scaling"] == "weak" and res["value"] == pytest.approx(72 * 72 / (res["ms_per_step"] * 1e-3))
@@ -77,7 +77,7 @@ def test_bench_eight_ranks_on_one_gpu_with_the_one_gpu_basis():
 
 def test_bench_rccl_path_on_one_rank():
     res = _run_bench({"PA_BENCH_FORCE_DIST": "1", "MASTER_PORT": str(_free_port())}, "--gpus", "1", "--genomes", "48", "--length", "300000",
-                     "--steps", "2", "--warmup", "1", "--no-also")
+                     "--steps", "2", "--warmup", "1", "--full", "--no-also")
     assert res["rccl_ranks"] == 1 and res["collective_backend"] == "nccl"
     assert "overlapped" in res["config"]["parallelism"]
 

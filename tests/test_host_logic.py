@@ -1159,3 +1159,41 @@ def test_work_based_roofline_is_reproducible_from_the_committed_profiles():
     bench_src = (ROOT / "bench.py").read_text()
     for key in ("frac_first_group", "frac_minimal_sort", "roofline_sparse", "roofline_index", "traffic_over_algorithmic"):
         assert key in bench_src
+
+
+def test_bench_dump_outputs_budget_sample_and_exact_hashes(tmp_path):
+    """``bench.py --dump-outputs``: matrices larger than the 64 MB budget are cut to one seeded sample of rows and
+    columns (the same in every run), the files stay within the budget, every value is finite (a NULL pair's NaN is
+    written as 0 and flagged in ``is_null``), and the u64 sketch hashes of the sampled genomes come back exactly from
+    their two float64 halves."""
+    torch = pytest.importorskip("torch")
+    import bench
+    from pyani_plus_amd.engine import DeviceSketches
+
+    rng = np.random.default_rng(7)
+    n = 3000
+    sizes = rng.integers(0, 90, n)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    hashes = np.sort(rng.integers(0, 2**63 - 1, int(off[-1]), dtype=np.int64))
+    sk = DeviceSketches(torch.from_numpy(hashes), torch.from_numpy(off), n, int(off[-1]))
+    ident = rng.random((n, n))
+    null = ident > 0.9
+    ident[null] = np.nan
+    matrices = {"identity": ident, "counts": rng.integers(0, 5000, (n, n)).astype(np.uint32)}
+    runs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), matrices, null, sk, 5)
+        runs.append({p.stem: np.load(p) for p in sorted((tmp_path / d).glob("*.npy"))})
+        assert sum(p.stat().st_size for p in (tmp_path / d).glob("*.npy")) <= bench.DUMP_BYTES
+    a, b = runs
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(x.dtype in (np.float32, np.float64) and np.isfinite(x).all() for x in a.values())
+    rows, cols = a["rows"].astype(np.int64), a["cols"].astype(np.int64) - 5
+    assert 0 < len(rows) < n and 0 < len(cols) < n
+    kept = null[np.ix_(rows, cols)]
+    assert kept.any() and np.array_equal(a["is_null"], kept.astype(np.float32))
+    assert np.array_equal(a["identity"], np.where(kept, 0.0, ident[np.ix_(rows, cols)]))
+    assert np.array_equal(a["sketch_sizes"], sizes.astype(np.float64))
+    got = (a["sketch_sample_hash_hi"].astype(np.uint64) << np.uint64(32)) | a["sketch_sample_hash_lo"].astype(np.uint64)
+    want = np.concatenate([hashes[off[g] : off[g + 1]] for g in a["sketch_sample_genomes"].astype(np.int64)]).view(np.uint64)
+    assert np.array_equal(got, want)

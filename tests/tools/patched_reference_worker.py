@@ -22,7 +22,10 @@ if not hasattr(datetime, "UTC"):
     datetime.UTC = datetime.timezone.utc  # the reference wants Python >= 3.11
 
 pkg = scratch / "pyani_plus"
-shutil.copytree(REFERENCE / "pyani_plus", pkg, ignore=shutil.ignore_patterns("__pycache__"))
+shutil.copytree(REFERENCE / "pyani_plus", pkg, ignore=shutil.ignore_patterns("__pycache__"), copy_function=shutil.copyfile)
+# the reference tree is read-only; its copy takes the edits below under any user (copytree still copies directory modes)
+for d in [pkg, *(p for p in pkg.rglob("*") if p.is_dir())]:
+    d.chmod(0o755)
 integration = (REPO / "INTEGRATION.md").read_text()
 
 # 2. the method module: the re-export printed in INTEGRATION.md section 2

@@ -48,7 +48,7 @@ drivers sharing the one device, gloo).
 
 | file | what |
 |---|---|
-| `r06_bench_n1000_result.json` | the JSON line of an un-profiled `python bench.py --steps 20 --warmup 5`: `value` {bench["value"]:.3g} pairs/s ({bench["ms_per_step"]:.2f} ms), `cpu_baseline.gpu_over_cpu` (T_e2e strict {goc["t_e2e_strict_pairs_per_s"]:.3g} pairs/s = {goc["t_e2e_strict_over_cpu"]:.0f} x the CPU port; `value` {goc["value_over_cpu"]:.0f} x), `also.fragment_ani` {fa["seconds_per_run"]:.3f} s per 10^6 pairs (index {fa["phases_ms_per_run"]["frag_index"]:.0f} ms, seeding {fa["phases_ms_per_run"]["frag_seed"]:.0f}, mapping {fa["phases_ms_per_run"]["frag_map"]:.0f}), `workspace_device_bytes` ({ws["all_columns"]["held_bytes"] / 1e9:.1f} / {ws["one_eighth_of_the_columns"]["held_bytes"] / 1e9:.1f} / {ws["one_column"]["held_bytes"] / 1e9:.1f} GB for all columns / an eighth / one), `also.fragment_ani_rearranged` {fr["seconds_per_run"]:.3f} s, `config1_files` (T_file {cf["seconds"]:.3f} s, matrices {cf["matrices"]}) as the line's last key |
+| `r06_bench_n1000_result.json` | the JSON line of an un-profiled `python bench.py --full --steps 20 --warmup 5`: `value` {bench["value"]:.3g} pairs/s ({bench["ms_per_step"]:.2f} ms), `cpu_baseline.gpu_over_cpu` (T_e2e strict {goc["t_e2e_strict_pairs_per_s"]:.3g} pairs/s = {goc["t_e2e_strict_over_cpu"]:.0f} x the CPU port; `value` {goc["value_over_cpu"]:.0f} x), `also.fragment_ani` {fa["seconds_per_run"]:.3f} s per 10^6 pairs (index {fa["phases_ms_per_run"]["frag_index"]:.0f} ms, seeding {fa["phases_ms_per_run"]["frag_seed"]:.0f}, mapping {fa["phases_ms_per_run"]["frag_map"]:.0f}), `workspace_device_bytes` ({ws["all_columns"]["held_bytes"] / 1e9:.1f} / {ws["one_eighth_of_the_columns"]["held_bytes"] / 1e9:.1f} / {ws["one_column"]["held_bytes"] / 1e9:.1f} GB for all columns / an eighth / one), `also.fragment_ani_rearranged` {fr["seconds_per_run"]:.3f} s, `config1_files` (T_file {cf["seconds"]:.3f} s, matrices {cf["matrices"]}) as the line's last key |
 | `r06_bench_n1000_kernel_stats.csv`, `hash_counters.json`, `r06_pmc_kmer_hash_summary.txt` | the headline step's kernels: `kmer_hash_kernel<31,true>` 11.3 ms, 92.4 vector instructions per wave-window, VALUBusy 106 %, traffic 1.38 GB per launch (1.07 x algorithmic): unchanged, untouched |
 | `r06_fragani_n1000_kernel_stats.csv` | `rocprofv3 --kernel-trace --stats -- python3 tools/bench_fragani.py 1000 0`: `minimizer_kernel<16>` **{kern("minimizer_kernel<16>")[1]:.1f} ms** (44.0 in round 5), `postings_kernel` {kern("postings_kernel")[1]:.1f} (19.3), `rs_scatter` 4 x {kern("rs_scatter_kernel")[1]:.1f}, `map_segments_kernel<320u, true>` {kern("map_segments_kernel<320u, true>")[2] / 2:.0f} ms per run, `map_sparse_kernel` {kern("map_sparse_kernel")[2] / 2:.0f}, `bucket_hits_staged_kernel` {kern("bucket_hits_staged_kernel")[2] / 2:.0f} |
 | `r06_pmc_minimizer_summary.txt`, `r06_pmc_postings_summary.txt`, `r06_pmc_rs_scatter_summary.txt` | counter passes of the index kernels (the round-5 verdict's missing evidence).  Minimizer: {mi["valu_instructions"]:.4g} vector instructions = **{mi["valu_instructions_per_position"]:.0f} per position** (263 before the hash-only winnowing), VALUBusy {mi["valu_busy"]:.2f}, {mi["waves_per_simd"]:.1f} waves per SIMD, {100 * mi["wait_share"]:.0f} % of wave time waiting; before the per-XCD tickets and the per-tile contig table the same instruction stream took 47 ms at VALUBusy 0.55 (a tile lived ~24 us of which it computed 3).  Postings: the scatter of the hash ids into position order (4-byte stores, a sector each; WRITE_SIZE 17 GB counted for 4*10^8 postings) is what it waits for (96 % of wave time).  `rs_scatter`: 3.6 ms per pass of 4*10^8 (key, value) pairs = 9.6 GB moved per pass = 2.6 TB/s |

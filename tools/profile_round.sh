@@ -6,6 +6,7 @@ set -u
 TAG=${1:-r02}
 ROOT=$(pwd)
 mkdir -p "$ROOT/gpurun_out"
+OUT=$_  # the directory made above
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/gpurun_out/${TAG}_stats_bench" -- python3 "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-pcie --no-also > "$ROOT/gpurun_out/${TAG}_stats_bench.json" 2> "$ROOT/gpurun_out/${TAG}_stats_bench.err"
 echo "bench stats rc=$?"
@@ -33,7 +34,7 @@ python3 tools/map_stats.py 1000 78 2>&1 | grep "pa_fragani:" > gpurun_out/${TAG}
 # where the mapping kernel's time goes: the kernel cut short after each phase (tools build)
 python3 tools/map_cut.py 1000 9,9,10,11,1,2,3,4,9,23,9 > gpurun_out/${TAG}_map_cut.txt 2>&1
 # the bench line itself, un-profiled
-python3 bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 for d in gpurun_out/${TAG}_stats_bench gpurun_out/${TAG}_stats_fragani; do
   f=$(find $d -name "*kernel_stats.csv" | head -1)
   if [ -n "$f" ]; then
