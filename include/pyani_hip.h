@@ -424,6 +424,50 @@ PA_API int pa_sqlite_insert_comparisons_ex(const char *database, int64_t configu
                                            const int64_t *h_aln_length, const int64_t *h_sim_errors,
                                            uint64_t *rows_inserted);
 
+/* ---- external alignment (method external-alignment-hip): an MSA -> per-pair counts ----
+ * Replaces compute_external_alignment_column (pyani_plus/methods/external_alignment.py:33-156), called per subject
+ * column by private_cli.compute_external_alignment (pyani_plus/private_cli.py:1930-2041).
+ *
+ *   pa_msa_load / _info / _record / _copy_rows / _free   the alignment file, read once
+ *        replaces the two fasta_bytes_iterator passes per column (external_alignment.py:63-99, parser
+ *        pyani_plus/utils.py:40-90) and file_md5sum of the alignment (private_cli.py:1985-1990).  One pass over the
+ *        bytes: the md5 of the raw file on its own thread, the records parsed in parallel (titles = line[1:].rstrip(),
+ *        sequence lines rstrip()ed and " \t\r\n" deleted; raw bytes, case-sensitive), a 256-bin histogram of the
+ *        residue bytes.  threads <= 0: pa_host_cpu_budget().  pa_msa_copy_rows writes rows [r0, r1) with row_stride
+ *        bytes each, a row's tail after its residues filled with '-'.
+ *   pa_msa_pack          rows -> bit planes + non-gap counts n_x (device)
+ *        d_rows: n_chunk_rows rows of row_stride bytes (a multiple of 32 covering ceil(n_cols / 32) words; 16-byte
+ *        aligned), rows row0 .. of an MSA of n_rows rows.  h_code256: byte -> code, '-' -> 0, codes below 2^bits
+ *        (1 <= bits <= 8).  d_planes: pa_msa_plane_words(n_rows, n_cols, bits) uint32, word-major
+ *        [(w * (bits + 1) + p) * n_pad + row], n_pad = n_rows rounded up to 64, plane `bits` = non-gap.  d_nongap:
+ *        n_rows uint32, zero before the first chunk; each chunk adds its rows' non-gap columns.
+ *   pa_msa_pair_counts   bit planes -> M (q == s, not gap) and B (neither gap), uint32 [q1 - q0][s1 - s0]
+ *        replaces the per-pair numpy passes (external_alignment.py:118-132).  symmetric != 0 (equal ranges): only the
+ *        64 x 64 tiles on and above the diagonal are evaluated and the rest mirrored on the device.
+ *   pa_msa_metrics       (M, B, n_q, n_s) per pair -> identity, aln_length, sim_errors, cov_query, cov_subject (host)
+ *        replaces external_alignment.py:134-156; IEEE divisions of integers below 2^53, bit-identical to the
+ *        reference's int / int.  PA_E_INVALID when a row has no residues (the reference divides by zero).
+ *   pa_append_msa_json   rows (q_idx[r], s_idx[r]) of the column file with the worker's seven keys
+ *        (private_cli.py:2009-2032), in the order given, byte-identical to json.dumps; the progressive form of
+ *        pa_append_comparisons_json. */
+typedef struct pa_msa pa_msa;
+PA_API int pa_msa_load(const char *path, int threads, pa_msa **out);
+PA_API int pa_msa_info(const pa_msa *msa, uint32_t *n_records, uint64_t *max_len, char md5hex33[33], uint64_t *h_hist256);
+PA_API int pa_msa_record(const pa_msa *msa, uint32_t i, const char **title, uint64_t *title_len, uint64_t *length);
+PA_API int pa_msa_copy_rows(const pa_msa *msa, uint32_t r0, uint32_t r1, uint64_t row_stride, uint8_t *h_rows);
+PA_API void pa_msa_free(pa_msa *msa);
+PA_API uint64_t pa_msa_plane_words(uint32_t n_rows, uint64_t n_cols, uint32_t bits);
+PA_API int pa_msa_pack(pa_ctx *ctx, const uint8_t *d_rows, uint64_t row_stride, uint32_t row0, uint32_t n_chunk_rows, uint32_t n_rows,
+                       uint64_t n_cols, const uint8_t *h_code256, uint32_t bits, uint32_t *d_planes, uint32_t *d_nongap);
+PA_API int pa_msa_pair_counts(pa_ctx *ctx, const uint32_t *d_planes, uint32_t n_rows, uint64_t n_cols, uint32_t bits, uint32_t q0,
+                              uint32_t q1, uint32_t s0, uint32_t s1, int symmetric, uint32_t *d_match, uint32_t *d_both);
+PA_API int pa_msa_metrics(const uint32_t *h_match, const uint32_t *h_both, const uint64_t *h_nq, const uint64_t *h_ns, uint64_t n_pairs,
+                          double *h_identity, int64_t *h_aln_length, int64_t *h_sim_errors, double *h_cov_query,
+                          double *h_cov_subject, uint32_t n_threads);
+PA_API int pa_append_msa_json(const char *path, const char *suffix, int file_has_rows, const char *const *hashes, uint32_t n_hashes,
+                              const uint32_t *q_idx, const uint32_t *s_idx, uint64_t n_rows, const double *identity,
+                              const int64_t *aln_length, const int64_t *sim_errors, const double *cov_query, const double *cov_subject);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */
@@ -434,7 +478,9 @@ PA_API int pa_sqlite_insert_comparisons_ex(const char *database, int64_t configu
 #define PA_PROF_FRAG_INDEX 5 /* fragment ANI: minimizers, hash dictionary, postings */
 #define PA_PROF_FRAG_SEED 6  /* fragment ANI: fragment sketches, seed hits bucketed by reference genome */
 #define PA_PROF_FRAG_MAP 7   /* fragment ANI: prefilter + map_segments_kernel + per-pair reduction */
-#define PA_PROF_NPHASES 8
+#define PA_PROF_MSA_PACK 8    /* external alignment: rows -> bit planes (msa_pack_kernel) */
+#define PA_PROF_MSA_PAIRS 9   /* external alignment: pair counts M, B (msa_pairs_kernel, mirror) */
+#define PA_PROF_NPHASES 10
 PA_API int pa_prof_enable(pa_ctx *ctx, int on);
 PA_API int pa_prof_reset(pa_ctx *ctx);
 /* total milliseconds and number of timed launches of a phase (syncs the stream) */

@@ -29,7 +29,8 @@ PA_FRAGANI_REUSE_INDEX = 1
 PA_FRAGANI_COLUMNS_ONLY = 2
 PA_PAIRS_AUTO, PA_PAIRS_BITROW, PA_PAIRS_MERGE, PA_PAIRS_BITROW_HASH = 0, 1, 2, 3
 PA_ALIGN_BASES = 64
-PROF_PHASES = {"kmer_hash": 0, "sketch_sort": 1, "pair_dict": 2, "pair_count": 3, "ani": 4, "frag_index": 5, "frag_seed": 6, "frag_map": 7}
+PROF_PHASES = {"kmer_hash": 0, "sketch_sort": 1, "pair_dict": 2, "pair_count": 3, "ani": 4, "frag_index": 5, "frag_seed": 6, "frag_map": 7,
+               "msa_pack": 8, "msa_pairs": 9}
 
 _u8p = C.POINTER(C.c_uint8)
 _u32p = C.POINTER(C.c_uint32)
@@ -141,6 +142,22 @@ SIGNATURES: dict[str, tuple] = {
         C.c_int,
         [C.c_char_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, _vp, _vp, _vp,
          _vp, _vp, _u64p],
+    ),
+    "pa_msa_load": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_vp)]),
+    "pa_msa_info": (C.c_int, [_vp, _u32p, _u64p, C.c_char_p, _u64p]),
+    "pa_msa_record": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_char_p), _u64p, _u64p]),
+    "pa_msa_copy_rows": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint64, _vp]),
+    "pa_msa_free": (None, [_vp]),
+    "pa_msa_plane_words": (C.c_uint64, [C.c_uint32, C.c_uint64, C.c_uint32]),
+    "pa_msa_pack": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _vp, C.c_uint32, _vp, _vp]),
+    "pa_msa_pair_counts": (
+        C.c_int,
+        [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp, _vp],
+    ),
+    "pa_msa_metrics": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
+    "pa_append_msa_json": (
+        C.c_int,
+        [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp],
     ),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),

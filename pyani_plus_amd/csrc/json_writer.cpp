@@ -216,6 +216,96 @@ extern "C" int pa_append_comparisons_json_ex(const char *path, const char *suffi
   });
 }
 
+// external-alignment rows: an explicit list of (query, subject) rows, in the order the reference's column worker yields
+// them (pyani_plus/private_cli.py:2009-2032), each with the worker's seven keys:
+//   {"query_hash": "Q", "subject_hash": "S", "identity": 0.99, "aln_length": 100, "sim_errors": 1, "cov_query": 1.0,
+//    "cov_subject": 0.98}
+namespace {
+void format_msa_rows(std::vector<char> &out, bool first, const char *const *hashes, const size_t *hlen, const uint32_t *q_idx,
+                     const uint32_t *s_idx, uint64_t r0, uint64_t r1, const double *identity, const int64_t *aln_length,
+                     const int64_t *sim_errors, const double *cov_query, const double *cov_subject) {
+  size_t fill = 0;
+  for (uint64_t r = r0; r < r1; ++r) {
+    const uint32_t q = q_idx[r], s = s_idx[r];
+    if (fill + hlen[q] + hlen[s] + 320 > out.size()) out.resize(out.size() * 2 + hlen[q] + hlen[s] + 320);
+    char *p = out.data() + fill;
+    char *const end = out.data() + out.size();
+    if (!first) { memcpy(p, ", ", 2); p += 2; }
+    first = false;
+    memcpy(p, "{\"query_hash\": \"", 16); p += 16;
+    memcpy(p, hashes[q], hlen[q]); p += hlen[q];
+    memcpy(p, "\", \"subject_hash\": \"", 20); p += 20;
+    memcpy(p, hashes[s], hlen[s]); p += hlen[s];
+    memcpy(p, "\", \"identity\": ", 15); p += 15;
+    p = put_double(p, end, identity[r]);
+    memcpy(p, ", \"aln_length\": ", 16); p += 16;
+    p = std::to_chars(p, end, aln_length[r]).ptr;
+    memcpy(p, ", \"sim_errors\": ", 16); p += 16;
+    p = std::to_chars(p, end, sim_errors[r]).ptr;
+    memcpy(p, ", \"cov_query\": ", 15); p += 15;
+    p = put_double(p, end, cov_query[r]);
+    memcpy(p, ", \"cov_subject\": ", 17); p += 17;
+    p = put_double(p, end, cov_subject[r]);
+    *p++ = '}';
+    fill = (size_t)(p - out.data());
+  }
+  out.resize(fill);
+}
+}  // namespace
+
+static int append_msa_json(const char *path, const char *suffix, int file_has_rows, const char *const *hashes, uint32_t n_hashes,
+                           const uint32_t *q_idx, const uint32_t *s_idx, uint64_t n_rows, const double *identity, const int64_t *aln_length,
+                           const int64_t *sim_errors, const double *cov_query, const double *cov_subject) {
+  if (!path || !suffix || (n_hashes && !hashes) ||
+      (n_rows && (!q_idx || !s_idx || !identity || !aln_length || !sim_errors || !cov_query || !cov_subject))) {
+    pa_set_error("pa_append_msa_json: null argument");
+    return PA_E_INVALID;
+  }
+  for (uint64_t r = 0; r < n_rows; ++r)
+    if (q_idx[r] >= n_hashes || s_idx[r] >= n_hashes) {
+      pa_set_error("pa_append_msa_json: row %llu names hash %u of %u", (unsigned long long)r, std::max(q_idx[r], s_idx[r]), n_hashes);
+      return PA_E_INVALID;
+    }
+  FILE *f = fopen(path, "r+b");
+  if (!f) { pa_set_error("cannot open %s for appending", path); return PA_E_INVALID; }
+  const size_t ls = strlen(suffix);
+  std::vector<char> tail(ls + 1, 0);
+  bool ok = fseeko(f, -(off_t)ls, SEEK_END) == 0 && fread(tail.data(), 1, ls, f) == ls && memcmp(tail.data(), suffix, ls) == 0;
+  if (!ok) { fclose(f); pa_set_error("%s does not end with the expected JSON suffix", path); return PA_E_INVALID; }
+  ok = fseeko(f, -(off_t)ls, SEEK_END) == 0;
+  std::vector<size_t> hlen(n_hashes);
+  for (uint32_t i = 0; i < n_hashes; ++i) hlen[i] = strlen(hashes[i]);
+  constexpr uint64_t kRowsPerChunk = 16384;  // ~3 MB of text
+  const uint64_t n_chunks = (n_rows + kRowsPerChunk - 1) / kRowsPerChunk;
+  const uint32_t nt = pa_host_threads(n_chunks, 1, 0);
+  std::vector<std::vector<char>> bufs(nt);
+  try {
+    for (uint64_t c0 = 0; c0 < n_chunks && ok; c0 += nt) {
+      const uint32_t in_round = (uint32_t)std::min<uint64_t>(nt, n_chunks - c0);
+      HostPool::get().run(in_round, [&](uint32_t w, uint32_t) {
+        const uint64_t c = c0 + w, r0 = c * kRowsPerChunk, r1 = std::min(n_rows, r0 + kRowsPerChunk);
+        bufs[w].resize(std::max<size_t>(bufs[w].capacity(), 1 << 20));
+        format_msa_rows(bufs[w], !file_has_rows && c == 0, hashes, hlen.data(), q_idx, s_idx, r0, r1, identity, aln_length, sim_errors,
+                        cov_query, cov_subject);
+      });
+      for (uint32_t w = 0; w < in_round && ok; ++w) ok = fwrite(bufs[w].data(), 1, bufs[w].size(), f) == bufs[w].size();
+    }
+  } catch (...) { fclose(f); throw; }
+  ok = ok && fwrite(suffix, 1, ls, f) == ls;
+  ok = (fclose(f) == 0) && ok;
+  if (!ok) { pa_set_error("short write to %s", path); return PA_E_INVALID; }
+  return PA_OK;
+}
+
+extern "C" int pa_append_msa_json(const char *path, const char *suffix, int file_has_rows, const char *const *hashes, uint32_t n_hashes,
+                                  const uint32_t *q_idx, const uint32_t *s_idx, uint64_t n_rows, const double *identity,
+                                  const int64_t *aln_length, const int64_t *sim_errors, const double *cov_query, const double *cov_subject) {
+  return pa_host_guard("pa_append_msa_json", pa_set_error, [&] {
+    return append_msa_json(path, suffix, file_has_rows, hashes, n_hashes, q_idx, s_idx, n_rows, identity, aln_length, sim_errors, cov_query,
+                           cov_subject);
+  });
+}
+
 // fastANI prints its identity through a C++ stream with the default precision (six significant digits) and the
 // reference parses that text (pyani_plus/methods/fastani.py:98-120): value -> "%.6g" -> value, in place; NaN stays.
 extern "C" int pa_round_sig6(double *h_values, uint64_t n) {

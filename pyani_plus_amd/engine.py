@@ -589,6 +589,51 @@ class HipEngine:
         the call and the sizes (``HipBackendError``), the workspace as it was."""
         self._check(self.lib.pa_fragani_set_workspace_cap(self.ctx, int(cap_bytes)), "pa_fragani_set_workspace_cap")
 
+    # -- external alignment
+    def msa_upload(self, msa: "LoadedMSA", *, chunk_bytes: int = 1 << 29) -> "DeviceMSA":
+        """Rows -> bit planes on the device (``pa_msa_pack``), the rows uploaded in chunks of at most ``chunk_bytes``."""
+        t = self.torch
+        code, bits = msa_code_table(msa.histogram)
+        n, stride = msa.n_rows, msa.rows.shape[1]
+        words = int(self.lib.pa_msa_plane_words(n, msa.n_cols, bits))
+        planes = t.empty(max(words, 1), dtype=t.int32, device=self.device)
+        nongap = t.zeros(max(n, 1), dtype=t.int32, device=self.device)
+        step = max(1, int(chunk_bytes) // stride)
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            d_rows = t.from_numpy(msa.rows[r0:r1]).to(self.device)
+            self._check(
+                self.lib.pa_msa_pack(
+                    self.ctx, d_rows.data_ptr(), stride, r0, r1 - r0, n, msa.n_cols, code.ctypes.data, bits, planes.data_ptr(), nongap.data_ptr()
+                ),
+                "pa_msa_pack",
+            )
+            self.sync()  # d_rows is freed by the next iteration
+        return DeviceMSA(planes, nongap, n, msa.n_cols, bits)
+
+
+    def msa_pair_counts(self, dm: "DeviceMSA", q_range=None, s_range=None, *, symmetric: bool = False):
+        """(M, B) as torch.int32 [nq, ns] on the device for rows q_range x s_range (uint32 values)."""
+        t = self.torch
+        q0, q1 = q_range or (0, dm.n_rows)
+        s0, s1 = s_range or (0, dm.n_rows)
+        match = t.empty((q1 - q0, s1 - s0), dtype=t.int32, device=self.device)
+        both = t.empty((q1 - q0, s1 - s0), dtype=t.int32, device=self.device)
+        if match.numel() == 0:
+            return match, both
+        self._check(
+            self.lib.pa_msa_pair_counts(
+                self.ctx, dm.planes.data_ptr(), dm.n_rows, dm.n_cols, dm.bits, q0, q1, s0, s1, int(bool(symmetric)), match.data_ptr(), both.data_ptr()
+            ),
+            "pa_msa_pair_counts",
+        )
+        return match, both
+
+    @staticmethod
+    def msa_metrics(match, both, n_q, n_s, threads: int = 0):
+        """``msa_metrics`` (host): the counts of ``msa_pair_counts`` -> the reference's five numbers per pair."""
+        return msa_metrics(match, both, n_q, n_s, threads)
+
     # -- profiling
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")
@@ -630,3 +675,97 @@ def ani_host(counts: np.ndarray, q_sizes, s_sizes, k: int, *, symmetric: bool = 
         "pa_ani_host",
     )
     return ident, cov, null.view(np.bool_) if null.dtype == np.uint8 else null
+
+
+# ------------------------------------------------------------------ external alignment (external-alignment-hip)
+GAP = ord("-")
+
+
+@dataclass
+class LoadedMSA:
+    """A FASTA multiple alignment read by ``pa_msa_load``: md5 of the raw file, one title and residue count per record,
+    a 256-bin histogram of the residue bytes, and the rows as an N x ``row_stride`` byte matrix (each row's tail after
+    its residues is '-'; ``row_stride`` = the longest row rounded up to 32)."""
+
+    md5: str
+    titles: list[bytes]
+    lengths: np.ndarray  # uint64 residues (gaps included) per record
+    histogram: np.ndarray  # uint64[256]
+    rows: np.ndarray  # uint8 [N, row_stride]
+    n_cols: int  # longest record
+
+    @property
+    def n_rows(self) -> int:
+        return len(self.titles)
+
+
+def load_msa(path, threads: int = 0) -> LoadedMSA:
+    """One pass over the alignment file: md5 beside a parallel parse (``pa_msa_load``), then the rows copied out."""
+    lib = _capi.load_library()
+    handle = C.c_void_p()
+    check(lib.pa_msa_load(str(path).encode(), int(threads), C.byref(handle)), "pa_msa_load", lib)
+    try:
+        n = C.c_uint32(0)
+        max_len = C.c_uint64(0)
+        md5 = C.create_string_buffer(33)
+        hist = np.zeros(256, dtype=np.uint64)
+        check(lib.pa_msa_info(handle, C.byref(n), C.byref(max_len), md5, hist.ctypes.data_as(C.POINTER(C.c_uint64))), "pa_msa_info", lib)
+        titles, lengths = [], np.zeros(n.value, dtype=np.uint64)
+        title, tlen, length = C.c_char_p(), C.c_uint64(0), C.c_uint64(0)
+        for i in range(n.value):
+            check(lib.pa_msa_record(handle, i, C.byref(title), C.byref(tlen), C.byref(length)), "pa_msa_record", lib)
+            titles.append(C.string_at(title, tlen.value))
+            lengths[i] = length.value
+        stride = max(32, (int(max_len.value) + 31) // 32 * 32)
+        rows = np.empty((n.value, stride), dtype=np.uint8)
+        if n.value:
+            check(lib.pa_msa_copy_rows(handle, 0, n.value, stride, rows.ctypes.data), "pa_msa_copy_rows", lib)
+        return LoadedMSA(md5.value.decode(), titles, lengths, hist, rows, int(max_len.value))
+    finally:
+        lib.pa_msa_free(handle)
+
+
+def msa_code_table(histogram) -> tuple[np.ndarray, int]:
+    """Byte -> code for the pack kernel: '-' 0, the residue bytes present 1..A in byte order; bits = ceil(log2(A + 1))
+    (at least 1).  Comparison is on raw bytes: 'a' and 'A' are different residues, '.' is a residue."""
+    hist = np.asarray(histogram, dtype=np.uint64)
+    present = [b for b in range(256) if hist[b] and b != GAP]
+    code = np.zeros(256, dtype=np.uint8)
+    for i, b in enumerate(present, start=1):
+        code[b] = i
+    bits = max(1, int(len(present)).bit_length())
+    return code, bits
+
+
+@dataclass
+class DeviceMSA:
+    planes: object  # torch.int32 [pa_msa_plane_words] on the device
+    nongap: object  # torch.int32 [n_rows]: residues (non-gap columns) per row
+    n_rows: int
+    n_cols: int
+    bits: int
+
+
+def msa_metrics(match, both, n_q, n_s, threads: int = 0):
+    """(M, B, n_q, n_s) per pair -> (identity, aln_length, sim_errors, cov_query, cov_subject), ``pa_msa_metrics`` on the
+    host thread pool; bit-identical to the reference's int / int divisions."""
+    lib = _capi.load_library()
+    match = np.ascontiguousarray(match, dtype=np.uint32)
+    shape = match.shape  # n_q / n_s broadcast against it (a column of query lengths, a row of subject lengths)
+    match = match.ravel()
+    both = np.ascontiguousarray(both, dtype=np.uint32).ravel()
+    n_q = np.ascontiguousarray(np.broadcast_to(np.asarray(n_q, dtype=np.uint64), shape)).ravel()
+    n_s = np.ascontiguousarray(np.broadcast_to(np.asarray(n_s, dtype=np.uint64), shape)).ravel()
+    n = match.size
+    assert both.size == n
+    ident, covq, covs = (np.empty(n, dtype=np.float64) for _ in range(3))
+    aln, err = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+    check(
+        lib.pa_msa_metrics(
+            match.ctypes.data, both.ctypes.data, n_q.ctypes.data, n_s.ctypes.data, n, ident.ctypes.data, aln.ctypes.data,
+            err.ctypes.data, covq.ctypes.data, covs.ctypes.data, int(threads),
+        ),  # fmt: skip
+        "pa_msa_metrics",
+        lib,
+    )
+    return ident, aln, err, covq, covs

@@ -813,9 +813,9 @@ def resume(database: Path | str, *, run_id: int | None = None, cache: Path | Non
     logger.info("This is a %s run on %d genomes, using %s version %s", config.method, n, config.program, config.version)
     if not n:
         sourmash_hip.log_sys_exit(logger, f"No genomes recorded for run-id {run_id}, cannot resume.")
-    from .methods import fastani_hip
+    from .methods import external_alignment_hip, fastani_hip
 
-    if config.method not in {sourmash_hip.METHOD, fastani_hip.METHOD}:
+    if config.method not in {sourmash_hip.METHOD, fastani_hip.METHOD, external_alignment_hip.METHOD}:
         sourmash_hip.log_sys_exit(logger, f"Unknown method {config.method} for run-id {run_id} in {database}")
     tool = sourmash_hip.get_sourmash_hip()
     if tool.exe_path.stem != config.program or tool.version != config.version:
@@ -837,6 +837,11 @@ def resume(database: Path | str, *, run_id: int | None = None, cache: Path | Non
     mark = _phase_clock(None)
     tmp_dir = Path(temp) if temp else Path(tempfile.mkdtemp(prefix="pyani_hip_"))
     tmp_dir.mkdir(parents=True, exist_ok=True)
+    if config.method == external_alignment_hip.METHOD:
+        if int(gpus) != 1:
+            sourmash_hip.log_sys_exit(logger, f"{config.method} runs on one GPU; --gpus {gpus} is not supported")
+        _compute_missing_external_alignment(logger, conn, session, run, tmp_dir, engine, mark)
+        return _finish_run(logger, conn, session, run, None, mark)
     if config.method == fastani_hip.METHOD:
         direct = _compute_missing_fastani(logger, conn, session, run, tmp_dir, engine, gpus, engine_factory, ingest, mark)
         return _finish_run(logger, conn, session, run, direct, mark)
@@ -1169,9 +1174,98 @@ def run_fastani_hip(  # noqa: PLR0913
     return _finish_run(logger, conn, session, run, direct, mark)
 
 
+def _compute_missing_external_alignment(logger, conn, session, run: Run, tmp_dir: Path, engine, mark) -> None:
+    """The subject columns the database does not complete yet, through the column worker and its JSON file: all of them
+    in one device call for a new run, the incomplete ones (one call each, as the reference's resume) otherwise."""
+    from .methods import external_alignment_hip
+
+    n = len(run.fasta_hashes)
+    done = count_run_comparisons(conn, run)
+    if done == n * n:
+        logger.info("Database already has all %d=%d^2 %s comparisons", n * n, n, external_alignment_hip.METHOD)
+        return
+    columns = [""] if done == 0 else _incomplete_columns(conn, run)
+    run.status = "Running"
+    session.commit()
+    hash_to_filename = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
+    query_hashes = {h: 0 for h in hash_to_filename}
+    for c, subject in enumerate(columns):
+        json_file = tmp_dir / f"{external_alignment_hip.METHOD}.run_{run.run_id}.column_{c if subject else 0}.json"
+        status = external_alignment_hip.compute_external_alignment_hip(
+            logger, tmp_dir, session, run, json_file, Path(run.fasta_directory), hash_to_filename,
+            {v: k for k, v in hash_to_filename.items()}, query_hashes, subject, engine=engine,
+        )  # fmt: skip
+        if status:
+            sourmash_hip.log_sys_exit(logger, f"Column worker failed with return code {status}")
+        mark("pairs_and_column_file")
+        import_json_comparisons(logger, conn, json_file)
+        mark("import_column_file")
+        if run.status == "Worker interrupted":
+            break
+
+
+def run_external_alignment_hip(  # noqa: PLR0913
+    fasta: Path,
+    database: Path | str,
+    *,
+    alignment: Path,
+    label: str = "stem",
+    name: str | None = None,
+    temp: Path | None = None,
+    logger: logging.Logger | None = None,
+    engine=None,
+    gpus: int = 1,
+    timings: dict | None = None,
+) -> Run:
+    """FASTA directory + its MSA -> database with all N^2 external-alignment comparisons and cached matrices: counterpart
+    of ``pyani-plus external-alignment <fasta> -d <db> --alignment <msa> --label <label> --create-db``
+    (pyani_plus/public_cli.py:642-699).  As there, the configuration records the MSA's md5 and its file name only: the
+    worker looks for the file next to the database.  One GPU: ``gpus`` > 1 is refused."""
+    from .engine import load_fasta_files
+    from .methods import external_alignment_hip
+
+    mark = _phase_clock(timings)
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    if int(gpus) != 1:
+        sourmash_hip.log_sys_exit(logger, f"{external_alignment_hip.METHOD} runs on one GPU; --gpus {gpus} is not supported")
+    if label not in {"md5", "filename", "stem"}:
+        sourmash_hip.log_sys_exit(logger, f"label must be md5, filename or stem, not {label!r}")
+    alignment = Path(alignment)
+    if not alignment.is_file():
+        sourmash_hip.log_sys_exit(logger, f"Missing alignment file {alignment}")
+    fasta = Path(fasta)
+    fasta_names = check_fasta(logger, fasta)
+    tool = external_alignment_hip.get_external_alignment_hip()
+    import hashlib
+
+    with alignment.open("rb") as handle:
+        aln_md5 = hashlib.file_digest(handle, "md5").hexdigest() if hasattr(hashlib, "file_digest") else hashlib.md5(handle.read()).hexdigest()
+    conn = connect_to_db(database)
+    config = db_configuration(conn, external_alignment_hip.METHOD, tool.exe_path.stem, tool.version,
+                              extra=external_alignment_hip.make_extra(aln_md5, label, alignment))  # fmt: skip
+    infos, _arena = load_fasta_files(fasta_names)
+    filename_to_md5: dict[Path, str] = {}
+    for filename, info in zip(fasta_names, infos):
+        if info.status != 0:
+            sourmash_hip.log_sys_exit(logger, info.message)
+        if info.md5 in filename_to_md5.values():
+            _duplicate_md5_exit(logger, info.md5, [k for k, v in filename_to_md5.items() if v == info.md5] + [filename])
+        filename_to_md5[filename] = info.md5
+        db_genome(conn, filename, info.md5, info.length, info.description)
+    del _arena
+    mark("register_genomes")
+    run = add_run(conn, config, " ".join(sys.argv), fasta, "Initialising", f"Import of {alignment.name}" if name is None else name,
+                  filename_to_md5)  # fmt: skip
+    session = Session(conn, run)
+    tmp_dir = Path(temp) if temp else Path(tempfile.mkdtemp(prefix="pyani_hip_"))
+    tmp_dir.mkdir(parents=True, exist_ok=True)
+    _compute_missing_external_alignment(logger, conn, session, run, tmp_dir, engine, mark)
+    return _finish_run(logger, conn, session, run, None, mark)
+
+
 # ------------------------------------------------------------------ the driver as a process
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,resume,export-run} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,resume,export-run} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -1205,6 +1299,10 @@ def main(argv: list[str] | None = None) -> int:
     p_f.add_argument("--fragsize", type=int, default=None)
     p_f.add_argument("--minmatch", type=float, default=None)
     p_f.add_argument("--query-batch", type=int, default=None)
+    p_x = sub.add_parser("external-alignment", help="FASTA directory + its MSA -> all N^2 external-alignment-hip comparisons")
+    common(p_x, run_options=True)
+    p_x.add_argument("--alignment", required=True, type=Path, help="FASTA MSA of the genomes, one row per genome")
+    p_x.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
     p_r = sub.add_parser("resume", help="complete a partial run")
     common(p_r, run_options=False)
     p_r.add_argument("--run-id", type=int, default=None)
@@ -1226,6 +1324,9 @@ def main(argv: list[str] | None = None) -> int:
             run = run_fastani_hip(args.fasta, args.database, name=args.name, kmersize=args.kmersize, fragsize=args.fragsize,
                                   minmatch=args.minmatch, temp=args.temp, logger=logger, ingest=args.ingest, gpus=args.gpus,
                                   engine_factory=args.engine_factory, query_batch=args.query_batch)
+        elif args.command == "external-alignment":
+            run = run_external_alignment_hip(args.fasta, args.database, alignment=args.alignment, label=args.label, name=args.name,
+                                             temp=args.temp, logger=logger, gpus=args.gpus)
         elif args.command == "resume":
             run = resume(args.database, run_id=args.run_id, cache=args.cache, temp=args.temp, logger=logger, ingest=args.ingest,
                          gpus=args.gpus, engine_factory=args.engine_factory)
