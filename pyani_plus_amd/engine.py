@@ -629,11 +629,6 @@ class HipEngine:
         )
         return match, both
 
-    @staticmethod
-    def msa_metrics(match, both, n_q, n_s, threads: int = 0):
-        """``msa_metrics`` (host): the counts of ``msa_pair_counts`` -> the reference's five numbers per pair."""
-        return msa_metrics(match, both, n_q, n_s, threads)
-
     # -- profiling
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")

@@ -1,9 +1,11 @@
-"""Run driver and persistence for the ``sourmash-hip`` method (stdlib ``sqlite3``).
+"""Run driver and persistence for the three methods ``sourmash-hip``, ``fastANI-hip`` and ``external-alignment-hip``
+(stdlib ``sqlite3``).
 
 The reference's Python (Typer CLI, SQLAlchemy ORM, snakemake) does not travel to the GPU
-box, so this module is the build's own counterpart of ``cli_sourmash`` +
-``start_and_run_method`` + ``run_method`` minus snakemake (pyani_plus/public_cli.py:115-329,
-598-639) and of the parts of ``db_orm`` they use (last row):
+box, so this module is the build's own counterpart of ``cli_sourmash`` / ``fastani`` / ``external_alignment`` +
+``start_and_run_method`` + ``run_method`` minus snakemake (pyani_plus/public_cli.py:115-329, 502-554,
+598-699), of ``resume`` and ``export-run`` (702-828, 974-1091) and of the parts of ``db_orm`` they use (SURVEY.md
+section 8b, last row):
 
 * FASTA enumeration by the four extensions +- ``.gz`` (pyani_plus/utils.py:226-242)
 * genome identity = md5 of the decompressed bytes (utils.py:142-196); length = sum of
@@ -14,26 +16,43 @@ box, so this module is the build's own counterpart of ``cli_sourmash`` +
 * ``cache_comparisons``: N x N matrices over sorted md5, pandas ``to_json(orient="split")``
   (db_orm.py:393-466) -- built without the reference's O(N^3) ``hashes.index`` loop.
 
+Every run takes the same steps: register the genomes, record the run, find what the database lacks
+(``_begin_missing``), compute it (the method's ``_compute_missing_<method>``, listed in ``_METHODS``) and finish
+(``_finish_run``); ``_RunState`` carries what the steps share.
+
 Databases written here can be opened by the reference and vice versa.
 """
 
 from __future__ import annotations
 
+import argparse
+import ctypes as C
 import datetime
+import enum
+import hashlib
+import importlib
 import logging
+import math
 import os
+import platform
 import sqlite3
-import zipfile
 import sys
 import tempfile
+import time
+import zipfile
+from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
+from io import StringIO
 from pathlib import Path
 
 import numpy as np
 
-from . import wire
+from . import _capi, launch, wire
 from ._capi import HipBackendError
-from .methods import sourmash_hip
+from .distributed import shard_bounds_by_cost
+from .engine import load_fasta_files
+from .methods import external_alignment_hip, fastani_hip, sourmash_hip
+from .methods.external_alignment_hip import filename_stem  # also reached as ``rundb.filename_stem``
 
 FASTA_EXTENSIONS = {".fasta", ".fas", ".fna", ".fa"}  # pyani_plus/__init__.py:48
 
@@ -161,14 +180,19 @@ def connect_to_db(database: Path | str) -> sqlite3.Connection:
     return conn
 
 
+def _find_configuration(conn, values: tuple):
+    """The (configuration_id,) row with these values of ``wire.CONFIG_FIELDS``, or None."""
+    return conn.execute(
+        "SELECT configuration_id FROM configurations WHERE method=? AND program=? AND version=? AND fragsize IS ? "
+        "AND mode IS ? AND kmersize IS ? AND minmatch IS ? AND extra IS ?",
+        values,
+    ).fetchone()
+
+
 def db_configuration(conn, method, program, version, fragsize=None, mode=None, kmersize=None, minmatch=None,
                      extra=None) -> Configuration:
     """Return the matching configuration row, creating it if needed (db_orm.py:705-782)."""
-    row = conn.execute(
-        "SELECT configuration_id FROM configurations WHERE method=? AND program=? AND version=? AND fragsize IS ? "
-        "AND mode IS ? AND kmersize IS ? AND minmatch IS ? AND extra IS ?",
-        (method, program, version, fragsize, mode, kmersize, minmatch, extra),
-    ).fetchone()
+    row = _find_configuration(conn, (method, program, version, fragsize, mode, kmersize, minmatch, extra))
     if row is None:
         cur = conn.execute(
             "INSERT INTO configurations (method, program, version, fragsize, mode, kmersize, minmatch, extra) "
@@ -227,15 +251,42 @@ def load_run(conn, run_id: int) -> Run:
     return Run(run_id, Configuration(*crow), row[1], assoc, row[2], row[3])
 
 
-def count_run_comparisons(conn, run: Run) -> int:
-    """Comparisons among this run's genomes under its configuration (Run.comparisons(), db_orm.py:353-391)."""
+def _open_run(logger, database: Path | str, run_id: int | None, doing: str) -> tuple[sqlite3.Connection, Run]:
+    """The database and its run ``run_id`` (None: the latest one), with the reference's messages
+    (pyani_plus/public_cli.py:718-741)."""
+    conn = connect_to_db(database)
+    if run_id is None:
+        row = conn.execute("SELECT MAX(run_id) FROM runs").fetchone()
+        if row is None or row[0] is None:
+            sourmash_hip.log_sys_exit(logger, f"Database {database} contains no runs.")
+        run_id = row[0]
+        logger.info("%s run-id %d", doing, run_id)
+    try:
+        return conn, load_run(conn, run_id)
+    except ValueError:
+        sourmash_hip.log_sys_exit(logger, f"Database {database} has no run-id {run_id}.")
+
+
+def _select_run_comparisons(conn, run: Run, what: str, tail: str = "") -> sqlite3.Cursor:
+    """``what`` of the comparisons among this run's genomes under its configuration (Run.comparisons(),
+    db_orm.py:353-391)."""
     return conn.execute(
-        "SELECT COUNT(*) FROM comparisons c "
+        f"SELECT {what} FROM comparisons c "
         "JOIN runs_genomes q ON c.query_hash = q.genome_hash AND q.run_id = ? "
         "JOIN runs_genomes s ON c.subject_hash = s.genome_hash AND s.run_id = ? "
-        "WHERE c.configuration_id = ?",
+        f"WHERE c.configuration_id = ? {tail}",
         (run.run_id, run.run_id, run.configuration_id),
-    ).fetchone()[0]
+    )
+
+
+def count_run_comparisons(conn, run: Run) -> int:
+    return _select_run_comparisons(conn, run, "COUNT(*)").fetchone()[0]
+
+
+INSERT_COMPARISON = (
+    "INSERT OR IGNORE INTO comparisons (query_hash, subject_hash, configuration_id, identity, aln_length, "
+    "sim_errors, cov_query, uname_system, uname_release, uname_machine) VALUES (?,?,?,?,?,?,?,?,?,?)"
+)
 
 
 def import_json_comparisons(logger: logging.Logger, conn, json_filename: Path) -> int:
@@ -243,11 +294,7 @@ def import_json_comparisons(logger: logging.Logger, conn, json_filename: Path) -
     (pyani_plus/private_cli.py:507-614)."""
     data = wire.load_json_comparisons(json_filename)
     cfg = data["configuration"]
-    row = conn.execute(
-        "SELECT configuration_id FROM configurations WHERE method=? AND program=? AND version=? AND fragsize IS ? "
-        "AND mode IS ? AND kmersize IS ? AND minmatch IS ? AND extra IS ?",
-        tuple(cfg[k] for k in wire.CONFIG_FIELDS),
-    ).fetchone()
+    row = _find_configuration(conn, tuple(cfg[k] for k in wire.CONFIG_FIELDS))
     if row is None:
         sourmash_hip.log_sys_exit(logger, f"JSON file {json_filename} configuration not in database")
     cid = row[0]
@@ -259,19 +306,9 @@ def import_json_comparisons(logger: logging.Logger, conn, json_filename: Path) -
         )  # fmt: skip
         for e in data["comparisons"]
     ]
-    conn.executemany(
-        "INSERT OR IGNORE INTO comparisons (query_hash, subject_hash, configuration_id, identity, aln_length, "
-        "sim_errors, cov_query, uname_system, uname_release, uname_machine) VALUES (?,?,?,?,?,?,?,?,?,?)",
-        rows,
-    )
+    conn.executemany(INSERT_COMPARISON, rows)
     conn.commit()
     return len(rows)
-
-
-INSERT_COMPARISON = (
-    "INSERT OR IGNORE INTO comparisons (query_hash, subject_hash, configuration_id, identity, aln_length, "
-    "sim_errors, cov_query, uname_system, uname_release, uname_machine) VALUES (?,?,?,?,?,?,?,?,?,?)"
-)
 
 
 def _database_file(conn) -> str | None:
@@ -287,11 +324,6 @@ def ingest_matrices_native(conn, run: Run, queries: list[str], subjects: list[st
     """``ingest_matrices`` through ``pa_sqlite_insert_comparisons`` (one prepared statement stepped from C on a
     connection of its own).  Returns the number of comparisons handled, or None when the native route does not
     apply (in-memory database, libsqlite3.so.0 not loadable) -- the caller then uses Python's sqlite3 module."""
-    import ctypes as C
-    import platform
-
-    from . import _capi
-
     path = _database_file(conn)
     if path is None:
         return None
@@ -332,8 +364,6 @@ def ingest_matrices(conn, run: Run, queries: list[str], subjects: list[str], ide
     configuration_id) index when both lists are sorted, so the index grows by appends.  With ``native`` the rows
     are stepped from C (``ingest_matrices_native``); otherwise, or when that route does not apply, in chunks of
     ``chunk_rows`` through one ``executemany`` each."""
-    import platform
-
     if native:
         done = ingest_matrices_native(conn, run, queries, subjects, identity, cov_query, is_null, aln_length=aln_length, sim_errors=sim_errors)
         if done is not None:
@@ -369,11 +399,20 @@ def ingest_matrices(conn, run: Run, queries: list[str], subjects: list[str], ide
     return nq * ns
 
 
+def _matrices_to_json(hashes: list[str], mats: dict) -> dict[str, str]:
+    """The five ``runs.df_*`` strings as pandas writes them (db_orm.py:442-465); hadamard = identity * cov_query."""
+    import pandas as pd  # loaded when the first matrix cache is formatted, not with the module
+
+    mats["hadamard"] = mats["identity"] * mats["cov_query"]
+    return {
+        f"df_{key}": pd.DataFrame(data=mat, index=hashes, columns=hashes, dtype=float).to_json(orient="split")
+        for key, mat in mats.items()
+    }
+
+
 def format_matrix_cache(hashes: list[str], identity, cov_query, is_null, *, aln_length=None, sim_errors=None) -> dict[str, str] | None:
     """The five ``runs.df_*`` strings from matrices in memory (rows = query, columns = subject, both in ``hashes``
     order = sorted md5); None when they would not fit a SQLite value."""
-    import pandas as pd
-
     assert hashes == sorted(hashes)
     n = len(hashes)
     if _matrix_cache_too_big(n):
@@ -383,11 +422,7 @@ def format_matrix_cache(hashes: list[str], identity, cov_query, is_null, *, aln_
     nan = np.full((n, n), np.nan)
     aln = nan if aln_length is None else np.where(is_null, np.nan, np.asarray(aln_length, dtype=np.float64))
     err = nan if sim_errors is None else np.where(is_null, np.nan, np.asarray(sim_errors, dtype=np.float64))
-    mats = {"identity": ident, "cov_query": cov, "aln_length": aln, "sim_errors": err, "hadamard": ident * cov}
-    return {
-        f"df_{key}": pd.DataFrame(data=mat, index=hashes, columns=hashes, dtype=float).to_json(orient="split")
-        for key, mat in mats.items()
-    }
+    return _matrices_to_json(hashes, {"identity": ident, "cov_query": cov, "aln_length": aln, "sim_errors": err})
 
 
 def cache_matrices(conn, run: Run, hashes: list[str], identity, cov_query, is_null, *, formatted=None) -> dict[str, str]:
@@ -430,8 +465,6 @@ def _store_matrix_cache(conn, run: Run, out: dict[str, str] | None) -> bool:
 
 def cache_comparisons(conn, run: Run) -> dict[str, str]:
     """Fill runs.df_* with the N x N matrices (rows = query, columns = subject, sorted md5)."""
-    import pandas as pd
-
     hashes = sorted(a.genome_hash for a in run.fasta_hashes)
     index = {h: i for i, h in enumerate(hashes)}
     n = len(hashes)
@@ -439,91 +472,34 @@ def cache_comparisons(conn, run: Run) -> dict[str, str]:
         _store_matrix_cache(conn, run, None)
         return {}
     mats = {k: np.full((n, n), np.nan, float) for k in ("identity", "cov_query", "aln_length", "sim_errors")}
-    rows = conn.execute(
-        "SELECT c.query_hash, c.subject_hash, c.identity, c.cov_query, c.aln_length, c.sim_errors FROM comparisons c "
-        "JOIN runs_genomes rq ON c.query_hash = rq.genome_hash AND rq.run_id = ? "
-        "JOIN runs_genomes rs ON c.subject_hash = rs.genome_hash AND rs.run_id = ? WHERE c.configuration_id = ?",
-        (run.run_id, run.run_id, run.configuration_id),
-    ).fetchall()
+    rows = _select_run_comparisons(conn, run, "c.query_hash, c.subject_hash, c.identity, c.cov_query, c.aln_length, c.sim_errors").fetchall()
     if rows:
         # one dictionary lookup per row (the reference does a list.index per row: O(N^3) overall)
         r_idx = np.fromiter((index[r[0]] for r in rows), dtype=np.int64, count=len(rows))
         c_idx = np.fromiter((index[r[1]] for r in rows), dtype=np.int64, count=len(rows))
         for col, key in enumerate(("identity", "cov_query", "aln_length", "sim_errors"), start=2):
             mats[key][r_idx, c_idx] = np.array([r[col] for r in rows], dtype=float)  # None -> NaN
-    mats["hadamard"] = mats["identity"] * mats["cov_query"]
-    out = {
-        f"df_{key}": pd.DataFrame(data=mat, index=hashes, columns=hashes, dtype=float).to_json(orient="split")
-        for key, mat in mats.items()
-    }
+    out = _matrices_to_json(hashes, mats)
     _store_matrix_cache(conn, run, out)
     return out
 
 
-def _compute_direct(logger, conn, run: Run, cache_dir: Path, tmp_dir: Path, engine, mark, *, subjects: list[str] | None = None):
-    """Subject tiles -> binary column files + matrices in host memory -> rows inserted in index order.
-    ``subjects``: only these subject columns (resuming a partial run); the matrices then hold those columns."""
-    config = run.configuration
-    hashes = sorted(a.genome_hash for a in run.fasta_hashes)
-    cols = hashes if subjects is None else sorted(subjects)
-    n, nc = len(hashes), len(cols)
-    ident = np.empty((n, nc), dtype=np.float64)
-    cov = np.empty((n, nc), dtype=np.float64)
-    null = np.empty((n, nc), dtype=bool)
-    sig_cache = sourmash_hip.sig_cache_dir(cache_dir, config.kmersize, config.extra)
-    col = 0
-    try:
-        for t, (queries, tile, t_cov, t_ident, t_null) in enumerate(
-            sourmash_hip.iter_sourmash_tiles(
-                logger, cols, hashes, sig_cache, kmersize=config.kmersize, scaled=sourmash_hip.parse_scaled(config.extra), engine=engine
-            )
-        ):
-            assert queries == hashes and tile == cols[col : col + len(tile)]
-            wire.save_tile(tmp_dir / f"{sourmash_hip.METHOD}.run_{run.run_id}.tile_{t}.npz", config, queries, tile, t_ident, t_cov, t_null)
-            ident[:, col : col + len(tile)] = t_ident
-            cov[:, col : col + len(tile)] = t_cov
-            null[:, col : col + len(tile)] = t_null
-            col += len(tile)
-    except HipBackendError as err:
-        sourmash_hip.backend_failure(logger, f"{sourmash_hip.METHOD} comparison", err)
-    mark("pairs_and_tile_files")
-    return _ingest_direct(conn, run, hashes, cols, ident, cov, null, mark)
-
-
-def _ingest_direct(conn, run: Run, hashes: list[str], cols: list[str], ident, cov, null, mark, *, aln_length=None, sim_errors=None):
-    """Matrices in host memory (rows = ``hashes``, columns = ``cols``, both sorted) -> comparison rows in index order,
-    the five cached matrices formatted on a second thread meanwhile (when the block is the whole square)."""
-    # synchronous=NORMAL for the bulk insert: a handful of fsyncs per transaction instead of one per page group, and
-    # -- unlike OFF -- no way for a crash of the machine to corrupt the user's multi-run database
-    conn.execute("PRAGMA synchronous=NORMAL")
-    conn.execute("PRAGMA cache_size=-1048576")
-    from concurrent.futures import ThreadPoolExecutor
-
-    square = cols == hashes
-    with ThreadPoolExecutor(max_workers=1) as side:
-        formatting = side.submit(format_matrix_cache, hashes, ident, cov, null, aln_length=aln_length, sim_errors=sim_errors) if square else None
-        ingest_matrices(conn, run, hashes, cols, ident, cov, null, aln_length=aln_length, sim_errors=sim_errors)
-        formatted = formatting.result() if formatting is not None else None
-    conn.execute("PRAGMA synchronous=FULL")
-    mark("insert_rows")
-    # what is in the database now, not what was handed to the insert (INSERT OR IGNORE reports nothing per row)
-    rows = count_run_comparisons(conn, run)
-    return rows, hashes, ident, cov, null, formatted if square else False
+def _load_tile(logger, tile_file: Path, config: Configuration) -> tuple:
+    """(queries, subjects, identity, cov_query, is_null) of a ``wire.save_tile`` file made under ``config``."""
+    tile_config, *tile = wire.load_tile(tile_file)
+    for key in wire.CONFIG_FIELDS:
+        if tile_config[key] != getattr(config, key):
+            sourmash_hip.log_sys_exit(logger, f"Tile file {tile_file} configuration does not match the run ({key})")
+    return tuple(tile)
 
 
 def import_tile(logger: logging.Logger, conn, run: Run, tile_file: Path) -> int:
     """Import one binary column file written by ``wire.save_tile`` (resuming a direct-ingest run)."""
-    config, queries, subjects, ident, cov, null = wire.load_tile(tile_file)
-    for key in wire.CONFIG_FIELDS:
-        if config[key] != getattr(run.configuration, key):
-            sourmash_hip.log_sys_exit(logger, f"Tile file {tile_file} configuration does not match the run ({key})")
-    return ingest_matrices(conn, run, queries, subjects, ident, cov, null)
+    return ingest_matrices(conn, run, *_load_tile(logger, tile_file, run.configuration))
 
 
-# ------------------------------------------------------------------ the run itself
+# ------------------------------------------------------------------ what the steps of a run share
 def _phase_clock(timings: dict | None):
-    import time
-
     marks = {"start": time.perf_counter()}
 
     def mark(name: str) -> None:
@@ -535,10 +511,248 @@ def _phase_clock(timings: dict | None):
     return mark
 
 
-def _duplicate_md5_exit(logger, md5: str, filenames) -> None:
-    """Two input files with the same content (pyani_plus/public_cli.py:165-171)."""
-    dups = "\n" + "\n".join(sorted({str(f) for f in filenames}))
-    sourmash_hip.log_sys_exit(logger, f"Multiple genomes with same MD5 checksum {md5}:{dups}")
+@dataclass
+class _RunState:
+    """What the steps of one run share: built once by ``run_*_hip`` / ``resume``."""
+
+    logger: logging.Logger
+    conn: sqlite3.Connection
+    tmp_dir: Path
+    cache_dir: Path | None  # sourmash-hip's signature cache as the caller named it (None: a temporary one)
+    engine: object
+    gpus: int
+    engine_factory: str | None
+    ingest: str
+    mark: object  # ``_phase_clock``'s
+    run: Run | None = None  # set by ``_record_run`` (sourmash-hip's workers read the files before there is a run)
+    session: Session | None = None
+
+
+class _MatrixCache(enum.Enum):
+    """Where ``_finish_run`` takes the five ``runs.df_*`` strings of a directly ingested run from."""
+
+    FORMATTED = enum.auto()  # ``_DirectResult.formatted`` holds them
+    TOO_BIG = enum.auto()  # beyond a SQLite value (``_matrix_cache_too_big``): the columns stay NULL
+    REBUILD = enum.auto()  # a resumed run, only some columns in memory: read the table back
+
+
+@dataclass
+class _DirectResult:
+    """What ``_ingest_direct`` leaves for ``_finish_run``: the rows the table holds now and the matrices in memory."""
+
+    rows: int
+    hashes: list[str]
+    identity: np.ndarray
+    cov_query: np.ndarray
+    is_null: np.ndarray
+    matrix_cache: _MatrixCache
+    formatted: dict[str, str] | None = None
+
+
+def _work_dir(path: Path | None, prefix: str = "pyani_hip_") -> Path:
+    """The directory the caller named, or a fresh temporary one; it exists afterwards."""
+    path = Path(path) if path else Path(tempfile.mkdtemp(prefix=prefix))
+    path.mkdir(parents=True, exist_ok=True)
+    return path
+
+
+def _record_genome(logger, conn, md5_to_filename: dict[str, Path], filename: Path, md5: str, length: int, description: str) -> None:
+    """One input file into ``genomes``; a second file with the same content ends the run
+    (pyani_plus/public_cli.py:165-171)."""
+    if md5 in md5_to_filename:
+        dups = "\n" + "\n".join(sorted({str(md5_to_filename[md5]), str(filename)}))
+        sourmash_hip.log_sys_exit(logger, f"Multiple genomes with same MD5 checksum {md5}:{dups}")
+    md5_to_filename[md5] = filename
+    db_genome(conn, filename, md5, length, description)
+
+
+def _register_genomes(logger, conn, fasta_names: list[Path], mark) -> dict[str, Path]:
+    """Checksum, length and title of every file into ``genomes``, on host threads only (this process touches no GPU);
+    returns checksum -> file, in file order."""
+    infos, _arena = load_fasta_files(fasta_names)
+    md5_to_filename: dict[str, Path] = {}
+    for filename, info in zip(fasta_names, infos):
+        if info.status != 0:
+            sourmash_hip.log_sys_exit(logger, info.message)
+        _record_genome(logger, conn, md5_to_filename, filename, info.md5, info.length, info.description)
+    del _arena
+    mark("register_genomes")
+    return md5_to_filename
+
+
+def _record_run(state: _RunState, config: Configuration, fasta: Path, status: str, name: str | None, md5_to_filename: dict[str, Path]) -> None:
+    """The new run (``name`` None: "N genomes using <method>"), its genomes in file order, and the session that
+    persists its status."""
+    filename_to_md5 = {filename: md5 for md5, filename in md5_to_filename.items()}
+    if name is None:
+        name = f"{len(filename_to_md5)} genomes using {config.method}"
+    state.run = add_run(state.conn, config, " ".join(sys.argv), fasta, status, name, filename_to_md5)
+    state.session = Session(state.conn, state.run)
+
+
+def _incomplete_columns(conn, run: Run) -> list[str]:
+    """Subject genomes of the run with fewer than N comparisons recorded (the columns the reference's ``resume``
+    recomputes, pyani_plus/public_cli.py:243-261)."""
+    n = len(run.fasta_hashes)
+    have = dict(_select_run_comparisons(conn, run, "c.subject_hash, COUNT(*)", "GROUP BY c.subject_hash"))
+    return sorted(a.genome_hash for a in run.fasta_hashes if have.get(a.genome_hash, 0) < n)
+
+
+def _begin_missing(state: _RunState) -> tuple[int, list[str] | None] | None:
+    """What the database does not hold yet, for a new run (all of it) or a resumed one (the incomplete subject columns
+    only: rows that are there are never recomputed, nor -- INSERT OR IGNORE -- written twice).  Returns (rows there,
+    those columns or None for all) with the run marked "Running"; None when nothing is missing."""
+    run, method = state.run, state.run.configuration.method
+    n = len(run.fasta_hashes)
+    done = count_run_comparisons(state.conn, run)
+    if done == n * n:
+        state.logger.info("Database already has all %d=%d^2 %s comparisons", n * n, n, method)
+        return None
+    state.logger.info("Database already has %d of %d^2=%d %s comparisons, %d needed", done, n, n * n, method, n * n - done)
+    columns = None if done == 0 else _incomplete_columns(state.conn, run)
+    run.status = "Running"
+    state.session.commit()
+    return done, columns
+
+
+def _genome_lengths(state: _RunState) -> dict[str, int]:
+    """The column workers' ``query_hashes``: every genome of the run with its length."""
+    lengths = dict(state.conn.execute("SELECT genome_hash, length FROM genomes"))
+    return {a.genome_hash: lengths[a.genome_hash] for a in state.run.fasta_hashes}
+
+
+def _column_worker(state: _RunState, compute, json_file: Path, query_hashes: dict[str, int], subject: str, **kwargs) -> None:
+    """One call of a method's column worker, with the ten positional arguments the reference gives its own
+    (pyani_plus/private_cli.py:956-968); a return code ends the run."""
+    run = state.run
+    hash_to_filename = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
+    status = compute(
+        state.logger, state.tmp_dir, state.session, run, json_file, Path(run.fasta_directory), hash_to_filename,
+        {v: k for k, v in hash_to_filename.items()}, query_hashes, subject, engine=state.engine, **kwargs,
+    )  # fmt: skip
+    if status:
+        sourmash_hip.log_sys_exit(state.logger, f"Column worker failed with return code {status}")
+
+
+def _json_columns(state: _RunState, compute, query_hashes: dict[str, int], columns: list[str] | None, **kwargs) -> None:
+    """The reference's route: one column file per subject of ``columns`` (None: one file with all columns), each
+    imported as soon as it is written; an interrupted worker's partial file is the last."""
+    run = state.run
+    for c, subject in enumerate([""] if columns is None else columns):
+        json_file = state.tmp_dir / f"{run.configuration.method}.run_{run.run_id}.column_{c if subject else 0}.json"
+        _column_worker(state, compute, json_file, query_hashes, subject, **kwargs)
+        state.mark("pairs_and_column_file")
+        import_json_comparisons(state.logger, state.conn, json_file)
+        state.mark("import_column_file")
+        if run.status == "Worker interrupted":
+            break
+
+
+def _launch_workers(logger, gpus: int, spec: dict, work_dir: Path, engine_factory: str | None) -> list[dict]:
+    """``gpus`` worker processes on ``spec`` -> their reports; a failing rank's message ends the run."""
+    if engine_factory:
+        spec["engine_factory"] = engine_factory
+    try:
+        return launch.launch_workers(gpus, spec, work_dir)
+    except launch.WorkerFailure as err:
+        sourmash_hip.log_sys_exit(logger, str(err))
+
+
+def _place_blocks(hashes: list[str], blocks, out) -> int:
+    """Blocks ``(queries, subjects, one array per matrix of out)`` into the square matrices ``out`` (rows and columns in
+    ``hashes`` order): the blocks arrive in their makers' order, so every one is placed by checksum.  Returns the
+    number of cells placed."""
+    pos = {h: i for i, h in enumerate(hashes)}
+    cells = 0
+    for queries, subjects, *arrays in blocks:
+        at = np.ix_([pos[q] for q in queries], [pos[x] for x in subjects])
+        for matrix, block in zip(out, arrays):
+            matrix[at] = block
+        cells += len(queries) * len(subjects)
+    return cells
+
+
+def _ingest_direct(state: _RunState, hashes: list[str], cols: list[str], ident, cov, null, *, aln_length=None, sim_errors=None) -> _DirectResult:
+    """Matrices in host memory (rows = ``hashes``, columns = ``cols``, both sorted) -> comparison rows in index order,
+    the five cached matrices formatted on a second thread meanwhile (when the block is the whole square)."""
+    conn, run = state.conn, state.run
+    # synchronous=NORMAL for the bulk insert: a handful of fsyncs per transaction instead of one per page group, and
+    # -- unlike OFF -- no way for a crash of the machine to corrupt the user's multi-run database
+    conn.execute("PRAGMA synchronous=NORMAL")
+    conn.execute("PRAGMA cache_size=-1048576")
+    square = cols == hashes
+    with ThreadPoolExecutor(max_workers=1) as side:
+        formatting = side.submit(format_matrix_cache, hashes, ident, cov, null, aln_length=aln_length, sim_errors=sim_errors) if square else None
+        ingest_matrices(conn, run, hashes, cols, ident, cov, null, aln_length=aln_length, sim_errors=sim_errors)
+        formatted = formatting.result() if formatting is not None else None
+    conn.execute("PRAGMA synchronous=FULL")
+    state.mark("insert_rows")
+    if not square:
+        matrix_cache = _MatrixCache.REBUILD
+    else:
+        matrix_cache = _MatrixCache.TOO_BIG if formatted is None else _MatrixCache.FORMATTED
+    # what is in the database now, not what was handed to the insert (INSERT OR IGNORE reports nothing per row)
+    return _DirectResult(count_run_comparisons(conn, run), hashes, ident, cov, null, matrix_cache, formatted)
+
+
+def _finish_run(state: _RunState, result: _DirectResult | None) -> Run:
+    """Completion test, matrix cache, status "Done" (pyani_plus/public_cli.py:302-324).  ``result``: None after the
+    JSON route (and whenever the rows went in piecewise)."""
+    logger, conn, run = state.logger, state.conn, state.run
+    n = len(run.fasta_hashes)
+    done = count_run_comparisons(conn, run) if result is None else result.rows
+    if done != n * n and run.status == "Worker interrupted":
+        # the reference's worker ends with return code 0 after an interrupt, its partial results recorded and the run
+        # marked (pyani_plus/private_cli.py:1889-1902); ``resume`` completes such a run
+        logger.warning("Interrupted: %d of %d^2=%d %s comparisons recorded; the run can be resumed", done, n, n * n, run.configuration.method)
+        state.session.commit()
+        conn.close()
+        return run
+    if done != n * n:
+        sourmash_hip.log_sys_exit(logger, f"Only have {done} of {n}^2={n * n} {run.configuration.method} comparisons needed")
+    if result is None or result.matrix_cache is _MatrixCache.REBUILD:
+        cache_comparisons(conn, run)
+    elif result.matrix_cache is _MatrixCache.TOO_BIG:
+        _store_matrix_cache(conn, run, None)
+    else:
+        cache_matrices(conn, run, result.hashes, result.identity, result.cov_query, result.is_null, formatted=result.formatted)
+    state.mark("matrix_cache")
+    run.status = "Done"
+    state.session.commit()
+    conn.close()
+    return run
+
+
+# ------------------------------------------------------------------ sourmash-hip (pyani_plus/public_cli.py:115-329)
+def _compute_direct(state: _RunState, *, subjects: list[str] | None = None) -> _DirectResult:
+    """Subject tiles -> binary column files + matrices in host memory -> rows inserted in index order.
+    ``subjects``: only these subject columns (resuming a partial run); the matrices then hold those columns."""
+    logger, run = state.logger, state.run
+    config = run.configuration
+    hashes = sorted(a.genome_hash for a in run.fasta_hashes)
+    cols = hashes if subjects is None else sorted(subjects)
+    n, nc = len(hashes), len(cols)
+    ident = np.empty((n, nc), dtype=np.float64)
+    cov = np.empty((n, nc), dtype=np.float64)
+    null = np.empty((n, nc), dtype=bool)
+    sig_cache = sourmash_hip.sig_cache_dir(state.cache_dir, config.kmersize, config.extra)
+    col = 0
+    try:
+        for t, (queries, tile, t_cov, t_ident, t_null) in enumerate(
+            sourmash_hip.iter_sourmash_tiles(
+                logger, cols, hashes, sig_cache, kmersize=config.kmersize, scaled=sourmash_hip.parse_scaled(config.extra), engine=state.engine
+            )
+        ):
+            assert queries == hashes and tile == cols[col : col + len(tile)]
+            wire.save_tile(state.tmp_dir / f"{sourmash_hip.METHOD}.run_{run.run_id}.tile_{t}.npz", config, queries, tile, t_ident, t_cov, t_null)
+            ident[:, col : col + len(tile)] = t_ident
+            cov[:, col : col + len(tile)] = t_cov
+            null[:, col : col + len(tile)] = t_null
+            col += len(tile)
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, f"{sourmash_hip.METHOD} comparison", err)
+    state.mark("pairs_and_tile_files")
+    return _ingest_direct(state, hashes, cols, ident, cov, null)
 
 
 def _file_cost(path: Path) -> int:
@@ -550,36 +764,105 @@ def _file_cost(path: Path) -> int:
     return 4 * size if path.name.endswith(".gz") else size
 
 
-def _sharded_sourmash_tiles(logger, fasta: Path, fasta_names: list[Path], config: Configuration, cache_dir: Path, tmp_dir: Path,
-                            gpus: int, engine_factory: str | None, columns: list[str] | None = None):
+def _sharded_sourmash_tiles(state: _RunState, config: Configuration, fasta: Path, fasta_names: list[Path], gpus: int,
+                            columns: list[str] | None = None):
     """The multi-GPU form of "sketch everything, compare everything" (DESIGN.md section 6): ``gpus`` fresh worker
     processes (``launch.launch_workers`` -- started before this process has touched a GPU), each sketching a
     length-balanced share of the files, ONE all-gather of the sketches, each rank evaluating all queries against its
     own genomes as subject columns (``columns``, checksums: only those of them -- what a resumed run still needs).
-    Returns (metadata per file in file order, the ranks' tile files, the ranks' reports); None when the ranks were
-    interrupted (their columns need every rank's sketches: there is nothing partial to keep)."""
-    from . import launch
-    from .distributed import shard_bounds_by_cost
-
+    Returns (metadata per file in file order, the ranks' tile files); None when the ranks were interrupted (their
+    columns need every rank's sketches: there is nothing partial to keep)."""
     shards = shard_bounds_by_cost([max(1, _file_cost(p)) for p in fasta_names], gpus)
-    work_dir = tmp_dir / f"{sourmash_hip.METHOD}.workers"
+    work_dir = state.tmp_dir / f"{sourmash_hip.METHOD}.workers"
     spec = {
         "task": "sourmash", "fasta_dir": str(fasta), "fasta_files": [str(p) for p in fasta_names], "shards": shards,
-        "configuration": {k: getattr(config, k) for k in wire.CONFIG_FIELDS}, "cache": str(cache_dir), "work_dir": str(work_dir),
+        "configuration": {k: getattr(config, k) for k in wire.CONFIG_FIELDS}, "cache": str(state.cache_dir), "work_dir": str(work_dir),
     }  # fmt: skip
-    if engine_factory:
-        spec["engine_factory"] = engine_factory
     if columns is not None:
         spec["columns"] = list(columns)
-    try:
-        results = launch.launch_workers(gpus, spec, work_dir)
-    except launch.WorkerFailure as err:
-        sourmash_hip.log_sys_exit(logger, str(err))
+    results = _launch_workers(state.logger, gpus, spec, work_dir, state.engine_factory)
     if any(r.get("interrupted") for r in results):
         return None
     meta = [m for r in results for m in r["meta"]]
     assert [m["path"] for m in meta] == [str(p) for p in fasta_names]
-    return meta, [Path(r["tile"]) for r in results if r.get("tile")], results
+    return meta, [Path(r["tile"]) for r in results if r.get("tile")]
+
+
+def _run_sourmash_sharded(state: _RunState, config: Configuration, fasta: Path, fasta_names: list[Path], name: str | None) -> Run:
+    """A new run on worker processes.  The genomes' checksums come from the ranks, so the run is recorded after their
+    work, and the ranks' tiles -- all N^2 comparisons -- go in as one square."""
+    logger, mark = state.logger, state.mark
+    sharded = _sharded_sourmash_tiles(state, config, fasta, fasta_names, state.gpus)
+    if sharded is None:
+        sourmash_hip.log_sys_exit(logger, "Interrupted before the sketches were exchanged; no run was recorded")
+    meta, tile_files = sharded
+    md5_to_filename: dict[str, Path] = {}
+    for filename, m in zip(fasta_names, meta):
+        _record_genome(logger, state.conn, md5_to_filename, filename, m["md5"], m["length"], m["description"])
+    mark("workers_front_end_sketch_and_pairs")
+    _record_run(state, config, fasta, "Running", name, md5_to_filename)
+    hashes = sorted(md5_to_filename)
+    n = len(hashes)
+    ident = np.empty((n, n), dtype=np.float64)
+    cov = np.empty((n, n), dtype=np.float64)
+    null = np.empty((n, n), dtype=bool)
+    tiles = (_load_tile(logger, tile_file, config) for tile_file in tile_files)  # one in memory at a time
+    filled = _place_blocks(hashes, tiles, (ident, cov, null))  # every tile holds all n queries
+    if filled != n * n:
+        sourmash_hip.log_sys_exit(logger, f"The workers returned {filled // n} of {n} subject columns")
+    mark("assemble_tiles")
+    return _finish_run(state, _ingest_direct(state, hashes, hashes, ident, cov, null))
+
+
+def _resume_sourmash_sharded(state: _RunState, gpus: int) -> None:
+    """The missing columns of a recorded run through the same executor as the run itself (pyani_plus/public_cli.py:243-261
+    re-runs the missing columns through the workflow they came from): worker processes, one all-gather, and each rank's
+    tile cut down to the missing columns."""
+    logger, run = state.logger, state.run
+    fasta = Path(run.fasta_directory)
+    columns = _incomplete_columns(state.conn, run)
+    logger.info("%d subject columns to compute on %d worker processes", len(columns), gpus)
+    run.status = "Running"
+    state.session.commit()
+    names = [fasta / a.fasta_filename for a in sorted(run.fasta_hashes, key=lambda a: a.fasta_filename)]
+    sharded = _sharded_sourmash_tiles(state, run.configuration, fasta, names, gpus, columns=columns)
+    if sharded is None:
+        run.status = "Worker interrupted"
+        return
+    meta, tile_files = sharded
+    recorded = {a.fasta_filename: a.genome_hash for a in run.fasta_hashes}
+    for m in meta:  # the files must still be the ones the run was made from
+        if recorded[Path(m["path"]).name] != m["md5"]:
+            sourmash_hip.log_sys_exit(
+                logger, f"run-id {run.run_id} used {m['path']} with MD5 {recorded[Path(m['path']).name]} but the file now has MD5 {m['md5']}"
+            )
+    for tile_file in tile_files:
+        import_tile(logger, state.conn, run, tile_file)
+
+
+def _compute_missing_sourmash(state: _RunState, *, presketched=None) -> _DirectResult | None:
+    """The comparisons of a ``sourmash-hip`` run that the database does not hold yet: in this process through the
+    column worker's JSON files or directly from the tiles (``state.ingest``), or -- a resumed run with ``gpus`` > 1 --
+    on worker processes."""
+    conn, run = state.conn, state.run
+    n = len(run.fasta_hashes)
+    state.cache_dir = _work_dir(state.cache_dir, "pyani_hip_cache_")
+    gpus = max(1, min(int(state.gpus), n))
+    if gpus > 1 and count_run_comparisons(conn, run) != n * n:
+        _resume_sourmash_sharded(state, gpus)
+        return None
+    missing = _begin_missing(state)
+    if missing is None:
+        return None
+    _done, columns = missing
+    # the genomes were sketched while their checksums were taken: only the signature files remain to be written
+    for _ in sourmash_hip.prepare_genomes(state.logger, run, state.cache_dir, engine=state.engine, presketched=presketched):
+        pass
+    state.mark("signature_files")
+    if state.ingest == "direct":
+        return _compute_direct(state, subjects=columns)
+    _json_columns(state, sourmash_hip.compute_sourmash_hip, _genome_lengths(state), columns, cache=state.cache_dir)
+    return None
 
 
 def run_sourmash_hip(  # noqa: PLR0913
@@ -608,7 +891,7 @@ def run_sourmash_hip(  # noqa: PLR0913
     files (``wire.save_tile``) plus in-memory matrices, inserts the rows in index order straight from them and
     writes the matrix cache from memory: the form that stays feasible at N = 10^4 (10^8 rows).
     ``gpus`` > 1: the sketching and the comparisons are spread over that many worker processes, one per GPU
-    (``_sharded_sourmash_tiles``; the caller must not have initialised the GPU in this process); results always take
+    (``_run_sourmash_sharded``; the caller must not have initialised the GPU in this process); results always take
     the direct route.  ``timings`` (a dict) receives the wall seconds of the phases."""
     mark = _phase_clock(timings)
     logger = logger or logging.getLogger("pyani_plus_amd")
@@ -627,162 +910,273 @@ def run_sourmash_hip(  # noqa: PLR0913
     config = db_configuration(
         conn, sourmash_hip.METHOD, tool.exe_path.stem, tool.version, kmersize=kmersize, extra=f"scaled={scaled}"
     )
-    filename_to_md5: dict[Path, str] = {}
-    seen: dict[str, Path] = {}
-    own_cache = cache is None
-    cache_dir = Path(tempfile.mkdtemp(prefix="pyani_hip_cache_")) if own_cache else Path(cache)
-    cache_dir.mkdir(parents=True, exist_ok=True)
-    tmp_dir = Path(temp) if temp else Path(tempfile.mkdtemp(prefix="pyani_hip_"))
-    tmp_dir.mkdir(parents=True, exist_ok=True)
-    sig_dir = sourmash_hip.sig_cache_dir(cache_dir, kmersize, f"scaled={scaled}")
     gpus = min(int(gpus), len(fasta_names))
+    state = _RunState(logger, conn, _work_dir(temp), _work_dir(cache, "pyani_hip_cache_"), engine, gpus, engine_factory, ingest, mark)
     # PYANI_HIP_FORCE_WORKERS=1 sends even one GPU's worth of work through a worker process (RCCL with world size 1):
     # the multi-GPU code path on a single-GPU box
     if gpus > 1 or os.environ.get("PYANI_HIP_FORCE_WORKERS") == "1":
-        sharded = _sharded_sourmash_tiles(logger, fasta, fasta_names, config, cache_dir, tmp_dir, gpus, engine_factory)
-        if sharded is None:  # the genomes' checksums come from the ranks: no run has been recorded yet
-            sourmash_hip.log_sys_exit(logger, "Interrupted before the sketches were exchanged; no run was recorded")
-        meta, tile_files, _results = sharded
-        for filename, m in zip(fasta_names, meta):
-            if m["md5"] in seen:
-                _duplicate_md5_exit(logger, m["md5"], [seen[m["md5"]], filename])
-            seen[m["md5"]] = filename
-            filename_to_md5[filename] = m["md5"]
-            db_genome(conn, filename, m["md5"], m["length"], m["description"])
-        mark("workers_front_end_sketch_and_pairs")
-        run = add_run(
-            conn, config, " ".join(sys.argv), fasta, "Running",
-            f"{len(filename_to_md5)} genomes using {sourmash_hip.METHOD}" if name is None else name, filename_to_md5,
-        )  # fmt: skip
-        session = Session(conn, run)
-        n = len(filename_to_md5)
-        hashes = sorted(filename_to_md5.values())
-        pos = {h: i for i, h in enumerate(hashes)}
-        ident = np.empty((n, n), dtype=np.float64)
-        cov = np.empty((n, n), dtype=np.float64)
-        null = np.empty((n, n), dtype=bool)
-        filled = 0
-        for tile_file in tile_files:  # rows and columns arrive in the ranks' file order: place them by checksum
-            t_config, queries, subjects, t_ident, t_cov, t_null = wire.load_tile(tile_file)
-            for key in wire.CONFIG_FIELDS:
-                if t_config[key] != getattr(config, key):
-                    sourmash_hip.log_sys_exit(logger, f"Tile file {tile_file} configuration does not match the run ({key})")
-            rows = np.array([pos[q] for q in queries])
-            cols = np.array([pos[x] for x in subjects])
-            ident[np.ix_(rows, cols)] = t_ident
-            cov[np.ix_(rows, cols)] = t_cov
-            null[np.ix_(rows, cols)] = t_null
-            filled += len(cols)
-        if filled != n:
-            sourmash_hip.log_sys_exit(logger, f"The workers returned {filled} of {n} subject columns")
-        mark("assemble_tiles")
-        direct = _ingest_direct(conn, run, hashes, hashes, ident, cov, null, mark)
-        return _finish_run(logger, conn, session, run, direct, mark)
+        return _run_sourmash_sharded(state, config, fasta, fasta_names, name)
     # One pass over the files: md5 of the decompressed bytes, length, first title AND the sketches -- the host
     # front-end of the next batch of files runs while the device hashes the current one (sketch_fasta_batches).
+    sig_dir = sourmash_hip.sig_cache_dir(state.cache_dir, kmersize, f"scaled={scaled}")
+    md5_to_filename: dict[str, Path] = {}
     presketched: dict[str, np.ndarray] = {}
     try:
         for batch_paths, infos, sketches in sourmash_hip.sketch_fasta_batches(
             logger, fasta_names, kmersize=kmersize, scaled=scaled, engine=engine, needed=lambda info: not (sig_dir / f"{info.md5}.sig").is_file()
         ):
             for filename, info, mins in zip(batch_paths, infos, sketches):
-                md5 = info.md5
-                if md5 in seen:
-                    _duplicate_md5_exit(logger, md5, [k for k, v in filename_to_md5.items() if v == md5] + [filename])
-                seen[md5] = filename
-                filename_to_md5[filename] = md5
+                _record_genome(logger, conn, md5_to_filename, filename, info.md5, info.length, info.description)
                 if mins is not None:
-                    presketched[md5] = mins
-                db_genome(conn, filename, md5, info.length, info.description)
+                    presketched[info.md5] = mins
     except HipBackendError as err:
         sourmash_hip.backend_failure(logger, f"{sourmash_hip.METHOD} sketching", err)
     mark("fasta_front_end_and_sketch")
-    run = add_run(
-        conn, config, " ".join(sys.argv), fasta, "Initialising",
-        f"{len(filename_to_md5)} genomes using {sourmash_hip.METHOD}" if name is None else name, filename_to_md5,
-    )  # fmt: skip
-    session = Session(conn, run)
-    direct = _compute_missing(logger, conn, session, run, cache_dir, tmp_dir, engine, ingest, mark, presketched=presketched)
-    return _finish_run(logger, conn, session, run, direct, mark)
+    _record_run(state, config, fasta, "Initialising", name, md5_to_filename)
+    return _finish_run(state, _compute_missing_sourmash(state, presketched=presketched))
 
 
-def _incomplete_columns(conn, run: Run) -> list[str]:
-    """Subject genomes of the run with fewer than N comparisons recorded (the columns the reference's ``resume``
-    recomputes, pyani_plus/public_cli.py:243-261)."""
-    n = len(run.fasta_hashes)
-    have = dict(
-        conn.execute(
-            "SELECT c.subject_hash, COUNT(*) FROM comparisons c "
-            "JOIN runs_genomes q ON c.query_hash = q.genome_hash AND q.run_id = ? "
-            "JOIN runs_genomes s ON c.subject_hash = s.genome_hash AND s.run_id = ? "
-            "WHERE c.configuration_id = ? GROUP BY c.subject_hash",
-            (run.run_id, run.run_id, run.configuration_id),
-        )
-    )
-    return sorted(a.genome_hash for a in run.fasta_hashes if have.get(a.genome_hash, 0) < n)
+# ------------------------------------------------------------------ fastANI-hip (pyani_plus/public_cli.py:502-554)
+def _fastani_workers(state: _RunState, hashes: list[str], column_runs: list[tuple[int, int]], query_hashes: dict[str, int], gpus: int,
+                     query_batch: int | None) -> list[tuple]:
+    """The missing columns as reference ranges of ``pa_fragani`` spread over ``gpus`` worker processes.  Every rank
+    writes the reference's JSON column file, imported here on the JSON route; on the direct route the ranks' binary
+    tile files come back as blocks."""
+    logger, run = state.logger, state.run
+    direct = state.ingest == "direct"
+    # every rank maps all queries; what differs is the reference range, whose cost follows the subjects' lengths
+    pieces = [(a + i, a + i + 1) for a, b in column_runs for i in range(b - a)]
+    bounds = shard_bounds_by_cost([max(1, query_hashes[hashes[a]]) for a, _ in pieces], gpus)
+    column_ranges = []
+    for a, b in bounds:
+        if a == b:
+            column_ranges.append((0, 0))
+            continue
+        lo, hi = pieces[a][0], pieces[b - 1][1]
+        if hi - lo != b - a:  # the rank's share is not one range (scattered missing columns): widen it, rows are idempotent
+            logger.debug("rank share %s widened to columns %d..%d", (a, b), lo, hi)
+        column_ranges.append((lo, hi))
+    work_dir = state.tmp_dir / f"{fastani_hip.METHOD}.run_{run.run_id}.workers"
+    spec = {
+        "task": "fastani", "run_id": run.run_id, "fasta_dir": str(Path(run.fasta_directory)),
+        "hash_to_filename": {a.genome_hash: a.fasta_filename for a in run.fasta_hashes},
+        "query_hashes": query_hashes, "column_ranges": column_ranges, "work_dir": str(work_dir), "tiles": direct,
+        "configuration": {**{k: getattr(run.configuration, k) for k in wire.CONFIG_FIELDS}, "configuration_id": run.configuration_id},
+    }  # fmt: skip
+    if query_batch:
+        spec["query_batch"] = int(query_batch)
+    results = _launch_workers(logger, gpus, spec, work_dir, state.engine_factory)
+    state.mark("workers")
+    blocks: list[tuple] = []
+    for rank, r in enumerate(results):
+        if r.get("interrupted"):
+            run.status = "Worker interrupted"
+        if direct:
+            for tile in r.get("tiles") or sorted(str(t) for t in work_dir.glob(f"{fastani_hip.METHOD}.rank_{rank}.tile_*.npz")):
+                try:
+                    _cfg, queries, subjects, ident, cov, null, aln, sim = wire.load_tile(Path(tile), with_proxies=True)
+                except (ValueError, OSError, KeyError, zipfile.BadZipFile) as err:
+                    # tiles are written under another name and renamed: a rank that ended while it wrote (interrupted, or
+                    # ended by this process) may leave an unreadable one, and the other ranks' batches still go in; from
+                    # a rank that reported success it is damage, and the run must not end quietly incomplete
+                    if not r.get("interrupted"):
+                        raise
+                    logger.warning("Skipping unreadable tile file %s of rank %d: %s", tile, rank, err)
+                    continue
+                blocks.append((queries, subjects, ident, aln, sim, cov, null))
+        else:
+            # the rank's column file: a complete JSON document after every finished query batch, also when the rank
+            # was interrupted (or ended by this process while it waited) and reported nothing about it
+            c0, c1 = column_ranges[rank]
+            json_file = Path(r["json"]) if r.get("json") else work_dir / f"{fastani_hip.METHOD}.run_{run.run_id}.columns_{c0 + 1}_{c1}.json"
+            if c0 != c1 and json_file.is_file():
+                try:
+                    import_json_comparisons(logger, state.conn, json_file)
+                except (ValueError, OSError) as err:  # a column file cut short by the end of its rank (it is rewritten whole after every batch)
+                    if not r.get("interrupted"):
+                        raise
+                    logger.warning("Skipping unreadable column file %s of rank %d: %s", json_file, rank, err)
+    if run.status == "Worker interrupted":
+        state.session.commit()
+    return blocks
 
 
-def _compute_missing(logger, conn, session, run: Run, cache_dir: Path, tmp_dir: Path, engine, ingest: str, mark, *, presketched=None):
-    """The comparisons the database does not hold yet, for a new run (all of them) or a resumed one (the incomplete
-    subject columns only: rows that are there are never recomputed, nor -- INSERT OR IGNORE -- written twice)."""
-    n = len(run.fasta_hashes)
-    done = count_run_comparisons(conn, run)
-    if done == n * n:
-        logger.info("Database already has all %d=%d^2 %s comparisons", n * n, n, sourmash_hip.METHOD)
-        return None
-    logger.info("Database already has %d of %d^2=%d %s comparisons, %d needed", done, n, n * n, sourmash_hip.METHOD, n * n - done)
-    columns = None if done == 0 else _incomplete_columns(conn, run)
-    run.status = "Running"
-    session.commit()
-    # the genomes were sketched while their checksums were taken: only the signature files remain to be written
-    for _ in sourmash_hip.prepare_genomes(logger, run, cache_dir, engine=engine, presketched=presketched):
-        pass
-    mark("signature_files")
-    hash_to_filename = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
-    if ingest == "direct":
-        return _compute_direct(logger, conn, run, cache_dir, tmp_dir, engine, mark, subjects=columns)
-    lengths = dict(conn.execute("SELECT genome_hash, length FROM genomes"))
-    for c, subject in enumerate([""] if columns is None else columns):
-        json_file = tmp_dir / f"{sourmash_hip.METHOD}.run_{run.run_id}.column_{c if subject else 0}.json"
-        status = sourmash_hip.compute_sourmash_hip(
-            logger, tmp_dir, session, run, json_file, Path(run.fasta_directory), hash_to_filename,
-            {v: k for k, v in hash_to_filename.items()}, {h: lengths[h] for h in hash_to_filename}, subject,
-            cache=cache_dir, engine=engine,
+def _fastani_in_process(state: _RunState, column_runs: list[tuple[int, int]], query_hashes: dict[str, int], query_batch: int | None) -> list[tuple]:
+    """The missing columns in this process: one call of the column worker per run of them.  Its JSON column file is
+    imported on the JSON route; on the direct route its batches are collected as blocks."""
+    run = state.run
+    direct = state.ingest == "direct"
+    if state.engine is None and state.engine_factory:  # the workers' engine, when their work has shrunk to one process's worth
+        module, _, attr = state.engine_factory.partition(":")
+        state.engine = getattr(importlib.import_module(module), attr)()
+    blocks: list[tuple] = []
+    for a, b in column_runs:
+        json_file = state.tmp_dir / f"{fastani_hip.METHOD}.run_{run.run_id}.columns_{a + 1}_{b}.json"
+        _column_worker(
+            state, fastani_hip.compute_fastani_hip, json_file, query_hashes, "", subject_range=(a, b),
+            on_block=(lambda *blk: blocks.append(blk)) if direct else None, **({"query_batch": int(query_batch)} if query_batch else {}),
         )  # fmt: skip
-        if status:
-            sourmash_hip.log_sys_exit(logger, f"Column worker failed with return code {status}")
-        mark("pairs_and_column_file")
-        import_json_comparisons(logger, conn, json_file)
-        mark("import_column_file")
+        if not direct:
+            import_json_comparisons(state.logger, state.conn, json_file)
         if run.status == "Worker interrupted":
             break
+    state.mark("worker")
+    return blocks
+
+
+def _ingest_fastani_blocks(state: _RunState, hashes: list[str], blocks: list[tuple], new_run: bool) -> _DirectResult | None:
+    """Blocks ``(queries, subjects, identity, aln_length, sim_errors, cov_query, is_null)`` -> comparison rows.  All of a
+    new run: one square, rows in index order, matrix cache from memory; otherwise block by block."""
+    conn, run = state.conn, state.run
+    n = len(hashes)
+    if new_run and run.status != "Worker interrupted" and sum(len(b[0]) * len(b[1]) for b in blocks) == n * n:
+        ident = np.full((n, n), np.nan)
+        cov = np.full((n, n), np.nan)
+        null = np.ones((n, n), dtype=bool)
+        aln = np.zeros((n, n), dtype=np.int64)
+        sim = np.zeros((n, n), dtype=np.int64)
+        _place_blocks(hashes, blocks, (ident, aln, sim, cov, null))
+        return _ingest_direct(state, hashes, hashes, ident, cov, null, aln_length=aln, sim_errors=sim)
+    for queries, subjects, ident, aln, sim, cov, null in blocks:
+        ingest_matrices(conn, run, queries, subjects, ident, cov, null, aln_length=aln, sim_errors=sim)
+    if run.status != "Worker interrupted":  # whatever blocks of an interrupted run arrived are in; the run stays partial
+        state.mark("insert_rows")
     return None
 
 
-def _finish_run(logger, conn, session, run: Run, direct, mark) -> Run:
-    """Completion test, matrix cache, status "Done" (pyani_plus/public_cli.py:302-324)."""
-    n = len(run.fasta_hashes)
-    done = count_run_comparisons(conn, run) if direct is None else direct[0]
-    if done != n * n and run.status == "Worker interrupted":
-        # the reference's worker ends with return code 0 after an interrupt, its partial results recorded and the run
-        # marked (pyani_plus/private_cli.py:1889-1902); ``resume`` completes such a run
-        logger.warning("Interrupted: %d of %d^2=%d %s comparisons recorded; the run can be resumed", done, n, n * n, run.configuration.method)
-        session.commit()
-        conn.close()
-        return run
-    if done != n * n:
-        sourmash_hip.log_sys_exit(logger, f"Only have {done} of {n}^2={n * n} {run.configuration.method} comparisons needed")
-    if direct is None or direct[5] is False:  # JSON route, or a resumed run that only holds some columns in memory
-        cache_comparisons(conn, run)
-    elif direct[5] is None:
-        _store_matrix_cache(conn, run, None)
+def _compute_missing_fastani(state: _RunState, *, query_batch: int | None = None) -> _DirectResult | None:
+    """The incomplete subject columns of a ``fastANI-hip`` run: in this process (one call per run of missing columns; a
+    new run is one call for all of them), or as reference ranges of ``pa_fragani`` spread over ``gpus`` worker
+    processes -- the reference's own one-process-per-column layout (pyani_plus/public_cli.py:236-261) with a GPU per
+    process and no exchange between them.  Every worker writes the reference's JSON column file.  ``ingest="json"``:
+    this process imports those files, what the reference's parent does (pyani_plus/workflows/__init__.py:75-87);
+    ``"direct"``: the rows go from the result arrays (binary tile files between processes) straight into the table.
+    Returns ``_ingest_direct``'s result when a new run went in directly (matrix cache from memory), else None."""
+    missing = _begin_missing(state)
+    if missing is None:
+        return None
+    done, columns = missing
+    hashes = sorted(a.genome_hash for a in state.run.fasta_hashes)
+    pos = {h: i for i, h in enumerate(hashes)}
+    # contiguous runs of missing columns; a new run is one run of all columns
+    column_runs: list[tuple[int, int]] = []
+    for i in (pos[c] for c in (hashes if columns is None else columns)):
+        if column_runs and column_runs[-1][1] == i:
+            column_runs[-1] = (column_runs[-1][0], i + 1)
+        else:
+            column_runs.append((i, i + 1))
+    query_hashes = _genome_lengths(state)
+    gpus = max(1, min(int(state.gpus), len(hashes if columns is None else columns)))
+    if gpus > 1:
+        blocks = _fastani_workers(state, hashes, column_runs, query_hashes, gpus, query_batch)
     else:
-        cache_matrices(conn, run, *direct[1:5], formatted=direct[5])
-    mark("matrix_cache")
-    run.status = "Done"
-    session.commit()
-    conn.close()
-    return run
+        blocks = _fastani_in_process(state, column_runs, query_hashes, query_batch)
+    if state.ingest != "direct":
+        state.mark("import_column_files")
+        return None
+    return _ingest_fastani_blocks(state, hashes, blocks, new_run=done == 0)
+
+
+def run_fastani_hip(  # noqa: PLR0913
+    fasta: Path,
+    database: Path | str,
+    *,
+    name: str | None = None,
+    kmersize: int | None = None,
+    fragsize: int | None = None,
+    minmatch: float | None = None,
+    temp: Path | None = None,
+    logger: logging.Logger | None = None,
+    engine=None,
+    gpus: int = 1,
+    engine_factory: str | None = None,
+    timings: dict | None = None,
+    ingest: str = "json",
+    query_batch: int | None = None,
+) -> Run:
+    """FASTA directory -> database with all N^2 fragment-ANI comparisons and cached matrices: counterpart of
+    ``pyani-plus fastani <fasta> -d <db> --create-db`` (pyani_plus/public_cli.py:502-554) with one in-process call --
+    or ``gpus`` worker processes, each mapping all queries against its own range of subject columns -- in place of the
+    snakemake jobs.  Defaults as pyani_plus/methods/fastani.py:27-30.  The registration pass (checksum, length and
+    title of every file) runs on host threads only, so this process never touches a GPU when ``gpus`` > 1."""
+    mark = _phase_clock(timings)
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    kmersize = fastani_hip.KMER_SIZE if kmersize is None else int(kmersize)
+    fragsize = fastani_hip.FRAG_LEN if fragsize is None else int(fragsize)
+    minmatch = fastani_hip.MIN_FRACTION if minmatch is None else float(minmatch)
+    fasta = Path(fasta)
+    fasta_names = check_fasta(logger, fasta)
+    tool = fastani_hip.get_fastani_hip()
+    conn = connect_to_db(database)
+    config = db_configuration(conn, fastani_hip.METHOD, tool.exe_path.stem, tool.version, fragsize=fragsize, kmersize=kmersize, minmatch=minmatch)
+    md5_to_filename = _register_genomes(logger, conn, fasta_names, mark)
+    state = _RunState(logger, conn, _work_dir(temp), None, engine, gpus, engine_factory, ingest, mark)
+    _record_run(state, config, fasta, "Initialising", name, md5_to_filename)
+    if ingest not in {"json", "direct"}:
+        sourmash_hip.log_sys_exit(logger, f"ingest must be 'json' or 'direct', not {ingest!r}")
+    return _finish_run(state, _compute_missing_fastani(state, query_batch=query_batch))
+
+
+# ------------------------------------------------------------------ external-alignment-hip (pyani_plus/public_cli.py:642-699)
+def _one_gpu_only(logger, gpus: int) -> None:
+    if int(gpus) != 1:
+        sourmash_hip.log_sys_exit(logger, f"{external_alignment_hip.METHOD} runs on one GPU; --gpus {gpus} is not supported")
+
+
+def _compute_missing_external_alignment(state: _RunState) -> None:
+    """The subject columns the database does not complete yet, through the column worker and its JSON file: all of them
+    in one device call for a new run, the incomplete ones (one call each, as the reference's resume) otherwise."""
+    _one_gpu_only(state.logger, state.gpus)
+    missing = _begin_missing(state)
+    if missing is not None:
+        query_hashes = {a.genome_hash: 0 for a in state.run.fasta_hashes}
+        _json_columns(state, external_alignment_hip.compute_external_alignment_hip, query_hashes, missing[1])
+
+
+def run_external_alignment_hip(  # noqa: PLR0913
+    fasta: Path,
+    database: Path | str,
+    *,
+    alignment: Path,
+    label: str = "stem",
+    name: str | None = None,
+    temp: Path | None = None,
+    logger: logging.Logger | None = None,
+    engine=None,
+    gpus: int = 1,
+    timings: dict | None = None,
+) -> Run:
+    """FASTA directory + its MSA -> database with all N^2 external-alignment comparisons and cached matrices: counterpart
+    of ``pyani-plus external-alignment <fasta> -d <db> --alignment <msa> --label <label> --create-db``
+    (pyani_plus/public_cli.py:642-699).  As there, the configuration records the MSA's md5 and its file name only: the
+    worker looks for the file next to the database.  One GPU: ``gpus`` > 1 is refused."""
+    mark = _phase_clock(timings)
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    _one_gpu_only(logger, gpus)
+    if label not in {"md5", "filename", "stem"}:
+        sourmash_hip.log_sys_exit(logger, f"label must be md5, filename or stem, not {label!r}")
+    alignment = Path(alignment)
+    if not alignment.is_file():
+        sourmash_hip.log_sys_exit(logger, f"Missing alignment file {alignment}")
+    fasta = Path(fasta)
+    fasta_names = check_fasta(logger, fasta)
+    tool = external_alignment_hip.get_external_alignment_hip()
+    with alignment.open("rb") as handle:
+        aln_md5 = hashlib.file_digest(handle, "md5").hexdigest() if hasattr(hashlib, "file_digest") else hashlib.md5(handle.read()).hexdigest()
+    conn = connect_to_db(database)
+    config = db_configuration(conn, external_alignment_hip.METHOD, tool.exe_path.stem, tool.version,
+                              extra=external_alignment_hip.make_extra(aln_md5, label, alignment))  # fmt: skip
+    md5_to_filename = _register_genomes(logger, conn, fasta_names, mark)
+    state = _RunState(logger, conn, _work_dir(temp), None, engine, gpus, None, "json", mark)
+    _record_run(state, config, fasta, "Initialising", f"Import of {alignment.name}" if name is None else name, md5_to_filename)
+    return _finish_run(state, _compute_missing_external_alignment(state))
+
+
+_METHODS = {  # method name -> (its tool, its "compute what is missing"): what ``resume`` needs to know of a method
+    sourmash_hip.METHOD: (sourmash_hip.get_sourmash_hip, _compute_missing_sourmash),
+    fastani_hip.METHOD: (fastani_hip.get_fastani_hip, _compute_missing_fastani),
+    external_alignment_hip.METHOD: (external_alignment_hip.get_external_alignment_hip, _compute_missing_external_alignment),
+}
 
 
 # ------------------------------------------------------------------ resume (pyani_plus/public_cli.py:702-828)
@@ -797,27 +1191,16 @@ def resume(database: Path | str, *, run_id: int | None = None, cache: Path | Non
     logger = logger or logging.getLogger("pyani_plus_amd")
     if str(database) == ":memory:" or not Path(database).is_file():
         sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
-    conn = connect_to_db(database)
-    if run_id is None:
-        row = conn.execute("SELECT MAX(run_id) FROM runs").fetchone()
-        if row is None or row[0] is None:
-            sourmash_hip.log_sys_exit(logger, f"Database {database} contains no runs.")
-        run_id = row[0]
-        logger.info("Resuming run-id %d", run_id)
-    try:
-        run = load_run(conn, run_id)
-    except ValueError:
-        sourmash_hip.log_sys_exit(logger, f"Database {database} has no run-id {run_id}.")
-    config = run.configuration
+    conn, run = _open_run(logger, database, run_id, "Resuming")
+    run_id, config = run.run_id, run.configuration
     n = len(run.fasta_hashes)
     logger.info("This is a %s run on %d genomes, using %s version %s", config.method, n, config.program, config.version)
     if not n:
         sourmash_hip.log_sys_exit(logger, f"No genomes recorded for run-id {run_id}, cannot resume.")
-    from .methods import external_alignment_hip, fastani_hip
-
-    if config.method not in {sourmash_hip.METHOD, fastani_hip.METHOD, external_alignment_hip.METHOD}:
+    if config.method not in _METHODS:
         sourmash_hip.log_sys_exit(logger, f"Unknown method {config.method} for run-id {run_id} in {database}")
-    tool = sourmash_hip.get_sourmash_hip()
+    get_tool, compute_missing = _METHODS[config.method]
+    tool = get_tool()
     if tool.exe_path.stem != config.program or tool.version != config.version:
         sourmash_hip.log_sys_exit(
             logger,
@@ -834,54 +1217,11 @@ def resume(database: Path | str, *, run_id: int | None = None, cache: Path | Non
     session = Session(conn, run)
     run.status = "Resuming"
     session.commit()
-    mark = _phase_clock(None)
-    tmp_dir = Path(temp) if temp else Path(tempfile.mkdtemp(prefix="pyani_hip_"))
-    tmp_dir.mkdir(parents=True, exist_ok=True)
-    if config.method == external_alignment_hip.METHOD:
-        if int(gpus) != 1:
-            sourmash_hip.log_sys_exit(logger, f"{config.method} runs on one GPU; --gpus {gpus} is not supported")
-        _compute_missing_external_alignment(logger, conn, session, run, tmp_dir, engine, mark)
-        return _finish_run(logger, conn, session, run, None, mark)
-    if config.method == fastani_hip.METHOD:
-        direct = _compute_missing_fastani(logger, conn, session, run, tmp_dir, engine, gpus, engine_factory, ingest, mark)
-        return _finish_run(logger, conn, session, run, direct, mark)
-    cache_dir = Path(tempfile.mkdtemp(prefix="pyani_hip_cache_")) if cache is None else Path(cache)
-    cache_dir.mkdir(parents=True, exist_ok=True)
-    gpus = max(1, min(int(gpus), n))
-    if gpus > 1 and count_run_comparisons(conn, run) != n * n:
-        # the same executor as the run itself (pyani_plus/public_cli.py:243-261 re-runs the missing columns through the
-        # workflow they came from): worker processes, one all-gather, and each rank's tile cut down to the missing columns
-        columns = _incomplete_columns(conn, run)
-        logger.info("%d subject columns to compute on %d worker processes", len(columns), gpus)
-        run.status = "Running"
-        session.commit()
-        names = [fasta / a.fasta_filename for a in sorted(run.fasta_hashes, key=lambda a: a.fasta_filename)]
-        sharded = _sharded_sourmash_tiles(logger, fasta, names, config, cache_dir, tmp_dir, gpus, engine_factory, columns=columns)
-        if sharded is None:
-            run.status = "Worker interrupted"
-            return _finish_run(logger, conn, session, run, None, mark)
-        meta, tile_files, _results = sharded
-        recorded = {a.fasta_filename: a.genome_hash for a in run.fasta_hashes}
-        for m in meta:  # the files must still be the ones the run was made from
-            if recorded[Path(m["path"]).name] != m["md5"]:
-                sourmash_hip.log_sys_exit(
-                    logger, f"run-id {run_id} used {m['path']} with MD5 {recorded[Path(m['path']).name]} but the file now has MD5 {m['md5']}"
-                )
-        for tile_file in tile_files:
-            import_tile(logger, conn, run, tile_file)
-        return _finish_run(logger, conn, session, run, None, mark)
-    direct = _compute_missing(logger, conn, session, run, cache_dir, tmp_dir, engine, ingest, mark)
-    return _finish_run(logger, conn, session, run, direct, mark)
+    state = _RunState(logger, conn, _work_dir(temp), cache, engine, gpus, engine_factory, ingest, _phase_clock(None), run, session)
+    return _finish_run(state, compute_missing(state))
 
 
 # ------------------------------------------------------------------ export-run (pyani_plus/public_cli.py:974-1091)
-def filename_stem(filename: str) -> str:
-    """The file name without directory, ``.gz`` and extension (pyani_plus/utils.py:93-105)."""
-    if "/" in filename:
-        filename = filename.rsplit("/", 1)[1]
-    return Path(filename[:-3]).stem if filename.endswith(".gz") else Path(filename).stem
-
-
 def export_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem",
                logger: logging.Logger | None = None) -> list[Path]:
     """Write ``<method>_run_<id>.tsv`` (long form) and the six matrices ``<method>_{identity,aln_lengths,sim_errors,
@@ -889,9 +1229,6 @@ def export_run(database: Path | str, outdir: Path, *, run_id: int | None = None,
     database: long form in ``Run.comparisons()`` order with ``NA`` for NULL and Python ``str(float)``; matrices from
     the cached ``df_*`` strings through pandas ``to_csv(sep="\t")``, labelled by ``md5``, ``filename`` or ``stem`` and
     sorted by label (db_orm.py:590-624).  A partial run gets the long form only and then the reference's error."""
-    import math
-    from io import StringIO
-
     import pandas as pd
 
     logger = logger or logging.getLogger("pyani_plus_amd")
@@ -901,17 +1238,8 @@ def export_run(database: Path | str, outdir: Path, *, run_id: int | None = None,
     if not outdir.is_dir():
         logger.warning("Output directory %s does not exist, making it.", outdir)
         outdir.mkdir()
-    conn = connect_to_db(database)
-    if run_id is None:
-        row = conn.execute("SELECT MAX(run_id) FROM runs").fetchone()
-        if row is None or row[0] is None:
-            sourmash_hip.log_sys_exit(logger, f"Database {database} contains no runs.")
-        run_id = row[0]
-        logger.info("Exporting run-id %d", run_id)
-    try:
-        run = load_run(conn, run_id)
-    except ValueError:
-        sourmash_hip.log_sys_exit(logger, f"Database {database} has no run-id {run_id}.")
+    conn, run = _open_run(logger, database, run_id, "Exporting")
+    run_id = run.run_id
     if not run.fasta_hashes:
         sourmash_hip.log_sys_exit(logger, f"Run-id {run_id} has no genomes")
     method = run.configuration.method
@@ -928,12 +1256,8 @@ def export_run(database: Path | str, outdir: Path, *, run_id: int | None = None,
         return "NA" if value is None else str(value)
 
     written = [outdir / f"{method}_run_{run_id}.tsv"]
-    rows = conn.execute(
-        "SELECT c.query_hash, c.subject_hash, c.identity, c.cov_query, c.cov_subject, c.aln_length, c.sim_errors FROM comparisons c "
-        "JOIN runs_genomes rq ON c.query_hash = rq.genome_hash AND rq.run_id = ? "
-        "JOIN runs_genomes rs ON c.subject_hash = rs.genome_hash AND rs.run_id = ? WHERE c.configuration_id = ? "
-        "ORDER BY c.comparison_id",
-        (run.run_id, run.run_id, run.configuration_id),
+    rows = _select_run_comparisons(
+        conn, run, "c.query_hash, c.subject_hash, c.identity, c.cov_query, c.cov_subject, c.aln_length, c.sim_errors", "ORDER BY c.comparison_id"
     ).fetchall()
     with written[0].open("w") as handle:
         handle.write("#Query\tSubject\tIdentity\tQuery-Cov\tSubject-Cov\tHadamard\ttANI\tAlign-Len\tSim-Errors\n")
@@ -971,298 +1295,6 @@ def export_run(database: Path | str, outdir: Path, *, run_id: int | None = None,
     return written
 
 
-# ------------------------------------------------------------------ the fragment-ANI run (pyani_plus/public_cli.py:502-554)
-def _compute_missing_fastani(logger, conn, session, run: Run, tmp_dir: Path, engine, gpus: int, engine_factory: str | None,
-                             ingest: str = "json", mark=None, query_batch: int | None = None):
-    """The incomplete subject columns of a ``fastANI-hip`` run: in this process (one call per run of missing columns; a
-    new run is one call for all of them), or as reference ranges of ``pa_fragani`` spread over ``gpus`` worker
-    processes -- the reference's own one-process-per-column layout (pyani_plus/public_cli.py:236-261) with a GPU per
-    process and no exchange between them.  Every worker writes the reference's JSON column file.  ``ingest="json"``:
-    this process imports those files, what the reference's parent does (pyani_plus/workflows/__init__.py:75-87);
-    ``"direct"``: the rows go from the result arrays (binary tile files between processes) straight into the table.
-    Returns the ``_ingest_direct`` tuple when a new run went in directly (matrix cache from memory), else None."""
-    from .methods import fastani_hip
-
-    mark = mark or (lambda _name: None)
-    n = len(run.fasta_hashes)
-    done = count_run_comparisons(conn, run)
-    if done == n * n:
-        logger.info("Database already has all %d=%d^2 %s comparisons", n * n, n, fastani_hip.METHOD)
-        return None
-    logger.info("Database already has %d of %d^2=%d %s comparisons, %d needed", done, n, n * n, fastani_hip.METHOD, n * n - done)
-    hashes = sorted(a.genome_hash for a in run.fasta_hashes)
-    columns = hashes if done == 0 else _incomplete_columns(conn, run)
-    run.status = "Running"
-    session.commit()
-    hash_to_filename = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
-    lengths = dict(conn.execute("SELECT genome_hash, length FROM genomes"))
-    query_hashes = {h: lengths[h] for h in hash_to_filename}
-    fasta_dir = Path(run.fasta_directory)
-    col_idx = [hashes.index(c) for c in columns]
-    # contiguous runs of missing columns; a new run is one run of all columns
-    runs_of_columns: list[tuple[int, int]] = []
-    for i in col_idx:
-        if runs_of_columns and runs_of_columns[-1][1] == i:
-            runs_of_columns[-1] = (runs_of_columns[-1][0], i + 1)
-        else:
-            runs_of_columns.append((i, i + 1))
-    direct = ingest == "direct"
-    blocks: list[tuple] = []  # (queries, subjects, identity, aln_length, sim_errors, cov_query, is_null) per block, direct route
-    gpus = max(1, min(int(gpus), len(columns)))
-    if gpus > 1:
-        from . import launch
-        from .distributed import shard_bounds_by_cost
-
-        # every rank maps all queries; what differs is the reference range, whose cost follows the subjects' lengths
-        pieces = [(a + i, a + i + 1) for a, b in runs_of_columns for i in range(b - a)]
-        bounds = shard_bounds_by_cost([max(1, lengths[hashes[a]]) for a, _ in pieces], gpus)
-        column_ranges = []
-        for a, b in bounds:
-            if a == b:
-                column_ranges.append((0, 0))
-                continue
-            lo, hi = pieces[a][0], pieces[b - 1][1]
-            if hi - lo != b - a:  # the rank's share is not one range (scattered missing columns): widen it, rows are idempotent
-                logger.debug("rank share %s widened to columns %d..%d", (a, b), lo, hi)
-            column_ranges.append((lo, hi))
-        work_dir = tmp_dir / f"{fastani_hip.METHOD}.run_{run.run_id}.workers"
-        spec = {
-            "task": "fastani", "run_id": run.run_id, "fasta_dir": str(fasta_dir), "hash_to_filename": hash_to_filename,
-            "query_hashes": query_hashes, "column_ranges": column_ranges, "work_dir": str(work_dir), "tiles": direct,
-            "configuration": {**{k: getattr(run.configuration, k) for k in wire.CONFIG_FIELDS}, "configuration_id": run.configuration_id},
-        }  # fmt: skip
-        if engine_factory:
-            spec["engine_factory"] = engine_factory
-        if query_batch:
-            spec["query_batch"] = int(query_batch)
-        try:
-            results = launch.launch_workers(gpus, spec, work_dir)
-        except launch.WorkerFailure as err:
-            sourmash_hip.log_sys_exit(logger, str(err))
-        mark("workers")
-        for rank, r in enumerate(results):
-            if r.get("interrupted"):
-                run.status = "Worker interrupted"
-            if direct:
-                for tile in r.get("tiles") or sorted(str(t) for t in work_dir.glob(f"{fastani_hip.METHOD}.rank_{rank}.tile_*.npz")):
-                    try:
-                        _cfg, queries, subjects, ident, cov, null, aln, sim = wire.load_tile(Path(tile), with_proxies=True)
-                    except (ValueError, OSError, KeyError, zipfile.BadZipFile) as err:
-                        # tiles are written under another name and renamed: a rank that ended while it wrote (interrupted, or
-                        # ended by this process) may leave an unreadable one, and the other ranks' batches still go in; from
-                        # a rank that reported success it is damage, and the run must not end quietly incomplete
-                        if not r.get("interrupted"):
-                            raise
-                        logger.warning("Skipping unreadable tile file %s of rank %d: %s", tile, rank, err)
-                        continue
-                    blocks.append((queries, subjects, ident, aln, sim, cov, null))
-            else:
-                # the rank's column file: a complete JSON document after every finished query batch, also when the rank
-                # was interrupted (or ended by this process while it waited) and reported nothing about it
-                c0, c1 = column_ranges[rank]
-                json_file = Path(r["json"]) if r.get("json") else work_dir / f"{fastani_hip.METHOD}.run_{run.run_id}.columns_{c0 + 1}_{c1}.json"
-                if c0 != c1 and json_file.is_file():
-                    try:
-                        import_json_comparisons(logger, conn, json_file)
-                    except (ValueError, OSError) as err:  # a column file cut short by the end of its rank (it is rewritten whole after every batch)
-                        if not r.get("interrupted"):
-                            raise
-                        logger.warning("Skipping unreadable column file %s of rank %d: %s", json_file, rank, err)
-        if run.status == "Worker interrupted":
-            session.commit()
-    else:
-        if engine is None and engine_factory:  # the workers' engine, when their work has shrunk to one process's worth
-            import importlib
-
-            module, _, attr = engine_factory.partition(":")
-            engine = getattr(importlib.import_module(module), attr)()
-        for a, b in runs_of_columns:
-            json_file = tmp_dir / f"{fastani_hip.METHOD}.run_{run.run_id}.columns_{a + 1}_{b}.json"
-            status = fastani_hip.compute_fastani_hip(
-                logger, tmp_dir, session, run, json_file, fasta_dir, hash_to_filename, {v: k for k, v in hash_to_filename.items()},
-                query_hashes, "", engine=engine, subject_range=(a, b), on_block=(lambda *blk: blocks.append(blk)) if direct else None,
-                **({"query_batch": int(query_batch)} if query_batch else {}),
-            )  # fmt: skip
-            if status:
-                sourmash_hip.log_sys_exit(logger, f"Column worker failed with return code {status}")
-            if not direct:
-                import_json_comparisons(logger, conn, json_file)
-            if run.status == "Worker interrupted":
-                break
-        mark("worker")
-    if not direct:
-        mark("import_column_files")
-        return None
-    if run.status == "Worker interrupted":  # whatever blocks arrived go in as they are; the run stays partial
-        for queries, subjects, ident, aln, sim, cov, null in blocks:
-            ingest_matrices(conn, run, queries, subjects, ident, cov, null, aln_length=aln, sim_errors=sim)
-        return None
-    whole = done == 0 and sum(len(b[0]) * len(b[1]) for b in blocks) == n * n
-    if whole:  # a new run: one square, rows in index order, matrix cache from memory
-        pos = {h: i for i, h in enumerate(hashes)}
-        ident = np.full((n, n), np.nan)
-        cov = np.full((n, n), np.nan)
-        null = np.ones((n, n), dtype=bool)
-        aln = np.zeros((n, n), dtype=np.int64)
-        sim = np.zeros((n, n), dtype=np.int64)
-        for queries, subjects, b_ident, b_aln, b_sim, b_cov, b_null in blocks:
-            at = np.ix_([pos[q] for q in queries], [pos[x] for x in subjects])
-            ident[at], cov[at], null[at], aln[at], sim[at] = b_ident, b_cov, b_null, b_aln, b_sim
-        return _ingest_direct(conn, run, hashes, hashes, ident, cov, null, mark, aln_length=aln, sim_errors=sim)
-    for queries, subjects, b_ident, b_aln, b_sim, b_cov, b_null in blocks:
-        ingest_matrices(conn, run, queries, subjects, b_ident, b_cov, b_null, aln_length=b_aln, sim_errors=b_sim)
-    mark("insert_rows")
-    return None
-
-
-def run_fastani_hip(  # noqa: PLR0913
-    fasta: Path,
-    database: Path | str,
-    *,
-    name: str | None = None,
-    kmersize: int | None = None,
-    fragsize: int | None = None,
-    minmatch: float | None = None,
-    temp: Path | None = None,
-    logger: logging.Logger | None = None,
-    engine=None,
-    gpus: int = 1,
-    engine_factory: str | None = None,
-    timings: dict | None = None,
-    ingest: str = "json",
-    query_batch: int | None = None,
-) -> Run:
-    """FASTA directory -> database with all N^2 fragment-ANI comparisons and cached matrices: counterpart of
-    ``pyani-plus fastani <fasta> -d <db> --create-db`` (pyani_plus/public_cli.py:502-554) with one in-process call --
-    or ``gpus`` worker processes, each mapping all queries against its own range of subject columns -- in place of the
-    snakemake jobs.  Defaults as pyani_plus/methods/fastani.py:27-30.  The registration pass (checksum, length and
-    title of every file) runs on host threads only, so this process never touches a GPU when ``gpus`` > 1."""
-    from .engine import load_fasta_files
-    from .methods import fastani_hip
-
-    mark = _phase_clock(timings)
-    logger = logger or logging.getLogger("pyani_plus_amd")
-    kmersize = fastani_hip.KMER_SIZE if kmersize is None else int(kmersize)
-    fragsize = fastani_hip.FRAG_LEN if fragsize is None else int(fragsize)
-    minmatch = fastani_hip.MIN_FRACTION if minmatch is None else float(minmatch)
-    fasta = Path(fasta)
-    fasta_names = check_fasta(logger, fasta)
-    tool = fastani_hip.get_fastani_hip()
-    conn = connect_to_db(database)
-    config = db_configuration(conn, fastani_hip.METHOD, tool.exe_path.stem, tool.version, fragsize=fragsize, kmersize=kmersize, minmatch=minmatch)
-    infos, _arena = load_fasta_files(fasta_names)
-    filename_to_md5: dict[Path, str] = {}
-    for filename, info in zip(fasta_names, infos):
-        if info.status != 0:
-            sourmash_hip.log_sys_exit(logger, info.message)
-        if info.md5 in filename_to_md5.values():
-            _duplicate_md5_exit(logger, info.md5, [k for k, v in filename_to_md5.items() if v == info.md5] + [filename])
-        filename_to_md5[filename] = info.md5
-        db_genome(conn, filename, info.md5, info.length, info.description)
-    del _arena
-    mark("register_genomes")
-    run = add_run(
-        conn, config, " ".join(sys.argv), fasta, "Initialising",
-        f"{len(filename_to_md5)} genomes using {fastani_hip.METHOD}" if name is None else name, filename_to_md5,
-    )  # fmt: skip
-    session = Session(conn, run)
-    tmp_dir = Path(temp) if temp else Path(tempfile.mkdtemp(prefix="pyani_hip_"))
-    tmp_dir.mkdir(parents=True, exist_ok=True)
-    if ingest not in {"json", "direct"}:
-        sourmash_hip.log_sys_exit(logger, f"ingest must be 'json' or 'direct', not {ingest!r}")
-    direct = _compute_missing_fastani(logger, conn, session, run, tmp_dir, engine, gpus, engine_factory, ingest, mark, query_batch)
-    return _finish_run(logger, conn, session, run, direct, mark)
-
-
-def _compute_missing_external_alignment(logger, conn, session, run: Run, tmp_dir: Path, engine, mark) -> None:
-    """The subject columns the database does not complete yet, through the column worker and its JSON file: all of them
-    in one device call for a new run, the incomplete ones (one call each, as the reference's resume) otherwise."""
-    from .methods import external_alignment_hip
-
-    n = len(run.fasta_hashes)
-    done = count_run_comparisons(conn, run)
-    if done == n * n:
-        logger.info("Database already has all %d=%d^2 %s comparisons", n * n, n, external_alignment_hip.METHOD)
-        return
-    columns = [""] if done == 0 else _incomplete_columns(conn, run)
-    run.status = "Running"
-    session.commit()
-    hash_to_filename = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
-    query_hashes = {h: 0 for h in hash_to_filename}
-    for c, subject in enumerate(columns):
-        json_file = tmp_dir / f"{external_alignment_hip.METHOD}.run_{run.run_id}.column_{c if subject else 0}.json"
-        status = external_alignment_hip.compute_external_alignment_hip(
-            logger, tmp_dir, session, run, json_file, Path(run.fasta_directory), hash_to_filename,
-            {v: k for k, v in hash_to_filename.items()}, query_hashes, subject, engine=engine,
-        )  # fmt: skip
-        if status:
-            sourmash_hip.log_sys_exit(logger, f"Column worker failed with return code {status}")
-        mark("pairs_and_column_file")
-        import_json_comparisons(logger, conn, json_file)
-        mark("import_column_file")
-        if run.status == "Worker interrupted":
-            break
-
-
-def run_external_alignment_hip(  # noqa: PLR0913
-    fasta: Path,
-    database: Path | str,
-    *,
-    alignment: Path,
-    label: str = "stem",
-    name: str | None = None,
-    temp: Path | None = None,
-    logger: logging.Logger | None = None,
-    engine=None,
-    gpus: int = 1,
-    timings: dict | None = None,
-) -> Run:
-    """FASTA directory + its MSA -> database with all N^2 external-alignment comparisons and cached matrices: counterpart
-    of ``pyani-plus external-alignment <fasta> -d <db> --alignment <msa> --label <label> --create-db``
-    (pyani_plus/public_cli.py:642-699).  As there, the configuration records the MSA's md5 and its file name only: the
-    worker looks for the file next to the database.  One GPU: ``gpus`` > 1 is refused."""
-    from .engine import load_fasta_files
-    from .methods import external_alignment_hip
-
-    mark = _phase_clock(timings)
-    logger = logger or logging.getLogger("pyani_plus_amd")
-    if int(gpus) != 1:
-        sourmash_hip.log_sys_exit(logger, f"{external_alignment_hip.METHOD} runs on one GPU; --gpus {gpus} is not supported")
-    if label not in {"md5", "filename", "stem"}:
-        sourmash_hip.log_sys_exit(logger, f"label must be md5, filename or stem, not {label!r}")
-    alignment = Path(alignment)
-    if not alignment.is_file():
-        sourmash_hip.log_sys_exit(logger, f"Missing alignment file {alignment}")
-    fasta = Path(fasta)
-    fasta_names = check_fasta(logger, fasta)
-    tool = external_alignment_hip.get_external_alignment_hip()
-    import hashlib
-
-    with alignment.open("rb") as handle:
-        aln_md5 = hashlib.file_digest(handle, "md5").hexdigest() if hasattr(hashlib, "file_digest") else hashlib.md5(handle.read()).hexdigest()
-    conn = connect_to_db(database)
-    config = db_configuration(conn, external_alignment_hip.METHOD, tool.exe_path.stem, tool.version,
-                              extra=external_alignment_hip.make_extra(aln_md5, label, alignment))  # fmt: skip
-    infos, _arena = load_fasta_files(fasta_names)
-    filename_to_md5: dict[Path, str] = {}
-    for filename, info in zip(fasta_names, infos):
-        if info.status != 0:
-            sourmash_hip.log_sys_exit(logger, info.message)
-        if info.md5 in filename_to_md5.values():
-            _duplicate_md5_exit(logger, info.md5, [k for k, v in filename_to_md5.items() if v == info.md5] + [filename])
-        filename_to_md5[filename] = info.md5
-        db_genome(conn, filename, info.md5, info.length, info.description)
-    del _arena
-    mark("register_genomes")
-    run = add_run(conn, config, " ".join(sys.argv), fasta, "Initialising", f"Import of {alignment.name}" if name is None else name,
-                  filename_to_md5)  # fmt: skip
-    session = Session(conn, run)
-    tmp_dir = Path(temp) if temp else Path(tempfile.mkdtemp(prefix="pyani_hip_"))
-    tmp_dir.mkdir(parents=True, exist_ok=True)
-    _compute_missing_external_alignment(logger, conn, session, run, tmp_dir, engine, mark)
-    return _finish_run(logger, conn, session, run, None, mark)
-
-
 # ------------------------------------------------------------------ the driver as a process
 def main(argv: list[str] | None = None) -> int:
     """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,resume,export-run} ...``: the run driver as a process of its own,
@@ -1270,10 +1302,6 @@ def main(argv: list[str] | None = None) -> int:
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
     Typer front end is out of scope."""
-    import argparse
-
-    from . import launch
-
     parser = argparse.ArgumentParser(prog="python -m pyani_plus_amd.rundb", description=main.__doc__)
     sub = parser.add_subparsers(dest="command", required=True)
 
