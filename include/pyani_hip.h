@@ -468,6 +468,47 @@ PA_API int pa_append_msa_json(const char *path, const char *suffix, int file_has
                               const uint32_t *q_idx, const uint32_t *s_idx, uint64_t n_rows, const double *identity,
                               const int64_t *aln_length, const int64_t *sim_errors, const double *cov_query, const double *cov_subject);
 
+/* ---- classify: a run's matrices -> its genome cliques ----
+ * Replaces construct_graph, find_initial_cliques, find_cliques_recursively and get_unique_cliques
+ * (pyani_plus/classify.py:64-207).  Node p is row and column p of the two n x n row-major f64 matrices (rows = query,
+ * columns = subject).  For every i < j: coverage = agg_cov(C[j,i], C[i,j]), score = agg_score(S[j,i], S[i,j]) with the
+ * reference's argument order and NaN behaviour (Python's min and max keep a NaN first argument and pass over a NaN second
+ * one; the mean is NaN for either); the pair is an edge iff neither is NaN and coverage > cov_min.
+ *
+ *   pa_classify_edges        (device) the edges in removal order: ascending score, equal scores (-0.0 equals 0.0) by
+ *        ascending (i, j).  The four outputs are device arrays with room for cap_edges elements; *n_edges = E always.
+ *        PA_E_CAPACITY when E > cap_edges (nothing written; n (n - 1) / 2 always suffices); PA_E_INVALID for
+ *        n > 65536 (edge positions are 32-bit) or an unknown aggregator.  One host synchronisation (E is read back).
+ *   pa_classify_edges_host   the same list from host matrices into host arrays (plain loops, std::stable_sort).
+ *   pa_classify_tani_host    score matrix of tANI mode from the Hadamard matrix: NaN stays, 0 -> NaN, else
+ *        (-log(h)) * -1 with the host libm log (db_orm.py:588, public_cli.py:1269); -log(1.0) * -1 is +0.0.
+ *   pa_classify_cliques      (host) edges in removal order -> rows.  The edges are walked backwards with a union-find
+ *        that counts nodes and edges per component; a component is recorded, when an edge of score s joins it to
+ *        another one, iff it is a clique, with min_score = s; the components left at the end are recorded with no
+ *        min_score if there is one of them or no edge at all, else with the smallest score of all.  Row order: if
+ *        more than one component is left, those that are cliques by smallest member; then the component tree in
+ *        pre-order (roots and children by smallest member), rows already listed skipped.
+ *   pa_cliques_info / _copy / _free   number of rows and of members; n_nodes[R], max_cov[R], min_score[R],
+ *        max_score[R], present[R] (bit 0: max_cov, 1: min_score, 2: max_score; an absent value is NaN), member_off[R + 1],
+ *        members[member_off[R]] (ascending inside a row). */
+#define PA_AGG_MIN 0
+#define PA_AGG_MAX 1
+#define PA_AGG_MEAN 2
+typedef struct pa_cliques pa_cliques;
+PA_API int pa_classify_edges(pa_ctx *ctx, const double *d_score, const double *d_cov, uint32_t n, int agg_score, int agg_cov,
+                             double cov_min, uint64_t cap_edges, uint32_t *d_i, uint32_t *d_j, double *d_edge_score,
+                             double *d_edge_cov, uint64_t *n_edges);
+PA_API int pa_classify_edges_host(const double *h_score, const double *h_cov, uint32_t n, int agg_score, int agg_cov, double cov_min,
+                                  uint64_t cap_edges, uint32_t *h_i, uint32_t *h_j, double *h_edge_score, double *h_edge_cov,
+                                  uint64_t *n_edges);
+PA_API int pa_classify_tani_host(const double *h_hadamard, uint64_t n_cells, double *h_score);
+PA_API int pa_classify_cliques(uint32_t n, uint64_t n_edges, const uint32_t *h_i, const uint32_t *h_j, const double *h_edge_score,
+                               const double *h_edge_cov, pa_cliques **out);
+PA_API int pa_cliques_info(const pa_cliques *cl, uint64_t *n_rows, uint64_t *n_members);
+PA_API int pa_cliques_copy(const pa_cliques *cl, uint32_t *n_nodes, double *max_cov, double *min_score, double *max_score,
+                           uint8_t *present, uint64_t *member_off, uint32_t *members);
+PA_API void pa_cliques_free(pa_cliques *cl);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */
@@ -480,7 +521,9 @@ PA_API int pa_append_msa_json(const char *path, const char *suffix, int file_has
 #define PA_PROF_FRAG_MAP 7   /* fragment ANI: prefilter + map_segments_kernel + per-pair reduction */
 #define PA_PROF_MSA_PACK 8    /* external alignment: rows -> bit planes (msa_pack_kernel) */
 #define PA_PROF_MSA_PAIRS 9   /* external alignment: pair counts M, B (msa_pairs_kernel, mirror) */
-#define PA_PROF_NPHASES 10
+#define PA_PROF_CLS_EDGES 10  /* classify: pair evaluation, counts, scan, compaction (cls_edges_kernel) */
+#define PA_PROF_CLS_SORT 11   /* classify: radix sort of the edges by score + gather */
+#define PA_PROF_NPHASES 12
 PA_API int pa_prof_enable(pa_ctx *ctx, int on);
 PA_API int pa_prof_reset(pa_ctx *ctx);
 /* total milliseconds and number of timed launches of a phase (syncs the stream) */

@@ -30,7 +30,8 @@ PA_FRAGANI_COLUMNS_ONLY = 2
 PA_PAIRS_AUTO, PA_PAIRS_BITROW, PA_PAIRS_MERGE, PA_PAIRS_BITROW_HASH = 0, 1, 2, 3
 PA_ALIGN_BASES = 64
 PROF_PHASES = {"kmer_hash": 0, "sketch_sort": 1, "pair_dict": 2, "pair_count": 3, "ani": 4, "frag_index": 5, "frag_seed": 6, "frag_map": 7,
-               "msa_pack": 8, "msa_pairs": 9}
+               "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11}
+PA_AGG = {"min": 0, "max": 1, "mean": 2}
 
 _u8p = C.POINTER(C.c_uint8)
 _u32p = C.POINTER(C.c_uint32)
@@ -159,6 +160,13 @@ SIGNATURES: dict[str, tuple] = {
         C.c_int,
         [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp],
     ),
+    "pa_classify_edges": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_int, C.c_int, C.c_double, C.c_uint64, _vp, _vp, _vp, _vp, _u64p]),
+    "pa_classify_edges_host": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int, C.c_int, C.c_double, C.c_uint64, _vp, _vp, _vp, _vp, _u64p]),
+    "pa_classify_tani_host": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "pa_classify_cliques": (C.c_int, [C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "pa_cliques_info": (C.c_int, [_vp, _u64p, _u64p]),
+    "pa_cliques_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pa_cliques_free": (None, [_vp]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),
     "pa_prof_get": (C.c_int, [_vp, C.c_int, _f64p, _u64p]),

@@ -131,6 +131,8 @@ struct pa_ctx {
   // u64 [1..2] fingerprint of the postings a prepared dictionary was built from, [3..4] of the tile that consumes it
   DevBuf dict_scalars;
   hipStream_t copy_stream = nullptr;  // uploads of pa_sketch_streamed, created on first use
+  // classify (classify.hip): the edges in (i, j) order, before the sort
+  DevBuf cls_i, cls_j, cls_score, cls_cov;
   void *frag_work = nullptr;  // fragment-ANI workspace (fragani.hip), created on first use
   // pinned host scalars
   uint64_t *h_pinned = nullptr;

@@ -629,6 +629,46 @@ class HipEngine:
         )
         return match, both
 
+    # -- classify
+    def classify_edges_device(self, score, cov, *, score_edges: str = "mean", coverage_edges: str = "min", cov_min: float = 0.5):
+        """``pa_classify_edges``: the edges of the genome graph in removal order as device tensors ``(i, j, score, cov)``
+        (int32 views of uint32, float64), trimmed to the number of edges.  ``score`` and ``cov`` are N x N float64,
+        host arrays or tensors on this device."""
+        t = self.torch
+
+        def on_device(m):
+            if not isinstance(m, t.Tensor):
+                m = t.from_numpy(np.ascontiguousarray(m, dtype=np.float64))
+            return m.to(device=self.device, dtype=t.float64).contiguous()
+
+        d_score, d_cov = on_device(score), on_device(cov)
+        n = d_score.shape[0]
+        if d_score.shape != (n, n) or d_cov.shape != (n, n):
+            raise ValueError(f"score {tuple(d_score.shape)} and coverage {tuple(d_cov.shape)} must be square and equal")
+        for name, role in ((score_edges, "score"), (coverage_edges, "coverage")):
+            if name not in _capi.PA_AGG:
+                raise ValueError(f"Unknown {role} aggregator {name!r}: expected one of min, max, mean")
+        cap = n * (n - 1) // 2
+        e_i = t.empty(cap, dtype=t.int32, device=self.device)
+        e_j = t.empty(cap, dtype=t.int32, device=self.device)
+        e_s = t.empty(cap, dtype=t.float64, device=self.device)
+        e_c = t.empty(cap, dtype=t.float64, device=self.device)
+        count = C.c_uint64(0)
+        self._check(
+            self.lib.pa_classify_edges(
+                self.ctx, d_score.data_ptr(), d_cov.data_ptr(), n, _capi.PA_AGG[score_edges], _capi.PA_AGG[coverage_edges], float(cov_min), cap,
+                e_i.data_ptr(), e_j.data_ptr(), e_s.data_ptr(), e_c.data_ptr(), C.byref(count),
+            ),  # fmt: skip
+            "pa_classify_edges",
+        )
+        m = count.value
+        return e_i[:m], e_j[:m], e_s[:m], e_c[:m]
+
+    def classify_edges(self, score, cov, *, score_edges: str = "mean", coverage_edges: str = "min", cov_min: float = 0.5):
+        """``classify_edges_device`` copied back: ``(i, j, score, cov)`` as host arrays (uint32, uint32, float64, float64)."""
+        e_i, e_j, e_s, e_c = self.classify_edges_device(score, cov, score_edges=score_edges, coverage_edges=coverage_edges, cov_min=cov_min)
+        return e_i.cpu().numpy().view(np.uint32), e_j.cpu().numpy().view(np.uint32), e_s.cpu().numpy(), e_c.cpu().numpy()
+
     # -- profiling
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")

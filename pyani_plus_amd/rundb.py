@@ -4,7 +4,7 @@
 The reference's Python (Typer CLI, SQLAlchemy ORM, snakemake) does not travel to the GPU
 box, so this module is the build's own counterpart of ``cli_sourmash`` / ``fastani`` / ``external_alignment`` +
 ``start_and_run_method`` + ``run_method`` minus snakemake (pyani_plus/public_cli.py:115-329, 502-554,
-598-699), of ``resume`` and ``export-run`` (702-828, 974-1091) and of the parts of ``db_orm`` they use (SURVEY.md
+598-699), of ``resume``, ``export-run`` and ``classify`` (702-828, 974-1091, 1211-1331) and of the parts of ``db_orm`` they use (SURVEY.md
 section 8b, last row):
 
 * FASTA enumeration by the four extensions +- ``.gz`` (pyani_plus/utils.py:226-242)
@@ -48,6 +48,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _capi, launch, wire
+from . import classify as classify_mod
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
 from .engine import load_fasta_files
@@ -465,12 +466,21 @@ def _store_matrix_cache(conn, run: Run, out: dict[str, str] | None) -> bool:
 
 def cache_comparisons(conn, run: Run) -> dict[str, str]:
     """Fill runs.df_* with the N x N matrices (rows = query, columns = subject, sorted md5)."""
+    if _matrix_cache_too_big(len(run.fasta_hashes)):
+        _store_matrix_cache(conn, run, None)
+        return {}
+    hashes, mats = _comparison_matrices(conn, run)
+    out = _matrices_to_json(hashes, mats)
+    _store_matrix_cache(conn, run, out)
+    return out
+
+
+def _comparison_matrices(conn, run: Run) -> tuple[list[str], dict]:
+    """(sorted md5s, the four N x N matrices of the run's comparisons: rows = query, columns = subject, NaN where there
+    is no value)."""
     hashes = sorted(a.genome_hash for a in run.fasta_hashes)
     index = {h: i for i, h in enumerate(hashes)}
     n = len(hashes)
-    if _matrix_cache_too_big(n):
-        _store_matrix_cache(conn, run, None)
-        return {}
     mats = {k: np.full((n, n), np.nan, float) for k in ("identity", "cov_query", "aln_length", "sim_errors")}
     rows = _select_run_comparisons(conn, run, "c.query_hash, c.subject_hash, c.identity, c.cov_query, c.aln_length, c.sim_errors").fetchall()
     if rows:
@@ -479,9 +489,7 @@ def cache_comparisons(conn, run: Run) -> dict[str, str]:
         c_idx = np.fromiter((index[r[1]] for r in rows), dtype=np.int64, count=len(rows))
         for col, key in enumerate(("identity", "cov_query", "aln_length", "sim_errors"), start=2):
             mats[key][r_idx, c_idx] = np.array([r[col] for r in rows], dtype=float)  # None -> NaN
-    out = _matrices_to_json(hashes, mats)
-    _store_matrix_cache(conn, run, out)
-    return out
+    return hashes, mats
 
 
 def _load_tile(logger, tile_file: Path, config: Configuration) -> tuple:
@@ -1295,9 +1303,89 @@ def export_run(database: Path | str, outdir: Path, *, run_id: int | None = None,
     return written
 
 
+# ------------------------------------------------------------------ classify (pyani_plus/public_cli.py:1211-1331)
+def classify(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", coverage_edges: str = "min",  # noqa: PLR0913
+             score_edges: str = "mean", cov_min: float = classify_mod.MIN_COVERAGE, mode: str = "identity", engine=None,
+             logger: logging.Logger | None = None) -> Path:
+    """Write ``<method>_classify.tsv``, the table of genome cliques of a complete run (``n_nodes, max_cov,
+    min_<score>, max_<score>, members``; the score is ``identity`` or ``-tANI``), with the reference's header and number
+    formatting and its messages for a missing database, an incomplete run, duplicate stems and an unknown label.
+
+    The matrices are the ones the reference reads: the cached ``runs.df_*`` JSON strings (10 decimals), filled with
+    ``cache_comparisons`` first when they are missing, relabelled and sorted by label.  Which rows there are is the
+    reference's answer whenever no two edges have the same score; with ties, and for the order of rows and members,
+    ``pyani_plus_amd.classify`` says what this project defines.  A run too large for the cache (about 8 500 genomes
+    and more) cannot be classified by the reference at all; its matrices are then taken from the comparisons table,
+    unrounded, which is beyond what the reference defines.
+
+    ``engine``: a ``HipEngine`` builds and sorts the edge list on the GPU; None does it on the host.  The plot of the
+    reference (``plot_classify``) is not made."""
+    import pandas as pd
+
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    if str(database) == ":memory:" or not Path(database).is_file():
+        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
+    for name, role in ((coverage_edges, "coverage"), (score_edges, "score")):
+        if name not in classify_mod.AGG_NAMES:
+            sourmash_hip.log_sys_exit(logger, f"Unknown {role} aggregator {name!r}: expected one of {', '.join(classify_mod.AGG_NAMES)}")
+    if mode not in classify_mod.MODES:
+        sourmash_hip.log_sys_exit(logger, f"Unknown classify mode {mode!r}: expected one of {', '.join(classify_mod.MODES)}")
+    outdir = Path(outdir)
+    if not outdir.is_dir():
+        logger.warning("Output directory %s does not exist, making it.", outdir)
+        outdir.mkdir()
+    conn, run = _open_run(logger, database, run_id, "Exporting")
+    run_id = run.run_id
+    n = len(run.fasta_hashes)
+    done = count_run_comparisons(conn, run)
+    if not n:
+        sourmash_hip.log_sys_exit(logger, f"Run-id {run_id} has no genomes")
+    if done != n * n:  # db_orm.load_run(check_complete=True)
+        sourmash_hip.log_sys_exit(logger, f"run-id {run_id} has {done} of {n}^2={n * n} comparisons, {n * n - done} needed")
+    method = run.configuration.method
+    keys = ("df_identity", "df_cov_query", "df_hadamard")
+    if _matrix_cache_too_big(n):
+        hashes, mats = _comparison_matrices(conn, run)
+        mats["hadamard"] = mats["identity"] * mats["cov_query"]
+        frames = [pd.DataFrame(mats[k], index=hashes, columns=hashes) for k in ("identity", "cov_query", "hadamard")]
+    else:
+        cached = conn.execute("SELECT df_identity, df_cov_query, df_hadamard FROM runs WHERE run_id=?", (run_id,)).fetchone()
+        if any(c is None for c in cached):
+            out = cache_comparisons(conn, run)
+            cached = tuple(out.get(k) for k in keys)
+            if any(c is None for c in cached):
+                sourmash_hip.log_sys_exit(logger, f"Could not load run {method} matrix")
+        frames = [pd.read_json(StringIO(c), orient="split", dtype=float) for c in cached]
+    conn.close()
+    if done == 1 and n == 1:
+        logger.warning("Run %d has %d comparison across %d genome. Reporting single clique.", run_id, done, n)
+    else:
+        logger.info("Run %d has %d comparisons across %d genomes.", run_id, done, n)
+    if label == "md5":
+        mapping = None
+    elif label == "filename":
+        mapping = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
+    elif label == "stem":
+        mapping = {a.genome_hash: filename_stem(a.fasta_filename) for a in run.fasta_hashes}
+        if len(set(mapping.values())) < len(mapping):
+            sourmash_hip.log_sys_exit(logger, "Duplicate filename stems, consider using MD5 labelling.")
+    else:
+        sourmash_hip.log_sys_exit(logger, f"Unexpected label scheme {label!r}")
+    if mapping is not None:
+        frames = [f.rename(index=mapping, columns=mapping).sort_index(axis=0).sort_index(axis=1) for f in frames]
+    identity, cov, hadamard = frames
+    score = identity.to_numpy(dtype=float) if mode == "identity" else classify_mod.tani_scores(hadamard.to_numpy(dtype=float))
+    rows = classify_mod.classify_matrices([str(x) for x in cov.columns], score, cov.to_numpy(dtype=float), coverage_edges=coverage_edges,
+                                          score_edges=score_edges, cov_min=cov_min, engine=engine)
+    written = outdir / f"{method}_classify.tsv"
+    written.write_text(classify_mod.classify_tsv(rows, mode))
+    logger.info("Wrote classify output to %s", outdir)
+    return written
+
+
 # ------------------------------------------------------------------ the driver as a process
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,resume,export-run} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,resume,export-run,classify} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -1341,6 +1429,17 @@ def main(argv: list[str] | None = None) -> int:
     p_e.add_argument("--run-id", type=int, default=None)
     p_e.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
     p_e.add_argument("--verbose", "-v", action="store_true")
+    p_c = sub.add_parser("classify", help="the genome cliques of a complete run as <method>_classify.tsv")
+    p_c.add_argument("--database", "-d", required=True, type=Path)
+    p_c.add_argument("--outdir", "-o", required=True, type=Path)
+    p_c.add_argument("--run-id", type=int, default=None)
+    p_c.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
+    p_c.add_argument("--coverage-edges", choices=classify_mod.AGG_NAMES, default="min")
+    p_c.add_argument("--score-edges", choices=classify_mod.AGG_NAMES, default="mean")
+    p_c.add_argument("--cov-min", type=float, default=classify_mod.MIN_COVERAGE)
+    p_c.add_argument("--mode", choices=classify_mod.MODES, default="identity")
+    p_c.add_argument("--device", type=int, default=None, help="build and sort the edge list on this GPU (default: on the host)")
+    p_c.add_argument("--verbose", "-v", action="store_true")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
     logger = logging.getLogger("pyani_plus_amd")
@@ -1358,6 +1457,19 @@ def main(argv: list[str] | None = None) -> int:
         elif args.command == "resume":
             run = resume(args.database, run_id=args.run_id, cache=args.cache, temp=args.temp, logger=logger, ingest=args.ingest,
                          gpus=args.gpus, engine_factory=args.engine_factory)
+        elif args.command == "classify":
+            engine = None
+            if args.device is not None:
+                from .engine import HipEngine
+
+                engine = HipEngine(args.device)
+            try:
+                print(classify(args.database, args.outdir, run_id=args.run_id, label=args.label, coverage_edges=args.coverage_edges,
+                               score_edges=args.score_edges, cov_min=args.cov_min, mode=args.mode, engine=engine, logger=logger))
+            finally:
+                if engine is not None:
+                    engine.close()
+            return 0
         else:
             for path in export_run(args.database, args.outdir, run_id=args.run_id, label=args.label, logger=logger):
                 print(path)

@@ -399,3 +399,35 @@ def msa_fasta_bytes(names: list[str], rows: np.ndarray, *, seed: int = 0, preamb
         if i % 3 == 2:
             out.append(eol)
     return b"".join(out)
+
+
+def synth_classify_matrices(n: int, seed: int = 0, *, groups: int = 3, subgroups: int = 3, nan_frac: float = 0.0, decimals: int | None = None,
+                            cross_cov: float = 0.45, low_group: bool = False) -> tuple[list[str], np.ndarray, np.ndarray]:
+    """(labels, identity, coverage) of a made-up run for classify: ``groups`` species of ``subgroups`` strains each.
+
+    Identity is about 0.98 inside a strain, 0.93 inside a species and 0.80 across species, coverage about 0.8 inside a
+    species and ``cross_cov`` across (each +- uniform noise, different in the two directions; the diagonal is 1).  With
+    ``cross_cov`` well below the coverage threshold the species are separate components from the start.  ``low_group``
+    lowers the identities inside species 0 by 0.25, so that the lowest edge of the whole graph lies inside one
+    component.  ``nan_frac`` of the off-diagonal cells, chosen per direction, are NaN in both matrices (a comparison
+    without a result).  ``decimals`` rounds both matrices, which makes many equal scores."""
+    rng = np.random.default_rng([int(seed), int(n)])
+    grp = rng.integers(0, groups, n)
+    sub = rng.integers(0, subgroups, n)
+    same_grp = grp[:, None] == grp[None, :]
+    same_sub = same_grp & (sub[:, None] == sub[None, :])
+    ident = np.where(same_grp, np.where(same_sub, 0.98, 0.93), 0.80) + rng.uniform(-0.02, 0.02, (n, n))
+    cov = np.where(same_grp, 0.8, cross_cov) + rng.uniform(-0.2, 0.2, (n, n))
+    if low_group:
+        ident = np.where(same_grp & (grp[:, None] == 0), ident - 0.25, ident)
+    if decimals is not None:
+        ident, cov = np.round(ident, decimals), np.round(cov, decimals)
+    np.fill_diagonal(ident, 1.0)
+    np.fill_diagonal(cov, 1.0)
+    if nan_frac:
+        mask = rng.random((n, n)) < nan_frac
+        np.fill_diagonal(mask, False)
+        ident[mask] = np.nan
+        cov[mask] = np.nan
+    width = max(3, len(str(max(n - 1, 0))))
+    return [f"g{i:0{width}d}" for i in range(n)], np.ascontiguousarray(ident), np.ascontiguousarray(cov)
