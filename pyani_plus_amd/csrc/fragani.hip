@@ -31,12 +31,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <optional>
 #include <type_traits>
 #include <vector>
 
 #include "murmur_dev.h"
-#include <optional>
-
 #include "pa_internal.h"
 #include "wave_dev.h"
 
@@ -50,6 +49,14 @@ constexpr int kQMax = 512;       // largest fragment sketch handled
 constexpr int kHitCapSmall = 256;  // segments up to this many hits run with the smaller LDS footprint
 constexpr int kHitCap = 512;     // seed hits of one (fragment, reference genome) segment staged in LDS
 constexpr double kPercIdentity = 80.0, kConfLevel = 0.9, kPvalCutoff = 1e-3, kRefSize = 5e6;
+// Query genomes go through in batches of up to 2^17 fragments (13 batches for 1 000 genomes of 5 Mb: 1.46 s against
+// 1.48 s with 2^16).  A batch whose seed hits do not fit 31-bit indices is halved and started again.
+#ifndef PA_FRAGANI_BATCH_FRAGS
+#define PA_FRAGANI_BATCH_FRAGS (1u << 17)
+#endif
+#ifndef PA_MAP_LDS_PAD
+#define PA_MAP_LDS_PAD 0u  // (an experiment's switch: LDS asked for and not used, to see what a wave less per SIMD costs)
+#endif
 
 // ============================================================== host statistics (Mashmap)
 double md2j(double d, int k) { return 1.0 / (2.0 * std::exp(k * d) - 1.0); }
@@ -201,12 +208,63 @@ int upload(pa_ctx *c, DevBuf &buf, const std::vector<T> &v) {
   return PA_OK;
 }
 
+// The device buffers of the workspace, each named here and nowhere else: the members of FragWork, their share in its
+// budget, their release after PA_E_NOMEM and in the destructor all follow from this list.  ONE(name): a buffer `name`;
+// PAIR(name): two, `name[0]` and `name[1]`.
+#define PA_FRAGWORK_BUFFERS(ONE, PAIR)                                                                                  \
+  ONE(contig_start) ONE(contig_len) ONE(contig_genome) ONE(block_counts) ONE(block_offsets) ONE(mini_hash)             \
+  ONE(mini_wpos) ONE(mini_contig) ONE(contig_mini_off) PAIR(keys) PAIR(vals) ONE(flags) ONE(mini_id) ONE(post_start)   \
+  ONE(prev_same) ONE(frag_contig) ONE(frag_no) ONE(frag_genome_local) ONE(q_hash) ONE(q_pos) ONE(q_id) ONE(q_s)        \
+  ONE(hit_count) ONE(hit_off) PAIR(hkeys) PAIR(hvals) ONE(seg_start) ONE(tab_min_hits) ONE(tab_min_shared)             \
+  ONE(ident_tab) ONE(contig_bin_off) ONE(genome_bin_off) ONE(table) ONE(matched) ONE(ident_sum) ONE(scalars)           \
+  ONE(run_g) ONE(seg_list) ONE(seg2_a0) ONE(seg2_nh) ONE(post_cw) ONE(seg_a0) ONE(seg_nh) ONE(genome_first_contig)     \
+  ONE(contig_bucket_off) ONE(bucket_first) ONE(post_g) ONE(seg_rec) ONE(hash_cut) ONE(q_cut) ONE(post_cw2)             \
+  ONE(post_g2) ONE(run_hist) ONE(long_runs) ONE(frag_d) ONE(uniq_hash) ONE(lookup_at) ONE(seg_f) ONE(seg2_f)           \
+  ONE(amb_pos) ONE(amb_byte) ONE(seg_over) ONE(q_tab)
+
+// The words of FragWork::scalars: the counters and cursors the kernels are handed, as (first 32-bit word, words).  Every
+// slot is zeroed by one hipMemsetAsync over exactly its own words (none covers two slots) and read back whole, both by
+// the function named with it.
+struct ScalarSlot {
+  uint32_t word, words;
+  constexpr uint32_t bytes() const { return words * 4u; }
+  constexpr bool apart_from(ScalarSlot o) const { return word + words <= o.word || o.word + o.words <= word; }
+};
+// run_minimizers: minimizer_kernel has the buffer to itself, all kMiniScalarBytes zeroed before every run: [0] ticket,
+// [1] minimizers, [2] a wait ran out, [3] unused -- the four words read back -- and one ticket counter per XCD behind them
+constexpr ScalarSlot kMiniScalars{0, kMiniScalarBytes / 4u}, kMiniResult{0, 4};
+constexpr uint32_t kMiniTotalWord = 1, kMiniRanOutWord = 2;  // within kMiniResult
+// From the dictionary on, the first 16 words (kBatchScalarBytes):
+constexpr ScalarSlot kScanTotal{0, 2};       // every pa_exclusive_scan_u32: its 64-bit total (written, never zeroed)
+constexpr ScalarSlot kSparseOver{3, 1};      // map_short_segments: segments map_sparse_kernel hands on to the general kernel
+constexpr ScalarSlot kSegCounters{4, 4};     // bucket_pass: [1] segments that need a sort of their own, [2] the longest of them
+constexpr ScalarSlot kSketchOverflow{8, 2};  // prepare_run, once per call: [0] fragment sketches cut at kQMax (read at the call's end)
+constexpr ScalarSlot kBigCursor{10, 1};      // list_segments_bucketed: cursor of big_segments_kernel; kPreCursor's first word, done with before that
+constexpr ScalarSlot kPreCursor{10, 2};      // map_short_segments: prefilter_segments_kernel's 64-bit word: [lo] general, [hi] sparse
+constexpr ScalarSlot kMaxHits{12, 2};        // stage_batch: [0] most seed hits of one fragment, [1] the longest sketch (read by seed_batch)
+constexpr ScalarSlot kSegCursor{14, 2};      // bucket_pass: one 64-bit word: [lo] short, [hi] long segments listed
+constexpr uint32_t kBatchScalarBytes = 64;
+constexpr bool slots_apart(std::initializer_list<ScalarSlot> slots) {
+  for (const ScalarSlot *a = slots.begin(); a != slots.end(); ++a) {
+    if ((a->word + a->words) * 4u > kBatchScalarBytes || (a->words == 2 && a->word % 2)) return false;  // (64-bit words aligned)
+    for (const ScalarSlot *b = a + 1; b != slots.end(); ++b)
+      if (!a->apart_from(*b)) return false;
+  }
+  return true;
+}
+static_assert(slots_apart({kScanTotal, kSparseOver, kSegCounters, kSketchOverflow, kPreCursor, kMaxHits, kSegCursor}) &&
+                  slots_apart({kScanTotal, kSegCounters, kSketchOverflow, kBigCursor, kMaxHits, kSegCursor}) &&
+                  kMiniResult.bytes() <= kMiniScalarBytes,
+              "two slots of FragWork::scalars that are live at the same time overlap");
+
 struct FragWork {
-  DevBuf contig_start, contig_len, contig_genome, block_counts, block_offsets, mini_hash, mini_wpos, mini_contig,
-      contig_mini_off, keys[2], vals[2], flags, mini_id, post_start, prev_same, sorted_idx, frag_contig, frag_no,
-      frag_genome_local, q_hash, q_pos, q_id, q_s, hit_count, hit_off, hkeys[2], hvals[2], seg_start, tab_min_hits,
-      tab_min_shared, ident_tab, contig_bin_off, genome_bin_off, table, matched, ident_sum, scalars, run_g, seg_list, seg2_a0, seg2_nh, post_cw, seg_a0, seg_nh, genome_first_contig,
-      contig_bucket_off, bucket_first, post_g, seg_rec, hash_cut, q_cut, post_cw2, post_g2, run_hist, long_runs, frag_d, uniq_hash, lookup_at, seg_f, seg2_f, amb_pos, amb_byte, seg_over, q_tab;
+#define PA_ONE(name) DevBuf name;
+#define PA_PAIR(name) DevBuf name[2];
+  PA_FRAGWORK_BUFFERS(PA_ONE, PA_PAIR)
+#undef PA_ONE
+#undef PA_PAIR
+  template <typename T = uint32_t>
+  T *slot(ScalarSlot s) const { return reinterpret_cast<T *>(scalars.as<uint32_t>() + s.word); }
   // the arena's residues that are neither ACGT nor N (pa_fragani_set_ambiguous), and the arena they belong to
   const void *amb_for = nullptr;
   uint32_t amb_n = 0;
@@ -230,13 +288,11 @@ struct FragWork {
   DevBudget budget;
   template <class Fn>
   void each_buffer(Fn &&fn) {
-    DevBuf *all[] = {&contig_start, &contig_len, &contig_genome, &block_counts, &block_offsets, &mini_hash, &mini_wpos,
-                     &mini_contig, &contig_mini_off, &keys[0], &keys[1], &vals[0], &vals[1], &flags, &mini_id,
-                     &post_start, &prev_same, &sorted_idx, &frag_contig, &frag_no, &frag_genome_local, &q_hash, &q_pos,
-                     &q_id, &q_s, &hit_count, &hit_off, &hkeys[0], &hkeys[1], &hvals[0], &hvals[1], &seg_start,
-                     &tab_min_hits, &tab_min_shared, &ident_tab, &contig_bin_off, &genome_bin_off, &table, &matched,
-                     &ident_sum, &scalars, &run_g, &seg_list, &seg2_a0, &seg2_nh, &post_cw, &seg_a0, &seg_nh, &genome_first_contig, &contig_bucket_off, &bucket_first, &post_g, &seg_rec, &hash_cut, &q_cut, &post_cw2, &post_g2, &run_hist, &long_runs, &frag_d, &uniq_hash, &lookup_at, &seg_f, &seg2_f, &amb_pos, &amb_byte, &seg_over, &q_tab};
-    for (DevBuf *b : all) fn(*b);
+#define PA_ONE(name) fn(name);
+#define PA_PAIR(name) fn(name[0]); fn(name[1]);
+    PA_FRAGWORK_BUFFERS(PA_ONE, PA_PAIR)
+#undef PA_ONE
+#undef PA_PAIR
   }
   FragWork() { each_buffer([this](DevBuf &b) { b.budget = &budget; }); }
   FragWork(const FragWork &) = delete;
@@ -324,8 +380,8 @@ int cut_frequent_postings(pa_ctx *c, FragWork &W, const uint32_t *d_heads, const
                      W.post_g.as<uint16_t>(), m, W.run_hist.as<uint32_t>(), scratch_a, W.hash_cut.as<uint32_t>());
   hipLaunchKernelGGL(mark_cut_minimizers_kernel, dim3(gm), dim3(kThreads), 0, c->stream, d_heads, d_ids_before, d_sorted_idx, m,
                      W.hash_cut.as<uint32_t>(), W.mini_id.as<uint32_t>());
-  PA_TRY(pa_exclusive_scan_u32(c, scratch_a, scratch_b, m, W.scalars.as<uint64_t>()));
-  PA_HIP(hipMemcpyAsync(c->h_pinned, W.scalars.p, 8, hipMemcpyDeviceToHost, c->stream));
+  PA_TRY(pa_exclusive_scan_u32(c, scratch_a, scratch_b, m, W.slot<uint64_t>(kScanTotal)));
+  PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
   PA_HIP(hipStreamSynchronize(c->stream));
   const uint32_t kept = (uint32_t)c->h_pinned[0];
   if (kept != m) {
@@ -346,7 +402,7 @@ int run_minimizers(pa_ctx *c, FragWork &W, const uint32_t *d_packed, const uint3
                    uint32_t n_contigs, int w, uint32_t *m_out, const std::function<void()> *meanwhile) {
   const uint32_t blocks = ceil_div_u64(arena_bases, kOwn);
   PA_TRY(W.block_counts.reserve((uint64_t)blocks * 8));  // the look-back words of minimizer_kernel
-  PA_TRY(W.scalars.reserve(kMiniScalarBytes));
+  PA_TRY(W.scalars.reserve(kMiniScalars.bytes()));
   PA_TRY(W.block_offsets.reserve((uint64_t)blocks * 4 + 16));  // the contig of every tile's first position
   hipLaunchKernelGGL(tile_contig_kernel, dim3(ceil_div_u64(blocks, kThreads)), dim3(kThreads), 0, c->stream, W.contig_start.as<uint64_t>(), n_contigs,
                      blocks, W.block_offsets.as<uint32_t>());
@@ -364,29 +420,29 @@ int run_minimizers(pa_ctx *c, FragWork &W, const uint32_t *d_packed, const uint3
     PA_TRY(W.mini_wpos.reserve(cap * 4 + 16));
     PA_TRY(W.mini_contig.reserve(cap * 4 + 16));
     PA_HIP(hipMemsetAsync(W.block_counts.p, 0, (uint64_t)blocks * 8, c->stream));
-    PA_HIP(hipMemsetAsync(W.scalars.p, 0, kMiniScalarBytes, c->stream));
+    PA_HIP(hipMemsetAsync(W.slot(kMiniScalars), 0, kMiniScalars.bytes(), c->stream));
     hipLaunchKernelGGL((minimizer_kernel<K>), dim3(blocks), dim3(kMiniThreads), 0, c->stream,
                        d_packed, d_mask, arena_bases, W.contig_start.as<uint64_t>(), W.contig_len.as<uint32_t>(), n_contigs, w,
-                       W.block_counts.as<unsigned long long>(), W.scalars.as<uint32_t>(), (uint32_t)cap,
+                       W.block_counts.as<unsigned long long>(), W.slot(kMiniScalars), (uint32_t)cap,
                        W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(), W.mini_contig.as<uint32_t>(), blocks, W.ambiguous(d_packed), ticket_mode,
                        W.block_offsets.as<uint32_t>());
     PA_HIP(hipGetLastError());
-    PA_HIP(hipMemcpyAsync(c->h_pinned, W.scalars.p, 16, hipMemcpyDeviceToHost, c->stream));
+    PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kMiniResult), kMiniResult.bytes(), hipMemcpyDeviceToHost, c->stream));
     if (meanwhile && *meanwhile) {  // the caller's host-side bookkeeping, while the kernel runs (once)
       (*meanwhile)();
       meanwhile = nullptr;
     }
     PA_HIP(hipStreamSynchronize(c->stream));
     const uint32_t *h = reinterpret_cast<const uint32_t *>(c->h_pinned);
-    bool ran_out = h[2] != 0;
+    bool ran_out = h[kMiniRanOutWord] != 0;
     if (const char *v = PA_TOOL_ENV("PA_FRAGANI_TICKET_TIMEOUT")) { if (atoi(v) && ticket_mode != 0) ran_out = true; }  // tests: as if a wait had run out
     if (ran_out && ticket_mode != 0) {  // a wait ran out with the tiles drawn per XCD: once more, from one counter
       ticket_mode = 0;
       --attempt;
       continue;
     }
-    PA_REQUIRE(h[2] == 0, "fragment ANI: the minimizer scan gave up waiting for a tile (%u tiles)", blocks);
-    const uint64_t m = h[1];
+    PA_REQUIRE(h[kMiniRanOutWord] == 0, "fragment ANI: the minimizer scan gave up waiting for a tile (%u tiles)", blocks);
+    const uint64_t m = h[kMiniTotalWord];
     if (m <= cap) {
       *m_out = (uint32_t)m;
       return PA_OK;
@@ -430,6 +486,778 @@ int stage_contigs(pa_ctx *c, FragWork &W, const uint64_t *h_contig_start, const 
   PA_TRY(upload(c, W.contig_len, cl));
   PA_TRY(upload(c, W.contig_genome, cg));
   PA_HIP(hipStreamSynchronize(c->stream));
+  return PA_OK;
+}
+
+// ============================================================== the stages of one pa_fragani_ex call
+// fragani_ex_impl (at the end) reads as the pipeline; every stage below is a plain function over the context, the
+// workspace and these few structs.
+
+// The call: its arguments as handed in and, from check_call, what follows from them alone.
+struct FragCall {
+  const uint32_t *d_packed, *d_mask;
+  uint64_t arena_bases;
+  const uint64_t *h_contig_start;
+  const uint32_t *h_contig_len, *h_contig_genome;
+  uint32_t n_contigs, n_genomes, k, frag_len, qry0, qry1, ref0, ref1, flags;
+  uint32_t *h_total_frags, *h_matched;
+  double *h_ident_sum;
+  int w = 0;                            // winnowing window
+  uint32_t count_windows = 0;           // windows of one fragment
+  uint32_t out_cols = 0, out_col0 = 0;  // the row length of the two result matrices on the host, and the first column they hold
+  bool reuse = false;
+};
+
+// Fragments and reference bins (layout_fragments)
+struct FragLayout {
+  std::vector<uint32_t> frag_contig, frag_no, genome_frag_off, contig_bin_off, genome_bin_off;
+};
+
+// What every batch of the call shares (prepare_run)
+struct FragRun {
+  int which = 0;            // W.vals[which]: the postings' minimizers; W.vals[1 - which]: spare
+  bool restricted = false;  // the dictionary holds a range of the genomes: hashes are looked up by value
+  uint64_t range_bins = 1;  // bins of the reference genomes asked for
+  uint64_t hit_limit = 1ULL << 31;
+  uint32_t ref_cap = 0;     // stretch capacity of the mapping kernel
+  bool use_buckets = false, trace = false;
+};
+
+// One batch of query genomes [g0, g1): fragments [f0, f0 + nf)
+struct FragBatch {
+  uint32_t g0 = 0, g1 = 0, f0 = 0, nf = 0, nq = 0;
+  uint32_t *q_hash = nullptr, *q_pos = nullptr, *q_id = nullptr;  // the fragments' sketches
+  uint64_t n_hits = 0;
+  uint32_t max_hits = 0, s_cap = 0;  // most seed hits of one fragment; the longest sketch, in steps of 64
+  unsigned long long *table = nullptr;  // best fragment per (query genome, reference bin)
+};
+
+// The batch's seed hits and its (fragment, reference genome) segments, as either way of listing them leaves them:
+// hits in hk[hw] / hv[hw]; segments [0, n_keep) of seg_a0 / seg_nh (/ seg_f) and, bucketed, n_large long ones from large_at.
+struct SegLists {
+  uint64_t *hk[2] = {nullptr, nullptr};
+  uint32_t *hv[2] = {nullptr, nullptr};
+  int hw = 0;
+  bool presorted = true;
+  uint32_t n_keep = 0, n_large = 0, large_at = 0;
+};
+
+int check_call(pa_ctx *c, FragCall &a) {
+  PA_REQUIRE(c && a.d_packed && a.d_mask && a.h_total_frags && a.h_matched && a.h_ident_sum, "pa_fragani: null argument");
+  PA_REQUIRE(a.ref0 <= a.ref1 && a.ref1 <= a.n_genomes, "pa_fragani: reference range [%u,%u) outside [0,%u)", a.ref0, a.ref1, a.n_genomes);
+  PA_REQUIRE(a.qry0 <= a.qry1 && a.qry1 <= a.n_genomes, "pa_fragani: query range [%u,%u) outside [0,%u)", a.qry0, a.qry1, a.n_genomes);
+  PA_REQUIRE(a.n_genomes <= 0xffffu, "pa_fragani: %u genomes (limit 65 535: a posting names its genome in 16 bits)", a.n_genomes);
+  PA_REQUIRE((a.flags & ~(uint32_t)(PA_FRAGANI_REUSE_INDEX | PA_FRAGANI_COLUMNS_ONLY)) == 0, "pa_fragani: unknown flags 0x%x", a.flags);
+  a.out_cols = (a.flags & PA_FRAGANI_COLUMNS_ONLY) ? a.ref1 - a.ref0 : a.n_genomes;
+  a.out_col0 = (a.flags & PA_FRAGANI_COLUMNS_ONLY) ? a.ref0 : 0u;
+  a.reuse = (a.flags & PA_FRAGANI_REUSE_INDEX) != 0;
+  PA_REQUIRE(a.frag_len >= 100 && a.frag_len <= 0xffffu, "pa_fragani: fragLen %u outside [100, 65535]", a.frag_len);
+  PA_HIP(hipSetDevice(c->device));
+  a.w = window_size_for((int)a.k, (int)a.frag_len);
+  PA_REQUIRE(a.w >= 1 && a.w <= 64, "pa_fragani: winnowing window %d outside [1,64] for k=%u fragLen=%u", a.w, a.k, a.frag_len);
+  PA_REQUIRE((int)a.frag_len > a.w + (int)a.k, "pa_fragani: fragLen %u too short for window %d", a.frag_len, a.w);
+  a.count_windows = a.frag_len - (uint32_t)(a.w - 1) - (a.k - 1);
+  FragWork &W = frag_work(c);
+  snprintf(W.budget.what, sizeof(W.budget.what), "pa_fragani: %u genomes (%llu residues of arena), queries [%u,%u), reference range [%u,%u), fragLen %u",
+           a.n_genomes, (unsigned long long)a.arena_bases, a.qry0, a.qry1, a.ref0, a.ref1, a.frag_len);
+  return PA_OK;
+}
+
+// PA_FRAGANI_REUSE_INDEX: the index the workspace holds is this call's.  `*no_fragments`: no contig holds a fragment, so
+// every pair is 0 of 0, whatever index an earlier call left (or did not leave) behind -- the results are written here.
+int check_reuse(const FragWork &W, const FragCall &a, bool *no_fragments) {
+  uint64_t any_frags = 0;
+  for (uint32_t ci = 0; ci < a.n_contigs; ++ci) any_frags += a.h_contig_len[ci] / a.frag_len;
+  *no_fragments = any_frags == 0;
+  if (*no_fragments) {
+    for (uint32_t g = 0; g < a.n_genomes; ++g) a.h_total_frags[g] = 0;
+    for (uint64_t i = (uint64_t)a.qry0 * a.out_cols; i < (uint64_t)a.qry1 * a.out_cols; ++i) { a.h_matched[i] = 0; a.h_ident_sum[i] = 0.0; }
+    return PA_OK;
+  }
+  PA_REQUIRE(W.index_valid && W.index_packed == (const void *)a.d_packed && W.index_arena_bases == a.arena_bases &&
+                 W.index_contigs == a.n_contigs && W.index_genomes == a.n_genomes && W.index_k == a.k && W.index_frag_len == a.frag_len &&
+                 W.index_ref0 <= a.ref0 && a.ref1 <= W.index_ref1,
+             "pa_fragani: PA_FRAGANI_REUSE_INDEX without a preceding call on the same arena, contigs, k and fragLen whose "
+             "reference range holds this one");
+  return PA_OK;
+}
+
+// Fragments and reference bins, and the caller's rows zeroed (host bookkeeping: some 10 ms for the 1.7 million fragments
+// and the two result matrices of 1 000 genomes -- on a fresh index done while minimizer_kernel runs, not before or after
+// it with the device idle)
+void layout_fragments(const FragCall &a, FragLayout &L) {
+  L.genome_frag_off.assign(a.n_genomes + 1, 0);
+  L.contig_bin_off.assign(a.n_contigs + 1, 0);
+  L.genome_bin_off.assign(a.n_genomes + 1, 0);
+  for (uint32_t g = 0; g < a.n_genomes; ++g) a.h_total_frags[g] = 0;
+  uint64_t all_frags = 0;
+  for (uint32_t ci = 0; ci < a.n_contigs; ++ci) all_frags += a.h_contig_len[ci] / a.frag_len;
+  L.frag_contig.resize(all_frags);
+  L.frag_no.resize(all_frags);
+  uint64_t at = 0;
+  for (uint32_t ci = 0; ci < a.n_contigs; ++ci) {
+    const uint32_t nf = a.h_contig_len[ci] / a.frag_len;
+    for (uint32_t f = 0; f < nf; ++f) { L.frag_contig[at + f] = ci; L.frag_no[at + f] = f; }
+    at += nf;
+    a.h_total_frags[a.h_contig_genome[ci]] += nf;
+    L.contig_bin_off[ci + 1] = L.contig_bin_off[ci] + a.h_contig_len[ci] / (a.frag_len - 20u) + 2;
+  }
+  for (uint32_t g = 0; g < a.n_genomes; ++g) L.genome_frag_off[g + 1] = L.genome_frag_off[g] + a.h_total_frags[g];
+  uint32_t ci = 0;
+  for (uint32_t g = 0; g < a.n_genomes; ++g) {
+    L.genome_bin_off[g] = L.contig_bin_off[ci];
+    while (ci < a.n_contigs && a.h_contig_genome[ci] == g) ++ci;
+  }
+  L.genome_bin_off[a.n_genomes] = L.contig_bin_off[a.n_contigs];
+  memset(a.h_matched + (uint64_t)a.qry0 * a.out_cols, 0, (uint64_t)(a.qry1 - a.qry0) * a.out_cols * sizeof(uint32_t));
+  for (uint64_t i = (uint64_t)a.qry0 * a.out_cols; i < (uint64_t)a.qry1 * a.out_cols; ++i) a.h_ident_sum[i] = 0.0;
+}
+
+// ---- 1. minimizers of every contig (the fragment layout made meanwhile), their offsets per contig, the per-contig
+// bucket index over window ids
+int build_minimizers(pa_ctx *c, FragWork &W, const FragCall &a, FragLayout &L, uint32_t *m_out) {
+  const std::function<void()> meanwhile = [&a, &L]() { layout_fragments(a, L); };
+  uint32_t m = 0;
+  PA_TRY(dispatch_minimizers(c, W, a.d_packed, a.d_mask, a.arena_bases, a.n_contigs, a.k, a.w, &m, &meanwhile));
+  PA_TRY(W.contig_mini_off.reserve((uint64_t)(a.n_contigs + 2) * 4));
+  hipLaunchKernelGGL(contig_offsets_kernel, dim3(ceil_div_u64(a.n_contigs + 1, kThreads)), dim3(kThreads), 0, c->stream,
+                     W.mini_contig.as<uint32_t>(), m, a.n_contigs, W.contig_mini_off.as<uint32_t>());
+  std::vector<uint32_t> cbo(a.n_contigs + 1, 0);
+  for (uint32_t ci = 0; ci < a.n_contigs; ++ci) cbo[ci + 1] = cbo[ci] + (a.h_contig_len[ci] >> kBucketShift) + 2;
+  PA_REQUIRE((uint64_t)cbo[a.n_contigs] < (1ULL << 31), "pa_fragani: bucket index too large");
+  PA_TRY(upload(c, W.contig_bucket_off, cbo));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  PA_TRY(W.bucket_first.reserve((uint64_t)cbo[a.n_contigs] * 4 + 16));
+  hipLaunchKernelGGL(bucket_index_kernel, dim3(ceil_div_u64(cbo[a.n_contigs], kThreads)), dim3(kThreads), 0, c->stream,
+                     W.mini_wpos.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(),
+                     a.n_contigs, cbo[a.n_contigs], W.bucket_first.as<uint32_t>());
+  *m_out = m;
+  return PA_OK;
+}
+
+// ---- 2. dictionary of minimizer hashes: ids, postings, same-hash links, frequency cut, look-up table
+// The dictionary holds the minimizers of the REFERENCE genomes asked for (a worker asked for one subject column sorts
+// and lists one genome's minimizers, and its seed-hit arrays are that small too); the query genomes' minimizers find
+// their hashes in it by value.  With every genome a reference the minimizers know their hash ids themselves.
+// `*which_out`: which of W.vals holds the postings' minimizers.
+int build_dictionary(pa_ctx *c, FragWork &W, const FragCall &a, uint32_t m, int *which_out) {
+  const bool restricted = !(a.ref0 == 0 && a.ref1 == a.n_genomes);
+  uint32_t m_lo = 0, m_hi = m;
+  if (restricted) {
+    uint32_t c_lo = 0, c_hi = a.n_contigs;  // the contigs of the reference range (contigs are listed genome by genome)
+    while (c_lo < a.n_contigs && a.h_contig_genome[c_lo] < a.ref0) ++c_lo;
+    c_hi = c_lo;
+    while (c_hi < a.n_contigs && a.h_contig_genome[c_hi] < a.ref1) ++c_hi;
+    PA_HIP(hipMemcpy(&m_lo, W.contig_mini_off.as<uint32_t>() + c_lo, 4, hipMemcpyDeviceToHost));
+    PA_HIP(hipMemcpy(&m_hi, W.contig_mini_off.as<uint32_t>() + c_hi, 4, hipMemcpyDeviceToHost));
+  }
+  const uint32_t md = m_hi - m_lo;  // minimizers in the dictionary
+  const uint64_t md_room = std::max<uint32_t>(md, 1u);
+  // (the two key buffers of the sort are the halves of ONE allocation: once the index stands they are free, and the seed
+  // hits of the batches, 8 bytes each, go there -- memory this process has touched already instead of fresh pages)
+  PA_TRY(W.keys[0].reserve(2 * md_room * 8));
+  for (int b = 0; b < 2; ++b) PA_TRY(W.vals[b].reserve(md_room * 4));
+  PA_TRY(W.flags.reserve(md_room * 8 + 64));
+  W.index_key_room = md_room;
+  PA_TRY(W.mini_id.reserve((uint64_t)m * 4));
+  PA_TRY(W.prev_same.reserve((uint64_t)m * 4));
+  PA_TRY(W.post_cw.reserve(md_room * 8));
+  PA_TRY(W.post_g.reserve(md_room * 2 + 16));
+  uint64_t *keys[2] = {W.keys[0].as<uint64_t>(), W.keys[0].as<uint64_t>() + W.index_key_room};
+  uint32_t *vals[2] = {W.vals[0].as<uint32_t>(), W.vals[1].as<uint32_t>()};
+  int which = 0;
+  PA_HIP(hipMemsetAsync(W.prev_same.p, 0xff, (uint64_t)m * 4, c->stream));  // -1: no earlier occurrence
+  uint32_t n_ids = 0;
+  if (md) {
+    const uint32_t gm = ceil_div_u64(md, kThreads);
+    hipLaunchKernelGGL(mini_keys_kernel, dim3(gm), dim3(kThreads), 0, c->stream, W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
+                       m_lo, md, keys[0], vals[0]);
+    PA_TRY(pa_radix_sort_pairs(c, keys, vals, md, 0, 32, false, &which));
+    uint32_t *d_flags = W.flags.as<uint32_t>(), *d_pos = d_flags + md;
+    hipLaunchKernelGGL(key_heads_kernel, dim3(gm), dim3(kThreads), 0, c->stream, keys[which], md, d_flags);
+    PA_TRY(pa_exclusive_scan_u32(c, d_flags, d_pos, md, W.slot<uint64_t>(kScanTotal)));
+    PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
+    PA_HIP(hipStreamSynchronize(c->stream));
+    n_ids = (uint32_t)c->h_pinned[0];
+    PA_REQUIRE(n_ids < (1u << 31), "pa_fragani: %u distinct minimizer hashes (limit 2^31)", n_ids);
+    PA_TRY(W.post_start.reserve((uint64_t)(n_ids + 2) * 4));
+    PA_TRY(W.uniq_hash.reserve((uint64_t)(n_ids + 2) * 4));
+    // (the contig of every block of minimizers: the look-back words of minimizer_kernel are free again)
+    const uint32_t n_blocks = (uint32_t)(((uint64_t)m + (1u << kContigBlockShift) - 1u) >> kContigBlockShift);
+    PA_TRY(W.block_counts.reserve((uint64_t)n_blocks * 4 + 16));
+    hipLaunchKernelGGL(block_contig_kernel, dim3(ceil_div_u64(n_blocks, kThreads)), dim3(kThreads), 0, c->stream, W.mini_contig.as<uint32_t>(), m,
+                       W.block_counts.as<uint32_t>());
+    hipLaunchKernelGGL(postings_kernel, dim3(gm), dim3(kThreads), 0, c->stream, keys[which], vals[which], d_flags, d_pos, md,
+                       n_ids, W.mini_contig.as<uint32_t>(), W.mini_id.as<uint32_t>(), W.post_start.as<uint32_t>(),
+                       W.prev_same.as<int32_t>(), W.mini_wpos.as<uint32_t>(), W.contig_genome.as<uint32_t>(),
+                       W.post_cw.as<uint64_t>(), W.post_g.as<uint16_t>(), W.contig_mini_off.as<uint32_t>(), a.n_contigs,
+                       W.uniq_hash.as<uint32_t>(), W.block_counts.as<uint32_t>());
+    PA_TRY(cut_frequent_postings(c, W, d_flags, d_pos, vals[which], vals[1 - which], reinterpret_cast<uint32_t *>(keys[1 - which]), md, n_ids,
+                                 a.h_contig_genome, a.n_contigs, a.n_genomes));
+  } else {  // the reference genomes hold no minimizer: an empty dictionary
+    PA_TRY(W.post_start.reserve(16));
+    PA_TRY(W.uniq_hash.reserve(16));
+    PA_TRY(W.hash_cut.reserve(16));
+    PA_HIP(hipMemsetAsync(W.post_start.p, 0, 8, c->stream));
+    PA_HIP(hipMemsetAsync(W.hash_cut.p, 0, 8, c->stream));
+  }
+  W.index_ids = n_ids;
+  if (restricted) {
+    uint32_t bits = 10;
+    while ((1ull << bits) < 2ull * n_ids + 1) ++bits;
+    W.index_lookup_bits = bits;
+    PA_TRY(W.lookup_at.reserve((16ull << bits) + 16));
+    PA_HIP(hipMemsetAsync(W.lookup_at.p, 0xff, 16ull << bits, c->stream));
+    if (n_ids)
+      hipLaunchKernelGGL(lookup_insert_kernel, dim3(ceil_div_u64(n_ids, kThreads)), dim3(kThreads), 0, c->stream, W.uniq_hash.as<uint32_t>(),
+                         W.post_start.as<uint32_t>(), W.hash_cut.as<uint32_t>(), n_ids, bits, W.lookup_at.as<uint4>());
+  }
+  *which_out = which;
+  return PA_OK;
+}
+
+// The index (minimizers, bucket index, dictionary, postings) is complete: a later call may take it over.  A call that
+// took it over itself leaves the reference range the dictionary was built for as it is.
+void remember_index(FragWork &W, const FragCall &a, uint32_t m, int which) {
+  W.index_packed = a.d_packed; W.index_arena_bases = a.arena_bases; W.index_contigs = a.n_contigs; W.index_genomes = a.n_genomes;
+  W.index_k = a.k; W.index_frag_len = a.frag_len; W.index_m = m; W.index_which = which;
+  if (!a.reuse) { W.index_ref0 = a.ref0; W.index_ref1 = a.ref1; }
+  W.index_valid = true;
+}
+
+// ---- what the batches share: the tables by sketch size, the bins of the reference range, each genome's first contig,
+// which way the segments are listed
+int prepare_run(pa_ctx *c, FragWork &W, const FragCall &a, const FragLayout &L, FragRun &R) {
+  const uint32_t bin_base = L.genome_bin_off[a.ref0];
+  R.range_bins = std::max<uint32_t>(L.genome_bin_off[a.ref1] - bin_base, 1u);
+  // Mashmap's statistics per sketch size and the identity of every (shared, s): functions of k alone, ~10 ms of binomial
+  // tails and logarithms on the host -- made once per context and k (the device copies stay where they are), not in
+  // every call with the device waiting
+  if (W.tables_k != a.k) {
+    std::vector<uint32_t> mh(kQMax + 1), ms(kQMax + 1);
+    PA_TRY(pa_fragani_tables(a.k, kQMax, mh.data(), ms.data()));
+    std::vector<float> ident((uint64_t)(kQMax + 1) * (kQMax + 1), 0.0f);
+    for (uint32_t s = 1; s <= (uint32_t)kQMax; ++s)
+      for (uint32_t x = 0; x <= s; ++x) ident[(uint64_t)s * (kQMax + 1) + x] = (float)pa_fragani_identity(x, s, a.k);
+    W.tables_k = 0;
+    PA_TRY(upload(c, W.tab_min_hits, mh));
+    PA_TRY(upload(c, W.tab_min_shared, ms));
+    PA_TRY(upload(c, W.ident_tab, ident));
+    PA_HIP(hipStreamSynchronize(c->stream));  // (the vectors go out of scope)
+    W.tables_k = a.k;
+  }
+  // The table of best fragments per reference bin holds the bins of the reference range only (a worker asked for one
+  // subject column keeps 1 700 bins per query genome instead of 1.7 million): bin numbers relative to the range's first;
+  // genomes outside it get an empty run of bins, so the reduction gives them nothing, as an all-zero table did.
+  std::vector<uint32_t> cbo_rel(L.contig_bin_off.size()), gbo_rel(L.genome_bin_off.size());
+  for (size_t i = 0; i < L.contig_bin_off.size(); ++i) cbo_rel[i] = L.contig_bin_off[i] - std::min(L.contig_bin_off[i], bin_base);
+  for (size_t g = 0; g < L.genome_bin_off.size(); ++g)
+    gbo_rel[g] = std::min<uint32_t>(L.genome_bin_off[g] - std::min(L.genome_bin_off[g], bin_base), (uint32_t)R.range_bins);
+  PA_TRY(upload(c, W.contig_bin_off, cbo_rel));
+  PA_TRY(upload(c, W.genome_bin_off, gbo_rel));
+  PA_HIP(hipStreamSynchronize(c->stream));
+
+  if (const char *v = PA_TOOL_ENV("PA_FRAGANI_BATCH_HITS")) R.hit_limit = std::max<uint64_t>(1, strtoull(v, nullptr, 10));  // tests: force the halving
+  PA_TRY(W.scalars.reserve(kBatchScalarBytes));
+  // The bucketed pipeline needs an LDS counter per reference genome for each of a workgroup's waves and
+  // 16-bit fields for query window ids and for contigs within a genome; otherwise the sorted pipeline runs.
+  std::vector<uint32_t> gfc(a.n_genomes + 1, a.n_contigs);
+  uint32_t most_contigs = 0;
+  for (uint32_t ci = a.n_contigs; ci-- > 0;) gfc[a.h_contig_genome[ci]] = ci;
+  for (uint32_t g = a.n_genomes; g-- > 0;) if (gfc[g] == a.n_contigs) gfc[g] = gfc[g + 1];  // genome without contigs
+  for (uint32_t g = 0; g < a.n_genomes; ++g) most_contigs = std::max(most_contigs, gfc[g + 1] - gfc[g]);
+  bool genome_major = true;
+  for (uint32_t ci = 1; ci < a.n_contigs; ++ci) genome_major = genome_major && a.h_contig_genome[ci] >= a.h_contig_genome[ci - 1];
+  PA_REQUIRE(genome_major, "pa_fragani: contigs must be listed genome by genome");
+  PA_TRY(upload(c, W.genome_first_contig, gfc));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  R.trace = PA_TOOL_ENV("PA_FRAGANI_TRACE") != nullptr;  // per-batch sizes on stderr
+  const char *hits_env = PA_TOOL_ENV("PA_FRAGANI_HITS");  // PA_FRAGANI_HITS=sorted: the path of more than 8 192 genomes, for any number (tests)
+  const bool force_sorted = hits_env && hits_env[0] == 's';
+  const bool fields_fit = a.count_windows <= 0xffffu && most_contigs <= 0xffffu;
+  PA_REQUIRE(fields_fit, "pa_fragani: fragment length %u or %u contigs in one genome exceed the 16-bit fields of the "
+                         "mapping kernel", a.frag_len, most_contigs);
+  R.use_buckets = !force_sorted && (uint64_t)kBucketWaves * a.n_genomes * 4u <= 128u * 1024u;
+  // stretch capacity: the expected minimizers of one window (density 2 / (w + 1)) plus a third, in steps of 64
+  const uint32_t per_window = (uint32_t)(2.0 * a.count_windows / (a.w + 1.0));
+  R.ref_cap = std::min<uint32_t>(kRefCapMax, std::max<uint32_t>(256u, (per_window * 4u / 3u + 63u) / 64u * 64u));
+  PA_HIP(hipMemsetAsync(W.slot(kSketchOverflow), 0, kSketchOverflow.bytes(), c->stream));
+  return PA_OK;
+}
+
+// ---- one batch
+// The query genomes from g0 on whose fragments and whose table of best fragments fit a batch
+int choose_batch(const FragCall &a, const FragLayout &L, const FragRun &R, uint32_t g0, uint32_t batch_frags, FragBatch &B) {
+  const uint64_t kMaxTableBytes = 1ULL << 31;
+  uint32_t g1 = g0 + 1;
+  while (g1 < a.qry1 && L.genome_frag_off[g1 + 1] - L.genome_frag_off[g0] <= batch_frags &&
+         (uint64_t)(g1 + 1 - g0) * R.range_bins * 8 <= kMaxTableBytes)
+    ++g1;
+  B.g0 = g0; B.g1 = g1; B.nq = g1 - g0;
+  B.f0 = L.genome_frag_off[g0];
+  B.nf = L.genome_frag_off[g1] - B.f0;
+  PA_REQUIRE(B.nf < (1u << 20), "pa_fragani: genome %u alone has %u fragments (limit 2^20)", g0, B.nf);
+  return PA_OK;
+}
+
+// The batch's fragments on the device, room for their sketches, the batch's counters zeroed
+int stage_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragLayout &L, const FragRun &R, FragBatch &B) {
+  const uint32_t f0 = B.f0, nf = B.nf;
+  std::vector<uint32_t> fc(L.frag_contig.begin() + f0, L.frag_contig.begin() + f0 + nf),
+      fn(L.frag_no.begin() + f0, L.frag_no.begin() + f0 + nf), fg(nf);
+  for (uint32_t i = 0; i < nf; ++i) fg[i] = a.h_contig_genome[fc[i]] - B.g0;
+  PA_TRY(upload(c, W.frag_contig, fc));
+  PA_TRY(upload(c, W.frag_no, fn));
+  PA_TRY(upload(c, W.frag_genome_local, fg));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  // The batch's working arrays go into memory the index build has left behind wherever they fit (a fresh process pays
+  // ~65 ms per GB for the FIRST use of device memory -- more than the kernels of a whole 1 000-genome run for the 6 GB
+  // these are): the fragments' sketches into the sort's spare value buffer, the seed hits into its key buffers, the
+  // table of best fragments into the flag / scan scratch.  (All three are dead once the index stands, also for a call
+  // that takes the index over.)
+  const uint64_t per = (uint64_t)nf * kQMax;
+  DevBuf &spare = W.vals[1 - R.which];
+  if (spare.bytes >= 3 * per * 4) {
+    B.q_hash = spare.as<uint32_t>(); B.q_pos = B.q_hash + per; B.q_id = B.q_pos + per;
+  } else {
+    PA_TRY(W.q_hash.reserve(per * 4));
+    PA_TRY(W.q_pos.reserve(per * 4));
+    PA_TRY(W.q_id.reserve(per * 4));
+    B.q_hash = W.q_hash.as<uint32_t>(); B.q_pos = W.q_pos.as<uint32_t>(); B.q_id = W.q_id.as<uint32_t>();
+  }
+  PA_TRY(W.q_s.reserve((uint64_t)nf * 4));
+  PA_TRY(W.q_tab.reserve((uint64_t)nf * kQtBuckets * 2));  // the sketches' bucket tables
+  PA_TRY(W.q_cut.reserve((uint64_t)nf * 4));
+  PA_TRY(W.hit_count.reserve((uint64_t)nf * 4));
+  PA_TRY(W.hit_off.reserve((uint64_t)nf * 4));
+  PA_HIP(hipMemsetAsync(W.slot(kMaxHits), 0, kMaxHits.bytes(), c->stream));
+  return PA_OK;
+}
+
+// ---- 3. the fragments' sketches and the number of seed hits of each
+int seed_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, FragBatch &B) {
+  const uint32_t nf = B.nf;
+  PA_TRY(W.frag_d.reserve((uint64_t)nf * 4));
+  hipLaunchKernelGGL(windows_without_selection_kernel, dim3(ceil_div_u64(nf, kThreads)), dim3(kThreads), 0, c->stream, a.d_packed, a.d_mask,
+                     a.arena_bases, W.contig_start.as<uint64_t>(), a.k, (uint32_t)a.w, W.frag_contig.as<uint32_t>(), W.frag_no.as<uint32_t>(),
+                     nf, a.frag_len, a.count_windows, W.frag_d.as<uint32_t>(), W.ambiguous(a.d_packed));
+  hipLaunchKernelGGL(query_sketch_kernel, dim3(ceil_div_u64(nf, kThreads / 64)), dim3(kThreads), 0, c->stream, W.frag_d.as<uint32_t>(),
+                     W.frag_contig.as<uint32_t>(), W.frag_no.as<uint32_t>(), nf, a.frag_len, a.count_windows, W.contig_mini_off.as<uint32_t>(),
+                     W.contig_bucket_off.as<uint32_t>(), W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
+                     W.mini_id.as<uint32_t>(), W.post_start.as<uint32_t>(), B.q_hash, B.q_pos, B.q_id, W.q_s.as<uint32_t>(),
+                     W.hit_count.as<uint32_t>(), W.slot(kSketchOverflow), W.slot(kMaxHits), W.q_cut.as<uint32_t>(),
+                     R.restricted ? W.lookup_at.as<uint4>() : nullptr, W.index_lookup_bits, W.q_tab.as<uint32_t>());
+  PA_TRY(pa_exclusive_scan_u32(c, W.hit_count.as<uint32_t>(), W.hit_off.as<uint32_t>(), nf, W.slot<uint64_t>(kScanTotal)));
+  PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipMemcpyAsync(c->h_pinned + 1, W.slot(kMaxHits), kMaxHits.bytes(), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  B.n_hits = c->h_pinned[0];
+  B.max_hits = (uint32_t)c->h_pinned[1];
+  B.s_cap = std::min<uint32_t>(kQMax, (((uint32_t)(c->h_pinned[1] >> 32) + 63u) / 64u) * 64u);
+  return PA_OK;
+}
+
+// The batch's table of best fragments, zeroed: in the index build's flag / scan scratch where it fits
+int clear_table(pa_ctx *c, FragWork &W, const FragRun &R, FragBatch &B) {
+  const uint64_t bytes = (uint64_t)B.nq * R.range_bins * 8;
+  if (R.use_buckets && W.flags.bytes >= bytes) {
+    B.table = W.flags.as<unsigned long long>();  // (the sorted path keeps its head flags there)
+  } else {
+    PA_TRY(W.table.reserve(bytes));
+    B.table = W.table.as<unsigned long long>();
+  }
+  PA_HIP(hipMemsetAsync(B.table, 0, bytes, c->stream));
+  return PA_OK;
+}
+
+// ---- 4. seed hits and their segments
+// Room for the hits: in the sort's key buffers where they fit
+int begin_hits(FragWork &W, const FragBatch &B, SegLists &S) {
+  const bool hits_in_sort_keys = W.keys[0].bytes >= B.n_hits * 8;
+  if (!hits_in_sort_keys) PA_TRY(W.hkeys[0].reserve(B.n_hits * 8));
+  PA_TRY(W.hvals[0].reserve(B.n_hits * 4));  // (written by the paths that order the hits as a whole only)
+  S.hk[0] = hits_in_sort_keys ? W.keys[0].as<uint64_t>() : W.hkeys[0].as<uint64_t>();
+  S.hv[0] = W.hvals[0].as<uint32_t>();
+  PA_TRY(W.run_g.reserve(256));  // the mapping kernel's event counters (-DPA_MAP_STATS)
+  return PA_OK;
+}
+// The radix sort of a whole batch's hits (only it needs the ping-pong copies), over the key's 44 low bits and the fragment number above them
+int sort_all_hits(pa_ctx *c, FragWork &W, const FragBatch &B, SegLists &S) {
+  PA_TRY(W.hkeys[1].reserve(B.n_hits * 8));
+  PA_TRY(W.hvals[1].reserve(B.n_hits * 4));
+  S.hk[1] = W.hkeys[1].as<uint64_t>();
+  S.hv[1] = W.hvals[1].as<uint32_t>();
+  int bits = 44;
+  for (uint32_t x = B.nf; x > 1; x >>= 1) ++bits;
+  bits = (bits + 1 + 7) & ~7;
+  if (bits > 64) bits = 64;
+  return pa_radix_sort_pairs(c, S.hk, S.hv, B.n_hits, 0, bits, false, &S.hw);
+}
+
+// The launch shapes of the two bucketing kernels, and what a pass found
+struct BucketPass {
+  uint32_t seg_cap, lds_bytes, stage_cap, stage_lds;
+  bool stage_hits;
+  uint32_t n_big = 0, max_big = 0;  // segments too long for the register sort, the longest of them
+};
+int bucket_pass(pa_ctx *c, FragWork &W, const FragCall &a, const FragBatch &B, SegLists &S, BucketPass &P, bool write_all) {
+  uint32_t *d_seg_counters = W.slot(kSegCounters);
+  unsigned long long *d_cursor64 = W.slot<unsigned long long>(kSegCursor);
+  PA_HIP(hipMemsetAsync(d_seg_counters, 0, kSegCounters.bytes(), c->stream));
+  PA_HIP(hipMemsetAsync(d_cursor64, 0, kSegCursor.bytes(), c->stream));
+  if (P.stage_hits && !write_all)
+    hipLaunchKernelGGL(bucket_hits_staged_kernel, dim3(B.nf), dim3(kStageWaves * 64), P.stage_lds, c->stream, B.nf, B.q_pos, B.q_id,
+                       W.q_s.as<uint32_t>(), W.hit_off.as<uint32_t>(), W.post_g.as<uint16_t>(),
+                       W.post_cw.as<uint64_t>(), a.n_genomes, W.tab_min_hits.as<uint32_t>(), S.hk[0], W.seg_a0.as<uint32_t>(),
+                       W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), P.seg_cap, d_seg_counters, d_cursor64, a.ref0, a.ref1, P.stage_cap);
+  else
+    hipLaunchKernelGGL(bucket_hits_kernel, dim3(ceil_div_u64(B.nf, kBucketWaves)), dim3(kBucketWaves * 64), P.lds_bytes,
+                       c->stream, B.nf, B.q_pos, B.q_id, W.q_s.as<uint32_t>(),
+                       W.hit_off.as<uint32_t>(), W.post_g.as<uint16_t>(), W.post_cw.as<uint64_t>(), a.n_genomes,
+                       W.tab_min_hits.as<uint32_t>(), S.hk[0], S.hv[0],
+                       W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), P.seg_cap, d_seg_counters,
+                       d_cursor64, a.ref0, a.ref1, write_all);
+  PA_HIP(hipMemcpyAsync(c->h_pinned, d_seg_counters, kSegCounters.bytes(), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipMemcpyAsync(c->h_pinned + 2, d_cursor64, kSegCursor.bytes(), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  const uint32_t *hc32 = reinterpret_cast<const uint32_t *>(c->h_pinned);
+  S.n_keep = (uint32_t)c->h_pinned[2];
+  S.n_large = (uint32_t)(c->h_pinned[2] >> 32);
+  S.large_at = P.seg_cap - S.n_large;
+  P.n_big = hc32[1];
+  P.max_big = hc32[2];
+  PA_REQUIRE((uint64_t)S.n_keep + S.n_large <= P.seg_cap, "pa_fragani: %u + %u segments exceed the list capacity %u",
+             S.n_keep, S.n_large, P.seg_cap);
+  return PA_OK;
+}
+
+// hits bucketed by (fragment, reference genome); segments listed by the same kernel, the long ones at the end of the lists
+int list_segments_bucketed(pa_ctx *c, FragWork &W, const FragCall &a, const FragBatch &B, SegLists &S) {
+  PA_TRY(begin_hits(W, B, S));
+  const uint32_t n_genomes = a.n_genomes;
+  BucketPass P;
+  const uint64_t seg_cap64 = std::min<uint64_t>(B.n_hits, (uint64_t)B.nf * n_genomes);
+  P.seg_cap = (uint32_t)std::min<uint64_t>(seg_cap64, 0xfffffff0ull);
+  PA_TRY(W.seg_a0.reserve((uint64_t)P.seg_cap * 4 + 16));
+  PA_TRY(W.seg_nh.reserve((uint64_t)P.seg_cap * 4 + 16));
+  PA_TRY(W.seg_f.reserve((uint64_t)P.seg_cap * 4 + 16));
+  P.lds_bytes = (uint32_t)kBucketWaves * n_genomes * 4u;
+  PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bucket_hits_kernel),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_bytes));
+  // one fragment per workgroup with the listed pairs' hits staged in LDS (whole-sector writes) when the two per-genome
+  // arrays leave room for a staging area; the batch that is about to be ordered as a whole (write_all) keeps the
+  // wave-per-fragment form, which writes every slot
+  // (four workgroups of eight waves per CU: 40 KB of LDS each)
+  const uint32_t lds_room = 40u * 1024u;
+  P.stage_cap = n_genomes * 8u + 8192u <= lds_room ? ((lds_room - n_genomes * 8u) / 8u) & ~63u : 0u;
+  P.stage_lds = P.stage_cap * 8u + n_genomes * 8u;
+  P.stage_hits = P.stage_cap >= 1024u;
+  if (P.stage_hits)
+    PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bucket_hits_staged_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.stage_lds));
+  PA_TRY(bucket_pass(c, W, a, B, S, P, false));
+  S.presorted = false;
+  uint32_t frag_sort_max = kFragSortMax;  // tests: PA_FRAGANI_SORT_MAX=600 sends a 60-copy repeat family down this path
+  if (const char *v = PA_TOOL_ENV("PA_FRAGANI_SORT_MAX")) frag_sort_max = (uint32_t)std::max(1, atoi(v));
+  if (P.n_big && P.max_big > frag_sort_max) {
+    // a repeat family with more hits than one LDS sort takes: order the whole batch by key; the
+    // (fragment, genome) slices keep their places because contigs are numbered genome by genome -- provided every
+    // slot holds its own key, so the bucketing runs again and this time also writes the hits of the pairs that are
+    // not listed (they are skipped otherwise: unwritten slots would be sorted into other fragments' ranges)
+    PA_TRY(bucket_pass(c, W, a, B, S, P, true));
+    PA_TRY(sort_all_hits(c, W, B, S));
+    S.presorted = true;
+  } else if (P.n_big) {
+    const uint32_t n_big = P.n_big;
+    PA_TRY(W.seg_list.reserve((uint64_t)n_big * 8 + 16));
+    uint32_t *big_a0 = W.seg_list.as<uint32_t>(), *big_nh = big_a0 + n_big;
+    PA_HIP(hipMemsetAsync(W.slot(kBigCursor), 0, kBigCursor.bytes(), c->stream));
+    hipLaunchKernelGGL(big_segments_kernel, dim3(ceil_div_u64(S.n_large, kThreads)), dim3(kThreads), 0, c->stream,
+                       W.seg_a0.as<uint32_t>() + S.large_at, W.seg_nh.as<uint32_t>() + S.large_at, S.n_large, big_a0,
+                       big_nh, W.slot(kBigCursor));
+    uint32_t np2_max = 2;
+    while (np2_max < P.max_big) np2_max <<= 1;
+    const uint32_t sort_lds = np2_max * 12u;
+    PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(frag_sort_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
+    hipLaunchKernelGGL(frag_sort_kernel, dim3(n_big), dim3(kFragSortThreads), sort_lds, c->stream, S.hk[0], S.hv[0],
+                       big_a0, big_nh, np2_max, 64u - kHitRankShift + 11u);  // (contig, window id) to the top, the rank below
+  }
+  return PA_OK;
+}
+
+// general path (more than 8 192 genomes): all hits sorted by key, segments from head flags
+int list_segments_sorted(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, const FragBatch &B, SegLists &S) {
+  PA_TRY(begin_hits(W, B, S));
+  const uint64_t n_hits = B.n_hits;
+  hipLaunchKernelGGL(fill_hits_kernel, dim3(ceil_div_u64(B.nf, kThreads / 64)), dim3(kThreads), 0, c->stream, B.nf, B.q_pos,
+                     B.q_id, W.q_s.as<uint32_t>(), W.hit_off.as<uint32_t>(),
+                     W.post_start.as<uint32_t>(), W.vals[R.which].as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
+                     W.mini_contig.as<uint32_t>(), S.hk[0], S.hv[0]);
+  if (B.max_hits <= kFragSortMax) {  // every fragment's hits fit one LDS sort
+    uint32_t np2_max = 2;
+    while (np2_max < B.max_hits) np2_max <<= 1;
+    const uint32_t lds_bytes = np2_max * 12u;
+    PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(frag_sort_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(frag_sort_kernel, dim3(B.nf), dim3(kFragSortThreads), lds_bytes, c->stream, S.hk[0], S.hv[0],
+                       W.hit_off.as<uint32_t>(), W.hit_count.as<uint32_t>(), np2_max, 0u);
+  } else {
+    PA_TRY(sort_all_hits(c, W, B, S));
+  }
+  PA_TRY(W.flags.reserve(n_hits * 8 + 64));
+  uint32_t *hf = W.flags.as<uint32_t>(), *hp = hf + n_hits;
+  const uint32_t gh = ceil_div_u64(n_hits, kThreads);
+  hipLaunchKernelGGL(segment_heads_kernel, dim3(gh), dim3(kThreads), 0, c->stream, S.hk[S.hw], (uint32_t)n_hits,
+                     W.contig_genome.as<uint32_t>(), hf);
+  PA_TRY(pa_exclusive_scan_u32(c, hf, hp, n_hits, W.slot<uint64_t>(kScanTotal)));
+  PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  const uint32_t n_segs = (uint32_t)c->h_pinned[0];
+  PA_TRY(W.seg_start.reserve((uint64_t)(n_segs + 2) * 4));
+  hipLaunchKernelGGL(segment_starts_kernel, dim3(gh), dim3(kThreads), 0, c->stream, hf, hp, (uint32_t)n_hits,
+                     W.seg_start.as<uint32_t>());
+  // most segments are chance hits of unrelated genomes (fewer hits than any L1 run needs): drop them
+  // here, one thread each, instead of spending a workgroup launch on each in the mapping kernel
+  const uint32_t gs = ceil_div_u64(n_segs, kThreads);
+  hipLaunchKernelGGL(segment_keep_kernel, dim3(gs), dim3(kThreads), 0, c->stream, S.hk[S.hw],
+                     W.seg_start.as<uint32_t>(), n_segs, W.q_s.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(),
+                     W.contig_genome.as<uint32_t>(), a.ref0, a.ref1, hf);
+  PA_TRY(pa_exclusive_scan_u32(c, hf, hp, n_segs, W.slot<uint64_t>(kScanTotal)));
+  PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  S.n_keep = (uint32_t)c->h_pinned[0];
+  PA_TRY(W.seg_list.reserve((uint64_t)(S.n_keep + 1) * 4));
+  PA_TRY(W.seg_a0.reserve((uint64_t)S.n_keep * 4 + 16));
+  PA_TRY(W.seg_nh.reserve((uint64_t)S.n_keep * 4 + 16));
+  hipLaunchKernelGGL(segment_list_kernel, dim3(gs), dim3(kThreads), 0, c->stream, hf, hp, n_segs,
+                     W.seg_list.as<uint32_t>());
+  if (S.n_keep)
+    hipLaunchKernelGGL(segments_from_list_kernel, dim3(ceil_div_u64(S.n_keep, kThreads)), dim3(kThreads), 0, c->stream,
+                       W.seg_start.as<uint32_t>(), W.seg_list.as<uint32_t>(), S.n_keep, W.seg_a0.as<uint32_t>(),
+                       W.seg_nh.as<uint32_t>());
+  return PA_OK;
+}
+
+// ---- 4. (continued) mapping
+// One list of segments through segment_records_kernel and the general mapping kernel.  kAll: every segment's hits fit the
+// smaller LDS footprint.
+#define PA_MAP_CASE(CAP)                                                                                                  \
+  case CAP:                                                                                                               \
+    hipLaunchKernelGGL((map_segments_kernel<CAP, kAll>), dim3(count), dim3(64), eval_lds_bytes(B.s_cap, hit_cap, CAP) + PA_MAP_LDS_PAD, c->stream,  \
+                       S.hk[S.hw], S.hv[S.hw], W.seg_rec.as<uint4>(), count, S.presorted, B.q_hash, W.q_tab.as<uint32_t>(), \
+                       W.frag_genome_local.as<uint32_t>(), a.frag_len, a.count_windows,                                    \
+                       W.tab_min_shared.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(),                                  \
+                       W.contig_bucket_off.as<uint32_t>(), W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(),      \
+                       W.mini_wpos.as<uint32_t>(), W.prev_same.as<int32_t>(), W.contig_bin_off.as<uint32_t>(), R.range_bins, \
+                       B.table, W.run_g.as<uint32_t>(), B.s_cap, hit_cap PA_MAP_CUT_ARG);                                  \
+    break;
+template <bool kAll>
+int launch_map(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, const FragBatch &B, const SegLists &S,
+               const uint32_t *list_a0, const uint32_t *list_nh, const uint32_t *list_f, uint32_t count, uint32_t hit_cap) {
+  if (count == 0) return PA_OK;
+#ifdef PA_TOOLS
+  const char *cut_env = PA_TOOL_ENV("PA_MAP_CUT");  // tools: the mapping kernel cut short after a phase (timing by difference)
+  const uint32_t map_cut = cut_env ? (uint32_t)atoi(cut_env) : 0xffffffffu;
+#endif
+  PA_TRY(W.seg_rec.reserve((uint64_t)count * 48));
+  hipLaunchKernelGGL(segment_records_kernel, dim3(ceil_div_u64(count, kThreads)), dim3(kThreads), 0, c->stream, S.hk[S.hw],
+                     list_a0, list_nh, list_f, count, W.q_s.as<uint32_t>(), W.q_cut.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(),
+                     W.tab_min_shared.as<uint32_t>(), W.contig_genome.as<uint32_t>(), W.genome_first_contig.as<uint32_t>(),
+                     W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(), W.frag_genome_local.as<uint32_t>(), W.seg_rec.as<uint4>());
+  switch (R.ref_cap) {
+    PA_MAP_CASE(256) PA_MAP_CASE(320) PA_MAP_CASE(384) PA_MAP_CASE(448)
+    default: PA_MAP_CASE(512)
+  }
+  return PA_OK;
+}
+#undef PA_MAP_CASE
+
+// The bucketed lists' short segments: the tiny-segment filter, then those of at most kSparseHits hits through
+// map_sparse_kernel and the rest -- and what the sparse kernel hands on -- through the general kernel
+int map_short_segments(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, const FragBatch &B, const SegLists &S) {
+  const uint32_t n_keep = S.n_keep;
+  PA_TRY(W.seg2_a0.reserve((uint64_t)n_keep * 4 + 16));
+  PA_TRY(W.seg2_nh.reserve((uint64_t)n_keep * 4 + 16));
+  PA_TRY(W.seg2_f.reserve((uint64_t)n_keep * 4 + 16));
+  // segments of at most kSparseHits hits go to map_sparse_kernel (listed from the back of the same arrays), unless
+  // the hits carry their ranks in the sort's payload (a batch ordered as a whole)
+  uint32_t sparse_max = S.presorted ? 0u : kSparseHits;
+  // tests: 0 = every segment through the general kernel (the switch can only take the sparse kernel away: its key layout
+  // is the bucketed one)
+  if (const char *v = PA_TOOL_ENV("PA_FRAGANI_SPARSE")) sparse_max = (atoi(v) && !S.presorted) ? kSparseHits : 0u;
+  unsigned long long *d_pre_cursor = W.slot<unsigned long long>(kPreCursor);
+  PA_HIP(hipMemsetAsync(d_pre_cursor, 0, kPreCursor.bytes(), c->stream));
+  hipLaunchKernelGGL(prefilter_segments_kernel, dim3(ceil_div_u64(n_keep, kThreads)), dim3(kThreads), 0, c->stream,
+                     S.hk[S.hw], W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), n_keep,
+                     W.q_s.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(), W.q_cut.as<uint32_t>(), a.frag_len, W.seg2_a0.as<uint32_t>(),
+                     W.seg2_nh.as<uint32_t>(), W.seg2_f.as<uint32_t>(), d_pre_cursor, sparse_max);
+  PA_HIP(hipMemcpyAsync(c->h_pinned, d_pre_cursor, kPreCursor.bytes(), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  const uint32_t n_small = (uint32_t)c->h_pinned[0], n_sparse = (uint32_t)(c->h_pinned[0] >> 32);
+  if (R.trace)
+    fprintf(stderr, "pa_fragani: genomes %u..%u: %u fragments, %llu seed hits, %u + %u listed segments, %u left "
+                    "after the tiny-segment filter\n", B.g0, B.g1, B.nf, (unsigned long long)B.n_hits, n_keep, S.n_large, n_small);
+  PA_TRY(launch_map<true>(c, W, a, R, B, S, W.seg2_a0.as<uint32_t>(), W.seg2_nh.as<uint32_t>(), W.seg2_f.as<uint32_t>(), n_small,
+                          (uint32_t)kHitCapSmall));
+  if (n_sparse == 0) return PA_OK;
+  const uint32_t at = n_keep - n_sparse;  // the sparse list sits at the back of the same arrays
+  PA_TRY(W.seg_over.reserve((uint64_t)n_sparse * 12 + 16));
+  uint32_t *over_a0 = W.seg_over.as<uint32_t>(), *over_nh = over_a0 + n_sparse, *over_f = over_nh + n_sparse;
+  uint32_t *d_over_n = W.slot(kSparseOver);
+  PA_HIP(hipMemsetAsync(d_over_n, 0, kSparseOver.bytes(), c->stream));
+  hipLaunchKernelGGL(map_sparse_kernel, dim3(n_sparse), dim3(64), 0, c->stream, S.hk[S.hw], W.seg2_a0.as<uint32_t>() + at,
+                     W.seg2_nh.as<uint32_t>() + at, W.seg2_f.as<uint32_t>() + at, n_sparse, W.q_s.as<uint32_t>(), B.q_hash,
+                     W.frag_genome_local.as<uint32_t>(), a.frag_len, a.count_windows, W.tab_min_hits.as<uint32_t>(),
+                     W.tab_min_shared.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(),
+                     W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
+                     W.prev_same.as<int32_t>(), W.contig_bin_off.as<uint32_t>(), R.range_bins, B.table, over_a0, over_nh, over_f,
+                     d_over_n
+#ifdef PA_MAP_STATS
+                     , W.run_g.as<uint32_t>()
+#endif
+  );
+  PA_HIP(hipMemcpyAsync(c->h_pinned, d_over_n, kSparseOver.bytes(), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  const uint32_t n_over = *reinterpret_cast<const uint32_t *>(c->h_pinned);
+  if (R.trace) fprintf(stderr, "pa_fragani: %u segments of at most %u hits in the sparse kernel, %u of them handed on\n", n_sparse, kSparseHits, n_over);
+  // what does not fit the simple form (a hash twice in a stretch, over-long windows or ranges) goes through the general kernel
+  return launch_map<true>(c, W, a, R, B, S, over_a0, over_nh, over_f, n_over, (uint32_t)kHitCapSmall);
+}
+
+int map_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, const FragBatch &B, const SegLists &S) {
+#ifdef PA_MAP_STATS
+  PA_HIP(hipMemsetAsync(W.run_g.p, 0, 256, c->stream));
+#endif
+  if (!R.use_buckets)
+    return launch_map<false>(c, W, a, R, B, S, W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), nullptr, S.n_keep, (uint32_t)kHitCap);
+  if (S.n_keep) PA_TRY(map_short_segments(c, W, a, R, B, S));
+  return launch_map<false>(c, W, a, R, B, S, W.seg_a0.as<uint32_t>() + S.large_at, W.seg_nh.as<uint32_t>() + S.large_at,
+                           W.seg_f.as<uint32_t>() + S.large_at, S.n_large, (uint32_t)kHitCap);
+}
+
+#ifdef PA_MAP_STATS
+// the event counters of the two mapping kernels (PA_FRAGANI_TRACE)
+int print_map_stats(const FragWork &W) {
+  uint32_t st[64];
+  PA_HIP(hipMemcpy(st, W.run_g.p, 256, hipMemcpyDeviceToHost));
+  fprintf(stderr, "pa_fragani: map stats: %u segments at L1 with %u hits, %u candidates, %u groups, %u begins past the bound, "
+                  "%u rounds, %u stretch entries, %u windows evaluated, %u fine passes, %u cooperative, %u begins in rounds, "
+                  "%u begins finished, %u rounds without items, %u second passes, %u windows with an exact value, %u of them at or above the bar, "
+                  "%u begins dropped by the tight bound, %u rounds ended by it; rounds by seed hits of the segment (<= 7, 8-15, 16-31, 32-63, "
+                  "64-127, 128-255, more): %u %u %u %u %u %u %u, segments: %u %u %u %u %u %u %u; work model: %u minimizers in the candidates' ranges, "
+                  "%u states tying their candidate's optimum; past the tight bound: %u rounds, %u begins, %u windows, %u of them at or above the bar; %u begins dropped by the bound asked at a round's end; %u segments that are one run of hits (no L1 scan) with %u hits; hits within 4096 window ids on one contig (ordered by counting): %u segments, all but one hit: %u, all but two: %u\n",
+          st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11], st[12], st[13], st[14], st[15], st[16], st[17],
+          st[18], st[19], st[20], st[21], st[22], st[23], st[24], st[25], st[26], st[27], st[28], st[29], st[30], st[31], st[32], st[33], st[40], st[39], st[37], st[38], st[41], st[42], st[46], st[43], st[44], st[45]);
+  fprintf(stderr, "pa_fragani: sparse stats: %u segments with a candidate, %u candidates, %u groups of begins evaluated, %u begins, %u states, %u begins tying "
+                  "their candidate's best when folded; %u one-run segments with strays; %u begins with enough hits left out because they lie between two tying begins and hold no more hits than those share, %u groups between the ties passed over unseen, %u groups that hold a candidate's first or last tying begin, %u candidates whose first hit lies past the batch of 512 window ids\n",
+          st[48], st[49], st[50], st[51], st[52], st[53], st[47], st[58], st[59], st[54], st[55]);
+  return PA_OK;
+}
+#endif
+
+// ---- 5. per pair of the batch: kept fragments and the sum of their identities
+int reduce_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, const FragBatch &B) {
+  PA_TRY(W.matched.reserve((uint64_t)B.nq * a.n_genomes * 4));
+  PA_TRY(W.ident_sum.reserve((uint64_t)B.nq * a.n_genomes * 8));
+  hipLaunchKernelGGL(reduce_pairs_kernel, dim3(B.nq * a.n_genomes), dim3(64), 0, c->stream,
+                     B.table, R.range_bins, W.genome_bin_off.as<uint32_t>(), a.n_genomes,
+                     W.ident_tab.as<float>(), W.matched.as<uint32_t>(), W.ident_sum.as<double>());
+  PA_HIP(hipGetLastError());
+  return PA_OK;
+}
+// the batch's rows of the two result matrices to the host: whole, or the columns of the reference range only
+int copy_out_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragBatch &B) {
+  const uint32_t n_genomes = a.n_genomes, out_cols = a.out_cols, nq = B.nq;
+  if (out_cols == n_genomes) {
+    PA_HIP(hipMemcpyAsync(a.h_matched + (uint64_t)B.g0 * n_genomes, W.matched.p, (uint64_t)nq * n_genomes * 4,
+                          hipMemcpyDeviceToHost, c->stream));
+    PA_HIP(hipMemcpyAsync(a.h_ident_sum + (uint64_t)B.g0 * n_genomes, W.ident_sum.p, (uint64_t)nq * n_genomes * 8,
+                          hipMemcpyDeviceToHost, c->stream));
+  } else if (out_cols) {
+    PA_HIP(hipMemcpy2DAsync(a.h_matched + (uint64_t)B.g0 * out_cols, (size_t)out_cols * 4, W.matched.as<uint32_t>() + a.out_col0,
+                            (size_t)n_genomes * 4, (size_t)out_cols * 4, nq, hipMemcpyDeviceToHost, c->stream));
+    PA_HIP(hipMemcpy2DAsync(a.h_ident_sum + (uint64_t)B.g0 * out_cols, (size_t)out_cols * 8, W.ident_sum.as<double>() + a.out_col0,
+                            (size_t)n_genomes * 8, (size_t)out_cols * 8, nq, hipMemcpyDeviceToHost, c->stream));
+  }
+  PA_HIP(hipStreamSynchronize(c->stream));
+  return PA_OK;
+}
+
+// ---- the pipeline
+int fragani_ex_impl(pa_ctx *c, FragCall &a) {
+  PA_TRY(check_call(c, a));
+  FragWork &W = frag_work(c);
+  PA_TRY(stage_contigs(c, W, a.h_contig_start, a.h_contig_len, a.h_contig_genome, a.n_contigs, a.n_genomes, a.arena_bases));
+  if (a.reuse) {
+    bool no_fragments = false;
+    PA_TRY(check_reuse(W, a, &no_fragments));
+    if (no_fragments) return PA_OK;
+  }
+
+  // the reference index: built (stages 1 and 2), or the last call's taken over
+  std::optional<ProfScope> prof;  // phases timed for bench.py: index build, seeding, mapping
+  W.index_valid = false;          // until this call has passed stage 2 (or taken it over)
+  prof.emplace(c, PA_PROF_FRAG_INDEX);
+  FragLayout L;
+  FragRun R;
+  uint32_t m = W.index_m;
+  if (a.reuse) layout_fragments(a, L);
+  else PA_TRY(build_minimizers(c, W, a, L, &m));
+  if (m == 0 || L.frag_contig.empty()) {  // nothing to map (and nothing a later call could not take over)
+    prof.reset();
+    PA_HIP(hipStreamSynchronize(c->stream));
+    if (m == 0) remember_index(W, a, m, 0);
+    return PA_OK;
+  }
+  R.which = W.index_which;
+  if (!a.reuse) PA_TRY(build_dictionary(c, W, a, m, &R.which));
+  remember_index(W, a, m, R.which);
+  R.restricted = !(W.index_ref0 == 0 && W.index_ref1 == a.n_genomes);
+  PA_TRY(prepare_run(c, W, a, L, R));
+  prof.reset();
+
+  // batches of query genomes
+  uint32_t batch_frags = PA_FRAGANI_BATCH_FRAGS;
+  for (uint32_t g0 = a.qry0; g0 < a.qry1;) {
+    FragBatch B;
+    PA_TRY(choose_batch(a, L, R, g0, batch_frags, B));
+    if (B.nf == 0) { g0 = B.g1; continue; }
+    PA_TRY(stage_batch(c, W, a, L, R, B));
+    prof.emplace(c, PA_PROF_FRAG_SEED);
+    PA_TRY(seed_batch(c, W, a, R, B));
+    if (B.n_hits >= R.hit_limit && B.nq > 1) {  // closely related or repetitive genomes: fewer query genomes per batch
+      batch_frags = std::max<uint32_t>(1u, std::min(batch_frags, B.nf) / 2u);
+      prof.reset();
+      continue;  // the same g0 again
+    }
+    if (R.trace) fprintf(stderr, "pa_fragani: batch of genomes %u..%u: %u fragments, %llu seed hits\n", B.g0, B.g1, B.nf, (unsigned long long)B.n_hits);
+    PA_REQUIRE(B.n_hits < (1ULL << 31), "pa_fragani: %llu seed hits for the fragments of genome %u alone (limit 2^31); highly "
+               "repetitive input", (unsigned long long)B.n_hits, g0);
+    PA_TRY(clear_table(c, W, R, B));
+    if (B.n_hits) {
+      SegLists S;
+      if (R.use_buckets) PA_TRY(list_segments_bucketed(c, W, a, B, S));
+      else PA_TRY(list_segments_sorted(c, W, a, R, B, S));
+      prof.reset();
+      prof.emplace(c, PA_PROF_FRAG_MAP);
+      PA_TRY(map_batch(c, W, a, R, B, S));
+#ifdef PA_MAP_STATS
+      if (R.trace) PA_TRY(print_map_stats(W));
+#endif
+    }
+    PA_TRY(reduce_batch(c, W, a, R, B));
+    prof.reset();
+    PA_TRY(copy_out_batch(c, W, a, B));
+    g0 = B.g1;
+  }
+  uint32_t h_over[2] = {0, 0};
+  PA_HIP(hipMemcpy(h_over, W.slot(kSketchOverflow), kSketchOverflow.bytes(), hipMemcpyDeviceToHost));
+  if (h_over[0]) {
+    pa_set_error("pa_fragani: %u fragment sketches exceeded %d minimizers (fragLen too long for this window); "
+                 "those sketches were truncated", h_over[0], kQMax);
+    return PA_E_CAPACITY;
+  }
   return PA_OK;
 }
 
@@ -544,665 +1372,25 @@ int pa_fragani(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, uint
                        n_genomes, k, frag_len, 0, n_genomes, ref0, ref1, 0, h_total_frags, h_matched, h_ident_sum);
 }
 
-static int fragani_ex_impl(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, uint64_t arena_bases,
-                           const uint64_t *h_contig_start, const uint32_t *h_contig_len, const uint32_t *h_contig_genome,
-                           uint32_t n_contigs, uint32_t n_genomes, uint32_t k, uint32_t frag_len, uint32_t qry0, uint32_t qry1,
-                           uint32_t ref0, uint32_t ref1, uint32_t flags, uint32_t *h_total_frags, uint32_t *h_matched,
-                           double *h_ident_sum);
 int pa_fragani_ex(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, uint64_t arena_bases,
                   const uint64_t *h_contig_start, const uint32_t *h_contig_len, const uint32_t *h_contig_genome,
                   uint32_t n_contigs, uint32_t n_genomes, uint32_t k, uint32_t frag_len, uint32_t qry0, uint32_t qry1,
                   uint32_t ref0, uint32_t ref1, uint32_t flags, uint32_t *h_total_frags, uint32_t *h_matched,
                   double *h_ident_sum) {
-  const int status = fragani_ex_impl(c, d_packed, d_mask, arena_bases, h_contig_start, h_contig_len, h_contig_genome, n_contigs, n_genomes, k,
-                                     frag_len, qry0, qry1, ref0, ref1, flags, h_total_frags, h_matched, h_ident_sum);
+  FragCall call{d_packed, d_mask, arena_bases, h_contig_start, h_contig_len, h_contig_genome, n_contigs, n_genomes, k,
+                frag_len, qry0, qry1, ref0, ref1, flags, h_total_frags, h_matched, h_ident_sum};
+  const int status = fragani_ex_impl(c, call);
   if (status == PA_E_NOMEM && c && c->frag_work) {
     // A call that ends for want of memory -- the cap, or the device -- gives back what the workspace held (the buffers that
     // had grown for it included), so that a smaller call starts from nothing instead of from a half-grown workspace; the
     // index of an earlier call goes with it.  The list of residues that are neither ACGT nor N stays (a few bytes).
     FragWork &W = frag_work(c);
     (void)hipStreamSynchronize(c->stream);
-    W.each_buffer([&](DevBuf &b) { if (&b != &W.amb_pos && &b != &W.amb_byte) b.release(); });
+    W.each_buffer([&W](DevBuf &b) { if (&b != &W.amb_pos && &b != &W.amb_byte) b.release(); });
     W.index_valid = false;
     W.tables_k = 0;
   }
   return status;
-}
-
-static int fragani_ex_impl(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, uint64_t arena_bases,
-                           const uint64_t *h_contig_start, const uint32_t *h_contig_len, const uint32_t *h_contig_genome,
-                           uint32_t n_contigs, uint32_t n_genomes, uint32_t k, uint32_t frag_len, uint32_t qry0, uint32_t qry1,
-                           uint32_t ref0, uint32_t ref1, uint32_t flags, uint32_t *h_total_frags, uint32_t *h_matched,
-                           double *h_ident_sum) {
-  PA_REQUIRE(c && d_packed && d_mask && h_total_frags && h_matched && h_ident_sum, "pa_fragani: null argument");
-  PA_REQUIRE(ref0 <= ref1 && ref1 <= n_genomes, "pa_fragani: reference range [%u,%u) outside [0,%u)", ref0, ref1, n_genomes);
-  PA_REQUIRE(qry0 <= qry1 && qry1 <= n_genomes, "pa_fragani: query range [%u,%u) outside [0,%u)", qry0, qry1, n_genomes);
-  PA_REQUIRE(n_genomes <= 0xffffu, "pa_fragani: %u genomes (limit 65 535: a posting names its genome in 16 bits)", n_genomes);
-  PA_REQUIRE((flags & ~(uint32_t)(PA_FRAGANI_REUSE_INDEX | PA_FRAGANI_COLUMNS_ONLY)) == 0, "pa_fragani: unknown flags 0x%x", flags);
-  // the row length of the two result matrices on the host, and the first column they hold
-  const uint32_t out_cols = (flags & PA_FRAGANI_COLUMNS_ONLY) ? ref1 - ref0 : n_genomes;
-  const uint32_t out_col0 = (flags & PA_FRAGANI_COLUMNS_ONLY) ? ref0 : 0u;
-  PA_REQUIRE(frag_len >= 100 && frag_len <= 0xffffu, "pa_fragani: fragLen %u outside [100, 65535]", frag_len);
-  PA_HIP(hipSetDevice(c->device));
-  const int w = window_size_for((int)k, (int)frag_len);
-  PA_REQUIRE(w >= 1 && w <= 64, "pa_fragani: winnowing window %d outside [1,64] for k=%u fragLen=%u", w, k, frag_len);
-  PA_REQUIRE((int)frag_len > w + (int)k, "pa_fragani: fragLen %u too short for window %d", frag_len, w);
-  const uint32_t count_windows = frag_len - (uint32_t)(w - 1) - (k - 1);
-  FragWork &W = frag_work(c);
-  snprintf(W.budget.what, sizeof(W.budget.what), "pa_fragani: %u genomes (%llu residues of arena), queries [%u,%u), reference range [%u,%u), fragLen %u",
-           n_genomes, (unsigned long long)arena_bases, qry0, qry1, ref0, ref1, frag_len);
-  PA_TRY(stage_contigs(c, W, h_contig_start, h_contig_len, h_contig_genome, n_contigs, n_genomes, arena_bases));
-
-  // ---- 1. minimizers of every contig
-  std::optional<ProfScope> prof;  // phases timed for bench.py: index build, seeding, mapping
-  const bool reuse = (flags & PA_FRAGANI_REUSE_INDEX) != 0;
-  {
-    // no contig holds a fragment: every pair is 0 of 0, whatever index an earlier call left (or did not leave) behind
-    uint64_t any_frags = 0;
-    for (uint32_t ci = 0; ci < n_contigs; ++ci) any_frags += h_contig_len[ci] / frag_len;
-    if (reuse && any_frags == 0) {
-      for (uint32_t g = 0; g < n_genomes; ++g) h_total_frags[g] = 0;
-      for (uint64_t i = (uint64_t)qry0 * out_cols; i < (uint64_t)qry1 * out_cols; ++i) { h_matched[i] = 0; h_ident_sum[i] = 0.0; }
-      return PA_OK;
-    }
-  }
-  if (reuse) {
-    PA_REQUIRE(W.index_valid && W.index_packed == (const void *)d_packed && W.index_arena_bases == arena_bases &&
-                   W.index_contigs == n_contigs && W.index_genomes == n_genomes && W.index_k == k && W.index_frag_len == frag_len &&
-                   W.index_ref0 <= ref0 && ref1 <= W.index_ref1,
-               "pa_fragani: PA_FRAGANI_REUSE_INDEX without a preceding call on the same arena, contigs, k and fragLen whose "
-               "reference range holds this one");
-  }
-  // ---- fragments and reference bins (host bookkeeping: some 10 ms for the 1.7 million fragments and the two result
-  // matrices of 1 000 genomes -- done while minimizer_kernel runs, not before or after it with the device idle)
-  std::vector<uint32_t> frag_contig, frag_no, genome_frag_off(n_genomes + 1, 0), contig_bin_off(n_contigs + 1, 0),
-      genome_bin_off(n_genomes + 1, 0);
-  const std::function<void()> bookkeeping = [&]() {
-    for (uint32_t g = 0; g < n_genomes; ++g) h_total_frags[g] = 0;
-    uint64_t all_frags = 0;
-    for (uint32_t ci = 0; ci < n_contigs; ++ci) all_frags += h_contig_len[ci] / frag_len;
-    frag_contig.resize(all_frags);
-    frag_no.resize(all_frags);
-    uint64_t at = 0;
-    for (uint32_t ci = 0; ci < n_contigs; ++ci) {
-      const uint32_t nf = h_contig_len[ci] / frag_len;
-      for (uint32_t f = 0; f < nf; ++f) { frag_contig[at + f] = ci; frag_no[at + f] = f; }
-      at += nf;
-      h_total_frags[h_contig_genome[ci]] += nf;
-      contig_bin_off[ci + 1] = contig_bin_off[ci] + h_contig_len[ci] / (frag_len - 20u) + 2;
-    }
-    for (uint32_t g = 0; g < n_genomes; ++g) genome_frag_off[g + 1] = genome_frag_off[g] + h_total_frags[g];
-    {
-      uint32_t ci = 0;
-      for (uint32_t g = 0; g < n_genomes; ++g) {
-        genome_bin_off[g] = contig_bin_off[ci];
-        while (ci < n_contigs && h_contig_genome[ci] == g) ++ci;
-      }
-      genome_bin_off[n_genomes] = contig_bin_off[n_contigs];
-    }
-    memset(h_matched + (uint64_t)qry0 * out_cols, 0, (uint64_t)(qry1 - qry0) * out_cols * sizeof(uint32_t));
-    for (uint64_t i = (uint64_t)qry0 * out_cols; i < (uint64_t)qry1 * out_cols; ++i) h_ident_sum[i] = 0.0;
-  };
-  W.index_valid = false;  // until this call has passed stage 2 (or taken it over)
-  prof.emplace(c, PA_PROF_FRAG_INDEX);
-  uint32_t m = reuse ? W.index_m : 0;
-  if (!reuse) {
-  PA_TRY(dispatch_minimizers(c, W, d_packed, d_mask, arena_bases, n_contigs, k, w, &m, &bookkeeping));
-  PA_TRY(W.contig_mini_off.reserve((uint64_t)(n_contigs + 2) * 4));
-  hipLaunchKernelGGL(contig_offsets_kernel, dim3(ceil_div_u64(n_contigs + 1, kThreads)), dim3(kThreads), 0, c->stream,
-                     W.mini_contig.as<uint32_t>(), m, n_contigs, W.contig_mini_off.as<uint32_t>());
-  }
-
-  // ---- per-contig bucket index over window ids
-  if (!reuse) {
-    std::vector<uint32_t> cbo(n_contigs + 1, 0);
-    for (uint32_t ci = 0; ci < n_contigs; ++ci) cbo[ci + 1] = cbo[ci] + (h_contig_len[ci] >> kBucketShift) + 2;
-    PA_REQUIRE((uint64_t)cbo[n_contigs] < (1ULL << 31), "pa_fragani: bucket index too large");
-    PA_TRY(upload(c, W.contig_bucket_off, cbo));
-    PA_HIP(hipStreamSynchronize(c->stream));
-    PA_TRY(W.bucket_first.reserve((uint64_t)cbo[n_contigs] * 4 + 16));
-    hipLaunchKernelGGL(bucket_index_kernel, dim3(ceil_div_u64(cbo[n_contigs], kThreads)), dim3(kThreads), 0, c->stream,
-                       W.mini_wpos.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(),
-                       n_contigs, cbo[n_contigs], W.bucket_first.as<uint32_t>());
-  }
-
-  if (reuse) bookkeeping();  // (otherwise done while the minimizer kernel ran)
-  const uint32_t bin_base = genome_bin_off[ref0];
-  const uint64_t range_bins = std::max<uint32_t>(genome_bin_off[ref1] - bin_base, 1u);  // bins of the reference genomes asked for
-  const uint32_t n_frags = (uint32_t)frag_contig.size();
-  const uint32_t dict_ref0 = ref0, dict_ref1 = ref1;  // the reference genomes a dictionary built by this call holds
-  auto remember_index = [&](int which_buf) {
-    W.index_packed = d_packed; W.index_arena_bases = arena_bases; W.index_contigs = n_contigs; W.index_genomes = n_genomes;
-    W.index_k = k; W.index_frag_len = frag_len; W.index_m = m; W.index_which = which_buf;
-    if (!reuse) { W.index_ref0 = dict_ref0; W.index_ref1 = dict_ref1; }
-    W.index_valid = true;
-  };
-  if (m == 0 || n_frags == 0) {  // nothing to map (and nothing a later call could not take over)
-    prof.reset();
-    PA_HIP(hipStreamSynchronize(c->stream));
-    if (m == 0) remember_index(0);
-    return PA_OK;
-  }
-
-  // ---- 2. dictionary of minimizer hashes: ids, postings, same-hash links
-  // The dictionary holds the minimizers of the REFERENCE genomes asked for (a worker asked for one subject column sorts
-  // and lists one genome's minimizers, and its seed-hit arrays are that small too); the query genomes' minimizers find
-  // their hashes in it by value.  With every genome a reference the minimizers know their hash ids themselves.
-  const bool restricted = reuse ? !(W.index_ref0 == 0 && W.index_ref1 == n_genomes) : !(ref0 == 0 && ref1 == n_genomes);
-  uint32_t m_lo = 0, m_hi = m;
-  if (!reuse && restricted) {
-    uint32_t c_lo = 0, c_hi = n_contigs;  // the contigs of the reference range (contigs are listed genome by genome)
-    while (c_lo < n_contigs && h_contig_genome[c_lo] < ref0) ++c_lo;
-    c_hi = c_lo;
-    while (c_hi < n_contigs && h_contig_genome[c_hi] < ref1) ++c_hi;
-    PA_HIP(hipMemcpy(&m_lo, W.contig_mini_off.as<uint32_t>() + c_lo, 4, hipMemcpyDeviceToHost));
-    PA_HIP(hipMemcpy(&m_hi, W.contig_mini_off.as<uint32_t>() + c_hi, 4, hipMemcpyDeviceToHost));
-  }
-  const uint32_t md = m_hi - m_lo;  // minimizers in the dictionary
-  if (!reuse) {  // (an index that is taken over stays where it is: asking for room again could move -- and lose -- it)
-    const uint64_t md_room = std::max<uint32_t>(md, 1u);
-    // (the two key buffers of the sort are the halves of ONE allocation: once the index stands they are free, and the seed
-    // hits of the batches, 8 bytes each, go there -- memory this process has touched already instead of fresh pages)
-    PA_TRY(W.keys[0].reserve(2 * md_room * 8));
-    for (int b = 0; b < 2; ++b) PA_TRY(W.vals[b].reserve(md_room * 4));
-    PA_TRY(W.flags.reserve(md_room * 8 + 64));
-    W.index_key_room = md_room;
-    PA_TRY(W.mini_id.reserve((uint64_t)m * 4));
-    PA_TRY(W.prev_same.reserve((uint64_t)m * 4));
-    PA_TRY(W.post_cw.reserve(md_room * 8));
-    PA_TRY(W.post_g.reserve(md_room * 2 + 16));
-  }
-  uint64_t *keys[2] = {W.keys[0].as<uint64_t>(), W.keys[0].as<uint64_t>() + W.index_key_room};
-  uint32_t *vals[2] = {W.vals[0].as<uint32_t>(), W.vals[1].as<uint32_t>()};
-  int which = reuse ? W.index_which : 0;
-  if (!reuse) {
-    PA_HIP(hipMemsetAsync(W.prev_same.p, 0xff, (uint64_t)m * 4, c->stream));  // -1: no earlier occurrence
-    uint32_t n_ids = 0;
-    if (md) {
-      const uint32_t gm = ceil_div_u64(md, kThreads);
-      hipLaunchKernelGGL(mini_keys_kernel, dim3(gm), dim3(kThreads), 0, c->stream, W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
-                         m_lo, md, keys[0], vals[0]);
-      PA_TRY(pa_radix_sort_pairs(c, keys, vals, md, 0, 32, false, &which));
-      uint32_t *d_flags = W.flags.as<uint32_t>(), *d_pos = d_flags + md;
-      hipLaunchKernelGGL(key_heads_kernel, dim3(gm), dim3(kThreads), 0, c->stream, keys[which], md, d_flags);
-      PA_TRY(pa_exclusive_scan_u32(c, d_flags, d_pos, md, W.scalars.as<uint64_t>()));
-      PA_HIP(hipMemcpyAsync(c->h_pinned, W.scalars.p, 8, hipMemcpyDeviceToHost, c->stream));
-      PA_HIP(hipStreamSynchronize(c->stream));
-      n_ids = (uint32_t)c->h_pinned[0];
-      PA_REQUIRE(n_ids < (1u << 31), "pa_fragani: %u distinct minimizer hashes (limit 2^31)", n_ids);
-      PA_TRY(W.post_start.reserve((uint64_t)(n_ids + 2) * 4));
-      PA_TRY(W.uniq_hash.reserve((uint64_t)(n_ids + 2) * 4));
-      // (the contig of every block of minimizers: the look-back words of minimizer_kernel are free again)
-      const uint32_t n_blocks = (uint32_t)(((uint64_t)m + (1u << kContigBlockShift) - 1u) >> kContigBlockShift);
-      PA_TRY(W.block_counts.reserve((uint64_t)n_blocks * 4 + 16));
-      hipLaunchKernelGGL(block_contig_kernel, dim3(ceil_div_u64(n_blocks, kThreads)), dim3(kThreads), 0, c->stream, W.mini_contig.as<uint32_t>(), m,
-                         W.block_counts.as<uint32_t>());
-      hipLaunchKernelGGL(postings_kernel, dim3(gm), dim3(kThreads), 0, c->stream, keys[which], vals[which], d_flags, d_pos, md,
-                         n_ids, W.mini_contig.as<uint32_t>(), W.mini_id.as<uint32_t>(), W.post_start.as<uint32_t>(),
-                         W.prev_same.as<int32_t>(), W.mini_wpos.as<uint32_t>(), W.contig_genome.as<uint32_t>(),
-                         W.post_cw.as<uint64_t>(), W.post_g.as<uint16_t>(), W.contig_mini_off.as<uint32_t>(), n_contigs,
-                         W.uniq_hash.as<uint32_t>(), W.block_counts.as<uint32_t>());
-      PA_TRY(cut_frequent_postings(c, W, d_flags, d_pos, vals[which], vals[1 - which], reinterpret_cast<uint32_t *>(keys[1 - which]), md, n_ids,
-                                   h_contig_genome, n_contigs, n_genomes));
-    } else {  // the reference genomes hold no minimizer: an empty dictionary
-      PA_TRY(W.post_start.reserve(16));
-      PA_TRY(W.uniq_hash.reserve(16));
-      PA_TRY(W.hash_cut.reserve(16));
-      PA_HIP(hipMemsetAsync(W.post_start.p, 0, 8, c->stream));
-      PA_HIP(hipMemsetAsync(W.hash_cut.p, 0, 8, c->stream));
-    }
-    W.index_ids = n_ids;
-    if (restricted) {
-      uint32_t bits = 10;
-      while ((1ull << bits) < 2ull * n_ids + 1) ++bits;
-      W.index_lookup_bits = bits;
-      PA_TRY(W.lookup_at.reserve((16ull << bits) + 16));
-      PA_HIP(hipMemsetAsync(W.lookup_at.p, 0xff, 16ull << bits, c->stream));
-      if (n_ids)
-        hipLaunchKernelGGL(lookup_insert_kernel, dim3(ceil_div_u64(n_ids, kThreads)), dim3(kThreads), 0, c->stream, W.uniq_hash.as<uint32_t>(),
-                           W.post_start.as<uint32_t>(), W.hash_cut.as<uint32_t>(), n_ids, bits, W.lookup_at.as<uint4>());
-    }
-  }
-  const uint32_t *d_sorted_idx = vals[which];
-  // the index (minimizers, bucket index, dictionary, postings) is complete: a later call may take it over
-  remember_index(which);
-
-  // ---- tables indexed by sketch size
-  {
-    // Mashmap's statistics per sketch size and the identity of every (shared, s): functions of k alone, ~10 ms of binomial
-    // tails and logarithms on the host -- made once per context and k (the device copies stay where they are), not in
-    // every call with the device waiting
-    if (W.tables_k != k) {
-      std::vector<uint32_t> mh(kQMax + 1), ms(kQMax + 1);
-      PA_TRY(pa_fragani_tables(k, kQMax, mh.data(), ms.data()));
-      std::vector<float> ident((uint64_t)(kQMax + 1) * (kQMax + 1), 0.0f);
-      for (uint32_t s = 1; s <= (uint32_t)kQMax; ++s)
-        for (uint32_t x = 0; x <= s; ++x) ident[(uint64_t)s * (kQMax + 1) + x] = (float)pa_fragani_identity(x, s, k);
-      W.tables_k = 0;
-      PA_TRY(upload(c, W.tab_min_hits, mh));
-      PA_TRY(upload(c, W.tab_min_shared, ms));
-      PA_TRY(upload(c, W.ident_tab, ident));
-      PA_HIP(hipStreamSynchronize(c->stream));  // (the vectors go out of scope)
-      W.tables_k = k;
-    }
-    // The table of best fragments per reference bin holds the bins of the reference range only (a worker asked for one
-    // subject column keeps 1 700 bins per query genome instead of 1.7 million): bin numbers relative to the range's first;
-    // genomes outside it get an empty run of bins, so the reduction gives them nothing, as an all-zero table did.
-    std::vector<uint32_t> cbo_rel(contig_bin_off.size()), gbo_rel(genome_bin_off.size());
-    for (size_t i = 0; i < contig_bin_off.size(); ++i) cbo_rel[i] = contig_bin_off[i] - std::min(contig_bin_off[i], bin_base);
-    for (size_t g = 0; g < genome_bin_off.size(); ++g)
-      gbo_rel[g] = std::min<uint32_t>(genome_bin_off[g] - std::min(genome_bin_off[g], bin_base), (uint32_t)range_bins);
-    PA_TRY(upload(c, W.contig_bin_off, cbo_rel));
-    PA_TRY(upload(c, W.genome_bin_off, gbo_rel));
-    PA_HIP(hipStreamSynchronize(c->stream));
-  }
-
-  // ---- batches of query genomes
-  // Query genomes go through in batches of up to 2^17 fragments (13 batches for 1 000 genomes of 5 Mb: 1.46 s against
-  // 1.48 s with 2^16).  A batch whose seed hits do not fit 31-bit indices is halved and started again.
-#ifndef PA_FRAGANI_BATCH_FRAGS
-#define PA_FRAGANI_BATCH_FRAGS (1u << 17)
-#endif
-  uint32_t batch_frags = PA_FRAGANI_BATCH_FRAGS;
-  uint64_t hit_limit = 1ULL << 31;
-  if (const char *v = PA_TOOL_ENV("PA_FRAGANI_BATCH_HITS")) hit_limit = std::max<uint64_t>(1, strtoull(v, nullptr, 10));  // tests: force the halving
-  const uint64_t kMaxTableBytes = 1ULL << 31;
-  PA_TRY(W.scalars.reserve(64));
-  uint32_t *d_overflow = W.scalars.as<uint32_t>() + 8;
-  uint32_t *d_max_hits = W.scalars.as<uint32_t>() + 12;  // most seed hits of one fragment in the batch
-  // [0] segments of <= kHitCapSmall hits, [1] of > kHitCap hits, [2] the longest of those, [3] of > kHitCapSmall hits;
-  // [6] cursor of big_segments_kernel
-  uint32_t *d_seg_counters = W.scalars.as<uint32_t>() + 4;
-  // The bucketed pipeline needs an LDS counter per reference genome for each of a workgroup's waves and
-  // 16-bit fields for query window ids and for contigs within a genome; otherwise the sorted pipeline runs.
-  std::vector<uint32_t> gfc(n_genomes + 1, n_contigs);
-  uint32_t most_contigs = 0;
-  {
-    for (uint32_t ci = n_contigs; ci-- > 0;) gfc[h_contig_genome[ci]] = ci;
-    for (uint32_t g = n_genomes; g-- > 0;) if (gfc[g] == n_contigs) gfc[g] = gfc[g + 1];  // genome without contigs
-    for (uint32_t g = 0; g < n_genomes; ++g) most_contigs = std::max(most_contigs, gfc[g + 1] - gfc[g]);
-    bool genome_major = true;
-    for (uint32_t ci = 1; ci < n_contigs; ++ci) genome_major = genome_major && h_contig_genome[ci] >= h_contig_genome[ci - 1];
-    PA_REQUIRE(genome_major, "pa_fragani: contigs must be listed genome by genome");
-  }
-  PA_TRY(upload(c, W.genome_first_contig, gfc));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  const bool trace = PA_TOOL_ENV("PA_FRAGANI_TRACE") != nullptr;  // per-batch sizes on stderr
-  const bool force_sorted = [] {  // PA_FRAGANI_HITS=sorted: the path of more than 8 192 genomes, for any number (tests)
-    const char *v = PA_TOOL_ENV("PA_FRAGANI_HITS");
-    return v && v[0] == 's';
-  }();
-  const bool fields_fit = count_windows <= 0xffffu && most_contigs <= 0xffffu;
-  PA_REQUIRE(fields_fit, "pa_fragani: fragment length %u or %u contigs in one genome exceed the 16-bit fields of the "
-                         "mapping kernel", frag_len, most_contigs);
-  const bool use_buckets = !force_sorted && (uint64_t)kBucketWaves * n_genomes * 4u <= 128u * 1024u;
-  PA_HIP(hipMemsetAsync(d_overflow, 0, 8, c->stream));
-  prof.reset();
-  for (uint32_t g0 = qry0; g0 < qry1;) {
-    uint32_t g1 = g0 + 1;
-    while (g1 < qry1 && genome_frag_off[g1 + 1] - genome_frag_off[g0] <= batch_frags &&
-           (uint64_t)(g1 + 1 - g0) * range_bins * 8 <= kMaxTableBytes)
-      ++g1;
-    const uint32_t f0 = genome_frag_off[g0], nf = genome_frag_off[g1] - f0, nq = g1 - g0;
-    PA_REQUIRE(nf < (1u << 20), "pa_fragani: genome %u alone has %u fragments (limit 2^20)", g0, nf);
-    if (nf == 0) { g0 = g1; continue; }
-    std::vector<uint32_t> fc(frag_contig.begin() + f0, frag_contig.begin() + f0 + nf),
-        fn(frag_no.begin() + f0, frag_no.begin() + f0 + nf), fg(nf);
-    for (uint32_t i = 0; i < nf; ++i) fg[i] = h_contig_genome[fc[i]] - g0;
-    PA_TRY(upload(c, W.frag_contig, fc));
-    PA_TRY(upload(c, W.frag_no, fn));
-    PA_TRY(upload(c, W.frag_genome_local, fg));
-    PA_HIP(hipStreamSynchronize(c->stream));
-    // The batch's working arrays go into memory the index build has left behind wherever they fit (a fresh process pays
-    // ~65 ms per GB for the FIRST use of device memory -- more than the kernels of a whole 1 000-genome run for the 6 GB
-    // these are): the fragments' sketches into the sort's spare value buffer, the seed hits into its key buffers, the
-    // table of best fragments into the flag / scan scratch.  (All three are dead once the index stands, also for a call
-    // that takes the index over.)
-    uint32_t *q_hash_p, *q_pos_p, *q_id_p;
-    {
-      const uint64_t per = (uint64_t)nf * kQMax;
-      DevBuf &spare = W.vals[1 - which];
-      if (spare.bytes >= 3 * per * 4) {
-        q_hash_p = spare.as<uint32_t>(); q_pos_p = q_hash_p + per; q_id_p = q_pos_p + per;
-      } else {
-        PA_TRY(W.q_hash.reserve(per * 4));
-        PA_TRY(W.q_pos.reserve(per * 4));
-        PA_TRY(W.q_id.reserve(per * 4));
-        q_hash_p = W.q_hash.as<uint32_t>(); q_pos_p = W.q_pos.as<uint32_t>(); q_id_p = W.q_id.as<uint32_t>();
-      }
-    }
-    PA_TRY(W.q_s.reserve((uint64_t)nf * 4));
-    PA_TRY(W.q_tab.reserve((uint64_t)nf * kQtBuckets * 2));  // the sketches' bucket tables
-    PA_TRY(W.q_cut.reserve((uint64_t)nf * 4));
-    PA_TRY(W.hit_count.reserve((uint64_t)nf * 4));
-    PA_TRY(W.hit_off.reserve((uint64_t)nf * 4));
-    const uint32_t gw = ceil_div_u64(nf, kThreads / 64);
-    PA_HIP(hipMemsetAsync(d_max_hits, 0, 8, c->stream));  // [0] most hits, [1] longest sketch of a fragment
-    prof.emplace(c, PA_PROF_FRAG_SEED);
-    PA_TRY(W.frag_d.reserve((uint64_t)nf * 4));
-    hipLaunchKernelGGL(windows_without_selection_kernel, dim3(ceil_div_u64(nf, kThreads)), dim3(kThreads), 0, c->stream, d_packed, d_mask,
-                       arena_bases, W.contig_start.as<uint64_t>(), k, (uint32_t)w, W.frag_contig.as<uint32_t>(), W.frag_no.as<uint32_t>(),
-                       nf, frag_len, count_windows, W.frag_d.as<uint32_t>(), W.ambiguous(d_packed));
-    hipLaunchKernelGGL(query_sketch_kernel, dim3(gw), dim3(kThreads), 0, c->stream, W.frag_d.as<uint32_t>(), W.frag_contig.as<uint32_t>(),
-                       W.frag_no.as<uint32_t>(), nf, frag_len, count_windows, W.contig_mini_off.as<uint32_t>(),
-                       W.contig_bucket_off.as<uint32_t>(), W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(), W.mini_id.as<uint32_t>(),
-                       W.post_start.as<uint32_t>(), q_hash_p, q_pos_p,
-                       q_id_p, W.q_s.as<uint32_t>(), W.hit_count.as<uint32_t>(), d_overflow, d_max_hits,
-                       W.q_cut.as<uint32_t>(), restricted ? W.lookup_at.as<uint4>() : nullptr, W.index_lookup_bits, W.q_tab.as<uint32_t>());
-    PA_TRY(pa_exclusive_scan_u32(c, W.hit_count.as<uint32_t>(), W.hit_off.as<uint32_t>(), nf, W.scalars.as<uint64_t>()));
-    PA_HIP(hipMemcpyAsync(c->h_pinned, W.scalars.p, 8, hipMemcpyDeviceToHost, c->stream));
-    PA_HIP(hipMemcpyAsync(c->h_pinned + 1, d_max_hits, 8, hipMemcpyDeviceToHost, c->stream));
-    PA_HIP(hipStreamSynchronize(c->stream));
-    const uint64_t n_hits = c->h_pinned[0];
-    const uint32_t max_hits = (uint32_t)c->h_pinned[1];
-    const uint32_t s_cap = std::min<uint32_t>(kQMax, (((uint32_t)(c->h_pinned[1] >> 32) + 63u) / 64u) * 64u);
-    if (n_hits >= hit_limit && nq > 1) {  // closely related or repetitive genomes: fewer query genomes per batch
-      batch_frags = std::max<uint32_t>(1u, std::min(batch_frags, nf) / 2u);
-      prof.reset();
-      continue;  // the same g0 again
-    }
-    if (trace) fprintf(stderr, "pa_fragani: batch of genomes %u..%u: %u fragments, %llu seed hits\n", g0, g1, nf, (unsigned long long)n_hits);
-    PA_REQUIRE(n_hits < (1ULL << 31), "pa_fragani: %llu seed hits for the fragments of genome %u alone (limit 2^31); highly "
-               "repetitive input", (unsigned long long)n_hits, g0);
-    unsigned long long *table_p;
-    if (use_buckets && W.flags.bytes >= (uint64_t)nq * range_bins * 8) {
-      table_p = W.flags.as<unsigned long long>();  // (the sorted path keeps its head flags there)
-    } else {
-      PA_TRY(W.table.reserve((uint64_t)nq * range_bins * 8));
-      table_p = W.table.as<unsigned long long>();
-    }
-    PA_HIP(hipMemsetAsync(table_p, 0, (uint64_t)nq * range_bins * 8, c->stream));
-    if (n_hits) {
-      const bool hits_in_sort_keys = W.keys[0].bytes >= n_hits * 8;
-      if (!hits_in_sort_keys) PA_TRY(W.hkeys[0].reserve(n_hits * 8));
-      PA_TRY(W.hvals[0].reserve(n_hits * 4));  // (written by the paths that order the hits as a whole only)
-      uint64_t *hk[2] = {hits_in_sort_keys ? W.keys[0].as<uint64_t>() : W.hkeys[0].as<uint64_t>(), nullptr};
-      uint32_t *hv[2] = {W.hvals[0].as<uint32_t>(), nullptr};
-      auto second_buffers = [&]() -> int {  // only the radix sort needs the ping-pong copies
-        PA_TRY(W.hkeys[1].reserve(n_hits * 8));
-        PA_TRY(W.hvals[1].reserve(n_hits * 4));
-        hk[1] = W.hkeys[1].as<uint64_t>();
-        hv[1] = W.hvals[1].as<uint32_t>();
-        return PA_OK;
-      };
-      PA_TRY(W.run_g.reserve(256));  // the mapping kernel's event counters (-DPA_MAP_STATS)
-      int bits = 44;
-      for (uint32_t x = nf; x > 1; x >>= 1) ++bits;
-      bits = (bits + 1 + 7) & ~7;
-      if (bits > 64) bits = 64;
-      int hw = 0;
-      uint32_t n_keep = 0, n_large = 0, large_at = 0;  // bucketed path: long segments sit at the end of the lists
-      bool presorted = true;
-      if (use_buckets) {
-        // hits bucketed by (fragment, reference genome); segments listed by the same kernel
-        const uint64_t seg_cap64 = std::min<uint64_t>(n_hits, (uint64_t)nf * n_genomes);
-        const uint32_t seg_cap = (uint32_t)std::min<uint64_t>(seg_cap64, 0xfffffff0ull);
-        PA_TRY(W.seg_a0.reserve((uint64_t)seg_cap * 4 + 16));
-        PA_TRY(W.seg_nh.reserve((uint64_t)seg_cap * 4 + 16));
-        PA_TRY(W.seg_f.reserve((uint64_t)seg_cap * 4 + 16));
-        unsigned long long *d_cursor64 = reinterpret_cast<unsigned long long *>(W.scalars.as<uint32_t>() + 14);  // [lo] short, [hi] long segments
-        const uint32_t lds_bytes = (uint32_t)kBucketWaves * n_genomes * 4u;
-        PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bucket_hits_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        uint32_t n_big = 0, max_big = 0;
-        // one fragment per workgroup with the listed pairs' hits staged in LDS (whole-sector writes) when the two per-genome
-        // arrays leave room for a staging area; the batch that is about to be ordered as a whole (write_all) keeps the
-        // wave-per-fragment form, which writes every slot
-        // (four workgroups of eight waves per CU: 40 KB of LDS each)
-        const uint32_t lds_room = 40u * 1024u;
-        const uint32_t stage_cap = n_genomes * 8u + 8192u <= lds_room ? ((lds_room - n_genomes * 8u) / 8u) & ~63u : 0u;
-        const uint32_t stage_lds = stage_cap * 8u + n_genomes * 8u;
-        const bool stage_hits = stage_cap >= 1024u;
-        if (stage_hits)
-          PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bucket_hits_staged_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_lds));
-        auto bucket_pass = [&](bool write_all) -> int {
-          PA_HIP(hipMemsetAsync(d_seg_counters, 0, 16, c->stream));
-          PA_HIP(hipMemsetAsync(d_cursor64, 0, 8, c->stream));
-          if (stage_hits && !write_all)
-            hipLaunchKernelGGL(bucket_hits_staged_kernel, dim3(nf), dim3(kStageWaves * 64), stage_lds, c->stream, nf, q_pos_p, q_id_p,
-                               W.q_s.as<uint32_t>(), W.hit_off.as<uint32_t>(), W.post_g.as<uint16_t>(),
-                               W.post_cw.as<uint64_t>(), n_genomes, W.tab_min_hits.as<uint32_t>(), hk[0], W.seg_a0.as<uint32_t>(),
-                               W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), seg_cap, d_seg_counters, d_cursor64, ref0, ref1, stage_cap);
-          else
-          hipLaunchKernelGGL(bucket_hits_kernel, dim3(ceil_div_u64(nf, kBucketWaves)), dim3(kBucketWaves * 64), lds_bytes,
-                             c->stream, nf, q_pos_p, q_id_p, W.q_s.as<uint32_t>(),
-                             W.hit_off.as<uint32_t>(), W.post_g.as<uint16_t>(), W.post_cw.as<uint64_t>(), n_genomes,
-                             W.tab_min_hits.as<uint32_t>(), hk[0], hv[0],
-                             W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), seg_cap, d_seg_counters,
-                             d_cursor64, ref0, ref1, write_all);
-          PA_HIP(hipMemcpyAsync(c->h_pinned, d_seg_counters, 16, hipMemcpyDeviceToHost, c->stream));
-          PA_HIP(hipMemcpyAsync(c->h_pinned + 2, d_cursor64, 8, hipMemcpyDeviceToHost, c->stream));
-          PA_HIP(hipStreamSynchronize(c->stream));
-          const uint32_t *hc32 = reinterpret_cast<const uint32_t *>(c->h_pinned);
-          n_keep = (uint32_t)c->h_pinned[2];
-          n_large = (uint32_t)(c->h_pinned[2] >> 32);
-          large_at = seg_cap - n_large;
-          n_big = hc32[1];
-          max_big = hc32[2];
-          PA_REQUIRE((uint64_t)n_keep + n_large <= seg_cap, "pa_fragani: %u + %u segments exceed the list capacity %u",
-                     n_keep, n_large, seg_cap);
-          return PA_OK;
-        };
-        PA_TRY(bucket_pass(false));
-        presorted = false;
-        uint32_t frag_sort_max = kFragSortMax;  // tests: PA_FRAGANI_SORT_MAX=600 sends a 60-copy repeat family down this path
-        if (const char *v = PA_TOOL_ENV("PA_FRAGANI_SORT_MAX")) frag_sort_max = (uint32_t)std::max(1, atoi(v));
-        if (n_big && max_big > frag_sort_max) {
-          // a repeat family with more hits than one LDS sort takes: order the whole batch by key; the
-          // (fragment, genome) slices keep their places because contigs are numbered genome by genome -- provided every
-          // slot holds its own key, so the bucketing runs again and this time also writes the hits of the pairs that are
-          // not listed (they are skipped otherwise: unwritten slots would be sorted into other fragments' ranges)
-          PA_TRY(bucket_pass(true));
-          PA_TRY(second_buffers());
-          PA_TRY(pa_radix_sort_pairs(c, hk, hv, n_hits, 0, bits, false, &hw));
-          presorted = true;
-        } else if (n_big) {
-          PA_TRY(W.seg_list.reserve((uint64_t)n_big * 8 + 16));
-          uint32_t *big_a0 = W.seg_list.as<uint32_t>(), *big_nh = big_a0 + n_big;
-          PA_HIP(hipMemsetAsync(d_seg_counters + 6, 0, 4, c->stream));
-          hipLaunchKernelGGL(big_segments_kernel, dim3(ceil_div_u64(n_large, kThreads)), dim3(kThreads), 0, c->stream,
-                             W.seg_a0.as<uint32_t>() + large_at, W.seg_nh.as<uint32_t>() + large_at, n_large, big_a0,
-                             big_nh, d_seg_counters + 6);
-          uint32_t np2_max = 2;
-          while (np2_max < max_big) np2_max <<= 1;
-          const uint32_t sort_lds = np2_max * 12u;
-          PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(frag_sort_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
-          hipLaunchKernelGGL(frag_sort_kernel, dim3(n_big), dim3(kFragSortThreads), sort_lds, c->stream, hk[0], hv[0],
-                             big_a0, big_nh, np2_max, 64u - kHitRankShift + 11u);  // (contig, window id) to the top, the rank below
-        }
-      } else {
-        // general path: all hits sorted by key, segments from head flags
-        hipLaunchKernelGGL(fill_hits_kernel, dim3(gw), dim3(kThreads), 0, c->stream, nf, q_pos_p,
-                           q_id_p, W.q_s.as<uint32_t>(), W.hit_off.as<uint32_t>(),
-                           W.post_start.as<uint32_t>(), d_sorted_idx, W.mini_wpos.as<uint32_t>(),
-                           W.mini_contig.as<uint32_t>(), hk[0], hv[0]);
-        if (max_hits <= kFragSortMax) {  // every fragment's hits fit one LDS sort
-          uint32_t np2_max = 2;
-          while (np2_max < max_hits) np2_max <<= 1;
-          const uint32_t lds_bytes = np2_max * 12u;
-          PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(frag_sort_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-          hipLaunchKernelGGL(frag_sort_kernel, dim3(nf), dim3(kFragSortThreads), lds_bytes, c->stream, hk[0], hv[0],
-                             W.hit_off.as<uint32_t>(), W.hit_count.as<uint32_t>(), np2_max, 0u);
-        } else {
-          PA_TRY(second_buffers());
-          PA_TRY(pa_radix_sort_pairs(c, hk, hv, n_hits, 0, bits, false, &hw));
-        }
-        PA_TRY(W.flags.reserve(n_hits * 8 + 64));
-        uint32_t *hf = W.flags.as<uint32_t>(), *hp = hf + n_hits;
-        const uint32_t gh = ceil_div_u64(n_hits, kThreads);
-        hipLaunchKernelGGL(segment_heads_kernel, dim3(gh), dim3(kThreads), 0, c->stream, hk[hw], (uint32_t)n_hits,
-                           W.contig_genome.as<uint32_t>(), hf);
-        PA_TRY(pa_exclusive_scan_u32(c, hf, hp, n_hits, W.scalars.as<uint64_t>()));
-        PA_HIP(hipMemcpyAsync(c->h_pinned, W.scalars.p, 8, hipMemcpyDeviceToHost, c->stream));
-        PA_HIP(hipStreamSynchronize(c->stream));
-        const uint32_t n_segs = (uint32_t)c->h_pinned[0];
-        PA_TRY(W.seg_start.reserve((uint64_t)(n_segs + 2) * 4));
-        hipLaunchKernelGGL(segment_starts_kernel, dim3(gh), dim3(kThreads), 0, c->stream, hf, hp, (uint32_t)n_hits,
-                           W.seg_start.as<uint32_t>());
-        // most segments are chance hits of unrelated genomes (fewer hits than any L1 run needs): drop them
-        // here, one thread each, instead of spending a workgroup launch on each in the mapping kernel
-        const uint32_t gs = ceil_div_u64(n_segs, kThreads);
-        hipLaunchKernelGGL(segment_keep_kernel, dim3(gs), dim3(kThreads), 0, c->stream, hk[hw],
-                           W.seg_start.as<uint32_t>(), n_segs, W.q_s.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(),
-                           W.contig_genome.as<uint32_t>(), ref0, ref1, hf);
-        PA_TRY(pa_exclusive_scan_u32(c, hf, hp, n_segs, W.scalars.as<uint64_t>()));
-        PA_HIP(hipMemcpyAsync(c->h_pinned, W.scalars.p, 8, hipMemcpyDeviceToHost, c->stream));
-        PA_HIP(hipStreamSynchronize(c->stream));
-        n_keep = (uint32_t)c->h_pinned[0];
-        PA_TRY(W.seg_list.reserve((uint64_t)(n_keep + 1) * 4));
-        PA_TRY(W.seg_a0.reserve((uint64_t)n_keep * 4 + 16));
-        PA_TRY(W.seg_nh.reserve((uint64_t)n_keep * 4 + 16));
-        hipLaunchKernelGGL(segment_list_kernel, dim3(gs), dim3(kThreads), 0, c->stream, hf, hp, n_segs,
-                           W.seg_list.as<uint32_t>());
-        if (n_keep)
-          hipLaunchKernelGGL(segments_from_list_kernel, dim3(ceil_div_u64(n_keep, kThreads)), dim3(kThreads), 0, c->stream,
-                             W.seg_start.as<uint32_t>(), W.seg_list.as<uint32_t>(), n_keep, W.seg_a0.as<uint32_t>(),
-                             W.seg_nh.as<uint32_t>());
-      }
-      prof.reset();
-      prof.emplace(c, PA_PROF_FRAG_MAP);
-      // stretch capacity: the expected minimizers of one window (density 2 / (w + 1)) plus a third, in steps of 64
-      const uint32_t per_window = (uint32_t)(2.0 * count_windows / (w + 1.0));
-      const uint32_t ref_cap = std::min<uint32_t>(kRefCapMax, std::max<uint32_t>(256u, (per_window * 4u / 3u + 63u) / 64u * 64u));
-#ifdef PA_MAP_STATS
-      PA_HIP(hipMemsetAsync(W.run_g.p, 0, 256, c->stream));
-#endif
-#ifdef PA_TOOLS
-      const char *cut_env = PA_TOOL_ENV("PA_MAP_CUT");  // tools: the mapping kernel cut short after a phase (timing by difference)
-      const uint32_t map_cut = cut_env ? (uint32_t)atoi(cut_env) : 0xffffffffu;
-#endif
-      auto launch_map = [&](const uint32_t *list_a0, const uint32_t *list_nh, const uint32_t *list_f, uint32_t count, uint32_t hit_cap,
-                            auto all_staged) -> int {
-        if (count == 0) return PA_OK;
-        constexpr bool kAll = decltype(all_staged)::value;
-        PA_TRY(W.seg_rec.reserve((uint64_t)count * 48));
-        hipLaunchKernelGGL(segment_records_kernel, dim3(ceil_div_u64(count, kThreads)), dim3(kThreads), 0, c->stream, hk[hw],
-                           list_a0, list_nh, list_f, count, W.q_s.as<uint32_t>(), W.q_cut.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(),
-                           W.tab_min_shared.as<uint32_t>(), W.contig_genome.as<uint32_t>(), W.genome_first_contig.as<uint32_t>(),
-                           W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(), W.frag_genome_local.as<uint32_t>(), W.seg_rec.as<uint4>());
-#ifndef PA_MAP_LDS_PAD
-#define PA_MAP_LDS_PAD 0u  // (an experiment's switch: LDS asked for and not used, to see what a wave less per SIMD costs)
-#endif
-#define PA_MAP_CASE(CAP)                                                                                                  \
-  case CAP:                                                                                                               \
-    hipLaunchKernelGGL((map_segments_kernel<CAP, kAll>), dim3(count), dim3(64), eval_lds_bytes(s_cap, hit_cap, CAP) + PA_MAP_LDS_PAD, c->stream,  \
-                       hk[hw], hv[hw], W.seg_rec.as<uint4>(), count, presorted, q_hash_p, W.q_tab.as<uint32_t>(),          \
-                       W.frag_genome_local.as<uint32_t>(), frag_len, count_windows,                                        \
-                       W.tab_min_shared.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(),                                  \
-                       W.contig_bucket_off.as<uint32_t>(), W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(),      \
-                       W.mini_wpos.as<uint32_t>(), W.prev_same.as<int32_t>(), W.contig_bin_off.as<uint32_t>(), range_bins, \
-                       table_p, W.run_g.as<uint32_t>(), s_cap, hit_cap PA_MAP_CUT_ARG);                                   \
-    break;
-        switch (ref_cap) {
-          PA_MAP_CASE(256) PA_MAP_CASE(320) PA_MAP_CASE(384) PA_MAP_CASE(448)
-          default: PA_MAP_CASE(512)
-        }
-#undef PA_MAP_CASE
-        return PA_OK;
-      };
-      if (use_buckets) {
-        if (n_keep) {
-          PA_TRY(W.seg2_a0.reserve((uint64_t)n_keep * 4 + 16));
-          PA_TRY(W.seg2_nh.reserve((uint64_t)n_keep * 4 + 16));
-          PA_TRY(W.seg2_f.reserve((uint64_t)n_keep * 4 + 16));
-          // segments of at most kSparseHits hits go to map_sparse_kernel (listed from the back of the same arrays), unless
-          // the hits carry their ranks in the sort's payload (a batch ordered as a whole)
-          uint32_t sparse_max = presorted ? 0u : kSparseHits;
-          if (const char *v = PA_TOOL_ENV("PA_FRAGANI_SPARSE")) sparse_max = (atoi(v) && !presorted) ? kSparseHits : 0u;  // tests: 0 = every segment through the general kernel (the switch can only take the sparse kernel away: its key layout is the bucketed one)
-          unsigned long long *d_pre_cursor = reinterpret_cast<unsigned long long *>(d_seg_counters + 6);  // [6] general, [7] sparse (8-byte aligned)
-          PA_HIP(hipMemsetAsync(d_pre_cursor, 0, 8, c->stream));
-          hipLaunchKernelGGL(prefilter_segments_kernel, dim3(ceil_div_u64(n_keep, kThreads)), dim3(kThreads), 0, c->stream,
-                             hk[hw], W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), n_keep,
-                             W.q_s.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(), W.q_cut.as<uint32_t>(), frag_len, W.seg2_a0.as<uint32_t>(),
-                             W.seg2_nh.as<uint32_t>(), W.seg2_f.as<uint32_t>(), d_pre_cursor, sparse_max);
-          PA_HIP(hipMemcpyAsync(c->h_pinned, d_pre_cursor, 8, hipMemcpyDeviceToHost, c->stream));
-          PA_HIP(hipStreamSynchronize(c->stream));
-          const uint32_t n_small = (uint32_t)c->h_pinned[0], n_sparse = (uint32_t)(c->h_pinned[0] >> 32);
-          if (trace)
-            fprintf(stderr, "pa_fragani: genomes %u..%u: %u fragments, %llu seed hits, %u + %u listed segments, %u left "
-                            "after the tiny-segment filter\n", g0, g1, nf, (unsigned long long)n_hits, n_keep, n_large, n_small);
-          PA_TRY(launch_map(W.seg2_a0.as<uint32_t>(), W.seg2_nh.as<uint32_t>(), W.seg2_f.as<uint32_t>(), n_small, (uint32_t)kHitCapSmall,
-                            std::true_type{}));
-          if (n_sparse) {
-            const uint32_t at = n_keep - n_sparse;  // the sparse list sits at the back of the same arrays
-            PA_TRY(W.seg_over.reserve((uint64_t)n_sparse * 12 + 16));
-            uint32_t *over_a0 = W.seg_over.as<uint32_t>(), *over_nh = over_a0 + n_sparse, *over_f = over_nh + n_sparse;
-            uint32_t *d_over_n = W.scalars.as<uint32_t>() + 3;
-            PA_HIP(hipMemsetAsync(d_over_n, 0, 4, c->stream));
-            hipLaunchKernelGGL(map_sparse_kernel, dim3(n_sparse), dim3(64), 0, c->stream, hk[hw], W.seg2_a0.as<uint32_t>() + at,
-                               W.seg2_nh.as<uint32_t>() + at, W.seg2_f.as<uint32_t>() + at, n_sparse, W.q_s.as<uint32_t>(), q_hash_p,
-                               W.frag_genome_local.as<uint32_t>(), frag_len, count_windows, W.tab_min_hits.as<uint32_t>(),
-                               W.tab_min_shared.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(),
-                               W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
-                               W.prev_same.as<int32_t>(), W.contig_bin_off.as<uint32_t>(), range_bins, table_p, over_a0, over_nh, over_f,
-                               d_over_n
-#ifdef PA_MAP_STATS
-                               , W.run_g.as<uint32_t>()
-#endif
-            );
-            PA_HIP(hipMemcpyAsync(c->h_pinned, d_over_n, 4, hipMemcpyDeviceToHost, c->stream));
-            PA_HIP(hipStreamSynchronize(c->stream));
-            const uint32_t n_over = *reinterpret_cast<const uint32_t *>(c->h_pinned);
-            if (trace) fprintf(stderr, "pa_fragani: %u segments of at most %u hits in the sparse kernel, %u of them handed on\n", n_sparse, kSparseHits, n_over);
-            // what does not fit the simple form (a hash twice in a stretch, over-long windows or ranges) goes through the general kernel
-            PA_TRY(launch_map(over_a0, over_nh, over_f, n_over, (uint32_t)kHitCapSmall, std::true_type{}));
-          }
-        }
-        PA_TRY(launch_map(W.seg_a0.as<uint32_t>() + large_at, W.seg_nh.as<uint32_t>() + large_at, W.seg_f.as<uint32_t>() + large_at, n_large,
-                          (uint32_t)kHitCap, std::false_type{}));
-      } else {
-        PA_TRY(launch_map(W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), nullptr, n_keep, (uint32_t)kHitCap, std::false_type{}));
-      }
-#ifdef PA_MAP_STATS
-      if (trace) {
-        uint32_t st[64];
-        PA_HIP(hipMemcpy(st, W.run_g.p, 256, hipMemcpyDeviceToHost));
-        fprintf(stderr, "pa_fragani: map stats: %u segments at L1 with %u hits, %u candidates, %u groups, %u begins past the bound, "
-                        "%u rounds, %u stretch entries, %u windows evaluated, %u fine passes, %u cooperative, %u begins in rounds, "
-                        "%u begins finished, %u rounds without items, %u second passes, %u windows with an exact value, %u of them at or above the bar, "
-                        "%u begins dropped by the tight bound, %u rounds ended by it; rounds by seed hits of the segment (<= 7, 8-15, 16-31, 32-63, "
-                        "64-127, 128-255, more): %u %u %u %u %u %u %u, segments: %u %u %u %u %u %u %u; work model: %u minimizers in the candidates' ranges, "
-                        "%u states tying their candidate's optimum; past the tight bound: %u rounds, %u begins, %u windows, %u of them at or above the bar; %u begins dropped by the bound asked at a round's end; %u segments that are one run of hits (no L1 scan) with %u hits; hits within 4096 window ids on one contig (ordered by counting): %u segments, all but one hit: %u, all but two: %u\n",
-                st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11], st[12], st[13], st[14], st[15], st[16], st[17],
-                st[18], st[19], st[20], st[21], st[22], st[23], st[24], st[25], st[26], st[27], st[28], st[29], st[30], st[31], st[32], st[33], st[40], st[39], st[37], st[38], st[41], st[42], st[46], st[43], st[44], st[45]);
-        fprintf(stderr, "pa_fragani: sparse stats: %u segments with a candidate, %u candidates, %u groups of begins evaluated, %u begins, %u states, %u begins tying "
-                        "their candidate's best when folded; %u one-run segments with strays; %u begins with enough hits left out because they lie between two tying begins and hold no more hits than those share, %u groups between the ties passed over unseen, %u groups that hold a candidate's first or last tying begin, %u candidates whose first hit lies past the batch of 512 window ids\n",
-                st[48], st[49], st[50], st[51], st[52], st[53], st[47], st[58], st[59], st[54], st[55]);
-      }
-#endif
-    }
-    PA_TRY(W.matched.reserve((uint64_t)nq * n_genomes * 4));
-    PA_TRY(W.ident_sum.reserve((uint64_t)nq * n_genomes * 8));
-    hipLaunchKernelGGL(reduce_pairs_kernel, dim3(nq * n_genomes), dim3(64), 0, c->stream,
-                       table_p, range_bins, W.genome_bin_off.as<uint32_t>(), n_genomes,
-                       W.ident_tab.as<float>(), W.matched.as<uint32_t>(), W.ident_sum.as<double>());
-    PA_HIP(hipGetLastError());
-    prof.reset();
-    if (out_cols == n_genomes) {
-      PA_HIP(hipMemcpyAsync(h_matched + (uint64_t)g0 * n_genomes, W.matched.p, (uint64_t)nq * n_genomes * 4,
-                            hipMemcpyDeviceToHost, c->stream));
-      PA_HIP(hipMemcpyAsync(h_ident_sum + (uint64_t)g0 * n_genomes, W.ident_sum.p, (uint64_t)nq * n_genomes * 8,
-                            hipMemcpyDeviceToHost, c->stream));
-    } else if (out_cols) {  // the columns of the reference range only
-      PA_HIP(hipMemcpy2DAsync(h_matched + (uint64_t)g0 * out_cols, (size_t)out_cols * 4, W.matched.as<uint32_t>() + out_col0,
-                              (size_t)n_genomes * 4, (size_t)out_cols * 4, nq, hipMemcpyDeviceToHost, c->stream));
-      PA_HIP(hipMemcpy2DAsync(h_ident_sum + (uint64_t)g0 * out_cols, (size_t)out_cols * 8, W.ident_sum.as<double>() + out_col0,
-                              (size_t)n_genomes * 8, (size_t)out_cols * 8, nq, hipMemcpyDeviceToHost, c->stream));
-    }
-    PA_HIP(hipStreamSynchronize(c->stream));
-    g0 = g1;
-  }
-  uint32_t h_over[2] = {0, 0};
-  PA_HIP(hipMemcpy(h_over, d_overflow, 8, hipMemcpyDeviceToHost));
-  if (h_over[0]) {
-    pa_set_error("pa_fragani: %u fragment sketches exceeded %d minimizers (fragLen too long for this window); "
-                 "those sketches were truncated", h_over[0], kQMax);
-    return PA_E_CAPACITY;
-  }
-  return PA_OK;
 }
 
 }  // extern "C"
