@@ -509,6 +509,35 @@ PA_API int pa_cliques_copy(const pa_cliques *cl, uint32_t *n_nodes, double *max_
                            uint8_t *present, uint64_t *member_off, uint32_t *members);
 PA_API void pa_cliques_free(pa_cliques *cl);
 
+/* ---- plot-run: clustered heatmap order ----
+ * Restates what seaborn's clustermap computes with its defaults for the reference's plot-run
+ * (pyani_plus/plot_run.py:114-147): scipy's linkage(rows, method="average", metric="euclidean") and the leaves of
+ * dendrogram(..., no_plot=True), bit for bit.
+ *
+ *   pa_rowdist_euclid        (device) x is a row-major n x m f64 matrix in device memory; out receives the condensed
+ *        distance vector, n (n - 1) / 2 doubles: out[n i - i (i + 1) / 2 + (j - i - 1)] = sqrt(sum over c = 0 .. m - 1,
+ *        in this order, of (x[i,c] - x[j,c])^2) for i < j, the index computed in 64 bits.  One accumulator per pair, the
+ *        square rounded before it is added (no FMA), the square root correctly rounded: the same bits as
+ *        scipy.spatial.distance.pdist(x, "euclidean").  The inputs must be finite (plot-run fills NaN cells first); with
+ *        NaN or infinite cells the result is whatever IEEE arithmetic gives and no order is promised to match.
+ *        PA_E_INVALID for n > 65536.  n < 2 writes nothing.  The call allocates no device memory and does not
+ *        synchronise; it runs on the context's stream.
+ *   pa_rowdist_euclid_host   the same vector from a host matrix into a host array, plain loops on n_threads host
+ *        threads (0: as many as the process may use).
+ *   pa_linkage_average       (host) condensed distances of n observations -> Z, scipy's (n - 1) x 4 row-major f64
+ *        linkage table (the two merged clusters, smaller id first; their distance; the size of the union; merge r is
+ *        cluster n + r), and leaves, the n observation indices in the dendrogram's order (pre-order from the last merge,
+ *        first child before the second).  Nearest-neighbour chain as in scipy: an empty chain restarts at the lowest
+ *        live index, the nearest live cluster is searched in ascending index with a strict <, starting from the
+ *        distance to the previous chain element, which therefore wins ties; the n - 1 merges are stable-sorted by
+ *        distance and relabelled with a union-find.  The distances are not modified (the call works on a copy).
+ *        n = 1: leaves = {0}, Z untouched (scipy raises; a one-genome run still plots); n = 0: nothing.
+ *        PA_E_INVALID for n > 65536 and for a distance that is NaN or infinite (finite matrix cells do not rule that
+ *        out: cells near 1e200 overflow the sum); PA_E_NOMEM when the copy cannot be made. */
+PA_API int pa_rowdist_euclid(pa_ctx *ctx, const double *d_x, uint32_t n, uint32_t m, double *d_out);
+PA_API int pa_rowdist_euclid_host(const double *h_x, uint32_t n, uint32_t m, double *h_out, uint32_t n_threads);
+PA_API int pa_linkage_average(uint32_t n, const double *h_condensed, double *h_Z, uint32_t *h_leaves);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */
@@ -523,7 +552,8 @@ PA_API void pa_cliques_free(pa_cliques *cl);
 #define PA_PROF_MSA_PAIRS 9   /* external alignment: pair counts M, B (msa_pairs_kernel, mirror) */
 #define PA_PROF_CLS_EDGES 10  /* classify: pair evaluation, counts, scan, compaction (cls_edges_kernel) */
 #define PA_PROF_CLS_SORT 11   /* classify: radix sort of the edges by score + gather */
-#define PA_PROF_NPHASES 12
+#define PA_PROF_ROWDIST 12   /* plot-run: all-pairs row distances (rowdist_euclid_kernel) */
+#define PA_PROF_NPHASES 13
 PA_API int pa_prof_enable(pa_ctx *ctx, int on);
 PA_API int pa_prof_reset(pa_ctx *ctx);
 /* total milliseconds and number of timed launches of a phase (syncs the stream) */

@@ -30,7 +30,7 @@ PA_FRAGANI_COLUMNS_ONLY = 2
 PA_PAIRS_AUTO, PA_PAIRS_BITROW, PA_PAIRS_MERGE, PA_PAIRS_BITROW_HASH = 0, 1, 2, 3
 PA_ALIGN_BASES = 64
 PROF_PHASES = {"kmer_hash": 0, "sketch_sort": 1, "pair_dict": 2, "pair_count": 3, "ani": 4, "frag_index": 5, "frag_seed": 6, "frag_map": 7,
-               "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11}
+               "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11, "rowdist": 12}
 PA_AGG = {"min": 0, "max": 1, "mean": 2}
 
 _u8p = C.POINTER(C.c_uint8)
@@ -167,6 +167,9 @@ SIGNATURES: dict[str, tuple] = {
     "pa_cliques_info": (C.c_int, [_vp, _u64p, _u64p]),
     "pa_cliques_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pa_cliques_free": (None, [_vp]),
+    "pa_rowdist_euclid": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp]),
+    "pa_rowdist_euclid_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32]),
+    "pa_linkage_average": (C.c_int, [C.c_uint32, _vp, _vp, _vp]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),
     "pa_prof_get": (C.c_int, [_vp, C.c_int, _f64p, _u64p]),

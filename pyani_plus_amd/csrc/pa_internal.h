@@ -76,6 +76,7 @@ struct DevBuf {
     bytes = 0;
     hipError_t e = hipMalloc(&p, sz);
     if (e != hipSuccess) {
+      (void)hipGetLastError();  // the failure is reported here: the next launch's hipGetLastError must not see it again
       if (budget)
         pa_set_error("%s: hipMalloc(%llu) failed with %llu bytes of workspace held: %s", budget->what[0] ? budget->what : "device workspace",
                      (unsigned long long)sz, (unsigned long long)budget->held, hipGetErrorString(e));

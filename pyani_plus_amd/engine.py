@@ -669,6 +669,27 @@ class HipEngine:
         e_i, e_j, e_s, e_c = self.classify_edges_device(score, cov, score_edges=score_edges, coverage_edges=coverage_edges, cov_min=cov_min)
         return e_i.cpu().numpy().view(np.uint32), e_j.cpu().numpy().view(np.uint32), e_s.cpu().numpy(), e_c.cpu().numpy()
 
+    # -- plot-run
+    def row_distances_device(self, matrix):
+        """``pa_rowdist_euclid``: the condensed Euclidean distances between the rows of ``matrix`` (n x m float64, a
+        host array or a tensor on this device; finite values) as a device tensor of n (n - 1) / 2 float64."""
+        t = self.torch
+        if not isinstance(matrix, t.Tensor):
+            matrix = t.from_numpy(np.ascontiguousarray(matrix, dtype=np.float64))
+        d_x = matrix.to(device=self.device, dtype=t.float64).contiguous()
+        if d_x.dim() != 2:
+            raise ValueError(f"matrix has shape {tuple(d_x.shape)}, expected two dimensions")
+        n, m = d_x.shape
+        if n > 1 << 16:  # the library's limit, checked before n (n - 1) / 2 doubles are allocated for it to refuse
+            raise ValueError(f"{n} rows; at most 65536")
+        out = t.empty(n * (n - 1) // 2, dtype=t.float64, device=self.device)
+        self._check(self.lib.pa_rowdist_euclid(self.ctx, d_x.data_ptr(), n, m, out.data_ptr()), "pa_rowdist_euclid")
+        return out
+
+    def row_distances(self, matrix) -> np.ndarray:
+        """``row_distances_device`` copied back: the same bits as ``scipy.spatial.distance.pdist(matrix, "euclidean")``."""
+        return self.row_distances_device(matrix).cpu().numpy()
+
     # -- profiling
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")

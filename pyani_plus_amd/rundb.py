@@ -4,7 +4,8 @@
 The reference's Python (Typer CLI, SQLAlchemy ORM, snakemake) does not travel to the GPU
 box, so this module is the build's own counterpart of ``cli_sourmash`` / ``fastani`` / ``external_alignment`` +
 ``start_and_run_method`` + ``run_method`` minus snakemake (pyani_plus/public_cli.py:115-329, 502-554,
-598-699), of ``resume``, ``export-run`` and ``classify`` (702-828, 974-1091, 1211-1331) and of the parts of ``db_orm`` they use (SURVEY.md
+598-699), of ``resume``, ``export-run``, ``plot-run`` (its tables; pyani_plus/plot_run.py) and ``classify`` (702-828, 974-1091,
+1095-1136, 1211-1331) and of the parts of ``db_orm`` they use (SURVEY.md
 section 8b, last row):
 
 * FASTA enumeration by the four extensions +- ``.gz`` (pyani_plus/utils.py:226-242)
@@ -49,6 +50,8 @@ import numpy as np
 
 from . import _capi, launch, wire
 from . import classify as classify_mod
+from . import cluster as cluster_mod
+from . import heatmap_figure
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
 from .engine import load_fasta_files
@@ -1303,6 +1306,43 @@ def export_run(database: Path | str, outdir: Path, *, run_id: int | None = None,
     return written
 
 
+# ------------------------------------------------------------------ what classify and plot-run read of a complete run
+def _score_frames(logger, conn, run: Run) -> list:
+    """The identity, query coverage and Hadamard matrices of a complete run as frames over sorted md5: the cached
+    ``runs.df_*`` strings the reference reads (10 decimals), filled with ``cache_comparisons`` first when they are missing;
+    for a run too large for the cache, the comparisons table, unrounded."""
+    import pandas as pd
+
+    kinds = ("identity", "cov_query", "hadamard")
+    if _matrix_cache_too_big(len(run.fasta_hashes)):
+        hashes, mats = _comparison_matrices(conn, run)
+        mats["hadamard"] = mats["identity"] * mats["cov_query"]
+        return [pd.DataFrame(mats[k], index=hashes, columns=hashes) for k in kinds]
+    cached = conn.execute("SELECT df_identity, df_cov_query, df_hadamard FROM runs WHERE run_id=?", (run.run_id,)).fetchone()
+    if any(c is None for c in cached):
+        out = cache_comparisons(conn, run)
+        cached = tuple(out.get(f"df_{k}") for k in kinds)
+        if any(c is None for c in cached):
+            sourmash_hip.log_sys_exit(logger, f"Could not load run {run.configuration.method} matrix")
+    return [pd.read_json(StringIO(c), orient="split", dtype=float) for c in cached]
+
+
+def _relabelled(logger, run: Run, frames: list, label: str) -> list:
+    """``Run.relabelled_matrix`` (db_orm.py:590-624) of every frame: labelled by ``md5`` (as they are), ``filename`` or
+    ``stem`` and sorted by label on both axes, with the reference's messages for duplicate stems and an unknown label."""
+    if label == "md5":
+        return frames
+    if label == "filename":
+        mapping = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
+    elif label == "stem":
+        mapping = {a.genome_hash: filename_stem(a.fasta_filename) for a in run.fasta_hashes}
+        if len(set(mapping.values())) < len(mapping):
+            sourmash_hip.log_sys_exit(logger, "Duplicate filename stems, consider using MD5 labelling.")
+    else:
+        sourmash_hip.log_sys_exit(logger, f"Unexpected label scheme {label!r}")
+    return [f.rename(index=mapping, columns=mapping).sort_index(axis=0).sort_index(axis=1) for f in frames]
+
+
 # ------------------------------------------------------------------ classify (pyani_plus/public_cli.py:1211-1331)
 def classify(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", coverage_edges: str = "min",  # noqa: PLR0913
              score_edges: str = "mean", cov_min: float = classify_mod.MIN_COVERAGE, mode: str = "identity", engine=None,
@@ -1320,8 +1360,6 @@ def classify(database: Path | str, outdir: Path, *, run_id: int | None = None, l
 
     ``engine``: a ``HipEngine`` builds and sorts the edge list on the GPU; None does it on the host.  The plot of the
     reference (``plot_classify``) is not made."""
-    import pandas as pd
-
     logger = logger or logging.getLogger("pyani_plus_amd")
     if str(database) == ":memory:" or not Path(database).is_file():
         sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
@@ -1343,37 +1381,13 @@ def classify(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     if done != n * n:  # db_orm.load_run(check_complete=True)
         sourmash_hip.log_sys_exit(logger, f"run-id {run_id} has {done} of {n}^2={n * n} comparisons, {n * n - done} needed")
     method = run.configuration.method
-    keys = ("df_identity", "df_cov_query", "df_hadamard")
-    if _matrix_cache_too_big(n):
-        hashes, mats = _comparison_matrices(conn, run)
-        mats["hadamard"] = mats["identity"] * mats["cov_query"]
-        frames = [pd.DataFrame(mats[k], index=hashes, columns=hashes) for k in ("identity", "cov_query", "hadamard")]
-    else:
-        cached = conn.execute("SELECT df_identity, df_cov_query, df_hadamard FROM runs WHERE run_id=?", (run_id,)).fetchone()
-        if any(c is None for c in cached):
-            out = cache_comparisons(conn, run)
-            cached = tuple(out.get(k) for k in keys)
-            if any(c is None for c in cached):
-                sourmash_hip.log_sys_exit(logger, f"Could not load run {method} matrix")
-        frames = [pd.read_json(StringIO(c), orient="split", dtype=float) for c in cached]
+    frames = _score_frames(logger, conn, run)
     conn.close()
     if done == 1 and n == 1:
         logger.warning("Run %d has %d comparison across %d genome. Reporting single clique.", run_id, done, n)
     else:
         logger.info("Run %d has %d comparisons across %d genomes.", run_id, done, n)
-    if label == "md5":
-        mapping = None
-    elif label == "filename":
-        mapping = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
-    elif label == "stem":
-        mapping = {a.genome_hash: filename_stem(a.fasta_filename) for a in run.fasta_hashes}
-        if len(set(mapping.values())) < len(mapping):
-            sourmash_hip.log_sys_exit(logger, "Duplicate filename stems, consider using MD5 labelling.")
-    else:
-        sourmash_hip.log_sys_exit(logger, f"Unexpected label scheme {label!r}")
-    if mapping is not None:
-        frames = [f.rename(index=mapping, columns=mapping).sort_index(axis=0).sort_index(axis=1) for f in frames]
-    identity, cov, hadamard = frames
+    identity, cov, hadamard = _relabelled(logger, run, frames, label)
     score = identity.to_numpy(dtype=float) if mode == "identity" else classify_mod.tani_scores(hadamard.to_numpy(dtype=float))
     rows = classify_mod.classify_matrices([str(x) for x in cov.columns], score, cov.to_numpy(dtype=float), coverage_edges=coverage_edges,
                                           score_edges=score_edges, cov_min=cov_min, engine=engine)
@@ -1383,9 +1397,116 @@ def classify(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     return written
 
 
+# ------------------------------------------------------------------ plot-run (pyani_plus/public_cli.py:1095-1136)
+# score, colour map, what a NaN cell counts as when the rows are clustered (pyani_plus/plot_run.py:320-325)
+_PLOT_SCORES = (("identity", "spbnd_BuRd", 0), ("query_cov", "BuRd", 0), ("hadamard", "viridis", 0), ("tANI", "viridis_r", -5))
+
+
+def _write_scatter_tables(logger, conn, run: Run, outdir: Path) -> list[Path]:
+    """``<method>_{query_cov,tANI}_scatter.tsv`` (pyani_plus/plot_run.py:231-293): identity, the y value and the query's
+    length of every comparison that has both, unrounded, in ``comparison_id`` order, numbers as Python's ``str``."""
+    method = run.configuration.method
+    lengths = dict(conn.execute("SELECT genome_hash, length FROM genomes"))
+    rows = [
+        (identity, cov_query, lengths[query])
+        for query, identity, cov_query in _select_run_comparisons(conn, run, "c.query_hash, c.identity, c.cov_query", "ORDER BY c.comparison_id")
+    ]
+    written = []
+    for caption, name in (("Query coverage", "query_cov"), ("tANI", "tANI")):
+        values = [(x, y, c) for x, y, c in rows if x is not None and y is not None]
+        if not values:
+            logger.warning("No valid identity, %s values from %s run", caption, method)
+            return written
+        logger.info("Plotting %d/%d %s vs identity %s comparisons", len(values), len(rows), caption, method)
+        if name == "tANI":
+            zeros = sum(1 for x, y, _c in values if x * y == 0)
+            if zeros:
+                # -log(0): the reference raises here and plots nothing more; this row is written with inf instead
+                logger.warning("%d %s comparisons have a zero Hadamard product: their tANI is written as inf", zeros, method)
+            values = [(x, -math.log(x * y) if x * y else math.inf, c) for x, y, c in values]
+        written.append(outdir / f"{method}_{name}_scatter.tsv")
+        with written[-1].open("w") as handle:
+            handle.write(f"#identity\t{name}\tquery_length\n")
+            for x, y, c in values:
+                handle.write(f"{x}\t{y}\t{c}\n")
+    return written
+
+
+def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", formats: tuple[str, ...] = ("tsv",),  # noqa: PLR0913
+             engine=None, logger: logging.Logger | None = None) -> list[Path]:
+    """Write what the reference's ``plot-run`` computes for a complete run: the clustered heatmap tables
+    ``<method>_{identity,query_cov,hadamard,tANI}_heatmap.tsv`` and the scatter tables
+    ``<method>_{query_cov,tANI}_scatter.tsv``, byte for byte what the reference writes from the same database, with its
+    messages for a missing database, an incomplete run, duplicate stems, an unknown label, an all-NaN matrix and a
+    matrix with some NaNs.
+
+    Each matrix (the cached ``runs.df_*`` strings; tANI is ``-log(h) if h else nan`` of the relabelled Hadamard matrix)
+    is relabelled, sorted by label, and put into the leaf order of the average-linkage clustering of its rows with NaN
+    cells counted as 0 (tANI: -5): what seaborn's ``clustermap`` computes for the reference, restated by
+    ``pyani_plus_amd.cluster`` with the same bits.  Every matrix is clustered on its own.
+
+    ``formats``: ``tsv`` writes the tables; any other format (``png``, ``pdf``, ``svg``, ``jpg``) adds the heatmap figure
+    with its row dendrogram, drawn with matplotlib alone.  The reference's distribution and scatter figures are not made.
+    A comparison with a zero Hadamard product is written to the tANI scatter table as ``inf``, where the reference raises.
+
+    ``engine``: a ``HipEngine`` computes the row distances on the GPU; None on the host.  Returns the written paths."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    if str(database) == ":memory:" or not Path(database).is_file():
+        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
+    formats = tuple(formats)
+    images = [ext for ext in formats if ext != "tsv"]
+    if images:
+        try:
+            importlib.import_module("matplotlib")
+        except ImportError:
+            sourmash_hip.log_sys_exit(logger, f"Image formats ({', '.join(images)}) need matplotlib, which cannot be imported; only tsv is available")
+    outdir = Path(outdir)
+    if not outdir.is_dir():
+        logger.warning("Output directory %s does not exist, making it.", outdir)
+        outdir.mkdir()
+    conn, run = _open_run(logger, database, run_id, "Plotting")
+    run_id = run.run_id
+    n = len(run.fasta_hashes)
+    done = count_run_comparisons(conn, run)
+    if not n:
+        sourmash_hip.log_sys_exit(logger, f"Run-id {run_id} has no genomes")
+    if done != n * n:  # db_orm.load_run(check_complete=True)
+        sourmash_hip.log_sys_exit(logger, f"run-id {run_id} has {done} of {n}^2={n * n} comparisons, {n * n - done} needed")
+    method = run.configuration.method
+    frames = dict(zip(("identity", "query_cov", "hadamard"), _relabelled(logger, run, _score_frames(logger, conn, run), label)))
+    written = _write_scatter_tables(logger, conn, run, outdir) if "tsv" in formats else []
+    conn.close()
+    for name, color_scheme, na_fill in _PLOT_SCORES:
+        if name == "tANI":
+            hadamard = frames["hadamard"]
+            matrix = hadamard.copy()
+            matrix.iloc[:, :] = -classify_mod.tani_scores(hadamard.to_numpy(dtype=float))  # -log(h) if h else nan; -log(1.0) is -0.0
+        else:
+            matrix = frames[name]
+        nulls = int(matrix.isna().to_numpy().sum())
+        if nulls == n * n:
+            logger.warning("Cannot plot %s as all NA", name)
+            continue
+        if nulls:
+            logger.warning("%s matrix contains %d nulls (out of %d\u00b2=%d %s comparisons)", name, nulls, n, n * n, method)
+        try:
+            tree, leaves = cluster_mod.cluster_tree(matrix.to_numpy(dtype=float), na_fill, engine)
+        except HipBackendError as err:
+            sourmash_hip.backend_failure(logger, f"plot-run clustering of {name}", err)
+        table = matrix.iloc[leaves, leaves]
+        for ext in formats:
+            written.append(outdir / f"{method}_{name}_heatmap.{ext}")
+            if ext == "tsv":
+                table.to_csv(written[-1], sep="\t")
+            else:
+                heatmap_figure.draw_heatmap(table, tree, leaves, name, color_scheme, written[-1])
+    logger.info("Wrote %d images to %s/%s_*.*", len(written), outdir, method)
+    return written
+
+
 # ------------------------------------------------------------------ the driver as a process
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,resume,export-run,classify} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,resume,export-run,classify,plot-run} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -1440,6 +1561,14 @@ def main(argv: list[str] | None = None) -> int:
     p_c.add_argument("--mode", choices=classify_mod.MODES, default="identity")
     p_c.add_argument("--device", type=int, default=None, help="build and sort the edge list on this GPU (default: on the host)")
     p_c.add_argument("--verbose", "-v", action="store_true")
+    p_p = sub.add_parser("plot-run", help="the clustered heatmap tables and the scatter tables of a complete run")
+    p_p.add_argument("--database", "-d", required=True, type=Path)
+    p_p.add_argument("--outdir", "-o", required=True, type=Path)
+    p_p.add_argument("--run-id", type=int, default=None)
+    p_p.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
+    p_p.add_argument("--formats", default="tsv", help="comma separated: tsv for the tables, png, pdf, svg or jpg for the heatmap figures (matplotlib)")
+    p_p.add_argument("--device", type=int, default=None, help="compute the row distances on this GPU (default: on the host)")
+    p_p.add_argument("--verbose", "-v", action="store_true")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
     logger = logging.getLogger("pyani_plus_amd")
@@ -1457,15 +1586,20 @@ def main(argv: list[str] | None = None) -> int:
         elif args.command == "resume":
             run = resume(args.database, run_id=args.run_id, cache=args.cache, temp=args.temp, logger=logger, ingest=args.ingest,
                          gpus=args.gpus, engine_factory=args.engine_factory)
-        elif args.command == "classify":
+        elif args.command in {"classify", "plot-run"}:
             engine = None
             if args.device is not None:
                 from .engine import HipEngine
 
                 engine = HipEngine(args.device)
             try:
-                print(classify(args.database, args.outdir, run_id=args.run_id, label=args.label, coverage_edges=args.coverage_edges,
-                               score_edges=args.score_edges, cov_min=args.cov_min, mode=args.mode, engine=engine, logger=logger))
+                if args.command == "classify":
+                    print(classify(args.database, args.outdir, run_id=args.run_id, label=args.label, coverage_edges=args.coverage_edges,
+                                   score_edges=args.score_edges, cov_min=args.cov_min, mode=args.mode, engine=engine, logger=logger))
+                else:
+                    formats = tuple(f for f in args.formats.split(",") if f)
+                    for path in plot_run(args.database, args.outdir, run_id=args.run_id, label=args.label, formats=formats, engine=engine, logger=logger):
+                        print(path)
             finally:
                 if engine is not None:
                     engine.close()
