@@ -538,6 +538,44 @@ PA_API int pa_rowdist_euclid(pa_ctx *ctx, const double *d_x, uint32_t n, uint32_
 PA_API int pa_rowdist_euclid_host(const double *h_x, uint32_t n, uint32_t m, double *h_out, uint32_t n_threads);
 PA_API int pa_linkage_average(uint32_t n, const double *h_condensed, double *h_Z, uint32_t *h_leaves);
 
+/* ---- plot-run-comp: two runs joined pair by pair, and the histograms of the joined values ----
+ * Replaces the dictionaries keyed by (query_hash, subject_hash), the list comprehensions and the Axes.hist calls of
+ * plot_run_comparison (pyani_plus/plot_run.py:404-575).  The reference run R is its n_ref x n_ref row-major f64
+ * identity matrix (rows = query, columns = subject, NaN where R has no value); the other run O is one row per
+ * comparison, in the caller's order: q and s, the u32 row and column of the comparison's genomes in R's matrix
+ * (0xFFFFFFFF: a genome R does not have), and y, O's identity (NaN for NULL).
+ *
+ *   pa_runcomp_join          (device) a row survives iff q < n_ref, s < n_ref, y is not NaN and ref[q, s] is not NaN (the
+ *        cell index q * n_ref + s is computed in 64 bits).  The survivors are written densely and in input order:
+ *        x = ref[q, s], y, and diff = y - x (one f64 subtraction), into three device arrays with room for n_rows
+ *        elements each; *n_common = their number.  Two passes with a prefix sum between them, no atomics; one host
+ *        synchronisation (n_common is read back).  PA_E_INVALID for n_ref > 65536 and n_rows >= 2^32; n_rows = 0 is
+ *        valid and writes nothing.
+ *   pa_minmax_f64            (device) out[0], out[1] = minimum and maximum of the non-NaN values of d_v[n], *n_valid =
+ *        their number; with n_valid = 0 out is untouched.  Compared as values: when -0.0 and 0.0 both occur, which of
+ *        them comes back is not defined.  One host synchronisation.
+ *   pa_hist_uniform_f64      (device) numpy.histogram's counts for uniform bins: h_edges are bins + 1 ascending finite
+ *        doubles from the caller (numpy.linspace(first, last, bins + 1) in the driver, so they have numpy's bits),
+ *        h_counts is u64[bins].  v is counted iff v >= edges[0] && v <= edges[bins] (NaN is not).  Its bin is
+ *        ((v - edges[0]) / (edges[bins] - edges[0])) * bins truncated -- a correctly rounded division, then the
+ *        multiplication, two roundings -- set to bins - 1 where it came out bins, decremented where v < edges[i], then
+ *        incremented where v >= edges[i + 1] and i != bins - 1 (numpy/lib/_histograms_impl.py, the uniform-bins branch).
+ *        PA_E_INVALID for bins outside 1 .. 1024, an edge that is not finite or lies below the one before it, and
+ *        edges[bins] - edges[0] not positive and finite.  One host synchronisation.
+ *   pa_runcomp_join_host, pa_minmax_f64_host, pa_hist_uniform_f64_host   the same from host arrays into host arrays,
+ *        plain loops, the same bits.
+ *   pa_write_pairs_tsv       (host) `header` and a newline, then n lines repr(x) TAB repr(y) with Python's
+ *        float.__repr__: what f"{x}\t{y}\n" writes for two Python floats. */
+PA_API int pa_runcomp_join(pa_ctx *ctx, const double *d_ref, uint32_t n_ref, const uint32_t *d_q, const uint32_t *d_s, const double *d_y,
+                           uint64_t n_rows, double *d_x, double *d_y_out, double *d_diff, uint64_t *n_common);
+PA_API int pa_minmax_f64(pa_ctx *ctx, const double *d_v, uint64_t n, double *out, uint64_t *n_valid);
+PA_API int pa_hist_uniform_f64(pa_ctx *ctx, const double *d_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts);
+PA_API int pa_runcomp_join_host(const double *h_ref, uint32_t n_ref, const uint32_t *h_q, const uint32_t *h_s, const double *h_y,
+                                uint64_t n_rows, double *h_x, double *h_y_out, double *h_diff, uint64_t *n_common);
+PA_API int pa_minmax_f64_host(const double *h_v, uint64_t n, double *out, uint64_t *n_valid);
+PA_API int pa_hist_uniform_f64_host(const double *h_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts);
+PA_API int pa_write_pairs_tsv(const char *path, const char *header, const double *h_x, const double *h_y, uint64_t n);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */

@@ -170,6 +170,13 @@ SIGNATURES: dict[str, tuple] = {
     "pa_rowdist_euclid": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp]),
     "pa_rowdist_euclid_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32]),
     "pa_linkage_average": (C.c_int, [C.c_uint32, _vp, _vp, _vp]),
+    "pa_runcomp_join": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _u64p]),
+    "pa_minmax_f64": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _u64p]),
+    "pa_hist_uniform_f64": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "pa_runcomp_join_host": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _u64p]),
+    "pa_minmax_f64_host": (C.c_int, [_vp, C.c_uint64, _vp, _u64p]),
+    "pa_hist_uniform_f64_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "pa_write_pairs_tsv": (C.c_int, [C.c_char_p, C.c_char_p, _vp, _vp, C.c_uint64]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),
     "pa_prof_get": (C.c_int, [_vp, C.c_int, _f64p, _u64p]),

@@ -318,3 +318,62 @@ extern "C" int pa_round_sig6(double *h_values, uint64_t n) {
   }
   return PA_OK;
 }
+
+// plot-run-comp's table: the header line, then one line per joined pair, `repr(x)\trepr(y)\n` -- what the reference's
+// f"{x}\t{y}\n" writes for two Python floats (pyani_plus/plot_run.py:537-540).
+namespace {
+// Python float.__repr__ for every double: "nan", "inf" and "-inf" besides the finite forms
+inline char *put_repr(char *p, char *end, double v) {
+  if (v != v) { memcpy(p, "nan", 3); return p + 3; }
+  if (std::isinf(v)) {
+    if (v < 0) *p++ = '-';
+    memcpy(p, "inf", 3);
+    return p + 3;
+  }
+  return put_double(p, end, v);
+}
+
+void format_pairs(std::vector<char> &out, const double *x, const double *y, uint64_t r0, uint64_t r1) {
+  out.resize((size_t)(r1 - r0) * 64);  // a repr is at most 24 characters
+  char *p = out.data();
+  char *const end = p + out.size();
+  for (uint64_t r = r0; r < r1; ++r) {
+    p = put_repr(p, end, x[r]);
+    *p++ = '\t';
+    p = put_repr(p, end, y[r]);
+    *p++ = '\n';
+  }
+  out.resize((size_t)(p - out.data()));
+}
+}  // namespace
+
+static int write_pairs_tsv(const char *path, const char *header, const double *h_x, const double *h_y, uint64_t n) {
+  if (!path || !header || (n && (!h_x || !h_y))) {
+    pa_set_error("pa_write_pairs_tsv: null argument");
+    return PA_E_INVALID;
+  }
+  FILE *f = fopen(path, "wb");
+  if (!f) { pa_set_error("cannot open %s for writing", path); return PA_E_INVALID; }
+  bool ok = fwrite(header, 1, strlen(header), f) == strlen(header) && fputc('\n', f) != EOF;
+  constexpr uint64_t kRowsPerChunk = 32768;  // ~1.3 MB of text
+  const uint64_t n_chunks = (n + kRowsPerChunk - 1) / kRowsPerChunk;
+  const uint32_t nt = n_chunks ? pa_host_threads(n_chunks, 1, 0) : 0;
+  std::vector<std::vector<char>> bufs(nt);
+  try {
+    for (uint64_t c0 = 0; c0 < n_chunks && ok; c0 += nt) {
+      const uint32_t in_round = (uint32_t)std::min<uint64_t>(nt, n_chunks - c0);
+      HostPool::get().run(in_round, [&](uint32_t w, uint32_t) {
+        const uint64_t r0 = (c0 + w) * kRowsPerChunk;
+        format_pairs(bufs[w], h_x, h_y, r0, std::min(n, r0 + kRowsPerChunk));
+      });
+      for (uint32_t w = 0; w < in_round && ok; ++w) ok = fwrite(bufs[w].data(), 1, bufs[w].size(), f) == bufs[w].size();
+    }
+  } catch (...) { fclose(f); throw; }
+  ok = (fclose(f) == 0) && ok;
+  if (!ok) { pa_set_error("short write to %s", path); return PA_E_INVALID; }
+  return PA_OK;
+}
+
+extern "C" int pa_write_pairs_tsv(const char *path, const char *header, const double *h_x, const double *h_y, uint64_t n) {
+  return pa_host_guard("pa_write_pairs_tsv", pa_set_error, [&] { return write_pairs_tsv(path, header, h_x, h_y, n); });
+}

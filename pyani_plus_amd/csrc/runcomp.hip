@@ -1,0 +1,285 @@
+// runcomp.hip -- plot-run-comp on the device (gfx950, wave64): two runs joined pair by pair, the minimum and maximum
+// of a vector, and numpy's uniform-bin histogram of it.
+//
+// The reference keeps one Python dictionary per run, keyed by (query_hash, subject_hash) tuples, looks every pair of
+// the other run up in the reference run's dictionary and hands the joined lists to Axes.hist
+// (pyani_plus/plot_run.py:404-575).  Here the reference run R is its n_ref x n_ref identity matrix (NaN: no value) and
+// the other run O is three arrays in database order: the row and the column of each of its comparisons in R's matrix,
+// and its own identity.  The join is then a gather and a stream compaction, and the histograms are reductions.
+// DESIGN.md section 7d has the definition and the measurements.
+//
+// pa_runcomp_join, the shape of classify.hip:
+//   1. rc_join_kernel<false>: a lane per row.  A row survives iff q < n_ref, s < n_ref, y is not NaN and ref[q, s] is
+//      not NaN; the indices are checked before the cell is read, and the cell index q * n_ref + s is 64-bit.  Each
+//      wave counts the survivors of its 64 consecutive rows with one ballot and writes the count of that group.
+//   2. pa_exclusive_scan_u32 over the group counts, which lie in row order: the offset of a group is the number of
+//      survivors before it.  The total is read back, the call's only host synchronisation.
+//   3. rc_join_kernel<true>: the same evaluation again; a surviving lane writes x = ref[q, s], y and d = y - x at
+//      offset + popcount(ballot below the lane).  The output is therefore dense and in input order, and no atomic
+//      decides a position.
+//
+// Rows per workgroup: T = 1024 (256 threads, four 64-row groups per wave).  In iteration k the workgroup takes the 256
+// consecutive rows base + 256 k ..., so q, s and y are read coalesced, and the four iterations are unrolled with the
+// loads first: a lane has four independent gathers in flight, which is what there is to hide the latency of a cell
+// that misses the caches.  More rows per workgroup would only add registers; at 10^8 rows T = 1024 is 97 657
+// workgroups, far more than the 256 CUs hold at once, so the tail is short.
+//
+// The ref gather is the random-access part, and what it costs depends on O's order.  O's rows usually come in the
+// order a run was written, over the same sorted genomes as R: row by row (q fixed over n consecutive rows, s
+// ascending) the 64 lanes of a wave read 512 contiguous bytes, the same as a stream; column by column (s fixed, q
+// ascending) every lane reads its own cache line, n_ref * 8 bytes from its neighbour's, and that line is used again
+// only n rows later by the next column, so the reuse needs n_ref lines to stay cached between two columns (1.3 MB of
+// 128-byte lines at n_ref = 10^4).  A run over other genomes or in another order is a random gather from an
+// 8 n_ref^2 byte table: 8 MB at n_ref = 1000, 800 MB (beyond every cache) at n_ref = 10^4.  Nothing about the cache
+// behaviour of any of these has been measured; tools/runcomp_bench.py times whole calls only.
+//
+// pa_minmax_f64: a grid-stride pass, at most 1024 workgroups, each reduces its share through LDS to one (min, max,
+// count) triple; a one-workgroup second pass reduces the triples.  No atomics; values are compared as values.
+//
+// pa_hist_uniform_f64: numpy.histogram's uniform-bin rule (numpy/lib/_histograms_impl.py): the bin of v is
+// ((v - first) / (last - first)) * bins truncated, with the three corrections against the edges.  The division is
+// the IEEE one (v_div_scale / v_div_fmas / v_div_fixup, correctly rounded) and the product is rounded on its own:
+// contraction is off for this file, by the pragma below and by the Makefile.  The edges are the caller's (numpy's
+// linspace in the driver), staged in LDS; the counters of a workgroup are u32 in LDS (a workgroup sees at most
+// n / 1024 + 256 values) and are added once to the u64 counters in global memory, which decides no position.  All
+// loads are 8 bytes per lane: the callers pass slices of tensors, which promise no wider alignment.
+#include <cstring>
+
+#include "pa_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kGroups = 4;                                      // 64-row groups per wave
+constexpr uint32_t kRowsPerWg = (uint32_t)kThreads * kGroups;  // T
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kMaxBlocks = 1024;  // grid-stride passes: four workgroups for each of the 256 CUs
+constexpr uint32_t kMaxBins = 1024;
+
+template <bool SCATTER>
+__global__ __launch_bounds__(kThreads) void rc_join_kernel(const double *__restrict__ ref, uint32_t n_ref, const uint32_t *__restrict__ q,
+                                                           const uint32_t *__restrict__ s, const double *__restrict__ y, uint64_t n_rows,
+                                                           uint32_t *__restrict__ counts /*per 64 rows: counts out, or offsets in*/,
+                                                           uint64_t n_common, double *__restrict__ o_x, double *__restrict__ o_y,
+                                                           double *__restrict__ o_d) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint64_t base = (uint64_t)blockIdx.x * kRowsPerWg;
+  const double nan = __builtin_nan("");
+  uint32_t qi[kGroups], si[kGroups];
+  double yv[kGroups], xv[kGroups];
+#pragma unroll
+  for (int k = 0; k < kGroups; ++k) {
+    const uint64_t r = base + (uint64_t)k * kThreads + threadIdx.x;
+    const bool in = r < n_rows;
+    qi[k] = in ? q[r] : kNone;
+    si[k] = in ? s[r] : kNone;
+    yv[k] = in ? y[r] : nan;
+  }
+#pragma unroll
+  for (int k = 0; k < kGroups; ++k) {
+    const bool ok = qi[k] < n_ref && si[k] < n_ref && yv[k] == yv[k];
+    xv[k] = ok ? ref[(uint64_t)qi[k] * n_ref + si[k]] : nan;
+  }
+  const uint64_t below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));
+#pragma unroll
+  for (int k = 0; k < kGroups; ++k) {
+    const uint64_t g = (uint64_t)blockIdx.x * (kRowsPerWg / 64) + (uint64_t)k * (kThreads / 64) + wave;  // rows 64 g .. 64 g + 63
+    if (g * 64 >= n_rows) break;  // uniform in the wave; the groups of later k lie further on
+    const bool keep = xv[k] == xv[k];  // NaN also where an index or y ruled the row out
+    const uint64_t mask = __ballot(keep);
+    if (!SCATTER) {
+      if (lane == 0) counts[g] = (uint32_t)__popcll(mask);
+    } else if (keep) {
+      const uint64_t at = (uint64_t)counts[g] + __popcll(mask & below);
+      if (at < n_common) {  // always: the offsets are the scan of the counts of the same evaluation
+        o_x[at] = xv[k];
+        o_y[at] = yv[k];
+        o_d[at] = yv[k] - xv[k];
+      }
+    }
+  }
+}
+
+// the workgroup's (min, max, count) in thread 0; s_* hold kThreads elements each
+__device__ __forceinline__ void block_minmax(double &lo, double &hi, unsigned long long &cnt, double *s_lo, double *s_hi,
+                                             unsigned long long *s_cnt) {
+  s_lo[threadIdx.x] = lo;
+  s_hi[threadIdx.x] = hi;
+  s_cnt[threadIdx.x] = cnt;
+  __syncthreads();
+  for (uint32_t step = kThreads / 2; step > 0; step >>= 1) {
+    if (threadIdx.x < step) {
+      const double a = s_lo[threadIdx.x + step], b = s_hi[threadIdx.x + step];
+      if (a < s_lo[threadIdx.x]) s_lo[threadIdx.x] = a;
+      if (b > s_hi[threadIdx.x]) s_hi[threadIdx.x] = b;
+      s_cnt[threadIdx.x] += s_cnt[threadIdx.x + step];
+    }
+    __syncthreads();
+  }
+  lo = s_lo[0];
+  hi = s_hi[0];
+  cnt = s_cnt[0];
+}
+
+// partial[3 b .. 3 b + 2] = min, max and (as its bits) the count of the non-NaN values of workgroup b's share
+__global__ __launch_bounds__(kThreads) void rc_minmax_kernel(const double *__restrict__ v, uint64_t n, double *__restrict__ partial) {
+  __shared__ double s_lo[kThreads], s_hi[kThreads];
+  __shared__ unsigned long long s_cnt[kThreads];
+  double lo = __builtin_inf(), hi = -__builtin_inf();
+  unsigned long long cnt = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads) {
+    const double x = v[i];
+    if (x == x) {
+      lo = x < lo ? x : lo;
+      hi = x > hi ? x : hi;
+      ++cnt;
+    }
+  }
+  block_minmax(lo, hi, cnt, s_lo, s_hi, s_cnt);
+  if (threadIdx.x == 0) {
+    partial[3 * (uint64_t)blockIdx.x] = lo;
+    partial[3 * (uint64_t)blockIdx.x + 1] = hi;
+    partial[3 * (uint64_t)blockIdx.x + 2] = __longlong_as_double((long long)cnt);
+  }
+}
+
+// one workgroup: the n_partial triples -> result[0 .. 2] (min, max, the count's bits)
+__global__ __launch_bounds__(kThreads) void rc_minmax_final_kernel(const double *__restrict__ partial, uint32_t n_partial,
+                                                                  double *__restrict__ result) {
+  __shared__ double s_lo[kThreads], s_hi[kThreads];
+  __shared__ unsigned long long s_cnt[kThreads];
+  double lo = __builtin_inf(), hi = -__builtin_inf();
+  unsigned long long cnt = 0;
+  for (uint32_t b = threadIdx.x; b < n_partial; b += kThreads) {
+    const unsigned long long c = (unsigned long long)__double_as_longlong(partial[3 * (uint64_t)b + 2]);
+    if (c) {  // an empty share holds the identities, which compare correctly, but skip them all the same
+      const double a = partial[3 * (uint64_t)b], z = partial[3 * (uint64_t)b + 1];
+      lo = a < lo ? a : lo;
+      hi = z > hi ? z : hi;
+      cnt += c;
+    }
+  }
+  block_minmax(lo, hi, cnt, s_lo, s_hi, s_cnt);
+  if (threadIdx.x == 0) {
+    result[0] = lo;
+    result[1] = hi;
+    result[2] = __longlong_as_double((long long)cnt);
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void rc_hist_kernel(const double *__restrict__ v, uint64_t n, const double *__restrict__ edges /*[bins + 1]*/,
+                                                           uint32_t bins, unsigned long long *__restrict__ counts /*[bins]*/) {
+  __shared__ double s_edges[kMaxBins + 1];
+  __shared__ uint32_t s_counts[kMaxBins];
+  for (uint32_t b = threadIdx.x; b <= bins; b += kThreads) s_edges[b] = edges[b];
+  for (uint32_t b = threadIdx.x; b < bins; b += kThreads) s_counts[b] = 0;
+  __syncthreads();
+  const double first = s_edges[0], last = s_edges[bins];
+  const double span = last - first, nb = (double)bins;
+  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads) {
+    const double x = v[i];
+    if (x >= first && x <= last) {  // false for NaN
+      const double t = (x - first) / span;  // in [0, 1]: both differences are rounded the same way
+      uint32_t b = (uint32_t)(t * nb);      // in [0, bins]
+      if (b >= bins) b = bins - 1;          // the last edge belongs to the last bin
+      if (x < s_edges[b]) --b;              // never at b = 0: x >= first
+      if (x >= s_edges[b + 1] && b != bins - 1) ++b;
+      atomicAdd(&s_counts[b], 1u);
+    }
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < bins; b += kThreads)
+    if (s_counts[b]) atomicAdd(&counts[b], (unsigned long long)s_counts[b]);
+}
+
+inline uint32_t stride_blocks(uint64_t n) {
+  const uint64_t want = (n + kThreads - 1) / kThreads;
+  return (uint32_t)(want < kMaxBlocks ? want : kMaxBlocks);
+}
+
+}  // namespace
+
+extern "C" int pa_runcomp_join(pa_ctx *c, const double *d_ref, uint32_t n_ref, const uint32_t *d_q, const uint32_t *d_s, const double *d_y,
+                               uint64_t n_rows, double *d_x, double *d_y_out, double *d_diff, uint64_t *n_common) {
+  PA_REQUIRE(c != nullptr && n_common != nullptr, "pa_runcomp_join: null argument");
+  PA_REQUIRE(n_ref <= (1u << 16), "pa_runcomp_join: %u genomes in the reference run; at most 65536", n_ref);
+  // the offsets of the compaction are 32-bit
+  PA_REQUIRE(n_rows < (1ULL << 32), "pa_runcomp_join: %llu rows; at most 2^32 - 1", (unsigned long long)n_rows);
+  *n_common = 0;
+  if (n_rows == 0) return PA_OK;
+  PA_REQUIRE(d_q && d_s && d_y && d_x && d_y_out && d_diff && (n_ref == 0 || d_ref), "pa_runcomp_join: null array");
+  PA_HIP(hipSetDevice(c->device));
+  const uint64_t n_groups = (n_rows + 63) / 64;
+  PA_TRY(c->flags.reserve(n_groups * sizeof(uint32_t)));
+  uint32_t *d_counts = c->flags.as<uint32_t>();
+  uint64_t *d_total = c->counters.as<uint64_t>() + 4;
+  const dim3 grid(ceil_div_u64(n_rows, kRowsPerWg));
+  hipLaunchKernelGGL(rc_join_kernel<false>, grid, dim3(kThreads), 0, c->stream, d_ref, n_ref, d_q, d_s, d_y, n_rows, d_counts, 0ULL, nullptr,
+                     nullptr, nullptr);
+  PA_HIP(hipGetLastError());
+  PA_TRY(pa_exclusive_scan_u32(c, d_counts, d_counts, n_groups, d_total));
+  PA_HIP(hipMemcpyAsync(c->h_pinned, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  const uint64_t total = c->h_pinned[0];
+  *n_common = total;
+  if (total == 0) return PA_OK;
+  hipLaunchKernelGGL(rc_join_kernel<true>, grid, dim3(kThreads), 0, c->stream, d_ref, n_ref, d_q, d_s, d_y, n_rows, d_counts, total, d_x,
+                     d_y_out, d_diff);
+  PA_HIP(hipGetLastError());
+  return PA_OK;
+}
+
+extern "C" int pa_minmax_f64(pa_ctx *c, const double *d_v, uint64_t n, double *out, uint64_t *n_valid) {
+  PA_REQUIRE(c != nullptr && out != nullptr && n_valid != nullptr, "pa_minmax_f64: null argument");
+  *n_valid = 0;
+  if (n == 0) return PA_OK;
+  PA_REQUIRE(d_v != nullptr, "pa_minmax_f64: null array");
+  PA_HIP(hipSetDevice(c->device));
+  const uint32_t blocks = stride_blocks(n);
+  PA_TRY(c->hist.reserve(((uint64_t)blocks + 1) * 3 * sizeof(double)));
+  double *d_partial = c->hist.as<double>();
+  double *d_result = d_partial + 3 * (uint64_t)blocks;
+  hipLaunchKernelGGL(rc_minmax_kernel, dim3(blocks), dim3(kThreads), 0, c->stream, d_v, n, d_partial);
+  hipLaunchKernelGGL(rc_minmax_final_kernel, dim3(1), dim3(kThreads), 0, c->stream, d_partial, blocks, d_result);
+  PA_HIP(hipGetLastError());
+  PA_HIP(hipMemcpyAsync(c->h_pinned, d_result, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  const uint64_t valid = c->h_pinned[2];
+  *n_valid = valid;
+  if (valid) {
+    double mm[2];
+    memcpy(mm, c->h_pinned, sizeof mm);
+    out[0] = mm[0];
+    out[1] = mm[1];
+  }
+  return PA_OK;
+}
+
+extern "C" int pa_hist_uniform_f64(pa_ctx *c, const double *d_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts) {
+  PA_REQUIRE(c != nullptr && h_edges != nullptr && h_counts != nullptr, "pa_hist_uniform_f64: null argument");
+  PA_REQUIRE(bins >= 1 && bins <= kMaxBins, "pa_hist_uniform_f64: %u bins; 1 to 1024", bins);
+  PA_REQUIRE(n < (1ULL << 40), "pa_hist_uniform_f64: %llu values; a workgroup's counters are 32-bit", (unsigned long long)n);
+  for (uint32_t b = 0; b <= bins; ++b) {
+    const double e = h_edges[b];
+    PA_REQUIRE(e - e == 0.0, "pa_hist_uniform_f64: edge %u is not finite", b);
+    PA_REQUIRE(b == 0 || h_edges[b - 1] <= e, "pa_hist_uniform_f64: edge %u is below edge %u", b, b - 1);
+  }
+  const double span = h_edges[bins] - h_edges[0];
+  PA_REQUIRE(span > 0.0 && span - span == 0.0, "pa_hist_uniform_f64: the last edge must be above the first and their difference finite");
+  for (uint32_t b = 0; b < bins; ++b) h_counts[b] = 0;
+  if (n == 0) return PA_OK;
+  PA_REQUIRE(d_v != nullptr, "pa_hist_uniform_f64: null array");
+  PA_HIP(hipSetDevice(c->device));
+  PA_TRY(c->hist.reserve((2 * (uint64_t)bins + 1) * 8));
+  unsigned long long *d_counts = c->hist.as<unsigned long long>();
+  double *d_edges = reinterpret_cast<double *>(d_counts + bins);
+  PA_HIP(hipMemsetAsync(d_counts, 0, (uint64_t)bins * 8, c->stream));
+  PA_HIP(hipMemcpyAsync(d_edges, h_edges, ((uint64_t)bins + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(rc_hist_kernel, dim3(stride_blocks(n)), dim3(kThreads), 0, c->stream, d_v, n, d_edges, bins, d_counts);
+  PA_HIP(hipGetLastError());
+  PA_HIP(hipMemcpyAsync(h_counts, d_counts, (uint64_t)bins * 8, hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));  // the caller's edges and counts are not touched after the return
+  return PA_OK;
+}

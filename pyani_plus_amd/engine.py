@@ -690,6 +690,76 @@ class HipEngine:
         """``row_distances_device`` copied back: the same bits as ``scipy.spatial.distance.pdist(matrix, "euclidean")``."""
         return self.row_distances_device(matrix).cpu().numpy()
 
+    # -- plot-run-comp
+    def _f64_on_device(self, values):
+        t = self.torch
+        if not isinstance(values, t.Tensor):
+            values = t.from_numpy(np.ascontiguousarray(values, dtype=np.float64))
+        return values.to(device=self.device, dtype=t.float64).contiguous()
+
+    def _u32_on_device(self, index):
+        """A u32 index array as an int32 tensor with the same bits (0xFFFFFFFF is -1)."""
+        t = self.torch
+        if not isinstance(index, t.Tensor):
+            index = t.from_numpy(np.ascontiguousarray(index, dtype=np.uint32).view(np.int32))
+        if index.dtype != t.int32:
+            raise ValueError(f"index tensor of {index.dtype}, expected int32 (the bits of the u32 indices)")
+        return index.to(device=self.device).contiguous()
+
+    def run_join_device(self, ref, q, s, y):
+        """``pa_runcomp_join``: ``(x, y, d)`` as device tensors trimmed to the rows in common, in input order.  ``ref``
+        is the reference run's N x N float64 identity matrix (NaN: no value), ``q`` and ``s`` the u32 row and column of
+        each comparison of the other run (0xFFFFFFFF: not a genome of the reference run; int32 tensors with those bits),
+        ``y`` its identity (NaN: NULL); host arrays or tensors on this device."""
+        t = self.torch
+        d_ref, d_q, d_s, d_y = self._f64_on_device(ref), self._u32_on_device(q), self._u32_on_device(s), self._f64_on_device(y)
+        n_ref = d_ref.shape[0] if d_ref.dim() == 2 else -1
+        if d_ref.dim() != 2 or d_ref.shape != (n_ref, n_ref):
+            raise ValueError(f"reference matrix of shape {tuple(d_ref.shape)}, expected a square one")
+        n_rows = d_y.numel()
+        if d_q.shape != (n_rows,) or d_s.shape != (n_rows,) or d_y.shape != (n_rows,):
+            raise ValueError(f"q {tuple(d_q.shape)}, s {tuple(d_s.shape)} and y {tuple(d_y.shape)} must be vectors of one length")
+        if n_ref > 1 << 16:  # the library's limit
+            raise ValueError(f"{n_ref} genomes in the reference run; at most 65536")
+        out =t.empty((3, n_rows), dtype=t.float64, device=self.device)
+        count = C.c_uint64(0)
+        self._check(
+            self.lib.pa_runcomp_join(
+                self.ctx, d_ref.data_ptr(), n_ref, d_q.data_ptr(), d_s.data_ptr(), d_y.data_ptr(), n_rows, out[0].data_ptr(), out[1].data_ptr(),
+                out[2].data_ptr(), C.byref(count),
+            ),  # fmt: skip
+            "pa_runcomp_join",
+        )
+        m = count.value
+        return out[0, :m], out[1, :m], out[2, :m]
+
+    def run_join(self, ref, q, s, y):
+        """``run_join_device`` copied back: ``(x, y, d)`` as host float64 arrays."""
+        return tuple(v.cpu().numpy() for v in self.run_join_device(ref, q, s, y))
+
+    def minmax(self, values) -> tuple[float, float, int]:
+        """``pa_minmax_f64``: ``(minimum, maximum, n_valid)`` of the non-NaN values of ``values`` (a host array or a
+        float64 tensor on this device, which is not copied); ``(nan, nan, 0)`` when there is none."""
+        d_v = self._f64_on_device(values).reshape(-1)
+        out = (C.c_double * 2)(float("nan"), float("nan"))
+        valid = C.c_uint64(0)
+        self._check(self.lib.pa_minmax_f64(self.ctx, d_v.data_ptr(), d_v.numel(), out, C.byref(valid)), "pa_minmax_f64")
+        return float(out[0]), float(out[1]), int(valid.value)
+
+    def hist_uniform(self, values, edges) -> np.ndarray:
+        """``pa_hist_uniform_f64``: the uint64 counts of ``numpy.histogram`` over the uniform bins whose ascending
+        ``edges`` the caller made (``run_comp.hist_edges``); ``values`` is a host array or a float64 tensor on this
+        device, which is not copied.  NaN and values outside the edges are not counted."""
+        d_v = self._f64_on_device(values).reshape(-1)
+        h_edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if h_edges.ndim != 1 or len(h_edges) < 2:
+            raise ValueError(f"edges of shape {h_edges.shape}, expected at least two in one dimension")
+        counts = np.zeros(len(h_edges) - 1, dtype=np.uint64)
+        self._check(
+            self.lib.pa_hist_uniform_f64(self.ctx, d_v.data_ptr(), d_v.numel(), h_edges.ctypes.data, len(counts), counts.ctypes.data), "pa_hist_uniform_f64"
+        )
+        return counts
+
     # -- profiling
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")

@@ -4,8 +4,8 @@
 The reference's Python (Typer CLI, SQLAlchemy ORM, snakemake) does not travel to the GPU
 box, so this module is the build's own counterpart of ``cli_sourmash`` / ``fastani`` / ``external_alignment`` +
 ``start_and_run_method`` + ``run_method`` minus snakemake (pyani_plus/public_cli.py:115-329, 502-554,
-598-699), of ``resume``, ``export-run``, ``plot-run`` (its tables; pyani_plus/plot_run.py) and ``classify`` (702-828, 974-1091,
-1095-1136, 1211-1331) and of the parts of ``db_orm`` they use (SURVEY.md
+598-699), of ``resume``, ``export-run``, ``plot-run`` and ``plot-run-comp`` (their tables; pyani_plus/plot_run.py) and ``classify``
+(702-828, 974-1091, 1095-1208, 1211-1331) and of the parts of ``db_orm`` they use (SURVEY.md
 section 8b, last row):
 
 * FASTA enumeration by the four extensions +- ``.gz`` (pyani_plus/utils.py:226-242)
@@ -51,7 +51,8 @@ import numpy as np
 from . import _capi, launch, wire
 from . import classify as classify_mod
 from . import cluster as cluster_mod
-from . import heatmap_figure
+from . import heatmap_figure, run_comp_figure
+from . import run_comp as run_comp_mod
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
 from .engine import load_fasta_files
@@ -1504,9 +1505,114 @@ def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     return written
 
 
+# ------------------------------------------------------------------ plot-run-comp (pyani_plus/public_cli.py:1140-1208)
+_RUN_COMP_CHUNK = 1 << 16  # comparisons fetched from SQLite at a time
+
+
+def _run_comparison_columns(conn, run: Run) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(q, s, identity)`` of the run's comparisons in ``comparison_id`` order: uint32 positions of the query and the
+    subject in the TEMP table ``run_comp_ref`` (``run_comp.NONE`` for a genome that is not in it) and float64 identities
+    (NaN for NULL).  The hashes are turned into positions by SQLite and the rows become arrays a chunk at a time: no
+    Python dictionary is consulted per row and no list of all the rows is built."""
+    cursor = _select_run_comparisons(
+        conn, run,
+        "COALESCE((SELECT h.idx FROM temp.run_comp_ref h WHERE h.genome_hash = c.query_hash), -1), "
+        "COALESCE((SELECT h.idx FROM temp.run_comp_ref h WHERE h.genome_hash = c.subject_hash), -1), c.identity",
+        "ORDER BY c.comparison_id",
+    )  # fmt: skip
+    parts: list[tuple[np.ndarray, np.ndarray, np.ndarray]] = []
+    while rows := cursor.fetchmany(_RUN_COMP_CHUNK):
+        q, s, y = zip(*rows)
+        parts.append((np.array(q, dtype=np.int64).astype(np.uint32), np.array(s, dtype=np.int64).astype(np.uint32), np.array(y, dtype=np.float64)))
+    if not parts:
+        return np.empty(0, dtype=np.uint32), np.empty(0, dtype=np.uint32), np.empty(0, dtype=np.float64)
+    return tuple(np.concatenate(column) for column in zip(*parts))
+
+
+def plot_run_comp(database: Path | str, outdir: Path, run_ids, *, columns: int = 0, formats: tuple[str, ...] = ("tsv",),  # noqa: PLR0913
+                  engine=None, logger: logging.Logger | None = None) -> list[Path]:
+    """Compare the identities of runs of one database pair by pair, as the reference's ``plot-run-comp`` does: the first
+    of ``run_ids`` (a comma separated string, or integers) is the reference run, and for each further run the table
+    ``<method>_identity_<ref>_vs_<other>.tsv`` holds a line ``x TAB y`` for every ordered genome pair both runs have an
+    identity for (x the reference run's, y the other's, unrounded, under the header ``#<ref name> TAB <other name>``),
+    with the reference's messages.  The rows are in the order of the other run's ``comparison_id``, where the reference
+    leaves the order to the SQLite planner.  The runs need not be complete.
+
+    ``formats``: ``tsv`` writes the tables; any other format (``png``, ``pdf``, ``svg``, ``jpg``) adds
+    ``<method>_identity_<ref>_{scatter,diff}_vs_others.<ext>`` on the reference's grid (``columns`` panels a row, 0 for a
+    square tiling), drawn with matplotlib alone from the computed 30-bin histograms (``pyani_plus_amd.run_comp``).
+
+    ``engine``: a ``HipEngine`` joins the runs and takes the histograms on the GPU; None on the host, with the same
+    bytes.  Returns the written paths."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    if str(database) == ":memory:" or not Path(database).is_file():
+        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
+    formats = tuple(formats)
+    images = [ext for ext in formats if ext != "tsv"]
+    if images:
+        try:
+            importlib.import_module("matplotlib")
+        except ImportError:
+            sourmash_hip.log_sys_exit(logger, f"Image formats ({', '.join(images)}) need matplotlib, which cannot be imported; only tsv is available")
+    outdir = Path(outdir)
+    if not outdir.is_dir():
+        logger.warning("Output directory %s does not exist, making it.", outdir)
+        outdir.mkdir()
+    try:
+        runs = [int(x) for x in (run_ids.split(",") if isinstance(run_ids, str) else run_ids)]
+    except (TypeError, ValueError):
+        sourmash_hip.log_sys_exit(logger, f"Expected comma separated list of runs, not: {run_ids}")
+    if len(runs) < 2:  # noqa: PLR2004
+        sourmash_hip.log_sys_exit(logger, "Need at least two runs for a comparison")
+    ref_id, other_ids = runs[0], runs[1:]
+    conn, ref_run = _open_run(logger, database, ref_id, "Plotting")
+    if not count_run_comparisons(conn, ref_run):
+        sourmash_hip.log_sys_exit(logger, f"Run {ref_id} has no comparisons")
+    method = ref_run.configuration.method
+    hashes = sorted(a.genome_hash for a in ref_run.fasta_hashes)
+    conn.execute("DROP TABLE IF EXISTS temp.run_comp_ref")
+    conn.execute("CREATE TEMP TABLE run_comp_ref (genome_hash VARCHAR NOT NULL PRIMARY KEY, idx INTEGER NOT NULL)")
+    conn.executemany("INSERT INTO temp.run_comp_ref VALUES (?, ?)", zip(hashes, range(len(hashes))))
+    q, s, y = _run_comparison_columns(conn, ref_run)
+    ref = np.full((len(hashes), len(hashes)), np.nan)
+    ref[q, s] = y  # (query, subject) is unique under one configuration
+    del q, s, y
+    logger.info("Plotting %d runs against %s run %d which has %d comparisons", len(other_ids), method, ref_id, int(np.count_nonzero(~np.isnan(ref))))
+    written: list[Path] = []
+    comparisons, other_names = [], []
+    try:
+        ref_values = engine.torch.from_numpy(ref).to(engine.device) if engine is not None else ref  # uploaded once
+        x_hist = run_comp_mod.range_and_counts(ref_values, engine)
+        for other_id in other_ids:
+            try:
+                other = load_run(conn, other_id)
+            except ValueError:
+                sourmash_hip.log_sys_exit(logger, f"Database {database} has no run-id {other_id}.")
+            comp = run_comp_mod.compare(ref_values, *_run_comparison_columns(conn, other), engine, x_hist=x_hist)
+            if not len(comp.x):
+                sourmash_hip.log_sys_exit(logger, f"Runs {ref_id} and {other_id} have no comparisons in common")
+            logger.info("Plotting %s run %d vs %s run %d, with %d comparisons in common", other.configuration.method, other_id, method, ref_id, len(comp.x))
+            if "tsv" in formats:
+                written.append(outdir / f"{method}_identity_{ref_id}_vs_{other_id}.tsv")
+                run_comp_mod.write_pairs_tsv(written[-1], f"#{ref_run.name}\t{other.name}", comp.x, comp.y)
+            if images:  # the figures need every run's values at once; the tables do not
+                comparisons.append(comp)
+                other_names.append(other.name)
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, "plot-run-comp", err)
+    finally:
+        conn.close()
+    for mode in ("scatter", "diff"):
+        for ext in images:
+            written.append(outdir / f"{method}_identity_{ref_id}_{mode}_vs_others.{ext}")
+            run_comp_figure.draw_comparison(mode, ref_run.name, other_names, comparisons, written[-1], columns)
+    logger.info("Wrote %d images to %s/%s_identity_%d_vs_*.*", 2 * len(images), outdir, method, ref_id)
+    return written
+
+
 # ------------------------------------------------------------------ the driver as a process
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,resume,export-run,classify,plot-run} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,resume,export-run,classify,plot-run,plot-run-comp} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -1569,6 +1675,14 @@ def main(argv: list[str] | None = None) -> int:
     p_p.add_argument("--formats", default="tsv", help="comma separated: tsv for the tables, png, pdf, svg or jpg for the heatmap figures (matplotlib)")
     p_p.add_argument("--device", type=int, default=None, help="compute the row distances on this GPU (default: on the host)")
     p_p.add_argument("--verbose", "-v", action="store_true")
+    p_pc = sub.add_parser("plot-run-comp", help="the identities of further runs against a reference run's, pair by pair")
+    p_pc.add_argument("--database", "-d", required=True, type=Path)
+    p_pc.add_argument("--outdir", "-o", required=True, type=Path)
+    p_pc.add_argument("--run-ids", required=True, help="comma separated list of runs, the reference run first")
+    p_pc.add_argument("--columns", type=int, default=0, help="panels per row of the figures (default 0: a square tiling)")
+    p_pc.add_argument("--formats", default="tsv", help="comma separated: tsv for the tables, png, pdf, svg or jpg for the two figures (matplotlib)")
+    p_pc.add_argument("--device", type=int, default=None, help="join the runs and take the histograms on this GPU (default: on the host)")
+    p_pc.add_argument("--verbose", "-v", action="store_true")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
     logger = logging.getLogger("pyani_plus_amd")
@@ -1586,7 +1700,7 @@ def main(argv: list[str] | None = None) -> int:
         elif args.command == "resume":
             run = resume(args.database, run_id=args.run_id, cache=args.cache, temp=args.temp, logger=logger, ingest=args.ingest,
                          gpus=args.gpus, engine_factory=args.engine_factory)
-        elif args.command in {"classify", "plot-run"}:
+        elif args.command in {"classify", "plot-run", "plot-run-comp"}:
             engine = None
             if args.device is not None:
                 from .engine import HipEngine
@@ -1596,6 +1710,10 @@ def main(argv: list[str] | None = None) -> int:
                 if args.command == "classify":
                     print(classify(args.database, args.outdir, run_id=args.run_id, label=args.label, coverage_edges=args.coverage_edges,
                                    score_edges=args.score_edges, cov_min=args.cov_min, mode=args.mode, engine=engine, logger=logger))
+                elif args.command == "plot-run-comp":
+                    formats = tuple(f for f in args.formats.split(",") if f)
+                    for path in plot_run_comp(args.database, args.outdir, args.run_ids, columns=args.columns, formats=formats, engine=engine, logger=logger):
+                        print(path)
                 else:
                     formats = tuple(f for f in args.formats.split(",") if f)
                     for path in plot_run(args.database, args.outdir, run_id=args.run_id, label=args.label, formats=formats, engine=engine, logger=logger):

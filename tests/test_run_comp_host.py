@@ -1,0 +1,363 @@
+"""plot-run-comp without a GPU: the host join against the dictionary definition and a numpy restatement, the host
+histogram against ``numpy.histogram``, the host minimum and maximum against numpy's, the table writer against Python's
+float formatting, and ``rundb.plot_run_comp`` end to end on a database with four runs, with its messages."""
+
+from __future__ import annotations
+
+import datetime
+import logging
+import sqlite3
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from pyani_plus_amd import _capi, run_comp, rundb
+from pyani_plus_amd._capi import HipBackendError
+from tests.fake_engine import OracleEngine
+from tests.helpers import FIXTURE_SETS, GOLDEN
+from tests.run_comp_cases import (
+    HIST_BINS,
+    HIST_FAMILIES,
+    JOIN_PATTERNS,
+    JOIN_REFS,
+    NONE,
+    T,
+    adversarial_values,
+    as_rows,
+    dict_join,
+    expected_table,
+    hist_inputs,
+    join_inputs,
+    join_reference,
+    make_viral_db,
+    numpy_hist,
+    numpy_join,
+    run_rows,
+    same_bits,
+)
+
+REFERENCE = Path("/root/reference")
+
+
+# ------------------------------------------------------------------ join
+@pytest.mark.parametrize("n_ref", JOIN_REFS)
+@pytest.mark.parametrize("n_rows", [0, 1, 63, 64, 65, T - 1, T, T + 1, 3 * T + 7])
+def test_host_join_equals_the_definition(n_rows, n_ref):
+    ref = join_reference(n_ref)
+    for pattern in JOIN_PATTERNS:
+        q, s, y, survivors = join_inputs(n_rows, ref, pattern)
+        x, yy, d = run_comp.join_host(ref, q, s, y)
+        assert len(x) == survivors, pattern
+        want = dict_join(*as_rows(ref, q, s, y))
+        same_bits(x, [a for a, _b in want])
+        same_bits(yy, [b for _a, b in want])
+        same_bits(d, [b - a for a, b in want])
+        for got, restated in zip((x, yy, d), numpy_join(ref, q, s, y)):
+            same_bits(got, restated)
+
+
+def test_host_join_arguments():
+    ref = join_reference(3)
+    x, y, d = run_comp.join_host(np.empty((0, 0)), [0, NONE], [0, 0], [0.5, 0.5])
+    assert len(x) == len(y) == len(d) == 0
+    with pytest.raises(ValueError, match="expected a square one"):
+        run_comp.join_host(np.zeros((2, 3)), [0], [0], [0.5])
+    with pytest.raises(ValueError, match="vectors of one length"):
+        run_comp.join_host(ref, [0, 1], [0], [0.5])
+    count = _capi.C.c_uint64(7)
+    lib = _capi.load_library()
+    assert lib.pa_runcomp_join_host(None, 65537, None, None, None, 0, None, None, None, _capi.C.byref(count)) == -1  # PA_E_INVALID
+    assert "at most 65536" in _capi.last_error()
+
+
+# ------------------------------------------------------------------ histogram, minimum and maximum
+@pytest.mark.parametrize("bins", HIST_BINS)
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 100_003])
+def test_host_histogram_equals_numpy(n, bins):
+    for family in HIST_FAMILIES:
+        v, edges = hist_inputs(family, n, bins)
+        counts = run_comp.hist_uniform_host(v, edges)
+        assert counts.dtype == np.uint64 and np.array_equal(counts, numpy_hist(v, edges)), family
+        if family not in {"adversarial", "outside"} and not np.isnan(v).all():
+            # the edges are the ones numpy chooses on its own, and range_and_counts finds them
+            assert np.array_equal(counts, np.histogram(v[~np.isnan(v)], bins)[0])
+            (lo, hi), again = run_comp.range_and_counts(v, bins=bins)
+            assert (lo, hi) == (np.nanmin(v), np.nanmax(v)) and np.array_equal(again, counts)
+
+
+def test_adversarial_values_cover_the_edges():
+    edges = run_comp.hist_edges(0.1, 0.7, 30)
+    v = adversarial_values(edges)
+    assert len(v) == 3 * 31 + 30 + 2 and set(edges) <= set(v) and v.min() < edges[0] and v.max() > edges[-1]
+    assert int(run_comp.hist_uniform_host(v, edges).sum()) == len(v) - 2  # one value below the first edge, one above the last
+
+
+def test_hist_edges_and_arguments():
+    same_bits(run_comp.hist_edges(0.25, 0.75), np.linspace(0.25, 0.75, 31))
+    same_bits(run_comp.hist_edges(1.0, 1.0, 7), np.linspace(0.5, 1.5, 8))
+    with pytest.raises(ValueError, match="finite and ascending"):
+        run_comp.hist_edges(1.0, 0.5)
+    with pytest.raises(ValueError, match="finite and ascending"):
+        run_comp.hist_edges(0.0, np.inf)
+    for bad, message in (([0.0, 0.5, 0.25, 1.0], "edge 2 is below edge 1"), ([0.0, np.nan, 1.0], "edge 1 is not finite"), ([1.0, 1.0], "above the first")):
+        with pytest.raises(HipBackendError, match=message) as caught:
+            run_comp.hist_uniform_host([0.5], bad)
+        assert caught.value.status == -1  # PA_E_INVALID
+    with pytest.raises(HipBackendError, match="1025 bins; 1 to 1024"):
+        run_comp.hist_uniform_host([0.5], np.linspace(0, 1, 1026))
+    assert run_comp.hist_uniform_host([0.5], np.linspace(0, 1, 1025)).sum() == 1
+    assert run_comp.hist_uniform_host([], [0.0, 1.0]).tolist() == [0]
+    none, zeros = run_comp.range_and_counts(np.full(5, np.nan))
+    assert none is None and zeros.tolist() == [0] * 30
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 100_003])
+def test_host_minmax_equals_numpy(n):
+    rng = np.random.default_rng(n)
+    v = rng.random(n) * 4 - 3  # negative values too
+    assert run_comp.minmax_host(v) == (v.min(), v.max(), n)
+    v[rng.random(n) < 0.3] = np.nan
+    if not np.isnan(v).all():
+        assert run_comp.minmax_host(v) == (np.nanmin(v), np.nanmax(v), int((~np.isnan(v)).sum()))
+    lo, hi, valid = run_comp.minmax_host(np.full(n, np.nan))
+    assert np.isnan(lo) and np.isnan(hi) and valid == 0
+    one = np.full(n, np.nan)
+    one[n // 2] = -0.125
+    assert run_comp.minmax_host(one) == (-0.125, -0.125, 1)
+
+
+# ------------------------------------------------------------------ the table writer
+def test_pairs_tsv_equals_the_f_string(tmp_path):
+    fixed = [1.0, 0.1 + 0.2, 0.9999999999999999, 1e-5, 9.999e-5, 1e16, 1e22, 5e-324, -0.0, 0.30000000000000004, 0.0, 1e-4, 9999999999999998.0,
+             123456.789, -1.5e-7, 1.7976931348623157e308, 2.2250738585072014e-308, float("inf"), float("-inf"), float("nan")]  # fmt: skip
+    x = np.concatenate([fixed, np.random.default_rng(1).random(10_000)])
+    y = np.concatenate([np.random.default_rng(2).random(10_000), fixed[::-1]])
+    out = tmp_path / "pairs.tsv"
+    run_comp.write_pairs_tsv(out, "#first run\tsecond run", x, y)
+    want = "#first run\tsecond run\n" + "".join(f"{a}\t{b}\n" for a, b in zip(x.tolist(), y.tolist()))
+    assert out.read_bytes() == want.encode()
+    run_comp.write_pairs_tsv(out, "#a\tb", [], [])
+    assert out.read_bytes() == b"#a\tb\n"
+    many = np.random.default_rng(3).random(70_001)  # more than two chunks of the writer
+    run_comp.write_pairs_tsv(out, "#a\tb", many, many[::-1].copy())
+    assert out.read_bytes() == ("#a\tb\n" + "".join(f"{a}\t{b}\n" for a, b in zip(many.tolist(), many[::-1].tolist()))).encode()
+    with pytest.raises(ValueError, match="vectors of one length"):
+        run_comp.write_pairs_tsv(out, "#a\tb", [1.0], [])
+    with pytest.raises(HipBackendError, match="cannot open"):
+        run_comp.write_pairs_tsv(tmp_path / "no_such_dir" / "pairs.tsv", "#a\tb", [1.0], [1.0])
+
+
+# ------------------------------------------------------------------ rundb.plot_run_comp
+@pytest.fixture(scope="module")
+def runs_db(tmp_path_factory):
+    return make_viral_db(tmp_path_factory.mktemp("run_comp_db"))
+
+
+def test_the_database_has_what_the_cases_need(runs_db):
+    rows = {run: run_rows(runs_db, run) for run in (1, 2, 3, 4)}
+    assert [len(rows[run]) for run in (1, 2, 3, 4)] == [9, 9, 9, 4]
+    # every comparison of this fixture has an identity, the fastANI run's too: test_plot_run_comp_with_null_identities has the NULLs
+    assert all(identity is not None for run in rows.values() for _q, _s, identity in run)
+    assert [r[2] for r in rows[1]] != [r[2] for r in rows[3]], "another scaled gives other identities"
+    assert len(dict_join(rows[1], rows[2])) == 9 and len(dict_join(rows[1], rows[4])) == 4 and len(dict_join(rows[4], rows[1])) == 4
+
+
+def test_plot_run_comp_writes_the_tables(runs_db, tmp_path, caplog):
+    caplog.set_level(logging.INFO)
+    out = tmp_path / "out"
+    written = rundb.plot_run_comp(runs_db, out, "1,2,3,4")
+    assert [p.name for p in written] == [f"sourmash-hip_identity_1_vs_{other}.tsv" for other in (2, 3, 4)] and all(p.parent == out for p in written)
+    for other, path in zip((2, 3, 4), written):
+        assert path.read_bytes() == expected_table(runs_db, 1, other), other
+    common = [len(dict_join(run_rows(runs_db, 1), run_rows(runs_db, other))) for other in (2, 3, 4)]
+    assert f"Output directory {out} does not exist, making it." in caplog.text
+    assert "Plotting 3 runs against sourmash-hip run 1 which has 9 comparisons" in caplog.text
+    assert f"Plotting fastANI-hip run 2 vs sourmash-hip run 1, with {common[0]} comparisons in common" in caplog.text
+    assert f"Plotting sourmash-hip run 3 vs sourmash-hip run 1, with {common[1]} comparisons in common" in caplog.text
+    assert f"Plotting sourmash-hip run 4 vs sourmash-hip run 1, with {common[2]} comparisons in common" in caplog.text
+    assert f"Wrote 0 images to {out}/sourmash-hip_identity_1_vs_*.*" in caplog.text
+    # another reference run: the fastANI run with its NULLs, and the run over two genomes (rows of genomes it lacks drop out)
+    caplog.clear()
+    for ref, others in ((2, (1, 4)), (4, (1, 2, 3))):
+        again = rundb.plot_run_comp(runs_db, tmp_path / f"ref{ref}", [ref, *others])
+        method = "fastANI-hip" if ref == 2 else "sourmash-hip"  # noqa: PLR2004
+        assert [p.name for p in again] == [f"{method}_identity_{ref}_vs_{other}.tsv" for other in others]
+        for other, path in zip(others, again):
+            assert path.read_bytes() == expected_table(runs_db, ref, other), (ref, other)
+    valid = sum(identity is not None for _q, _s, identity in run_rows(runs_db, 2))
+    assert f"Plotting 2 runs against fastANI-hip run 2 which has {valid} comparisons" in caplog.text
+    # the command line form
+    assert rundb.main(["plot-run-comp", "-d", str(runs_db), "-o", str(tmp_path / "cli"), "--run-ids", "1,2"]) == 0
+    assert (tmp_path / "cli" / "sourmash-hip_identity_1_vs_2.tsv").read_bytes() == expected_table(runs_db, 1, 2)
+    assert sorted(p.name for p in (tmp_path / "cli").iterdir()) == ["sourmash-hip_identity_1_vs_2.tsv"]
+
+
+def test_plot_run_comp_with_null_identities(runs_db, tmp_path, caplog):
+    """NULL identities on either side: two comparisons of the reference run and two of the fastANI run set to NULL, one
+    pair of them the same; and the bad_alignments fixture, whose two genomes share nothing."""
+    copy = tmp_path / "nulls.sqlite"
+    copy.write_bytes(runs_db.read_bytes())
+    conn = sqlite3.connect(copy)
+    first = [r[0] for r in conn.execute("SELECT comparison_id FROM comparisons WHERE configuration_id = 1 AND query_hash != subject_hash ORDER BY comparison_id LIMIT 2")]
+    conn.execute(f"UPDATE comparisons SET identity = NULL, cov_query = NULL WHERE comparison_id IN ({first[0]}, {first[1]})")
+    pairs = conn.execute("SELECT query_hash, subject_hash FROM comparisons WHERE comparison_id = ?", (first[1],)).fetchall()
+    conn.execute("UPDATE comparisons SET identity = NULL WHERE configuration_id = 2 AND ((query_hash = ? AND subject_hash = ?) OR comparison_id = "
+                 "(SELECT MAX(comparison_id) FROM comparisons WHERE configuration_id = 2))", pairs[0])  # fmt: skip
+    conn.commit()
+    conn.close()
+    caplog.set_level(logging.INFO)
+    written = rundb.plot_run_comp(copy, tmp_path / "out", "1,2,3")
+    assert "Plotting 2 runs against sourmash-hip run 1 which has 7 comparisons" in caplog.text
+    assert "Plotting fastANI-hip run 2 vs sourmash-hip run 1, with 6 comparisons in common" in caplog.text
+    assert "Plotting sourmash-hip run 3 vs sourmash-hip run 1, with 7 comparisons in common" in caplog.text
+    for other, path in zip((2, 3), written):
+        assert path.read_bytes() == expected_table(copy, 1, other) and len(path.read_bytes().split(b"\n")) == (6 if other == 2 else 7) + 2  # noqa: PLR2004
+    (back,) = rundb.plot_run_comp(copy, tmp_path / "back", "2,1")
+    assert back.read_bytes() == expected_table(copy, 2, 1) and "with 6 comparisons in common" in caplog.text
+    scaled, _genomes = FIXTURE_SETS["bad_alignments"]
+    db = tmp_path / "bad.sqlite"
+    assert rundb.run_sourmash_hip(GOLDEN / "bad_alignments", db, cache=tmp_path / "cache", scaled=scaled, engine=OracleEngine(), temp=tmp_path / "t1").status == "Done"
+    assert rundb.run_fastani_hip(GOLDEN / "bad_alignments", db, engine=OracleEngine(), temp=tmp_path / "t2").status == "Done"
+    assert [identity for _q, _s, identity in run_rows(db, 1)].count(None) == 2  # noqa: PLR2004
+    (table,) = rundb.plot_run_comp(db, tmp_path / "bad", "1,2")
+    assert table.read_bytes() == expected_table(db, 1, 2) and table.read_text().endswith("\n1.0\t1.0\n1.0\t1.0\n")
+
+
+def test_plot_run_comp_messages(runs_db, tmp_path, monkeypatch):
+    with pytest.raises(SystemExit, match=f"Database {tmp_path / 'none.sqlite'} does not exist"):
+        rundb.plot_run_comp(tmp_path / "none.sqlite", tmp_path, "1,2")
+    with pytest.raises(SystemExit, match="Expected comma separated list of runs, not: 1,two"):
+        rundb.plot_run_comp(runs_db, tmp_path, "1,two")
+    with pytest.raises(SystemExit, match="Need at least two runs for a comparison"):
+        rundb.plot_run_comp(runs_db, tmp_path, "1")
+    with pytest.raises(SystemExit, match="has no run-id 9"):
+        rundb.plot_run_comp(runs_db, tmp_path, "9,1")
+    with pytest.raises(SystemExit, match="has no run-id 9"):
+        rundb.plot_run_comp(runs_db, tmp_path, "1,9")
+    with monkeypatch.context() as patch:
+        patch.setitem(sys.modules, "matplotlib", None)  # ``import matplotlib`` raises ImportError
+        with pytest.raises(SystemExit, match=r"Image formats \(png\) need matplotlib, which cannot be imported"):
+            rundb.plot_run_comp(runs_db, tmp_path, "1,2", formats=("tsv", "png"))
+        assert len(rundb.plot_run_comp(runs_db, tmp_path / "tables_only", "1,2")) == 1
+    # an empty run, and two runs over copies of genomes the other does not have
+    copy = tmp_path / "copy.sqlite"
+    copy.write_bytes(runs_db.read_bytes())
+    conn = sqlite3.connect(copy)
+    conn.execute("INSERT INTO configurations (method, program, version) VALUES ('empty', 'none', '0')")
+    config = conn.execute("SELECT MAX(configuration_id) FROM configurations").fetchone()[0]
+    conn.execute("INSERT INTO runs (configuration_id, cmdline, fasta_directory, date, status, name) SELECT ?, cmdline, fasta_directory, date, 'Empty', 'empty' FROM runs WHERE run_id = 1", (config,))
+    conn.execute("INSERT INTO runs_genomes (genome_hash, run_id, fasta_filename) SELECT genome_hash, 5, fasta_filename FROM runs_genomes WHERE run_id = 1")
+    # run 6: run 4's configuration over the one genome run 4 lacks
+    conn.execute("INSERT INTO runs (configuration_id, cmdline, fasta_directory, date, status, name) SELECT configuration_id, cmdline, fasta_directory, date, status, 'third genome' FROM runs WHERE run_id = 4")
+    conn.execute("INSERT INTO runs_genomes (genome_hash, run_id, fasta_filename) SELECT genome_hash, 6, fasta_filename FROM runs_genomes "
+                 "WHERE run_id = 1 AND genome_hash NOT IN (SELECT genome_hash FROM runs_genomes WHERE run_id = 4)")  # fmt: skip
+    conn.commit()
+    conn.close()
+    assert len(run_rows(copy, 5)) == 0 and len(run_rows(copy, 6)) == 1
+    with pytest.raises(SystemExit, match="Run 5 has no comparisons"):
+        rundb.plot_run_comp(copy, tmp_path, "5,1")
+    with pytest.raises(SystemExit, match="Runs 1 and 5 have no comparisons in common"):
+        rundb.plot_run_comp(copy, tmp_path, "1,5")
+    with pytest.raises(SystemExit, match="Runs 4 and 6 have no comparisons in common"):
+        rundb.plot_run_comp(copy, tmp_path, "4,6")
+    with pytest.raises(SystemExit, match="Runs 6 and 4 have no comparisons in common"):
+        rundb.plot_run_comp(copy, tmp_path, [6, 4])
+    # every identity of the other run NULL: nothing in common either
+    conn = sqlite3.connect(copy)
+    conn.execute("UPDATE comparisons SET identity = NULL WHERE configuration_id = (SELECT configuration_id FROM runs WHERE run_id = 2)")
+    conn.commit()
+    conn.close()
+    with pytest.raises(SystemExit, match="Runs 1 and 2 have no comparisons in common"):
+        rundb.plot_run_comp(copy, tmp_path, "1,2")
+
+
+def test_plot_run_comp_figures(runs_db, tmp_path, caplog):
+    pytest.importorskip("matplotlib")
+    import matplotlib.pyplot as plt
+    from matplotlib.patches import StepPatch
+
+    from pyani_plus_amd import run_comp_figure
+
+    caplog.set_level(logging.INFO)
+    out = tmp_path / "out"
+    written = rundb.plot_run_comp(runs_db, out, "1,2,3,4", formats=("tsv", "png"), columns=2)
+    names = [p.name for p in written]
+    assert names[3:] == ["sourmash-hip_identity_1_scatter_vs_others.png", "sourmash-hip_identity_1_diff_vs_others.png"]
+    assert all(p.read_bytes()[:8] == b"\x89PNG\r\n\x1a\n" and p.stat().st_size > 1000 for p in written[3:])
+    assert f"Wrote 2 images to {out}/sourmash-hip_identity_1_vs_*.*" in caplog.text
+    assert written[0].read_bytes() == expected_table(runs_db, 1, 2)
+    assert len(rundb.plot_run_comp(runs_db, tmp_path / "images_only", "1,2", formats=("png",))) == 2
+    # the histograms are drawn from the computed counts
+    rows = run_rows(runs_db, 1)
+    hashes = sorted({q for q, _s, _i in rows})
+    ref = np.full((3, 3), np.nan)
+    for q, s, identity in rows:
+        ref[hashes.index(q), hashes.index(s)] = np.nan if identity is None else identity
+    other = run_rows(runs_db, 2)
+    comp = run_comp.compare(ref, [hashes.index(q) for q, _s, _i in other], [hashes.index(s) for _q, s, _i in other],
+                            [np.nan if identity is None else identity for _q, _s, identity in other])  # fmt: skip
+    assert np.array_equal(comp.x_counts, np.histogram(ref[~np.isnan(ref)], 30)[0]) and np.array_equal(comp.d_counts, np.histogram(comp.d, 30)[0])
+    assert comp.y_range == (comp.y.min(), comp.y.max()) and int(comp.y_counts.sum()) == len(comp.y)
+    assert run_comp_figure.grid_shape(3) == (2, 2) and run_comp_figure.grid_shape(3, 3) == (3, 1) and run_comp_figure.grid_shape(5, 2) == (2, 3)
+    for mode, counts in (("scatter", comp.y_counts), ("diff", comp.d_counts)):
+        figure = run_comp_figure.comparison_figure(mode, "sourmash run", ["fastANI run"], [comp])
+        try:
+            axes = {ax.get_label(): ax for ax in figure.axes}
+            for label, want in (("hist_y_0", counts), ("hist_x_0", comp.x_counts)):
+                (steps,) = [p for p in axes[label].patches if isinstance(p, StepPatch)]
+                assert np.array_equal(steps.get_data().values, want), (mode, label)
+        finally:
+            plt.close(figure)
+
+
+# ------------------------------------------------------------------ the reference's own ORM on the same database
+def test_tables_equal_the_reference_as_sorted_lines(runs_db, tmp_path):
+    if not (REFERENCE / "pyani_plus" / "db_orm.py").is_file():
+        pytest.skip("the reference checkout is not here")
+    pytest.importorskip("sqlalchemy")
+    old_flag, old_path = sys.dont_write_bytecode, list(sys.path)
+    sys.dont_write_bytecode = True  # no bytecode into the reference's tree
+    if not hasattr(datetime, "UTC"):
+        datetime.UTC = datetime.timezone.utc  # the reference wants Python >= 3.11
+    sys.path.insert(0, str(REFERENCE))
+    try:
+        from pyani_plus import db_orm
+    except ImportError as err:  # a dependency of the reference this image lacks
+        pytest.skip(f"the reference does not import here: {err}")
+    finally:
+        sys.path[:] = old_path
+        sys.dont_write_bytecode = old_flag
+    written = rundb.plot_run_comp(runs_db, tmp_path / "out", "1,2,3,4")
+    session = db_orm.connect_to_db(logging.getLogger("reference"), runs_db)
+    try:
+        reference_run = db_orm.load_run(session, 1, check_complete=False)
+        reference_values = {(c.query_hash, c.subject_hash): c.identity for c in reference_run.comparisons() if c.identity is not None}
+        for other_id, path in zip((2, 3, 4), written):
+            other = db_orm.load_run(session, other_id, check_complete=False)
+            lines = [
+                f"{reference_values[c.query_hash, c.subject_hash]}\t{c.identity}\n"
+                for c in other.comparisons()
+                if c.identity is not None and (c.query_hash, c.subject_hash) in reference_values
+            ]
+            header, *got = path.read_text().splitlines(keepends=True)
+            assert header == f"#{reference_run.name}\t{other.name}\n"
+            assert sorted(got) == sorted(lines) and len(got) > 0, other_id
+    finally:
+        session.close()
+
+
+# ------------------------------------------------------------------ the host code under sanitizers
+def test_host_twins_and_table_writer_under_sanitizers():
+    """AddressSanitizer + UBSan over ``runcomp_host.cpp`` and ``pa_write_pairs_tsv`` in a stand-alone CPU program: random
+    joins with indices at and past the matrix, histograms of them, and tables of every kind of double read back."""
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("no host compiler")
+    script = Path(__file__).resolve().parent / "tools" / "sanitize" / "run_runcomp.sh"
+    done = subprocess.run(["bash", str(script), "300"], capture_output=True, text=True, timeout=600)
+    assert done.returncode == 0 and "sanitizer runs clean" in done.stdout, done.stdout[-2000:] + done.stderr[-2000:]
+    assert "MISMATCH" not in done.stdout

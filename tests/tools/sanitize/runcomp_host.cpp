@@ -1,0 +1,115 @@
+// The host twins of plot-run-comp (join, minimum and maximum, uniform-bin histogram) and the pairs table writer on
+// random inputs in exact-size heap buffers, under AddressSanitizer / UBSan (host build only).  The join and the
+// histogram are checked against a second, plainer statement of their rules; the table is read back and parsed.
+//   usage: runcomp_host <scratch file> [trials]
+#include <cstdarg>
+#include <cstdio>
+void pa_set_error(const char *fmt, ...) {}
+#include "../../../pyani_plus_amd/csrc/json_writer.cpp"
+#include "../../../pyani_plus_amd/csrc/runcomp_host.cpp"
+#include <random>
+int main(int argc, char **argv) {
+  if (argc < 2) { printf("usage: runcomp_host <scratch file> [trials]\n"); return 2; }
+  const int trials = argc > 2 ? atoi(argv[2]) : 2000;
+  std::mt19937_64 rng(7);
+  std::uniform_real_distribution<double> unit(0.0, 1.0);
+  const double nan = std::nan("");
+  size_t rows_checked = 0, values_checked = 0;
+  for (int t = 0; t < trials; ++t) {
+    // ---- join
+    const uint32_t n_ref = (uint32_t)(rng() % 9);
+    const uint64_t n_rows = rng() % 300;
+    double *ref = new double[(size_t)n_ref * n_ref ? (size_t)n_ref * n_ref : 1];
+    for (size_t i = 0; i < (size_t)n_ref * n_ref; ++i) ref[i] = rng() % 4 ? unit(rng) : nan;
+    uint32_t *q = new uint32_t[n_rows ? n_rows : 1], *s = new uint32_t[n_rows ? n_rows : 1];
+    double *y = new double[n_rows ? n_rows : 1], *ox = new double[n_rows ? n_rows : 1], *oy = new double[n_rows ? n_rows : 1],
+           *od = new double[n_rows ? n_rows : 1];
+    for (uint64_t r = 0; r < n_rows; ++r) {
+      // indices at and beyond the matrix, and the sentinel, among the valid ones
+      q[r] = rng() % 8 == 0 ? 0xFFFFFFFFu : (uint32_t)(rng() % (n_ref + 2));
+      s[r] = rng() % 8 == 0 ? 0xFFFFFFFFu : (uint32_t)(rng() % (n_ref + 2));
+      y[r] = rng() % 6 ? unit(rng) : nan;
+    }
+    uint64_t common = ~0ULL;
+    if (pa_runcomp_join_host(ref, n_ref, q, s, y, n_rows, ox, oy, od, &common) != PA_OK) { printf("join failed at trial %d\n", t); return 1; }
+    uint64_t at = 0;
+    for (uint64_t r = 0; r < n_rows; ++r) {
+      if (q[r] >= n_ref || s[r] >= n_ref || std::isnan(y[r]) || std::isnan(ref[(size_t)q[r] * n_ref + s[r]])) continue;
+      const double x = ref[(size_t)q[r] * n_ref + s[r]];
+      if (at >= common || ox[at] != x || oy[at] != y[r] || od[at] != y[r] - x) { printf("JOIN MISMATCH at trial %d row %llu\n", t, (unsigned long long)r); return 1; }
+      ++at;
+    }
+    if (at != common) { printf("JOIN COUNT MISMATCH at trial %d\n", t); return 1; }
+    rows_checked += n_rows;
+    // ---- minimum and maximum, histogram of the joined differences
+    double mm[2] = {nan, nan};
+    uint64_t valid = ~0ULL;
+    if (pa_minmax_f64_host(y, n_rows, mm, &valid) != PA_OK) return 1;
+    uint64_t want_valid = 0;
+    for (uint64_t r = 0; r < n_rows; ++r) want_valid += !std::isnan(y[r]);
+    if (valid != want_valid || (valid && !(mm[0] <= mm[1]))) { printf("MINMAX MISMATCH at trial %d\n", t); return 1; }
+    if (valid) {
+      const uint32_t bins = 1 + (uint32_t)(rng() % 40);
+      double lo = mm[0], hi = mm[1];
+      if (lo == hi) { lo -= 0.5; hi += 0.5; }
+      double *edges = new double[bins + 1];
+      for (uint32_t b = 0; b <= bins; ++b) edges[b] = b == bins ? hi : lo + (hi - lo) * ((double)b / bins);
+      uint64_t *counts = new uint64_t[bins];
+      if (pa_hist_uniform_f64_host(y, n_rows, edges, bins, counts) != PA_OK) { printf("histogram failed at trial %d\n", t); return 1; }
+      // every value lies in the bin it was counted in: count again by searching the edges
+      uint64_t *again = new uint64_t[bins]();
+      for (uint64_t r = 0; r < n_rows; ++r) {
+        if (std::isnan(y[r])) continue;
+        uint32_t b = 0;
+        while (b + 1 < bins && y[r] >= edges[b + 1]) ++b;
+        ++again[b];
+      }
+      uint64_t total = 0;
+      for (uint32_t b = 0; b < bins; ++b) {
+        total += counts[b];
+        if (counts[b] != again[b]) { printf("HISTOGRAM MISMATCH at trial %d bin %u\n", t, b); return 1; }
+      }
+      if (total != valid) { printf("HISTOGRAM TOTAL MISMATCH at trial %d\n", t); return 1; }
+      values_checked += valid;
+      delete[] edges; delete[] counts; delete[] again;
+    }
+    // ---- the table: written from exact-size buffers, read back and parsed
+    if (t % 50 == 0) {
+      const uint64_t n = t % 100 == 0 ? common : 70001;  // the second size spans three chunks of the writer
+      double *tx = new double[n ? n : 1], *ty = new double[n ? n : 1];
+      for (uint64_t i = 0; i < n; ++i) {
+        uint64_t bits = rng();
+        double any;  // every bit pattern: subnormals, huge values, infinities, NaN
+        memcpy(&any, &bits, sizeof any);
+        tx[i] = i < common ? ox[i] : any;
+        ty[i] = i % 3 ? unit(rng) : any;
+      }
+      if (pa_write_pairs_tsv(argv[1], "#a\tb", tx, ty, n) != PA_OK) { printf("writer failed at trial %d\n", t); return 1; }
+      FILE *f = fopen(argv[1], "rb");
+      char line[256];
+      if (!f || !fgets(line, sizeof line, f) || strcmp(line, "#a\tb\n")) { printf("TABLE HEADER MISMATCH at trial %d\n", t); return 1; }
+      for (uint64_t i = 0; i < n; ++i) {
+        char *end = nullptr;
+        if (!fgets(line, sizeof line, f)) { printf("TABLE SHORT at trial %d line %llu\n", t, (unsigned long long)i); return 1; }
+        const double a = strtod(line, &end);
+        const double b = (*end == '\t') ? strtod(end + 1, &end) : nan;
+        const bool same = (a == tx[i] || (std::isnan(a) && std::isnan(tx[i]))) && (b == ty[i] || (std::isnan(b) && std::isnan(ty[i])));
+        if (!same || *end != '\n') { printf("TABLE MISMATCH at trial %d line %llu: %s", t, (unsigned long long)i, line); return 1; }
+      }
+      if (fgets(line, sizeof line, f)) { printf("TABLE LONG at trial %d\n", t); return 1; }
+      fclose(f);
+      delete[] tx; delete[] ty;
+    }
+    delete[] ref; delete[] q; delete[] s; delete[] y; delete[] ox; delete[] oy; delete[] od;
+  }
+  // the argument checks return before they touch anything
+  uint64_t none = 0;
+  double two[2] = {0.0, 0.0};
+  uint64_t one_count[1];
+  if (pa_runcomp_join_host(nullptr, 65537, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, &none) != PA_E_INVALID ||
+      pa_hist_uniform_f64_host(two, 2, two, 1, one_count) != PA_E_INVALID || pa_hist_uniform_f64_host(two, 2, two, 0, one_count) != PA_E_INVALID) {
+    printf("an invalid argument was accepted\n");
+    return 1;
+  }
+  printf("join, histogram and table agree on %zu rows and %zu values\n", rows_checked, values_checked);
+}
