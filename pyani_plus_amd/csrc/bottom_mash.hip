@@ -234,13 +234,10 @@ int pa_sketch_bottom(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask
   }
   hipLaunchKernelGGL(truncated_sizes_kernel, dim3(ceil_div_u64(n_genomes, kThreads)), dim3(kThreads), 0, c->stream,
                      tmp_off.as<uint64_t>(), n_genomes, (uint64_t)m, sizes.as<uint32_t>());
-  PA_TRY(pa_exclusive_scan_u32(c, sizes.as<uint32_t>(), pos.as<uint32_t>(), n_genomes, c->counters.as<uint64_t>() + 1));
+  PA_TRY(pa_exclusive_scan_u32(c, sizes.as<uint32_t>(), pos.as<uint32_t>(), n_genomes, c->slot<uint64_t>(kSketchTotal)));
   hipLaunchKernelGGL(truncate_copy_kernel, dim3(n_genomes), dim3(kThreads), 0, c->stream, tmp_hashes.as<uint64_t>(),
                      tmp_off.as<uint64_t>(), pos.as<uint32_t>(), n_genomes, (uint64_t)m, d_hashes, d_off);
-  PA_HIP(hipMemcpyAsync(c->h_pinned, c->counters.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  *h_total = c->h_pinned[0];
-  return PA_OK;
+  return pa_read_back(c, c->slot<uint64_t>(kSketchTotal), h_total);
 }
 
 int pa_pair_mash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_off, uint32_t n, uint32_t q0, uint32_t q1,

@@ -74,10 +74,10 @@ int pa_ctx_create(int device, pa_ctx **out) {
   }
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; pa_set_error("hipStreamCreate failed"); return PA_E_HIP; }
   c->own_stream = true;
-  if (hipHostMalloc(reinterpret_cast<void **>(&c->h_pinned), 64, hipHostMallocDefault) != hipSuccess) {
+  if (hipHostMalloc(reinterpret_cast<void **>(&c->h_pinned), kPinnedBytes, hipHostMallocDefault) != hipSuccess) {
     (void)hipStreamDestroy(c->stream); delete c; pa_set_error("hipHostMalloc failed"); return PA_E_NOMEM;
   }
-  if (c->counters.reserve(64) != PA_OK) { (void)hipHostFree(c->h_pinned); (void)hipStreamDestroy(c->stream); delete c; return PA_E_NOMEM; }
+  if (c->counters.reserve(kCtxScalarBytes) != PA_OK) { (void)hipHostFree(c->h_pinned); (void)hipStreamDestroy(c->stream); delete c; return PA_E_NOMEM; }
   *out = c;
   return PA_OK;
 }
@@ -86,11 +86,7 @@ void pa_ctx_destroy(pa_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  DevBuf *bufs[] = {&c->cand_keys[0], &c->cand_keys[1], &c->cand_vals[0], &c->cand_vals[1], &c->genome_blk,
-                    &c->counters, &c->hist, &c->flags, &c->scan_tmp, &c->region_off, &c->region_cursor, &c->dirty, &c->dict_keys[0], &c->dict_keys[1],
-                    &c->dict_vals[0], &c->dict_vals[1], &c->ids, &c->post_genome, &c->bitrows, &c->dict_scalars, &c->cls_i, &c->cls_j, &c->cls_score,
-                    &c->cls_cov};
-  for (DevBuf *b : bufs) b->release();
+  c->each_buffer([](DevBuf &b) { b.release(); });
   pa_fragani_release(c);
   for (auto &ph : c->prof)
     for (auto &pr : ph.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -219,10 +215,10 @@ int pa_sketch(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const
   PA_HIP(hipStreamSynchronize(c->stream));  // blk and region_off are stack-owned vectors
 
   if (use_regions) {
-    uint32_t *d_overflow = c->counters.as<uint32_t>() + 12;
+    uint32_t *d_overflow = c->slot(kRegionOverflow);
     PA_TRY(c->cand_keys[0].reserve(region_off[n_genomes] * sizeof(uint64_t)));
     PA_HIP(hipMemsetAsync(c->region_cursor.p, 0, (uint64_t)n_genomes * sizeof(uint32_t), c->stream));
-    PA_HIP(hipMemsetAsync(d_overflow, 0, sizeof(uint32_t), c->stream));
+    PA_HIP(hipMemsetAsync(d_overflow, 0, kRegionOverflow.bytes(), c->stream));
     {
       ProfScope prof(c, PA_PROF_KMER_HASH);
       PA_TRY(pa_launch_kmer_hash(c, d_packed, d_mask, d_dirty, n_blocks, c->genome_blk.as<uint32_t>(), n_genomes, k, max_hash,
@@ -242,22 +238,20 @@ int pa_sketch(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const
   }
   uint64_t cap = (uint64_t)((double)arena_bases * frac * 1.25) + 65536;
   if (cap > arena_bases) cap = arena_bases;
-  uint64_t *d_count = c->counters.as<uint64_t>();
+  uint64_t *d_count = c->slot<uint64_t>(kCandCount);
   uint64_t n_cand = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
     for (int b = 0; b < 2; ++b) {
       PA_TRY(c->cand_keys[b].reserve(cap * sizeof(uint64_t)));
       PA_TRY(c->cand_vals[b].reserve(cap * sizeof(uint32_t)));
     }
-    PA_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), c->stream));
+    PA_HIP(hipMemsetAsync(d_count, 0, kCandCount.bytes(), c->stream));
     {
       ProfScope prof(c, PA_PROF_KMER_HASH);
       PA_TRY(pa_launch_kmer_hash(c, d_packed, d_mask, d_dirty, n_blocks, c->genome_blk.as<uint32_t>(), n_genomes, k, max_hash,
                                  c->cand_keys[0].as<uint64_t>(), c->cand_vals[0].as<uint32_t>(), cap, d_count));
     }
-    PA_HIP(hipMemcpyAsync(c->h_pinned, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PA_HIP(hipStreamSynchronize(c->stream));
-    n_cand = c->h_pinned[0];
+    PA_TRY(pa_read_back(c, d_count, &n_cand));
     if (n_cand <= cap) break;
     PA_REQUIRE(attempt == 0, "pa_sketch: candidate count changed between runs (%llu > %llu)",
                (unsigned long long)n_cand, (unsigned long long)cap);
@@ -296,9 +290,7 @@ int pa_pair_counts_ex(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_off
   if (h_off) {
     total = h_off[n];
   } else {
-    PA_HIP(hipMemcpyAsync(c->h_pinned, d_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PA_HIP(hipStreamSynchronize(c->stream));
-    total = c->h_pinned[0];
+    PA_TRY(pa_read_back(c, d_off + n, &total));
   }
   PA_REQUIRE(total == 0 || d_hashes, "pa_pair_counts: null hashes");
   if (algo != PA_PAIRS_AUTO && algo != PA_PAIRS_BITROW_HASH) c->dict_prepared = false;

@@ -19,7 +19,8 @@
 //      with one ballot and writes the count to counts[i][tj].
 //   2. pa_exclusive_scan_u32 over counts[n][nt], row-major: the offset of (row i, tile tj) is then the number of
 //      edges before it in (i, j) order, because inside one (row, tile) the lanes are consecutive j.  The total E is
-//      read back: the call's only host synchronisation (the workspaces of the next steps are sized by it).
+//      read back by the same call, pa_scan_total_u32: the call's only host synchronisation (the workspaces of the
+//      next steps are sized by it).
 //   3. cls_edges_kernel<true>: the same evaluation again; each surviving lane writes i, j, score, coverage, the
 //      sort key and its own position at offset + popcount(ballot below the lane).  The compacted list is therefore
 //      in (i, j) order and the value of element e is e.
@@ -154,17 +155,13 @@ extern "C" int pa_classify_edges(pa_ctx *c, const double *d_score, const double 
     ProfScope prof(c, PA_PROF_CLS_EDGES);
     PA_TRY(c->flags.reserve(n_counts * sizeof(uint32_t)));
     uint32_t *d_counts = c->flags.as<uint32_t>();
-    uint64_t *d_total = c->counters.as<uint64_t>() + 4;
     // the tiles below the diagonal are not evaluated: their counts are zero
     PA_HIP(hipMemsetAsync(d_counts, 0, n_counts * sizeof(uint32_t), c->stream));
     const dim3 grid(nt, nt);
     hipLaunchKernelGGL(cls_edges_kernel<false>, grid, dim3(kThreads), 0, c->stream, d_score, d_cov, n, nt, agg_score, agg_cov, cov_min,
                        d_counts, 0ULL, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     PA_HIP(hipGetLastError());
-    PA_TRY(pa_exclusive_scan_u32(c, d_counts, d_counts, n_counts, d_total));
-    PA_HIP(hipMemcpyAsync(c->h_pinned, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    PA_HIP(hipStreamSynchronize(c->stream));
-    E = c->h_pinned[0];
+    PA_TRY(pa_scan_total_u32(c, d_counts, d_counts, n_counts, c->slot<uint64_t>(kCompactTotal), &E));
     *n_edges = E;
     if (E > cap_edges) {
       pa_set_error("pa_classify_edges: %llu edges, caller gave room for %llu", (unsigned long long)E, (unsigned long long)cap_edges);

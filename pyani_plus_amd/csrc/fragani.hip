@@ -222,14 +222,9 @@ int upload(pa_ctx *c, DevBuf &buf, const std::vector<T> &v) {
   ONE(post_g2) ONE(run_hist) ONE(long_runs) ONE(frag_d) ONE(uniq_hash) ONE(lookup_at) ONE(seg_f) ONE(seg2_f)           \
   ONE(amb_pos) ONE(amb_byte) ONE(seg_over) ONE(q_tab)
 
-// The words of FragWork::scalars: the counters and cursors the kernels are handed, as (first 32-bit word, words).  Every
+// The words of FragWork::scalars: the counters and cursors the kernels are handed, as ScalarSlots (pa_internal.h).  Every
 // slot is zeroed by one hipMemsetAsync over exactly its own words (none covers two slots) and read back whole, both by
 // the function named with it.
-struct ScalarSlot {
-  uint32_t word, words;
-  constexpr uint32_t bytes() const { return words * 4u; }
-  constexpr bool apart_from(ScalarSlot o) const { return word + words <= o.word || o.word + o.words <= word; }
-};
 // run_minimizers: minimizer_kernel has the buffer to itself, all kMiniScalarBytes zeroed before every run: [0] ticket,
 // [1] minimizers, [2] a wait ran out, [3] unused -- the four words read back -- and one ticket counter per XCD behind them
 constexpr ScalarSlot kMiniScalars{0, kMiniScalarBytes / 4u}, kMiniResult{0, 4};
@@ -244,16 +239,8 @@ constexpr ScalarSlot kPreCursor{10, 2};      // map_short_segments: prefilter_se
 constexpr ScalarSlot kMaxHits{12, 2};        // stage_batch: [0] most seed hits of one fragment, [1] the longest sketch (read by seed_batch)
 constexpr ScalarSlot kSegCursor{14, 2};      // bucket_pass: one 64-bit word: [lo] short, [hi] long segments listed
 constexpr uint32_t kBatchScalarBytes = 64;
-constexpr bool slots_apart(std::initializer_list<ScalarSlot> slots) {
-  for (const ScalarSlot *a = slots.begin(); a != slots.end(); ++a) {
-    if ((a->word + a->words) * 4u > kBatchScalarBytes || (a->words == 2 && a->word % 2)) return false;  // (64-bit words aligned)
-    for (const ScalarSlot *b = a + 1; b != slots.end(); ++b)
-      if (!a->apart_from(*b)) return false;
-  }
-  return true;
-}
-static_assert(slots_apart({kScanTotal, kSparseOver, kSegCounters, kSketchOverflow, kPreCursor, kMaxHits, kSegCursor}) &&
-                  slots_apart({kScanTotal, kSegCounters, kSketchOverflow, kBigCursor, kMaxHits, kSegCursor}) &&
+static_assert(slots_apart(kBatchScalarBytes, {kScanTotal, kSparseOver, kSegCounters, kSketchOverflow, kPreCursor, kMaxHits, kSegCursor}) &&
+                  slots_apart(kBatchScalarBytes, {kScanTotal, kSegCounters, kSketchOverflow, kBigCursor, kMaxHits, kSegCursor}) &&
                   kMiniResult.bytes() <= kMiniScalarBytes,
               "two slots of FragWork::scalars that are live at the same time overlap");
 
@@ -380,10 +367,9 @@ int cut_frequent_postings(pa_ctx *c, FragWork &W, const uint32_t *d_heads, const
                      W.post_g.as<uint16_t>(), m, W.run_hist.as<uint32_t>(), scratch_a, W.hash_cut.as<uint32_t>());
   hipLaunchKernelGGL(mark_cut_minimizers_kernel, dim3(gm), dim3(kThreads), 0, c->stream, d_heads, d_ids_before, d_sorted_idx, m,
                      W.hash_cut.as<uint32_t>(), W.mini_id.as<uint32_t>());
-  PA_TRY(pa_exclusive_scan_u32(c, scratch_a, scratch_b, m, W.slot<uint64_t>(kScanTotal)));
-  PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  const uint32_t kept = (uint32_t)c->h_pinned[0];
+  uint64_t kept64 = 0;
+  PA_TRY(pa_scan_total_u32(c, scratch_a, scratch_b, m, W.slot<uint64_t>(kScanTotal), &kept64));
+  const uint32_t kept = (uint32_t)kept64;
   if (kept != m) {
     hipLaunchKernelGGL(posting_compact_kernel, dim3(gm), dim3(kThreads), 0, c->stream, scratch_a, scratch_b, W.post_cw.as<uint64_t>(),
                        W.post_g.as<uint16_t>(), d_sorted_idx, m, W.post_cw2.as<uint64_t>(), W.post_g2.as<uint16_t>(), d_idx_spare);
@@ -427,13 +413,14 @@ int run_minimizers(pa_ctx *c, FragWork &W, const uint32_t *d_packed, const uint3
                        W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(), W.mini_contig.as<uint32_t>(), blocks, W.ambiguous(d_packed), ticket_mode,
                        W.block_offsets.as<uint32_t>());
     PA_HIP(hipGetLastError());
-    PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kMiniResult), kMiniResult.bytes(), hipMemcpyDeviceToHost, c->stream));
+    uint32_t h[kMiniResult.words];
+    ReadBack rb(c);
+    PA_TRY(rb.queue(W.slot(kMiniResult), h, kMiniResult.words));
     if (meanwhile && *meanwhile) {  // the caller's host-side bookkeeping, while the kernel runs (once)
       (*meanwhile)();
       meanwhile = nullptr;
     }
-    PA_HIP(hipStreamSynchronize(c->stream));
-    const uint32_t *h = reinterpret_cast<const uint32_t *>(c->h_pinned);
+    PA_TRY(rb.wait());
     bool ran_out = h[kMiniRanOutWord] != 0;
     if (const char *v = PA_TOOL_ENV("PA_FRAGANI_TICKET_TIMEOUT")) { if (atoi(v) && ticket_mode != 0) ran_out = true; }  // tests: as if a wait had run out
     if (ran_out && ticket_mode != 0) {  // a wait ran out with the tiles drawn per XCD: once more, from one counter
@@ -675,10 +662,9 @@ int build_dictionary(pa_ctx *c, FragWork &W, const FragCall &a, uint32_t m, int 
     PA_TRY(pa_radix_sort_pairs(c, keys, vals, md, 0, 32, false, &which));
     uint32_t *d_flags = W.flags.as<uint32_t>(), *d_pos = d_flags + md;
     hipLaunchKernelGGL(key_heads_kernel, dim3(gm), dim3(kThreads), 0, c->stream, keys[which], md, d_flags);
-    PA_TRY(pa_exclusive_scan_u32(c, d_flags, d_pos, md, W.slot<uint64_t>(kScanTotal)));
-    PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
-    PA_HIP(hipStreamSynchronize(c->stream));
-    n_ids = (uint32_t)c->h_pinned[0];
+    uint64_t n_ids64 = 0;
+    PA_TRY(pa_scan_total_u32(c, d_flags, d_pos, md, W.slot<uint64_t>(kScanTotal), &n_ids64));
+    n_ids = (uint32_t)n_ids64;
     PA_REQUIRE(n_ids < (1u << 31), "pa_fragani: %u distinct minimizer hashes (limit 2^31)", n_ids);
     PA_TRY(W.post_start.reserve((uint64_t)(n_ids + 2) * 4));
     PA_TRY(W.uniq_hash.reserve((uint64_t)(n_ids + 2) * 4));
@@ -848,12 +834,13 @@ int seed_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, Frag
                      W.hit_count.as<uint32_t>(), W.slot(kSketchOverflow), W.slot(kMaxHits), W.q_cut.as<uint32_t>(),
                      R.restricted ? W.lookup_at.as<uint4>() : nullptr, W.index_lookup_bits, W.q_tab.as<uint32_t>());
   PA_TRY(pa_exclusive_scan_u32(c, W.hit_count.as<uint32_t>(), W.hit_off.as<uint32_t>(), nf, W.slot<uint64_t>(kScanTotal)));
-  PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipMemcpyAsync(c->h_pinned + 1, W.slot(kMaxHits), kMaxHits.bytes(), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  B.n_hits = c->h_pinned[0];
-  B.max_hits = (uint32_t)c->h_pinned[1];
-  B.s_cap = std::min<uint32_t>(kQMax, (((uint32_t)(c->h_pinned[1] >> 32) + 63u) / 64u) * 64u);
+  uint32_t longest[kMaxHits.words];  // [0] most seed hits of one fragment, [1] the longest sketch
+  ReadBack rb(c);
+  PA_TRY(rb.queue(W.slot<uint64_t>(kScanTotal), &B.n_hits));
+  PA_TRY(rb.queue(W.slot(kMaxHits), longest, kMaxHits.words));
+  PA_TRY(rb.wait());
+  B.max_hits = longest[0];
+  B.s_cap = std::min<uint32_t>(kQMax, ((longest[1] + 63u) / 64u) * 64u);
   return PA_OK;
 }
 
@@ -917,12 +904,14 @@ int bucket_pass(pa_ctx *c, FragWork &W, const FragCall &a, const FragBatch &B, S
                        W.tab_min_hits.as<uint32_t>(), S.hk[0], S.hv[0],
                        W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), P.seg_cap, d_seg_counters,
                        d_cursor64, a.ref0, a.ref1, write_all);
-  PA_HIP(hipMemcpyAsync(c->h_pinned, d_seg_counters, kSegCounters.bytes(), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipMemcpyAsync(c->h_pinned + 2, d_cursor64, kSegCursor.bytes(), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  const uint32_t *hc32 = reinterpret_cast<const uint32_t *>(c->h_pinned);
-  S.n_keep = (uint32_t)c->h_pinned[2];
-  S.n_large = (uint32_t)(c->h_pinned[2] >> 32);
+  uint32_t hc32[kSegCounters.words];
+  unsigned long long cursor64 = 0;
+  ReadBack rb(c);
+  PA_TRY(rb.queue(d_seg_counters, hc32, kSegCounters.words));
+  PA_TRY(rb.queue(d_cursor64, &cursor64));
+  PA_TRY(rb.wait());
+  S.n_keep = (uint32_t)cursor64;
+  S.n_large = (uint32_t)(cursor64 >> 32);
   S.large_at = P.seg_cap - S.n_large;
   P.n_big = hc32[1];
   P.max_big = hc32[2];
@@ -1010,10 +999,9 @@ int list_segments_sorted(pa_ctx *c, FragWork &W, const FragCall &a, const FragRu
   const uint32_t gh = ceil_div_u64(n_hits, kThreads);
   hipLaunchKernelGGL(segment_heads_kernel, dim3(gh), dim3(kThreads), 0, c->stream, S.hk[S.hw], (uint32_t)n_hits,
                      W.contig_genome.as<uint32_t>(), hf);
-  PA_TRY(pa_exclusive_scan_u32(c, hf, hp, n_hits, W.slot<uint64_t>(kScanTotal)));
-  PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  const uint32_t n_segs = (uint32_t)c->h_pinned[0];
+  uint64_t total = 0;
+  PA_TRY(pa_scan_total_u32(c, hf, hp, n_hits, W.slot<uint64_t>(kScanTotal), &total));
+  const uint32_t n_segs = (uint32_t)total;
   PA_TRY(W.seg_start.reserve((uint64_t)(n_segs + 2) * 4));
   hipLaunchKernelGGL(segment_starts_kernel, dim3(gh), dim3(kThreads), 0, c->stream, hf, hp, (uint32_t)n_hits,
                      W.seg_start.as<uint32_t>());
@@ -1023,10 +1011,8 @@ int list_segments_sorted(pa_ctx *c, FragWork &W, const FragCall &a, const FragRu
   hipLaunchKernelGGL(segment_keep_kernel, dim3(gs), dim3(kThreads), 0, c->stream, S.hk[S.hw],
                      W.seg_start.as<uint32_t>(), n_segs, W.q_s.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(),
                      W.contig_genome.as<uint32_t>(), a.ref0, a.ref1, hf);
-  PA_TRY(pa_exclusive_scan_u32(c, hf, hp, n_segs, W.slot<uint64_t>(kScanTotal)));
-  PA_HIP(hipMemcpyAsync(c->h_pinned, W.slot(kScanTotal), kScanTotal.bytes(), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  S.n_keep = (uint32_t)c->h_pinned[0];
+  PA_TRY(pa_scan_total_u32(c, hf, hp, n_segs, W.slot<uint64_t>(kScanTotal), &total));
+  S.n_keep = (uint32_t)total;
   PA_TRY(W.seg_list.reserve((uint64_t)(S.n_keep + 1) * 4));
   PA_TRY(W.seg_a0.reserve((uint64_t)S.n_keep * 4 + 16));
   PA_TRY(W.seg_nh.reserve((uint64_t)S.n_keep * 4 + 16));
@@ -1092,9 +1078,9 @@ int map_short_segments(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun 
                      S.hk[S.hw], W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), n_keep,
                      W.q_s.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(), W.q_cut.as<uint32_t>(), a.frag_len, W.seg2_a0.as<uint32_t>(),
                      W.seg2_nh.as<uint32_t>(), W.seg2_f.as<uint32_t>(), d_pre_cursor, sparse_max);
-  PA_HIP(hipMemcpyAsync(c->h_pinned, d_pre_cursor, kPreCursor.bytes(), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  const uint32_t n_small = (uint32_t)c->h_pinned[0], n_sparse = (uint32_t)(c->h_pinned[0] >> 32);
+  unsigned long long pre_cursor = 0;
+  PA_TRY(pa_read_back(c, d_pre_cursor, &pre_cursor));
+  const uint32_t n_small = (uint32_t)pre_cursor, n_sparse = (uint32_t)(pre_cursor >> 32);
   if (R.trace)
     fprintf(stderr, "pa_fragani: genomes %u..%u: %u fragments, %llu seed hits, %u + %u listed segments, %u left "
                     "after the tiny-segment filter\n", B.g0, B.g1, B.nf, (unsigned long long)B.n_hits, n_keep, S.n_large, n_small);
@@ -1117,9 +1103,8 @@ int map_short_segments(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun 
                      , W.run_g.as<uint32_t>()
 #endif
   );
-  PA_HIP(hipMemcpyAsync(c->h_pinned, d_over_n, kSparseOver.bytes(), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  const uint32_t n_over = *reinterpret_cast<const uint32_t *>(c->h_pinned);
+  uint32_t n_over = 0;
+  PA_TRY(pa_read_back(c, d_over_n, &n_over));
   if (R.trace) fprintf(stderr, "pa_fragani: %u segments of at most %u hits in the sparse kernel, %u of them handed on\n", n_sparse, kSparseHits, n_over);
   // what does not fit the simple form (a hash twice in a stretch, over-long windows or ranges) goes through the general kernel
   return launch_map<true>(c, W, a, R, B, S, over_a0, over_nh, over_f, n_over, (uint32_t)kHitCapSmall);

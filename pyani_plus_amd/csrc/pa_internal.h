@@ -6,7 +6,10 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
+#include <initializer_list>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pyani_hip.h"
@@ -108,40 +111,139 @@ struct ProfPhase {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// ---- device scalars ---------------------------------------------------------
+// A block of device scalars -- the counters and cursors that kernels are handed -- is divided into named slots:
+// (first 32-bit word, words).  A hipMemsetAsync or a read-back stays inside one slot (none covers two).  A block's
+// owner lists the slots that are live together in one static_assert(slots_apart(bytes, {...})).
+struct ScalarSlot {
+  uint32_t word, words;
+  constexpr uint32_t bytes() const { return words * 4u; }
+  constexpr bool apart_from(ScalarSlot o) const { return word + words <= o.word || o.word + o.words <= word; }
+};
+// Every slot inside the block's `region_bytes`, slots of whole 64-bit words on an even word, no two overlapping.
+constexpr bool slots_apart(uint32_t region_bytes, std::initializer_list<ScalarSlot> slots) {
+  for (const ScalarSlot *a = slots.begin(); a != slots.end(); ++a) {
+    if ((a->word + a->words) * 4u > region_bytes || (a->words % 2 == 0 && a->word % 2)) return false;
+    for (const ScalarSlot *b = a + 1; b != slots.end(); ++b)
+      if (!a->apart_from(*b)) return false;
+  }
+  return true;
+}
+
+// The words of pa_ctx::counters (pa_ctx::slot).  A new feature that needs a device scalar adds its slot here.
+constexpr uint32_t kCtxScalarBytes = 64;       // what pa_ctx_create reserves
+constexpr ScalarSlot kCandCount{0, 2};         // pa_sketch, general path: candidates of the k-mer hash kernel, 64-bit; zeroed and read per attempt
+constexpr ScalarSlot kSketchTotal{2, 2};       // pa_build_sketch_csr, pa_sketch_from_regions, pa_sketch_bottom: the 64-bit total of their scan (written, never zeroed)
+constexpr ScalarSlot kDenseIds{4, 4};          // pa_dense_ids_sorted, two 64-bit words zeroed as one: [0] OR of the keys, [1] distinct keys (its scan's total)
+constexpr uint32_t kDenseOr = 0, kDenseDistinct = 1;  // 64-bit words within kDenseIds
+constexpr ScalarSlot kCompactTotal{8, 2};      // pa_classify_edges, pa_runcomp_join: the 64-bit total of their scan (written, never zeroed)
+constexpr ScalarSlot kRegionOverflow{12, 1};   // pa_sketch, pa_sketch_streamed: a region was too small; zeroed there, read by pa_sketch_from_regions
+static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow}),
+              "two slots of pa_ctx::counters overlap or leave the block");
+
+// The words of pa_ctx::dict_scalars (pa_ctx::dict_slot), the hash dictionary's own block, touched by no other phase
+constexpr uint32_t kDictScalarBytes = 64;  // what dict_insert and pa_pairs_bitrow_hash reserve
+constexpr ScalarSlot kDictCounters{0, 2};  // dict_insert: [0] id counter (zeroed), [1] id of the key ~0 (set to ~0); read by pa_pairs_bitrow_hash
+constexpr uint32_t kDictIdCounter = 0, kDictSpecialId = 1;  // 32-bit words within kDictCounters
+constexpr ScalarSlot kDictPreparedFp{2, 4};  // pa_pair_dict_prepare_impl: 128-bit fingerprint of the postings a prepared dictionary was built from
+constexpr ScalarSlot kDictTileFp{6, 4};      // pa_pairs_bitrow_hash: the same of the tile that consumes it; zeroed there, read with the one above
+static_assert(slots_apart(kDictScalarBytes, {kDictCounters, kDictPreparedFp, kDictTileFp}),
+              "two slots of pa_ctx::dict_scalars overlap or leave the block");
+
+constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of ReadBack
+
+// The device buffers of the context, each named here and nowhere else: the members of pa_ctx and their release in
+// pa_ctx_destroy follow from this list.  ONE(name): a buffer `name`; PAIR(name): two, `name[0]` and `name[1]`.
+//   sketch phase: cand_keys / cand_vals, the double-buffered radix sort storage; genome_blk, genome start block index
+//   (u32[n+1]); counters, the small device scalars above; hist, radix histograms / scan scratch; flags and scan_tmp,
+//   compaction; region_off and region_cursor, per-genome candidate regions (LDS-sort path); dirty, the dirty-block
+//   bitmap for callers that pass none
+//   pair phase: dict_keys / dict_vals, ids, post_genome, bitrows; dict_scalars, the hash dictionary's scalars above
+//   classify (classify.hip): cls_i, cls_j, cls_score, cls_cov, the edges in (i, j) order, before the sort
+#define PA_CTX_BUFFERS(ONE, PAIR)                                                                                   \
+  PAIR(cand_keys) PAIR(cand_vals) ONE(genome_blk) ONE(counters) ONE(hist) ONE(flags) ONE(scan_tmp) ONE(region_off) \
+  ONE(region_cursor) ONE(dirty) PAIR(dict_keys) PAIR(dict_vals) ONE(ids) ONE(post_genome) ONE(bitrows)             \
+  ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov)
+
 struct pa_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   hipDeviceProp_t prop;
-  // workspaces (sketch phase)
-  DevBuf cand_keys[2], cand_vals[2];  // double-buffered radix sort storage
-  DevBuf genome_blk;                  // genome start block index (u32[n+1])
-  DevBuf counters;                    // small device scalars
-  DevBuf hist;                        // radix histograms / scan scratch
-  DevBuf flags, scan_tmp;             // compaction
-  DevBuf region_off, region_cursor;   // per-genome candidate regions (LDS-sort path)
-  DevBuf dirty;                       // dirty-block bitmap for callers that pass none
-  // workspaces (pair phase)
-  DevBuf dict_keys[2], dict_vals[2];
-  DevBuf ids, post_genome, bitrows;
+#define PA_ONE(name) DevBuf name;
+#define PA_PAIR(name) DevBuf name[2];
+  PA_CTX_BUFFERS(PA_ONE, PA_PAIR)
+#undef PA_ONE
+#undef PA_PAIR
+  template <class Fn>
+  void each_buffer(Fn &&fn) {
+#define PA_ONE(name) fn(name);
+#define PA_PAIR(name) fn(name[0]); fn(name[1]);
+    PA_CTX_BUFFERS(PA_ONE, PA_PAIR)
+#undef PA_ONE
+#undef PA_PAIR
+  }
+  template <typename T = uint32_t>
+  T *slot(ScalarSlot s) const { return reinterpret_cast<T *>(counters.as<uint32_t>() + s.word); }
+  template <typename T = uint32_t>
+  T *dict_slot(ScalarSlot s) const { return reinterpret_cast<T *>(dict_scalars.as<uint32_t>() + s.word); }
   // dictionary built ahead of the pair phase by pa_pair_dict_prepare (multi-GPU overlap)
   bool dict_prepared = false;
   uint64_t dict_prepared_postings = 0;
   uint32_t dict_prepared_cap = 0;
-  // scalars of the hash dictionary, touched by no other phase: [0] id counter, [1] id of the key ~0 (u32 each);
-  // u64 [1..2] fingerprint of the postings a prepared dictionary was built from, [3..4] of the tile that consumes it
-  DevBuf dict_scalars;
   hipStream_t copy_stream = nullptr;  // uploads of pa_sketch_streamed, created on first use
-  // classify (classify.hip): the edges in (i, j) order, before the sort
-  DevBuf cls_i, cls_j, cls_score, cls_cov;
   void *frag_work = nullptr;  // fragment-ANI workspace (fragani.hip), created on first use
-  // pinned host scalars
+  // pinned host scalars (kPinnedBytes), written and read through ReadBack only
   uint64_t *h_pinned = nullptr;
   // profiling
   bool prof_on = false;
   ProfPhase prof[PA_PROF_NPHASES];
   std::vector<hipEvent_t> event_pool;
 };
+
+// ---- reading device scalars back ---------------------------------------------
+// Copies of a few typed values from the device to the host through the context's pinned block, with one wait on the
+// context's stream: queue() once per value (or array of `count` values), host work that may overlap the stream, then
+// wait(), which fills the callers' variables.  Each copy gets a place of its own in the block and is checked against
+// kPinnedBytes; what is copied is exactly what *out receives, so no read is wider than its copy.
+class ReadBack {
+ public:
+  explicit ReadBack(pa_ctx *c) : c_(c) {}
+  template <typename T>
+  int queue(const T *d_src, T *out, uint32_t count = 1) {
+    static_assert(std::is_trivially_copyable<T>::value && alignof(T) <= 8, "ReadBack copies plain scalars");
+    const uint64_t bytes = (uint64_t)count * sizeof(T);
+    PA_REQUIRE(n_ < kMaxItems && used_ + bytes <= kPinnedBytes, "read-back of %llu bytes behind %u in %u copies exceeds the pinned block of %u bytes",
+               (unsigned long long)bytes, used_, n_, kPinnedBytes);
+    PA_HIP(hipMemcpyAsync(reinterpret_cast<char *>(c_->h_pinned) + used_, d_src, bytes, hipMemcpyDeviceToHost, c_->stream));
+    items_[n_++] = Item{out, used_, (uint32_t)bytes};
+    used_ = (used_ + (uint32_t)bytes + 7u) & ~7u;  // the next copy on a 64-bit boundary
+    return PA_OK;
+  }
+  int wait() {
+    PA_HIP(hipStreamSynchronize(c_->stream));
+    for (uint32_t i = 0; i < n_; ++i) memcpy(items_[i].out, reinterpret_cast<const char *>(c_->h_pinned) + items_[i].at, items_[i].bytes);
+    n_ = used_ = 0;
+    return PA_OK;
+  }
+
+ private:
+  static constexpr uint32_t kMaxItems = 4;
+  struct Item {
+    void *out;
+    uint32_t at, bytes;
+  };
+  pa_ctx *c_;
+  Item items_[kMaxItems];
+  uint32_t n_ = 0, used_ = 0;
+};
+// One value (or array): the copy, the wait on c->stream, *out filled.
+template <typename T>
+int pa_read_back(pa_ctx *c, const T *d_src, T *out, uint32_t count = 1) {
+  ReadBack rb(c);
+  PA_TRY(rb.queue(d_src, out, count));
+  return rb.wait();
+}
 
 // RAII-ish phase timer: records events around a group of launches when enabled.
 struct ProfScope {
@@ -162,9 +264,15 @@ static inline uint32_t ceil_div_u64(uint64_t a, uint64_t b) { return (uint32_t)(
 // the input on entry and the result on return.
 int pa_radix_sort_pairs(pa_ctx *c, uint64_t *keys[2], uint32_t *vals[2], uint64_t n, int bit_lo,
                         int bit_hi, bool by_val, int *which);
-// Exclusive prefix sum of u32 -> u32 (n up to 2^32-1 elements, total must fit u32... u64 total out).
+// Exclusive prefix sums of n u32 values, themselves u32: they wrap past 2^32.  The total is
+// added up in 64 bits from the tiles' 32-bit sums and goes to *d_total_u64 where that is not null.
 int pa_exclusive_scan_u32(pa_ctx *c, const uint32_t *d_in, uint32_t *d_out, uint64_t n,
                           uint64_t *d_total_u64 /*nullable device ptr*/);
+// The scan with its total read back: one wait on c->stream, directly after the scan's launches.
+inline int pa_scan_total_u32(pa_ctx *c, const uint32_t *d_in, uint32_t *d_out, uint64_t n, uint64_t *d_total_u64, uint64_t *h_total) {
+  PA_TRY(pa_exclusive_scan_u32(c, d_in, d_out, n, d_total_u64));
+  return pa_read_back(c, d_total_u64, h_total);
+}
 
 // fragani.hip
 void pa_fragani_release(pa_ctx *c);

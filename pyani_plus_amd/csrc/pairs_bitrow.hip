@@ -394,29 +394,25 @@ int pa_dense_ids_sorted(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_o
   uint32_t *d_id_sorted = c->post_genome.as<uint32_t>();
   uint32_t *d_genome_sorted = d_id_sorted + P;
   uint32_t *d_flags = c->flags.as<uint32_t>(), *d_pos = d_flags + P;
-  uint64_t *d_scalars = c->counters.as<uint64_t>();  // [2] = OR of keys, [3] = U
+  uint64_t *d_or = c->slot<uint64_t>(kDenseIds) + kDenseOr, *d_distinct = c->slot<uint64_t>(kDenseIds) + kDenseDistinct;
 
   const uint32_t grid = ceil_div_u64(P, kThreads);
   PA_HIP(hipMemcpyAsync(keys[0], d_hashes, P * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
-  PA_HIP(hipMemsetAsync(d_scalars + 2, 0, 2 * sizeof(uint64_t), c->stream));
+  PA_HIP(hipMemsetAsync(c->slot(kDenseIds), 0, kDenseIds.bytes(), c->stream));
   hipLaunchKernelGGL(iota_kernel, dim3(grid), dim3(kThreads), 0, c->stream, vals[0], P);
   hipLaunchKernelGGL(last_or_kernel, dim3(ceil_div_u64(n, kThreads)), dim3(kThreads), 0, c->stream, d_hashes, d_off,
-                     n, reinterpret_cast<unsigned long long *>(d_scalars + 2));
-  PA_HIP(hipMemcpyAsync(c->h_pinned, d_scalars + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  const uint64_t all_or = c->h_pinned[0];
+                     n, reinterpret_cast<unsigned long long *>(d_or));
+  uint64_t all_or = 0;
+  PA_TRY(pa_read_back(c, d_or, &all_or));
   int bit_hi = all_or ? 64 - __builtin_clzll(all_or) : 0;
   bit_hi = (bit_hi + 7) & ~7;
   int which = 0;
   PA_TRY(pa_radix_sort_pairs(c, keys, vals, P, 0, bit_hi, false, &which));
   hipLaunchKernelGGL(key_heads_kernel, dim3(grid), dim3(kThreads), 0, c->stream, keys[which], P, d_flags);
-  PA_TRY(pa_exclusive_scan_u32(c, d_flags, d_pos, P, d_scalars + 3));
+  PA_TRY(pa_exclusive_scan_u32(c, d_flags, d_pos, P, d_distinct));
   hipLaunchKernelGGL(assign_ids_kernel, dim3(grid), dim3(kThreads), 0, c->stream, vals[which], d_flags, d_pos, P,
                      d_off, n, d_ids, d_id_sorted, d_genome_sorted);
-  PA_HIP(hipMemcpyAsync(c->h_pinned, d_scalars + 3, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  *n_distinct = c->h_pinned[0];
-  return PA_OK;
+  return pa_read_back(c, d_distinct, n_distinct);
 }
 
 int pa_pairs_bitrow(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_off, uint32_t n, uint64_t total,
@@ -465,16 +461,16 @@ static int dict_insert(pa_ctx *c, const uint64_t *d_postings, uint64_t n_post, u
   const uint64_t cap64 = n_post + n_post / 2 + 1024;  // load <= 2/3
   PA_REQUIRE(cap64 < (1ULL << 32), "pair phase: tile with %llu subject postings is too large for the hash dictionary",
              (unsigned long long)n_post);
-  PA_TRY(c->dict_scalars.reserve(64));
-  uint32_t *d_counter = c->dict_scalars.as<uint32_t>();  // [0] counter, [1] special id
+  PA_TRY(c->dict_scalars.reserve(kDictScalarBytes));
+  uint32_t *d_counter = c->dict_slot(kDictCounters) + kDictIdCounter, *d_special = c->dict_slot(kDictCounters) + kDictSpecialId;
   PA_TRY(c->dict_keys[0].reserve(cap64 * sizeof(DictEntry)));
   PA_HIP(hipMemsetAsync(c->dict_keys[0].p, 0xff, cap64 * sizeof(DictEntry), c->stream));
   PA_HIP(hipMemsetAsync(d_counter, 0, 4, c->stream));
-  PA_HIP(hipMemsetAsync(d_counter + 1, 0xff, 4, c->stream));
+  PA_HIP(hipMemsetAsync(d_special, 0xff, 4, c->stream));
   if (n_post)
     hipLaunchKernelGGL(table_insert_kernel, dim3(ceil_div_u64(n_post, kThreads * kInsertPerThread)), dim3(kThreads), 0,
                        c->stream, d_postings, (uint64_t)0, n_post, c->dict_keys[0].as<DictEntry>(), (uint32_t)cap64,
-                       d_counter, d_counter + 1);
+                       d_counter, d_special);
   PA_HIP(hipGetLastError());
   *cap_out = (uint32_t)cap64;
   return PA_OK;
@@ -490,8 +486,8 @@ int pa_pair_dict_prepare_impl(pa_ctx *c, const uint64_t *d_subject_hashes, uint6
   uint32_t cap = 0;
   PA_TRY(dict_insert(c, d_subject_hashes, n_postings, &cap));
   // what the dictionary was built from, for the call that consumes it
-  unsigned long long *d_fp = c->dict_scalars.as<unsigned long long>() + 1;
-  PA_HIP(hipMemsetAsync(d_fp, 0, 16, c->stream));
+  unsigned long long *d_fp = c->dict_slot<unsigned long long>(kDictPreparedFp);
+  PA_HIP(hipMemsetAsync(d_fp, 0, kDictPreparedFp.bytes(), c->stream));
   if (n_postings)
     hipLaunchKernelGGL(postings_fingerprint_kernel, dim3(std::min<uint32_t>(1024u, ceil_div_u64(n_postings, kThreads))),
                        dim3(kThreads), 0, c->stream, d_subject_hashes, n_postings, d_fp);
@@ -525,9 +521,9 @@ int pa_pairs_bitrow_hash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_
     h_off = h_off_own.data();
   }
   PA_TRY(c->ids.reserve(total * sizeof(uint32_t)));
-  PA_TRY(c->dict_scalars.reserve(64));
+  PA_TRY(c->dict_scalars.reserve(kDictScalarBytes));
   uint32_t *d_ids = c->ids.as<uint32_t>();
-  uint32_t *d_counter = c->dict_scalars.as<uint32_t>();  // [0] counter, [1] special id
+  uint32_t *d_counter = c->dict_slot(kDictCounters) + kDictIdCounter, *d_special = c->dict_slot(kDictCounters) + kDictSpecialId;
   PA_REQUIRE(!prepared || ns <= kMaxTileSubjects, "pair phase: a prepared dictionary serves one tile of at most %u subjects",
              kMaxTileSubjects);
   // all-vs-all over several subject tiles: tile j takes the queries of tiles i <= j only, the rest is mirrored
@@ -549,14 +545,17 @@ int pa_pairs_bitrow_hash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_
                    (unsigned long long)c->dict_prepared_postings, (unsigned long long)(pt1 - pt0));
         // same number of postings is not the same postings: compare the fingerprints (one small copy and a wait;
         // the lookups below are then enqueued a few microseconds later than they could have been)
-        unsigned long long *d_fp = c->dict_scalars.as<unsigned long long>() + 1;
-        PA_HIP(hipMemsetAsync(d_fp + 2, 0, 16, c->stream));
+        unsigned long long *d_tile_fp = c->dict_slot<unsigned long long>(kDictTileFp);
+        PA_HIP(hipMemsetAsync(d_tile_fp, 0, kDictTileFp.bytes(), c->stream));
         if (pt1 > pt0)
           hipLaunchKernelGGL(postings_fingerprint_kernel, dim3(std::min<uint32_t>(1024u, ceil_div_u64(pt1 - pt0, kThreads))),
-                             dim3(kThreads), 0, c->stream, d_hashes + pt0, pt1 - pt0, d_fp + 2);
-        PA_HIP(hipMemcpyAsync(c->h_pinned, d_fp, 32, hipMemcpyDeviceToHost, c->stream));
-        PA_HIP(hipStreamSynchronize(c->stream));
-        PA_REQUIRE(c->h_pinned[0] == c->h_pinned[2] && c->h_pinned[1] == c->h_pinned[3],
+                             dim3(kThreads), 0, c->stream, d_hashes + pt0, pt1 - pt0, d_tile_fp);
+        unsigned long long fp_prepared[2], fp_tile[2];
+        ReadBack rb(c);
+        PA_TRY(rb.queue(c->dict_slot<unsigned long long>(kDictPreparedFp), fp_prepared, 2));
+        PA_TRY(rb.queue(d_tile_fp, fp_tile, 2));
+        PA_TRY(rb.wait());
+        PA_REQUIRE(fp_prepared[0] == fp_tile[0] && fp_prepared[1] == fp_tile[1],
                    "pair phase: the prepared dictionary was built from other postings than the subject tile's "
                    "(same count, %llu, different content)", (unsigned long long)(pt1 - pt0));
         cap = c->dict_prepared_cap;
@@ -570,9 +569,8 @@ int pa_pairs_bitrow_hash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_
       constexpr uint64_t kRowBoundBytes = 4ULL << 30;
       uint64_t row_bound = (pt1 - pt0) ? (pt1 - pt0) : 1;
       if (row_bound * w32 * sizeof(uint32_t) > kRowBoundBytes && row_bound * w32 * sizeof(uint32_t) > c->bitrows.bytes) {
-        PA_HIP(hipMemcpyAsync(c->h_pinned, d_counter, 8, hipMemcpyDeviceToHost, c->stream));
-        PA_HIP(hipStreamSynchronize(c->stream));
-        const uint64_t distinct = (uint32_t)c->h_pinned[0];  // ids drawn so far, the one of the key ~0 included
+        uint32_t distinct = 0;  // ids drawn so far, the one of the key ~0 included
+        PA_TRY(pa_read_back(c, d_counter, &distinct));
         row_bound = std::max<uint64_t>(1, std::min<uint64_t>(row_bound, distinct));
       }
       PA_TRY(c->bitrows.reserve(row_bound * w32 * sizeof(uint32_t)));
@@ -583,7 +581,7 @@ int pa_pairs_bitrow_hash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_
         uint64_t longest = 0;
         for (uint32_t g = t0; g < t1; ++g) longest = std::max(longest, h_off[g + 1] - h_off[g]);
         hipLaunchKernelGGL(table_lookup_kernel<true>, dim3(ceil_div_u64(longest, kThreads), cols), dim3(kThreads), 0,
-                           c->stream, d_hashes, pt0, pt1, table, cap, d_counter + 1, d_ids, d_off, n, t0, w32,
+                           c->stream, d_hashes, pt0, pt1, table, cap, d_special, d_ids, d_off, n, t0, w32,
                            c->bitrows.as<uint32_t>());
       }
       // query postings outside the tile's own range
@@ -591,11 +589,11 @@ int pa_pairs_bitrow_hash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_
       const uint64_t b0 = pq0 > pt1 ? pq0 : pt1, b1 = pq1;  // part after the tile
       if (a1 > a0)
         hipLaunchKernelGGL(table_lookup_kernel<false>, dim3(ceil_div_u64(a1 - a0, kThreads)), dim3(kThreads), 0,
-                           c->stream, d_hashes, a0, a1, table, cap, d_counter + 1, d_ids, d_off, n, t0, w32,
+                           c->stream, d_hashes, a0, a1, table, cap, d_special, d_ids, d_off, n, t0, w32,
                            (uint32_t *)nullptr);
       if (b1 > b0)
         hipLaunchKernelGGL(table_lookup_kernel<false>, dim3(ceil_div_u64(b1 - b0, kThreads)), dim3(kThreads), 0,
-                           c->stream, d_hashes, b0, b1, table, cap, d_counter + 1, d_ids, d_off, n, t0, w32,
+                           c->stream, d_hashes, b0, b1, table, cap, d_special, d_ids, d_off, n, t0, w32,
                            (uint32_t *)nullptr);
     }
     {

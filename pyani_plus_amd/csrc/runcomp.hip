@@ -13,7 +13,8 @@
 //      not NaN; the indices are checked before the cell is read, and the cell index q * n_ref + s is 64-bit.  Each
 //      wave counts the survivors of its 64 consecutive rows with one ballot and writes the count of that group.
 //   2. pa_exclusive_scan_u32 over the group counts, which lie in row order: the offset of a group is the number of
-//      survivors before it.  The total is read back, the call's only host synchronisation.
+//      survivors before it.  The total is read back by the same call, pa_scan_total_u32: the call's only host
+//      synchronisation.
 //   3. rc_join_kernel<true>: the same evaluation again; a surviving lane writes x = ref[q, s], y and d = y - x at
 //      offset + popcount(ballot below the lane).  The output is therefore dense and in input order, and no atomic
 //      decides a position.
@@ -214,15 +215,12 @@ extern "C" int pa_runcomp_join(pa_ctx *c, const double *d_ref, uint32_t n_ref, c
   const uint64_t n_groups = (n_rows + 63) / 64;
   PA_TRY(c->flags.reserve(n_groups * sizeof(uint32_t)));
   uint32_t *d_counts = c->flags.as<uint32_t>();
-  uint64_t *d_total = c->counters.as<uint64_t>() + 4;
   const dim3 grid(ceil_div_u64(n_rows, kRowsPerWg));
   hipLaunchKernelGGL(rc_join_kernel<false>, grid, dim3(kThreads), 0, c->stream, d_ref, n_ref, d_q, d_s, d_y, n_rows, d_counts, 0ULL, nullptr,
                      nullptr, nullptr);
   PA_HIP(hipGetLastError());
-  PA_TRY(pa_exclusive_scan_u32(c, d_counts, d_counts, n_groups, d_total));
-  PA_HIP(hipMemcpyAsync(c->h_pinned, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  const uint64_t total = c->h_pinned[0];
+  uint64_t total = 0;
+  PA_TRY(pa_scan_total_u32(c, d_counts, d_counts, n_groups, c->slot<uint64_t>(kCompactTotal), &total));
   *n_common = total;
   if (total == 0) return PA_OK;
   hipLaunchKernelGGL(rc_join_kernel<true>, grid, dim3(kThreads), 0, c->stream, d_ref, n_ref, d_q, d_s, d_y, n_rows, d_counts, total, d_x,
@@ -244,15 +242,14 @@ extern "C" int pa_minmax_f64(pa_ctx *c, const double *d_v, uint64_t n, double *o
   hipLaunchKernelGGL(rc_minmax_kernel, dim3(blocks), dim3(kThreads), 0, c->stream, d_v, n, d_partial);
   hipLaunchKernelGGL(rc_minmax_final_kernel, dim3(1), dim3(kThreads), 0, c->stream, d_partial, blocks, d_result);
   PA_HIP(hipGetLastError());
-  PA_HIP(hipMemcpyAsync(c->h_pinned, d_result, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  const uint64_t valid = c->h_pinned[2];
+  double result[3];  // min, max, the count's bits
+  PA_TRY(pa_read_back(c, d_result, result, 3));
+  uint64_t valid;
+  memcpy(&valid, &result[2], sizeof valid);
   *n_valid = valid;
   if (valid) {
-    double mm[2];
-    memcpy(mm, c->h_pinned, sizeof mm);
-    out[0] = mm[0];
-    out[1] = mm[1];
+    out[0] = result[0];
+    out[1] = result[1];
   }
   return PA_OK;
 }

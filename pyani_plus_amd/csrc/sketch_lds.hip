@@ -194,7 +194,7 @@ int pa_sketch_from_regions(pa_ctx *c, uint64_t *d_regions, const uint64_t *d_reg
   const uint32_t lds_bytes = np2 * (uint32_t)sizeof(uint64_t);
   PA_TRY(c->flags.reserve((uint64_t)n_genomes * sizeof(uint32_t)));
   uint32_t *d_uniq = c->flags.as<uint32_t>();
-  uint64_t *d_total = c->counters.as<uint64_t>() + 1;
+  uint64_t *d_total = c->slot<uint64_t>(kSketchTotal);
   PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(genome_sort_kernel),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   // value ranges of the bucket sort: equal shares of [0, max_hash]
@@ -206,13 +206,16 @@ int pa_sketch_from_regions(pa_ctx *c, uint64_t *d_regions, const uint64_t *d_reg
                      d_region_off, d_cursor, d_uniq, key_shift, key_mult);
   hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(kSortThreads), 0, c->stream, d_uniq, n_genomes, d_off, d_total);
   PA_HIP(hipGetLastError());
-  // one round trip for both scalars: [0] total, [1] overflow flag
-  PA_HIP(hipMemcpyAsync(c->h_pinned, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipMemcpyAsync(c->h_pinned + 1, d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
-  *h_overflow = (uint32_t)c->h_pinned[1] != 0u;
+  // one round trip for both scalars: the total and the overflow flag
+  uint64_t total = 0;
+  uint32_t overflow = 0;
+  ReadBack rb(c);
+  PA_TRY(rb.queue(d_total, &total));
+  PA_TRY(rb.queue(d_overflow, &overflow));
+  PA_TRY(rb.wait());
+  *h_overflow = overflow != 0u;
   if (*h_overflow) return PA_OK;  // caller falls back to the global sort
-  *h_total = c->h_pinned[0];
+  *h_total = total;
   if (*h_total > cap_hashes) {
     pa_set_error("sketch output needs %llu hashes, caller gave room for %llu", (unsigned long long)*h_total,
                  (unsigned long long)cap_hashes);

@@ -166,9 +166,9 @@ int pa_sketch_streamed(pa_ctx *c, const uint32_t *h_packed, const uint64_t *h_ru
                         c->stream));
   PA_HIP(hipMemcpyAsync(c->region_off.p, region_off.data(), (uint64_t)(n_genomes + 1) * sizeof(uint64_t),
                         hipMemcpyHostToDevice, c->stream));
-  uint32_t *d_overflow = c->counters.as<uint32_t>() + 12;
+  uint32_t *d_overflow = c->slot(kRegionOverflow);
   PA_HIP(hipMemsetAsync(c->region_cursor.p, 0, (uint64_t)n_genomes * sizeof(uint32_t), c->stream));
-  PA_HIP(hipMemsetAsync(d_overflow, 0, sizeof(uint32_t), c->stream));
+  PA_HIP(hipMemsetAsync(d_overflow, 0, kRegionOverflow.bytes(), c->stream));
   PA_HIP(hipStreamSynchronize(c->stream));  // blk / region_off are stack-owned; the copy stream starts after this
 
   // 64 MB of packed bases (2.7e8 positions) per chunk: ~1.2 ms on the bus, ~0.7 ms of hashing
