@@ -163,80 +163,77 @@ int pa_memset_d(pa_ctx *c, void *d_dst, int value, uint64_t bytes) {
   return PA_OK;
 }
 
+}  // extern "C"
+
 // ---- sketch -------------------------------------------------------------------
-int pa_sketch(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty_in, uint64_t arena_bases,
-              const uint64_t *h_genome_start, uint32_t n_genomes, uint32_t k, uint64_t max_hash, uint64_t *d_hashes,
-              uint64_t cap_hashes, uint64_t *d_off, uint64_t *h_total) {
-  PA_REQUIRE(c && d_off && h_total && h_genome_start, "pa_sketch: null argument");
-  PA_REQUIRE((arena_bases % PA_ALIGN_BASES) == 0, "pa_sketch: arena_bases %llu is not a multiple of %u",
-             (unsigned long long)arena_bases, PA_ALIGN_BASES);
-  PA_REQUIRE(arena_bases == 0 || (d_packed && d_mask), "pa_sketch: null arena");
-  PA_REQUIRE(k >= 1 && k <= PA_MAX_K, "pa_sketch: k=%u outside [1,%u]", k, PA_MAX_K);
-  PA_REQUIRE(h_genome_start[n_genomes] == arena_bases, "pa_sketch: genome_start[n] must equal arena_bases");
-  PA_HIP(hipSetDevice(c->device));
+int pa_regions_begin(pa_ctx *c, const SketchPlan &plan) {
+  const uint64_t n = plan.blk.size() - 1;
+  PA_TRY(c->genome_blk.reserve((n + 1) * sizeof(uint32_t)));
+  PA_TRY(c->region_off.reserve((n + 1) * sizeof(uint64_t)));
+  PA_TRY(c->region_cursor.reserve(n * sizeof(uint32_t)));
+  PA_TRY(c->cand_keys[0].reserve(plan.region_off[n] * sizeof(uint64_t)));
+  PA_HIP(hipMemcpyAsync(c->genome_blk.p, plan.blk.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  PA_HIP(hipMemcpyAsync(c->region_off.p, plan.region_off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  PA_HIP(hipMemsetAsync(c->region_cursor.p, 0, n * sizeof(uint32_t), c->stream));
+  PA_HIP(hipMemsetAsync(c->slot(kRegionOverflow), 0, kRegionOverflow.bytes(), c->stream));
+  return PA_OK;
+}
+
+CandSink pa_region_sink(pa_ctx *c, uint32_t n_genomes) {
+  CandSink s;
+  s.cand_hash = c->cand_keys[0].as<uint64_t>();
+  s.region_off = c->region_off.as<uint64_t>();
+  s.cursor = c->region_cursor.as<uint32_t>();
+  s.overflow = c->slot(kRegionOverflow);
+  s.genome_blk = c->genome_blk.as<uint32_t>();
+  s.n_genomes = n_genomes;
+  return s;
+}
+
+int pa_sketch_resident(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty_in,
+                       const SketchPlan &plan, uint32_t k, uint64_t max_hash, uint64_t *d_hashes, uint64_t cap_hashes,
+                       uint64_t *d_off, uint64_t *h_total) {
   *h_total = 0;
-  const uint64_t n_blocks = arena_bases / PA_ALIGN_BASES;
-  std::vector<uint32_t> blk(n_genomes + 1);
-  for (uint32_t g = 0; g <= n_genomes; ++g) {
-    const uint64_t s = h_genome_start[g];
-    PA_REQUIRE((s % PA_ALIGN_BASES) == 0 && (g == 0 || s >= h_genome_start[g - 1]) && s <= arena_bases,
-               "pa_sketch: genome_start[%u]=%llu must be an ascending multiple of %u inside the arena", g,
-               (unsigned long long)s, PA_ALIGN_BASES);
-    blk[g] = (uint32_t)(s / PA_ALIGN_BASES);
-  }
-  PA_REQUIRE(n_blocks < (1ULL << 32), "pa_sketch: arena too large");
-  PA_TRY(c->genome_blk.reserve((uint64_t)(n_genomes + 1) * sizeof(uint32_t)));
-  PA_HIP(hipMemcpyAsync(c->genome_blk.p, blk.data(), (uint64_t)(n_genomes + 1) * sizeof(uint32_t),
-                        hipMemcpyHostToDevice, c->stream));
-  // expected survivors: one window in 2^64/(max_hash+1)
-  const double frac = (max_hash == UINT64_MAX) ? 1.0 : ((double)max_hash + 1.0) / 18446744073709551616.0;
-  // Per-genome candidate regions (expectation + 25 % + 128 slots).  When the longest fits an LDS sort the
-  // sketches are finished by sketch_lds.hip; otherwise, or if a region overflows, by the global sort below.
+  const uint32_t n_genomes = (uint32_t)plan.blk.size() - 1;
+  const uint64_t arena_bases = plan.n_blocks * PA_ALIGN_BASES;
+  // When the longest region fits an LDS sort the sketches are finished by sketch_lds.hip; otherwise, or if a region
+  // overflows, by the global sort below.
   static const bool force_global = [] {
     const char *v = PA_TOOL_ENV("PA_SKETCH_SORT");
     return v && v[0] == 'g';
   }();
-  std::vector<uint64_t> region_off(n_genomes + 1, 0);
-  uint64_t longest_region = 0;
-  for (uint32_t g = 0; g < n_genomes; ++g) {
-    const uint64_t room = (uint64_t)((double)(h_genome_start[g + 1] - h_genome_start[g]) * frac * 1.25) + 128;
-    longest_region = std::max(longest_region, room);
-    region_off[g + 1] = region_off[g] + room;
-  }
-  const bool use_regions = !force_global && n_genomes > 0 && longest_region <= kLdsSortMax;
+  const bool use_regions = !force_global && n_genomes > 0 && plan.longest_region <= kLdsSortMax;
   if (use_regions) {
-    PA_TRY(c->region_off.reserve((uint64_t)(n_genomes + 1) * sizeof(uint64_t)));
-    PA_TRY(c->region_cursor.reserve((uint64_t)n_genomes * sizeof(uint32_t)));
-    PA_HIP(hipMemcpyAsync(c->region_off.p, region_off.data(), (uint64_t)(n_genomes + 1) * sizeof(uint64_t),
-                          hipMemcpyHostToDevice, c->stream));
+    PA_TRY(pa_regions_begin(c, plan));
+  } else {  // the global candidate list needs the block table only
+    PA_TRY(c->genome_blk.reserve(plan.blk.size() * sizeof(uint32_t)));
+    PA_HIP(hipMemcpyAsync(c->genome_blk.p, plan.blk.data(), plan.blk.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   }
-  const uint64_t *d_dirty = nullptr;
-  PA_TRY(pa_dirty_or_build(c, d_mask, n_blocks, d_dirty_in, &d_dirty));
-  PA_HIP(hipStreamSynchronize(c->stream));  // blk and region_off are stack-owned vectors
+  KmerHashArgs hash;
+  hash.arena = {d_packed, d_mask, nullptr, plan.n_blocks};
+  hash.k = k;
+  hash.max_hash = max_hash;
+  PA_TRY(pa_dirty_or_build(c, d_mask, plan.n_blocks, d_dirty_in, &hash.arena.dirty));
+  PA_HIP(hipStreamSynchronize(c->stream));  // the uploads read the caller's plan
 
   if (use_regions) {
-    uint32_t *d_overflow = c->slot(kRegionOverflow);
-    PA_TRY(c->cand_keys[0].reserve(region_off[n_genomes] * sizeof(uint64_t)));
-    PA_HIP(hipMemsetAsync(c->region_cursor.p, 0, (uint64_t)n_genomes * sizeof(uint32_t), c->stream));
-    PA_HIP(hipMemsetAsync(d_overflow, 0, kRegionOverflow.bytes(), c->stream));
+    hash.sink = pa_region_sink(c, n_genomes);
     {
       ProfScope prof(c, PA_PROF_KMER_HASH);
-      PA_TRY(pa_launch_kmer_hash(c, d_packed, d_mask, d_dirty, n_blocks, c->genome_blk.as<uint32_t>(), n_genomes, k, max_hash,
-                                 c->cand_keys[0].as<uint64_t>(), nullptr, 0, nullptr, c->region_off.as<uint64_t>(),
-                                 c->region_cursor.as<uint32_t>(), d_overflow));
+      PA_TRY(pa_launch_kmer_hash(c, hash));
     }
     bool overflow = false;
     {
       ProfScope prof(c, PA_PROF_SKETCH_SORT);
-      const int st = pa_sketch_from_regions(c, c->cand_keys[0].as<uint64_t>(), c->region_off.as<uint64_t>(),
-                                            c->region_cursor.as<uint32_t>(), d_overflow, n_genomes,
-                                            (uint32_t)longest_region, max_hash, d_hashes, cap_hashes, d_off, h_total, &overflow);
+      const int st = pa_sketch_from_regions(c, hash.sink.cand_hash, hash.sink.region_off, hash.sink.cursor, hash.sink.overflow,
+                                            n_genomes, (uint32_t)plan.longest_region, max_hash, d_hashes, cap_hashes, d_off,
+                                            h_total, &overflow);
       if (st != PA_OK) return st;
     }
     if (!overflow) return PA_OK;
     *h_total = 0;  // a region was too small (repeats, low-complexity sequence): take the general path
   }
-  uint64_t cap = (uint64_t)((double)arena_bases * frac * 1.25) + 65536;
+  uint64_t cap = (uint64_t)((double)arena_bases * plan.frac * 1.25) + 65536;
   if (cap > arena_bases) cap = arena_bases;
   uint64_t *d_count = c->slot<uint64_t>(kCandCount);
   uint64_t n_cand = 0;
@@ -246,10 +243,16 @@ int pa_sketch(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const
       PA_TRY(c->cand_vals[b].reserve(cap * sizeof(uint32_t)));
     }
     PA_HIP(hipMemsetAsync(d_count, 0, kCandCount.bytes(), c->stream));
+    hash.sink = CandSink{};
+    hash.sink.cand_hash = c->cand_keys[0].as<uint64_t>();
+    hash.sink.cand_genome = c->cand_vals[0].as<uint32_t>();
+    hash.sink.cap = cap;
+    hash.sink.count = d_count;
+    hash.sink.genome_blk = c->genome_blk.as<uint32_t>();
+    hash.sink.n_genomes = n_genomes;
     {
       ProfScope prof(c, PA_PROF_KMER_HASH);
-      PA_TRY(pa_launch_kmer_hash(c, d_packed, d_mask, d_dirty, n_blocks, c->genome_blk.as<uint32_t>(), n_genomes, k, max_hash,
-                                 c->cand_keys[0].as<uint64_t>(), c->cand_vals[0].as<uint32_t>(), cap, d_count));
+      PA_TRY(pa_launch_kmer_hash(c, hash));
     }
     PA_TRY(pa_read_back(c, d_count, &n_cand));
     if (n_cand <= cap) break;
@@ -273,6 +276,19 @@ int pa_sketch(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const
     if (st != PA_OK) return st;
   }
   return PA_OK;
+}
+
+extern "C" {
+
+int pa_sketch(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty_in, uint64_t arena_bases,
+              const uint64_t *h_genome_start, uint32_t n_genomes, uint32_t k, uint64_t max_hash, uint64_t *d_hashes,
+              uint64_t cap_hashes, uint64_t *d_off, uint64_t *h_total) {
+  PA_REQUIRE(c && d_off && h_total && h_genome_start, "pa_sketch: null argument");
+  PA_REQUIRE(arena_bases == 0 || (d_packed && d_mask), "pa_sketch: null arena");
+  SketchPlan plan;
+  PA_TRY(pa_sketch_plan(h_genome_start, n_genomes, arena_bases, k, max_hash, "pa_sketch", &plan));
+  PA_HIP(hipSetDevice(c->device));
+  return pa_sketch_resident(c, d_packed, d_mask, d_dirty_in, plan, k, max_hash, d_hashes, cap_hashes, d_off, h_total);
 }
 
 // ---- pairs ----------------------------------------------------------------------

@@ -18,6 +18,7 @@
 // atomic per workgroup and the stores are coalesced.
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "pa_internal.h"
 #include "murmur_dev.h"
@@ -41,19 +42,93 @@ __device__ __forceinline__ uint32_t find_genome(const uint32_t *__restrict__ gen
   return lo;
 }
 
+// ---- where a surviving hash goes (CandSink, pa_internal.h) ---------------------------------------------------------
 // one candidate into the region of genome g (slow path: one atomic per candidate)
-__device__ __forceinline__ void region_append(uint64_t *__restrict__ regions, const uint64_t *__restrict__ region_off,
-                                              uint32_t *__restrict__ cursor, uint32_t *__restrict__ overflow,
-                                              uint32_t g, uint64_t h) {
-  const uint64_t slot = atomicAdd(&cursor[g], 1u);
-  if (slot < region_off[g + 1] - region_off[g]) regions[region_off[g] + slot] = h; else *overflow = 1u;
+__device__ __forceinline__ void region_append(const CandSink &s, uint32_t g, uint64_t h) {
+  const uint64_t slot = atomicAdd(&s.cursor[g], 1u);
+  if (slot < s.region_off[g + 1] - s.region_off[g]) s.cand_hash[s.region_off[g] + slot] = h; else *s.overflow = 1u;
 }
 
-// LUT = true (default): the first multiply of every murmur word is looked up.  A word is
-// two 4-base groups (lo, hi); word*c = (ascii(lo) + ascii(hi)*2^32)*c
-//                                    = s_lo[j][lo] + (s_hi[j][hi] << 32)   (mod 2^64)
-// with s_lo[j][b] = ascii(b)*c_j (64 bit) and s_hi[j][b] = low32(ascii(b)*c_j): two LDS reads and
-// one add replace the ASCII expansion (8 VALU) and a 64-bit multiply (3 quarter-rate VALU).
+// one candidate of genome g, directly: to the genome's region, or to the global candidate list
+__device__ __forceinline__ void append_candidate(const CandSink &s, uint32_t g, uint64_t h) {
+  if (s.region_off) {
+    region_append(s, g, h);
+  } else {
+    const unsigned long long slot = atomicAdd(reinterpret_cast<unsigned long long *>(s.count), 1ULL);
+    if (slot < s.cap) {
+      s.cand_hash[slot] = h;
+      s.cand_genome[slot] = g;
+    }
+  }
+}
+
+// One candidate of arena block t into the workgroup's LDS staging (kStageCap slots, s_n counts them); with the staging
+// full (tiny `scaled`) it goes out directly.  Not through append_candidate: there the genome is looked up before the
+// slot is known to exist, here -- inside the window loop -- only after.
+__device__ __forceinline__ void stage_candidate(const CandSink &s, uint64_t (&s_hash)[kStageCap], uint32_t (&s_blk)[kStageCap],
+                                                uint32_t &s_n, uint32_t t, uint64_t h) {
+  const uint32_t slot = atomicAdd(&s_n, 1u);
+  if (slot < kStageCap) {
+    s_hash[slot] = h;
+    s_blk[slot] = t;
+  } else if (s.region_off) {
+    region_append(s, find_genome(s.genome_blk, s.n_genomes, t), h);
+  } else {
+    const unsigned long long g = atomicAdd(reinterpret_cast<unsigned long long *>(s.count), 1ULL);
+    if (g < s.cap) {
+      s.cand_hash[g] = h;
+      s.cand_genome[g] = find_genome(s.genome_blk, s.n_genomes, t);
+    }
+  }
+}
+
+// The end of a streaming kernel, reached by every thread of the workgroup: the staged candidates go out with one
+// atomic per workgroup and coalesced stores.  The workgroup holds blocks blk0 + blockIdx.x * kThreads onwards.
+__device__ __forceinline__ void flush_staged(const CandSink &s, const uint64_t (&s_hash)[kStageCap], const uint32_t (&s_blk)[kStageCap],
+                                             const uint32_t &s_n, unsigned long long &s_base, uint32_t blk0, uint32_t n_blocks64) {
+  const uint32_t tid = threadIdx.x;
+  __syncthreads();
+  const uint32_t n = min(s_n, kStageCap);
+  if (n == 0) return;
+  if (s.region_off) {
+    // per-genome regions (see sketch_lds.hip): a workgroup that lies inside one genome -- all but the
+    // few that straddle a boundary -- reserves its slots with one atomic on that genome's cursor
+    const uint32_t b0 = blk0 + blockIdx.x * kThreads;
+    const uint32_t b1 = min(b0 + (uint32_t)kThreads, n_blocks64) - 1u;
+    const uint32_t g0 = find_genome(s.genome_blk, s.n_genomes, b0);
+    if (s.genome_blk[g0 + 1] > b1) {
+      if (tid == 0) s_base = atomicAdd(&s.cursor[g0], n);
+      __syncthreads();
+      const uint64_t room = s.region_off[g0 + 1] - s.region_off[g0];
+      uint64_t *__restrict__ dst = s.cand_hash + s.region_off[g0];
+      for (uint32_t i = tid; i < n; i += kThreads) {
+        const uint64_t slot = s_base + i;
+        if (slot < room) dst[slot] = s_hash[i]; else *s.overflow = 1u;
+      }
+    } else {
+      for (uint32_t i = tid; i < n; i += kThreads)
+        region_append(s, find_genome(s.genome_blk, s.n_genomes, s_blk[i]), s_hash[i]);
+    }
+    return;
+  }
+  if (tid == 0) s_base = atomicAdd(reinterpret_cast<unsigned long long *>(s.count), (unsigned long long)n);
+  __syncthreads();
+  const unsigned long long base = s_base;
+  for (uint32_t i = tid; i < n; i += kThreads) {
+    const unsigned long long g = base + i;
+    if (g < s.cap) {
+      s.cand_hash[g] = s_hash[i];
+      s.cand_genome[g] = find_genome(s.genome_blk, s.n_genomes, s_blk[i]);
+    }
+  }
+}
+
+__device__ __forceinline__ uint32_t rev_groups32(uint32_t x) {  // the sixteen 2-bit groups of a word in reverse order
+  x = __builtin_bitreverse32(x);
+  return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+}
+
+// LUT = true (default): the first multiply of every murmur word is looked up (murmur_dev.h).
 // LUT = false keeps the arithmetic form (ablation / cross-check, PA_KMER_VARIANT=0).
 template <int K, bool LUT>
 __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
@@ -72,18 +147,12 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
   __shared__ uint32_t s_hi[LUT ? kWords : 1][256];
 
   const uint32_t tid = threadIdx.x;
+  const CandSink sink{cand_hash, cand_genome, cap, reinterpret_cast<uint64_t *>(count), region_off, cursor, overflow, genome_blk, n_genomes};
   const uint32_t max_hi = (uint32_t)(max_hash >> 32);
   const bool take_all = max_hi == 0xffffffffu;  // scaled = 1: no screen
   const uint32_t screen_hi = max_hi + 1u;
   if (tid == 0) s_n = 0;
-  if constexpr (LUT) {
-#pragma unroll
-    for (int j = 0; j < kWords; ++j) {
-      const uint64_t cj = (j & 1) ? kC2 : kC1;
-      s_lo[j][tid] = (uint64_t)ascii_group(tid, K - 8 * j) * cj;
-      s_hi[j][tid] = (uint32_t)((uint64_t)ascii_group(tid, K - 8 * j - 4) * cj);
-    }
-  }
+  if constexpr (LUT) fill_first_products(s_lo, s_hi, tid, std::integral_constant<int, K>{});
   __syncthreads();
 
   const uint32_t t = blk0 + blockIdx.x * kThreads + tid;  // blk0: first arena block of this launch (streamed uploads)
@@ -132,10 +201,7 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
       uint32_t fw[8] = {pw.x, pw.y, cur.x, cur.y, cur.z, cur.w, 0u, 0u};
       uint32_t rw[6];
 #pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const uint32_t x = __builtin_bitreverse32(fw[5 - j]);  // groups reversed, bits inside a group too
-        rw[j] = ~(((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1));
-      }
+      for (int j = 0; j < 6; ++j) rw[j] = ~rev_groups32(fw[5 - j]);
       // Windows are taken column by column: the four windows e = i, i+16, i+32, i+48 sit at the same bit offset of
       // consecutive dwords, so the five funnel shifts A[0..4] of the forward stream (and five of the reverse one) serve
       // all four -- the high dword of one window is the low dword of the next: 2.5 shifts per window and stream pair
@@ -170,41 +236,22 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
 #pragma unroll
           for (int j = 0; j < kWords; ++j) {
             const uint32_t src = j < 2 ? clo : chi;
-            const uint32_t glo = (src >> (16 * (j & 1))) & 0xffu, ghi = (src >> (16 * (j & 1) + 8)) & 0xffu;
             if constexpr (LUT) {
-              const uint64_t lo = s_lo[j][glo];
-              const uint32_t hi = (uint32_t)(lo >> 32) + s_hi[j][ghi];
-              P[j] = u64_of((uint32_t)lo, hi);
+              P[j] = first_product(s_lo, s_hi, j, src);
             } else {
+              const uint32_t glo = (src >> (16 * (j & 1))) & 0xffu, ghi = (src >> (16 * (j & 1) + 8)) & 0xffu;
               const uint64_t word = u64_of(ascii_group(glo, K - 8 * j), ascii_group(ghi, K - 8 * j - 4));
               P[j] = word * ((j & 1) ? kC2 : kC1);
             }
           }
           (void)kMaskHi;
-          // Screen on the high words: hash = (X ^ X>>33) + (Y ^ Y>>33) has high word X.hi + Y.hi + carry, so it can
-          // be <= max_hash only if X.hi + Y.hi is <= max_hash.hi or is 0xffffffff (the carry wraps it to 0) -- one
-          // unsigned compare of X.hi + Y.hi + 1 against max_hash.hi + 1.  The sum of the two high words is linear in
-          // the inputs of the last multiply (murmur_dev.h), so the 999 in 1000 windows that are dropped never form
-          // X and Y: 2 mul_hi + 2 mul_lo + 4 adds + 1 compare instead of two 64-bit multiplies, an add and 2 compares.
+          // the 999 in 1000 windows that the screen drops never form the last products (passes_screen, murmur_dev.h)
           uint64_t U, V;
           murmur3_pre_last_mul<K>(P, U, V);
-          if (take_all || last_mul_high_sum_plus1(U, V) <= screen_hi) {
-            const uint64_t X = U * kF2, Y = V * kF2;
-            const uint64_t h = (X ^ (X >> 33)) + (Y ^ (Y >> 33));
+          if (passes_screen(U, V, take_all, screen_hi)) {
+            const uint64_t h = last_mul_and_fold(U, V);
             if (h > max_hash || ((bad[wi >> 1] >> (16 * (wi & 1) + i)) & 1u)) continue;  // validity is only looked at for the 1 in 1000
-            const uint32_t slot = atomicAdd(&s_n, 1u);
-            if (slot < kStageCap) {
-              s_hash[slot] = h;
-              s_blk[slot] = t;
-            } else if (region_off) {  // staging full (tiny `scaled`): append straight to the genome's region
-              region_append(cand_hash, region_off, cursor, overflow, find_genome(genome_blk, n_genomes, t), h);
-            } else {  // ... or to the global candidate list
-              const unsigned long long g = atomicAdd(count, 1ULL);
-              if (g < cap) {
-                cand_hash[g] = h;
-                cand_genome[g] = find_genome(genome_blk, n_genomes, t);
-              }
-            }
+            stage_candidate(sink, s_hash, s_blk, s_n, t, h);
           }
           }
         }
@@ -214,71 +261,7 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
       if constexpr (kSplit < 16) columns(std::integral_constant<int, (kOff0 >> 4) + 1>{}, kSplit, 16);
     }
   }
-  __syncthreads();
-  const uint32_t n = min(s_n, kStageCap);
-  if (n == 0) return;
-  if (region_off) {
-    // per-genome regions (see sketch_lds.hip): a workgroup that lies inside one genome -- all but the
-    // few that straddle a boundary -- reserves its slots with one atomic on that genome's cursor
-    const uint32_t b0 = blk0 + blockIdx.x * kThreads;
-    const uint32_t b1 = min(b0 + (uint32_t)kThreads, n_blocks64) - 1u;
-    const uint32_t g0 = find_genome(genome_blk, n_genomes, b0);
-    if (genome_blk[g0 + 1] > b1) {
-      if (tid == 0) s_base = atomicAdd(&cursor[g0], n);
-      __syncthreads();
-      const uint64_t room = region_off[g0 + 1] - region_off[g0];
-      uint64_t *__restrict__ dst = cand_hash + region_off[g0];
-      for (uint32_t i = tid; i < n; i += kThreads) {
-        const uint64_t slot = s_base + i;
-        if (slot < room) dst[slot] = s_hash[i]; else *overflow = 1u;
-      }
-    } else {
-      for (uint32_t i = tid; i < n; i += kThreads)
-        region_append(cand_hash, region_off, cursor, overflow, find_genome(genome_blk, n_genomes, s_blk[i]), s_hash[i]);
-    }
-    return;
-  }
-  if (tid == 0) s_base = atomicAdd(count, (unsigned long long)n);
-  __syncthreads();
-  const unsigned long long base = s_base;
-  for (uint32_t i = tid; i < n; i += kThreads) {
-    const unsigned long long g = base + i;
-    if (g < cap) {
-      cand_hash[g] = s_hash[i];
-      cand_genome[g] = find_genome(genome_blk, n_genomes, s_blk[i]);
-    }
-  }
-}
-
-template <int K, bool LUT>
-int launch_variant(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty, uint64_t n_blocks64,
-           const uint32_t *d_genome_blk, uint32_t n_genomes, uint64_t max_hash, uint64_t *d_cand_hash,
-           uint32_t *d_cand_genome, uint64_t cap, uint64_t *d_count, const uint64_t *d_region_off, uint32_t *d_cursor,
-           uint32_t *d_overflow, uint64_t blk0, hipStream_t stream) {
-  const uint32_t grid = ceil_div_u64(n_blocks64 - blk0, kThreads);
-  hipLaunchKernelGGL((kmer_hash_kernel<K, LUT>), dim3(grid), dim3(kThreads), 0, stream ? stream : c->stream,
-                     reinterpret_cast<const uint4 *>(d_packed), reinterpret_cast<const uint2 *>(d_mask), d_dirty,
-                     (uint32_t)n_blocks64, d_genome_blk, n_genomes, max_hash, d_cand_hash, d_cand_genome, cap,
-                     reinterpret_cast<unsigned long long *>(d_count), d_region_off, d_cursor, d_overflow, (uint32_t)blk0);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
-}
-
-template <int K>
-int launch(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty, uint64_t n_blocks64,
-           const uint32_t *d_genome_blk, uint32_t n_genomes, uint64_t max_hash, uint64_t *d_cand_hash,
-           uint32_t *d_cand_genome, uint64_t cap, uint64_t *d_count, const uint64_t *d_region_off, uint32_t *d_cursor,
-           uint32_t *d_overflow, uint64_t blk0, hipStream_t stream) {
-  static const bool arithmetic = [] {
-    const char *v = PA_TOOL_ENV("PA_KMER_VARIANT");
-    return v && v[0] == '0';
-  }();
-  if constexpr (K == 31)  // the ablation build exists for the benchmarked k only
-    if (arithmetic)
-      return launch_variant<K, false>(c, d_packed, d_mask, d_dirty, n_blocks64, d_genome_blk, n_genomes, max_hash, d_cand_hash,
-                                    d_cand_genome, cap, d_count, d_region_off, d_cursor, d_overflow, blk0, stream);
-  return launch_variant<K, true>(c, d_packed, d_mask, d_dirty, n_blocks64, d_genome_blk, n_genomes, max_hash, d_cand_hash,
-                                 d_cand_genome, cap, d_count, d_region_off, d_cursor, d_overflow, blk0, stream);
+  flush_staged(sink, s_hash, s_blk, s_n, s_base, blk0, n_blocks64);
 }
 
 // ---- k from 33 to 64, sixty-four windows per thread --------------------------------------------------------------
@@ -305,16 +288,12 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_wide_kernel(
   __shared__ uint64_t s_lo[kWords][256];
   __shared__ uint32_t s_hi[kWords][256];
   const uint32_t tid = threadIdx.x;
+  const CandSink sink{cand_hash, cand_genome, cap, reinterpret_cast<uint64_t *>(count), region_off, cursor, overflow, genome_blk, n_genomes};
   const uint32_t max_hi = (uint32_t)(max_hash >> 32);
   const bool take_all = max_hi == 0xffffffffu;
   const uint32_t screen_hi = max_hi + 1u;
   if (tid == 0) s_n = 0;
-#pragma unroll
-  for (int j = 0; j < kWords; ++j) {
-    const uint64_t cj = (j & 1) ? kC2 : kC1;
-    s_lo[j][tid] = (uint64_t)ascii_group(tid, K - 8 * j) * cj;
-    s_hi[j][tid] = (uint32_t)((uint64_t)ascii_group(tid, K - 8 * j - 4) * cj);
-  }
+  fill_first_products(s_lo, s_hi, tid, std::integral_constant<int, K>{});
   __syncthreads();
 
   const uint32_t t = blk0 + blockIdx.x * kThreads + tid;
@@ -356,10 +335,7 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_wide_kernel(
       const uint32_t fw[10] = {prev.x, prev.y, prev.z, prev.w, cur.x, cur.y, cur.z, cur.w, 0u, 0u};
       uint32_t rw[10];
 #pragma unroll
-      for (int j = 0; j < 10; ++j) {
-        const uint32_t x = __builtin_bitreverse32(fw[9 - j]);
-        rw[j] = ~(((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1));
-      }
+      for (int j = 0; j < 10; ++j) rw[j] = ~rev_groups32(fw[9 - j]);
       auto columns = [&](auto base_tag, int i_begin, int i_end) {
         constexpr int kBase = decltype(base_tag)::value;
 #pragma unroll 1
@@ -390,31 +366,13 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_wide_kernel(
             const uint32_t cw[4] = {c0, c1, c2, c3};
             uint64_t P[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-            for (int j = 0; j < kWords; ++j) {
-              const uint32_t src = cw[j >> 1];
-              const uint32_t glo = (src >> (16 * (j & 1))) & 0xffu, ghi = (src >> (16 * (j & 1) + 8)) & 0xffu;
-              const uint64_t lo = s_lo[j][glo];
-              P[j] = u64_of((uint32_t)lo, (uint32_t)(lo >> 32) + s_hi[j][ghi]);
-            }
+            for (int j = 0; j < kWords; ++j) P[j] = first_product(s_lo, s_hi, j, cw[j >> 1]);
             uint64_t U, V;
             murmur3_pre_last_mul<K>(P, U, V);
-            if (take_all || last_mul_high_sum_plus1(U, V) <= screen_hi) {
-              const uint64_t X = U * kF2, Y = V * kF2;
-              const uint64_t h = (X ^ (X >> 33)) + (Y ^ (Y >> 33));
+            if (passes_screen(U, V, take_all, screen_hi)) {
+              const uint64_t h = last_mul_and_fold(U, V);
               if (h > max_hash || ((bad[wi >> 1] >> (16 * (wi & 1) + i)) & 1u)) continue;
-              const uint32_t slot = atomicAdd(&s_n, 1u);
-              if (slot < kStageCap) {
-                s_hash[slot] = h;
-                s_blk[slot] = t;
-              } else if (region_off) {
-                region_append(cand_hash, region_off, cursor, overflow, find_genome(genome_blk, n_genomes, t), h);
-              } else {
-                const unsigned long long g = atomicAdd(count, 1ULL);
-                if (g < cap) {
-                  cand_hash[g] = h;
-                  cand_genome[g] = find_genome(genome_blk, n_genomes, t);
-                }
-              }
+              stage_candidate(sink, s_hash, s_blk, s_n, t, h);
             }
           }
         }
@@ -424,38 +382,7 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_wide_kernel(
       if constexpr (kSplit < 16) columns(std::integral_constant<int, (kOff0 >> 4) + 1>{}, kSplit, 16);
     }
   }
-  __syncthreads();
-  const uint32_t n = min(s_n, kStageCap);
-  if (n == 0) return;
-  if (region_off) {
-    const uint32_t b0 = blk0 + blockIdx.x * kThreads;
-    const uint32_t b1 = min(b0 + (uint32_t)kThreads, n_blocks64) - 1u;
-    const uint32_t g0 = find_genome(genome_blk, n_genomes, b0);
-    if (genome_blk[g0 + 1] > b1) {
-      if (tid == 0) s_base = atomicAdd(&cursor[g0], n);
-      __syncthreads();
-      const uint64_t room = region_off[g0 + 1] - region_off[g0];
-      uint64_t *__restrict__ dst = cand_hash + region_off[g0];
-      for (uint32_t i = tid; i < n; i += kThreads) {
-        const uint64_t slot = s_base + i;
-        if (slot < room) dst[slot] = s_hash[i]; else *overflow = 1u;
-      }
-    } else {
-      for (uint32_t i = tid; i < n; i += kThreads)
-        region_append(cand_hash, region_off, cursor, overflow, find_genome(genome_blk, n_genomes, s_blk[i]), s_hash[i]);
-    }
-    return;
-  }
-  if (tid == 0) s_base = atomicAdd(count, (unsigned long long)n);
-  __syncthreads();
-  const unsigned long long base = s_base;
-  for (uint32_t i = tid; i < n; i += kThreads) {
-    const unsigned long long g = base + i;
-    if (g < cap) {
-      cand_hash[g] = s_hash[i];
-      cand_genome[g] = find_genome(genome_blk, n_genomes, s_blk[i]);
-    }
-  }
+  flush_staged(sink, s_hash, s_blk, s_n, s_base, blk0, n_blocks64);
 }
 
 // ---- k from 33 to 64, one window per thread-step (PA_KMER_LONG=plain: the cross-check of the kernel above) ---------
@@ -466,42 +393,6 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_wide_kernel(
 // already there -- also when the arena arrives in chunks), both strands as four 32-bit words, the first multiply
 // of each of the up to eight murmur words from the same kind of LDS tables as above, the high-word screen before
 // the last multiply.  Same results as the oracle for every k.
-__device__ __forceinline__ uint32_t rev_groups32(uint32_t x) {  // the sixteen 2-bit groups of a word in reverse order
-  x = __builtin_bitreverse32(x);
-  return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
-}
-
-// everything of MurmurHash3_x64_128 between the first multiply of every word (P[j], from the tables) and the last
-// multiply of the two fmix64: U and V as in murmur3_pre_last_mul, for a run-time k (uniform over the launch)
-__device__ __forceinline__ void murmur3_pre_last_mul_rt(const uint64_t (&P)[8], uint32_t k, uint64_t &U, uint64_t &V) {
-  uint64_t h1 = 42, h2 = 42;
-  const uint32_t nblocks = k >> 4, tail = k & 15u;
-#pragma unroll
-  for (uint32_t i = 0; i < 4; ++i) {
-    if (i >= nblocks) break;
-    h1 ^= rotl64(P[2 * i], 31) * kC2;
-    h1 = rotl64(h1, 27) + h2;
-    h1 = times5_plus(h1, 0x52dce729ULL);
-    h2 ^= rotl64(P[2 * i + 1], 33) * kC1;
-    h2 = rotl64(h2, 31) + h1;
-    h2 = times5_plus(h2, 0x38495ab5ULL);
-  }
-  uint64_t t1 = 0, t2 = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < 4; ++i)
-    if (i == nblocks) { t1 = P[2 * i]; t2 = P[2 * i + 1]; }
-  if (tail > 8) h2 ^= rotl64(t2, 33) * kC1;
-  if (tail > 0) h1 ^= rotl64(t1, 31) * kC2;
-  h1 ^= (uint64_t)k;
-  h2 ^= (uint64_t)k;
-  h1 += h2;
-  h2 += h1;
-  h1 ^= h1 >> 33; h1 *= kF1; h1 ^= h1 >> 33;
-  h2 ^= h2 >> 33; h2 *= kF1; h2 ^= h2 >> 33;
-  U = h1;
-  V = h2;
-}
-
 constexpr int kLongIter = 32;  // window ends per thread of kmer_hash_long_kernel
 __global__ __launch_bounds__(kThreads) void kmer_hash_long_kernel(
     const uint32_t *__restrict__ packed, const uint32_t *__restrict__ mask, uint64_t pos0, uint64_t pos1, uint32_t k,
@@ -511,12 +402,12 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_long_kernel(
   __shared__ uint64_t s_lo[8][256];
   __shared__ uint32_t s_hi[8][256];
   const uint32_t tid = threadIdx.x;
+  const CandSink sink{cand_hash, cand_genome, cap, reinterpret_cast<uint64_t *>(count), region_off, cursor, overflow, genome_blk, n_genomes};
   const uint32_t n_words = (k + 7u) >> 3;
-  for (uint32_t j = 0; j < n_words; ++j) {  // word j of the k-mer: bases 8j .. 8j+7, the last one partial
-    const uint64_t cj = (j & 1u) ? kC2 : kC1;
-    s_lo[j][tid] = (uint64_t)ascii_group(tid, (int)k - 8 * (int)j) * cj;
-    s_hi[j][tid] = (uint32_t)((uint64_t)ascii_group(tid, (int)k - 8 * (int)j - 4) * cj);
-  }
+  const uint32_t max_hi = (uint32_t)(max_hash >> 32);
+  const bool take_all = max_hi == 0xffffffffu;
+  const uint32_t screen_hi = max_hi + 1u;
+  fill_first_products(s_lo, s_hi, tid, k);
   __syncthreads();
   // A workgroup takes kLongIter * 256 consecutive window ends, 256 at a time (the tables above cost as much as hashing
   // a window: they have to serve many).  The grid is two-dimensional: an arena of 1 000 genomes of 5 Mb has 5 * 10^9
@@ -568,88 +459,77 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_long_kernel(
 #pragma unroll
   for (uint32_t j = 0; j < 8; ++j) {
     if (j >= n_words) break;
-    const uint32_t src = c[j >> 1], glo = (src >> (16u * (j & 1u))) & 0xffu, ghi = (src >> (16u * (j & 1u) + 8u)) & 0xffu;
-    const uint64_t lo = s_lo[j][glo];
-    P[j] = u64_of((uint32_t)lo, (uint32_t)(lo >> 32) + s_hi[j][ghi]);
+    P[j] = first_product(s_lo, s_hi, j, c[j >> 1]);
   }
   uint64_t U, V;
   murmur3_pre_last_mul_rt(P, k, U, V);
-  const uint32_t max_hi = (uint32_t)(max_hash >> 32);
-  if (max_hi != 0xffffffffu && last_mul_high_sum_plus1(U, V) > max_hi + 1u) continue;  // the screen of the kernel above
-  const uint64_t X = U * kF2, Y = V * kF2;
-  const uint64_t h = (X ^ (X >> 33)) + (Y ^ (Y >> 33));
+  if (!passes_screen(U, V, take_all, screen_hi)) continue;  // the screen of the kernels above
+  const uint64_t h = last_mul_and_fold(U, V);
   if (h > max_hash) continue;
-  const uint32_t blk = (uint32_t)(e >> 6);
-  const uint32_t g = find_genome(genome_blk, n_genomes, blk);
-  if (region_off) {
-    region_append(cand_hash, region_off, cursor, overflow, g, h);
-  } else {
-    const unsigned long long slot = atomicAdd(count, 1ULL);
-    if (slot < cap) {
-      cand_hash[slot] = h;
-      cand_genome[slot] = g;
-    }
-  }
+  append_candidate(sink, find_genome(genome_blk, n_genomes, (uint32_t)(e >> 6)), h);
   }  // window ends of this workgroup
+}
+
+// ---- launch ----------------------------------------------------------------------------------------------------------
+// one thread per arena block from a.blk0 on: the two streaming kernels
+template <class Kernel>
+int launch_blocks(pa_ctx *c, Kernel kernel, const KmerHashArgs &a) {
+  const ArenaView &v = a.arena;
+  const CandSink &s = a.sink;
+  const uint32_t grid = ceil_div_u64(v.n_blocks64 - a.blk0, kThreads);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, a.stream ? a.stream : c->stream,
+                     reinterpret_cast<const uint4 *>(v.packed), reinterpret_cast<const uint2 *>(v.mask), v.dirty,
+                     (uint32_t)v.n_blocks64, s.genome_blk, s.n_genomes, a.max_hash, s.cand_hash, s.cand_genome, s.cap,
+                     reinterpret_cast<unsigned long long *>(s.count), s.region_off, s.cursor, s.overflow, (uint32_t)a.blk0);
+  PA_HIP(hipGetLastError());
+  return PA_OK;
+}
+
+template <int K>
+int launch_k(pa_ctx *c, const KmerHashArgs &a) {
+  if constexpr (K > 32) {
+    return launch_blocks(c, kmer_hash_wide_kernel<K>, a);
+  } else {
+    if constexpr (K == 31) {  // the ablation build exists for the benchmarked k only
+      static const bool arithmetic = [] {
+        const char *v = PA_TOOL_ENV("PA_KMER_VARIANT");
+        return v && v[0] == '0';
+      }();
+      if (arithmetic) return launch_blocks(c, kmer_hash_kernel<K, false>, a);
+    }
+    return launch_blocks(c, kmer_hash_kernel<K, true>, a);
+  }
+}
+
+// the kernel of a.k, which is one of KMinus1 + 1 ..., or an error
+template <int... KMinus1>
+int launch_for_k(pa_ctx *c, const KmerHashArgs &a, std::integer_sequence<int, KMinus1...>) {
+  int status = PA_E_INVALID;
+  const bool found = ((a.k == (uint32_t)(KMinus1 + 1) && ((status = launch_k<KMinus1 + 1>(c, a)), true)) || ...);
+  if (!found) pa_set_error("k=%u outside [1,64]", a.k);
+  return status;
 }
 
 }  // namespace
 
-int pa_launch_kmer_hash(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty, uint64_t n_blocks64,
-                        const uint32_t *d_genome_blk, uint32_t n_genomes, uint32_t k, uint64_t max_hash,
-                        uint64_t *d_cand_hash, uint32_t *d_cand_genome, uint64_t cap, uint64_t *d_count,
-                        const uint64_t *d_region_off, uint32_t *d_cursor, uint32_t *d_overflow, uint64_t blk0,
-                        hipStream_t stream) {
+int pa_launch_kmer_hash(pa_ctx *c, const KmerHashArgs &a) {
+  const uint64_t n_blocks64 = a.arena.n_blocks64;
   PA_REQUIRE(n_blocks64 < (1ULL << 32), "arena too large: %llu blocks of 64 bases", (unsigned long long)n_blocks64);
-  if (n_blocks64 <= blk0) return PA_OK;
+  if (n_blocks64 <= a.blk0) return PA_OK;
   const char *long_form = PA_TOOL_ENV("PA_KMER_LONG");  // "plain": the one-window-per-step form (cross-check, read per launch)
-  const bool long_plain = long_form && long_form[0] == 'p';
-  if (k > 32 && k <= 64 && !long_plain) {
-    PA_REQUIRE((blk0 & 63u) == 0, "k-mer hash launch must start at a multiple of 64 blocks, not %llu", (unsigned long long)blk0);
-    const uint32_t grid = ceil_div_u64(n_blocks64 - blk0, kThreads);
-#define PA_WIDE_CASE(KK)                                                                                                   \
-  case KK:                                                                                                                 \
-    hipLaunchKernelGGL((kmer_hash_wide_kernel<KK>), dim3(grid), dim3(kThreads), 0, stream ? stream : c->stream,            \
-                       reinterpret_cast<const uint4 *>(d_packed), reinterpret_cast<const uint2 *>(d_mask), d_dirty,        \
-                       (uint32_t)n_blocks64, d_genome_blk, n_genomes, max_hash, d_cand_hash, d_cand_genome, cap,           \
-                       reinterpret_cast<unsigned long long *>(d_count), d_region_off, d_cursor, d_overflow, (uint32_t)blk0); \
-    break;
-    switch (k) {
-      PA_WIDE_CASE(33) PA_WIDE_CASE(34) PA_WIDE_CASE(35) PA_WIDE_CASE(36) PA_WIDE_CASE(37) PA_WIDE_CASE(38) PA_WIDE_CASE(39)
-      PA_WIDE_CASE(40) PA_WIDE_CASE(41) PA_WIDE_CASE(42) PA_WIDE_CASE(43) PA_WIDE_CASE(44) PA_WIDE_CASE(45) PA_WIDE_CASE(46)
-      PA_WIDE_CASE(47) PA_WIDE_CASE(48) PA_WIDE_CASE(49) PA_WIDE_CASE(50) PA_WIDE_CASE(51) PA_WIDE_CASE(52) PA_WIDE_CASE(53)
-      PA_WIDE_CASE(54) PA_WIDE_CASE(55) PA_WIDE_CASE(56) PA_WIDE_CASE(57) PA_WIDE_CASE(58) PA_WIDE_CASE(59) PA_WIDE_CASE(60)
-      PA_WIDE_CASE(61) PA_WIDE_CASE(62) PA_WIDE_CASE(63) PA_WIDE_CASE(64)
-      default: break;
-    }
-#undef PA_WIDE_CASE
-    PA_HIP(hipGetLastError());
-    return PA_OK;
-  }
-  if (k > 32 && k <= 64) {
-    const uint64_t pos0 = blk0 * 64, pos1 = n_blocks64 * 64;
+  if (a.k > 32 && a.k <= 64 && long_form && long_form[0] == 'p') {
+    const CandSink &s = a.sink;
+    const uint64_t pos0 = a.blk0 * 64, pos1 = n_blocks64 * 64;
     const uint64_t per_wg = (uint64_t)kThreads * kLongIter;
     const uint64_t n_wg = (pos1 - pos0 + per_wg - 1) / per_wg;
     const uint32_t gx = (uint32_t)std::min<uint64_t>(n_wg, 1u << 20), gy = (uint32_t)((n_wg + gx - 1) / gx);
     PA_REQUIRE(gy <= 65535u, "arena too large for one launch of the long k-mer kernel: %llu positions", (unsigned long long)(pos1 - pos0));
-    hipLaunchKernelGGL(kmer_hash_long_kernel, dim3(gx, gy), dim3(kThreads), 0,
-                       stream ? stream : c->stream, d_packed, d_mask, pos0, pos1, k, d_genome_blk, n_genomes, max_hash,
-                       d_cand_hash, d_cand_genome, cap, reinterpret_cast<unsigned long long *>(d_count), d_region_off,
-                       d_cursor, d_overflow);
+    hipLaunchKernelGGL(kmer_hash_long_kernel, dim3(gx, gy), dim3(kThreads), 0, a.stream ? a.stream : c->stream, a.arena.packed,
+                       a.arena.mask, pos0, pos1, a.k, s.genome_blk, s.n_genomes, a.max_hash, s.cand_hash, s.cand_genome, s.cap,
+                       reinterpret_cast<unsigned long long *>(s.count), s.region_off, s.cursor, s.overflow);
     PA_HIP(hipGetLastError());
     return PA_OK;
   }
-#define PA_K_CASE(KK) \
-  case KK: return launch<KK>(c, d_packed, d_mask, d_dirty, n_blocks64, d_genome_blk, n_genomes, max_hash, d_cand_hash, d_cand_genome, cap, d_count, d_region_off, d_cursor, d_overflow, blk0, stream);
-  PA_REQUIRE((blk0 & 63u) == 0, "k-mer hash launch must start at a multiple of 64 blocks, not %llu", (unsigned long long)blk0);
-  switch (k) {
-    PA_K_CASE(1) PA_K_CASE(2) PA_K_CASE(3) PA_K_CASE(4) PA_K_CASE(5) PA_K_CASE(6) PA_K_CASE(7) PA_K_CASE(8)
-    PA_K_CASE(9) PA_K_CASE(10) PA_K_CASE(11) PA_K_CASE(12) PA_K_CASE(13) PA_K_CASE(14) PA_K_CASE(15) PA_K_CASE(16)
-    PA_K_CASE(17) PA_K_CASE(18) PA_K_CASE(19) PA_K_CASE(20) PA_K_CASE(21) PA_K_CASE(22) PA_K_CASE(23) PA_K_CASE(24)
-    PA_K_CASE(25) PA_K_CASE(26) PA_K_CASE(27) PA_K_CASE(28) PA_K_CASE(29) PA_K_CASE(30) PA_K_CASE(31) PA_K_CASE(32)
-    default:
-      pa_set_error("k=%u outside [1,64]", k);
-      return PA_E_INVALID;
-  }
-#undef PA_K_CASE
+  PA_REQUIRE((a.blk0 & 63u) == 0, "k-mer hash launch must start at a multiple of 64 blocks, not %llu", (unsigned long long)a.blk0);
+  return launch_for_k(c, a, std::make_integer_sequence<int, 64>{});
 }

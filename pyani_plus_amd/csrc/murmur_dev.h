@@ -99,6 +99,36 @@ __device__ __forceinline__ void murmur3_pre_last_mul(const uint64_t (&P)[N], uin
   V = h2;
 }
 
+// the same for a run-time k (uniform over the launch, at most 64); P holds eight first products, the unused ones 0
+__device__ __forceinline__ void murmur3_pre_last_mul_rt(const uint64_t (&P)[8], uint32_t k, uint64_t &U, uint64_t &V) {
+  uint64_t h1 = 42, h2 = 42;
+  const uint32_t nblocks = k >> 4, tail = k & 15u;
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i) {
+    if (i >= nblocks) break;
+    h1 ^= rotl64(P[2 * i], 31) * kC2;
+    h1 = rotl64(h1, 27) + h2;
+    h1 = times5_plus(h1, 0x52dce729ULL);
+    h2 ^= rotl64(P[2 * i + 1], 33) * kC1;
+    h2 = rotl64(h2, 31) + h1;
+    h2 = times5_plus(h2, 0x38495ab5ULL);
+  }
+  uint64_t t1 = 0, t2 = 0;
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i)
+    if (i == nblocks) { t1 = P[2 * i]; t2 = P[2 * i + 1]; }
+  if (tail > 8) h2 ^= rotl64(t2, 33) * kC1;
+  if (tail > 0) h1 ^= rotl64(t1, 31) * kC2;
+  h1 ^= (uint64_t)k;
+  h2 ^= (uint64_t)k;
+  h1 += h2;
+  h2 += h1;
+  h1 ^= h1 >> 33; h1 *= kF1; h1 ^= h1 >> 33;
+  h2 ^= h2 >> 33; h2 *= kF1; h2 ^= h2 >> 33;
+  U = h1;
+  V = h2;
+}
+
 // X.hi + Y.hi + 1 (mod 2^32) for X = U*kF2, Y = V*kF2, without forming X and Y (see above)
 __device__ __forceinline__ uint32_t last_mul_high_sum_plus1(uint64_t U, uint64_t V) {
   constexpr uint32_t c0 = (uint32_t)kF2, c1 = (uint32_t)(kF2 >> 32);
@@ -106,18 +136,59 @@ __device__ __forceinline__ uint32_t last_mul_high_sum_plus1(uint64_t U, uint64_t
   return (__umulhi(u0, c0) + __umulhi(v0, c0) + 1u) + ((u0 + v0) * c1 + (u1 + v1) * c0);
 }
 
+// The last step for a FracMinHash with threshold max_hash, in two parts: the screen, then -- for the windows it lets
+// through -- the last multiply and the fold.
+// Screen on the high words: hash = (X ^ X>>33) + (Y ^ Y>>33) has high word X.hi + Y.hi + carry, so it can be
+// <= max_hash only if X.hi + Y.hi is <= max_hash.hi or is 0xffffffff (the carry wraps it to 0) -- one unsigned compare
+// of X.hi + Y.hi + 1 against screen_hi = max_hash.hi + 1.  The 999 in 1000 windows that are dropped never form X and
+// Y: 2 mul_hi + 2 mul_lo + 4 adds + 1 compare instead of two 64-bit multiplies, an add and 2 compares.
+// take_all = (max_hash.hi == 0xffffffff), scaled = 1: no screen.  Both are per-thread constants of the caller.
+__device__ __forceinline__ bool passes_screen(uint64_t U, uint64_t V, bool take_all, uint32_t screen_hi) {
+  return take_all || last_mul_high_sum_plus1(U, V) <= screen_hi;
+}
+__device__ __forceinline__ uint64_t last_mul_and_fold(uint64_t U, uint64_t V) {
+  const uint64_t X = U * kF2, Y = V * kF2;
+  return (X ^ (X >> 33)) + (Y ^ (Y >> 33));
+}
+
 template <int K, int N>
 __device__ __forceinline__ uint64_t murmur3_from_products(const uint64_t (&P)[N]) {
   uint64_t U, V;
   murmur3_pre_last_mul<K, N>(P, U, V);
-  const uint64_t X = U * kF2, Y = V * kF2;
-  return (X ^ (X >> 33)) + (Y ^ (Y >> 33));
+  return last_mul_and_fold(U, V);
 }
 
 // the 4-base group `b8` (base j at bits 2j) as ASCII, keeping only its first `nv` bytes
 __device__ __forceinline__ uint32_t ascii_group(uint32_t b8, int nv) {
   const uint32_t a = ascii4(b8);
   return nv >= 4 ? a : (nv <= 0 ? 0u : (a & ((1u << (8 * nv)) - 1u)));
+}
+
+// ---- the first multiply of every murmur word, looked up -----------------------------
+// Word j of the k-mer (bases 8j .. 8j+7, the last one partial) is two 4-base groups (lo, hi), and
+//   word*c_j = (ascii(lo) + ascii(hi)*2^32)*c_j = s_lo[j][lo] + (s_hi[j][hi] << 32)   (mod 2^64)
+// with s_lo[j][b] = ascii(b)*c_j (64 bit) and s_hi[j][b] = low32(ascii(b)*c_j): two LDS reads and one add replace the
+// ASCII expansion (8 VALU) and a 64-bit multiply (3 quarter-rate VALU).
+// Fills the tables of a k-mer of k bases, thread `tid` of 256 one entry of each; k may be a compile-time or a
+// run-time value.  The caller puts a barrier between this and the first look-up.
+template <int W, class KInt>
+__device__ __forceinline__ void fill_first_products(uint64_t (&s_lo)[W][256], uint32_t (&s_hi)[W][256], uint32_t tid, KInt k_) {
+  const int k = (int)k_;
+  const int n_words = (int)(((uint32_t)k + 7u) >> 3);
+#pragma unroll
+  for (int j = 0; j < n_words; ++j) {
+    const uint64_t cj = (j & 1) ? kC2 : kC1;
+    s_lo[j][tid] = (uint64_t)ascii_group(tid, k - 8 * j) * cj;
+    s_hi[j][tid] = (uint32_t)((uint64_t)ascii_group(tid, k - 8 * j - 4) * cj);
+  }
+}
+
+// P[j] from the tables; src is the 32-bit word j/2 of the k-mer (base i at bits 2i), which holds word j's two groups
+template <int W>
+__device__ __forceinline__ uint64_t first_product(const uint64_t (&s_lo)[W][256], const uint32_t (&s_hi)[W][256], uint32_t j, uint32_t src) {
+  const uint32_t glo = (src >> (16u * (j & 1u))) & 0xffu, ghi = (src >> (16u * (j & 1u) + 8u)) & 0xffu;
+  const uint64_t lo = s_lo[j][glo];
+  return u64_of((uint32_t)lo, (uint32_t)(lo >> 32) + s_hi[j][ghi]);
 }
 
 }  // namespace pa_dev

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -278,15 +279,81 @@ inline int pa_scan_total_u32(pa_ctx *c, const uint32_t *d_in, uint32_t *d_out, u
 void pa_fragani_release(pa_ctx *c);
 
 // kmer_hash.hip
-int pa_launch_kmer_hash(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty, uint64_t n_blocks64,
-                        const uint32_t *d_genome_blk, uint32_t n_genomes, uint32_t k, uint64_t max_hash,
-                        uint64_t *d_cand_hash, uint32_t *d_cand_genome, uint64_t cap, uint64_t *d_count,
-                        const uint64_t *d_region_off = nullptr, uint32_t *d_cursor = nullptr,
-                        uint32_t *d_overflow = nullptr, uint64_t blk0 = 0, hipStream_t stream = nullptr);
-// The launch covers arena blocks [blk0, n_blocks64) on `stream` (default: the context's); blk0 is a multiple of 64.
-// d_dirty: one bit per block, set when the block needs its mask words (pa_build_dirty).
-// With d_region_off != nullptr the survivors of genome g go, unordered, to d_cand_hash[region_off[g] + i),
-// i < cursor[g] (zeroed by the caller); *d_overflow is set if a region was too small.
+// The arena as the hash kernels read it.  dirty: one bit per block, set when the block needs its mask words
+// (pa_build_dirty).
+struct ArenaView {
+  const uint32_t *packed = nullptr, *mask = nullptr;
+  const uint64_t *dirty = nullptr;
+  uint64_t n_blocks64 = 0;
+};
+// Where a surviving hash goes.  With region_off != nullptr the survivors of genome g go, unordered, to
+// cand_hash[region_off[g] + i), i < cursor[g] (zeroed by the caller), and *overflow is set if a region was too small;
+// otherwise (hash, genome) goes to slot atomicAdd(count) of cand_hash / cand_genome while that is below cap.
+struct CandSink {
+  uint64_t *cand_hash = nullptr;
+  uint32_t *cand_genome = nullptr;
+  uint64_t cap = 0;
+  uint64_t *count = nullptr;
+  const uint64_t *region_off = nullptr;
+  uint32_t *cursor = nullptr, *overflow = nullptr;
+  const uint32_t *genome_blk = nullptr;  // genome g is blocks [genome_blk[g], genome_blk[g + 1])
+  uint32_t n_genomes = 0;
+};
+// One launch: arena blocks [blk0, arena.n_blocks64) on `stream` (default: the context's); blk0 is a multiple of 64.
+struct KmerHashArgs {
+  ArenaView arena;
+  uint32_t k = 0;
+  uint64_t max_hash = 0;
+  CandSink sink;
+  uint64_t blk0 = 0;
+  hipStream_t stream = nullptr;
+};
+int pa_launch_kmer_hash(pa_ctx *c, const KmerHashArgs &a);
+
+// The host plan of a sketch call (pa_sketch, pa_sketch_streamed): what follows from the genome starts alone.
+struct SketchPlan {
+  std::vector<uint32_t> blk;         // genome g is arena blocks [blk[g], blk[g + 1])
+  std::vector<uint64_t> region_off;  // its candidate region is slots [region_off[g], region_off[g + 1])
+  uint64_t longest_region = 0;
+  double frac = 1.0;  // expected survivors: one window in 2^64/(max_hash+1)
+  uint64_t n_blocks = 0;
+};
+// Checks everything the entry points require of the arena's size, k and the genome starts (`who` begins the messages),
+// then fills the plan.  A region is the genome's expected survivors + 25 % + 128 slots.
+inline int pa_sketch_plan(const uint64_t *h_genome_start, uint32_t n_genomes, uint64_t arena_bases, uint32_t k, uint64_t max_hash,
+                          const char *who, SketchPlan *plan) {
+  PA_REQUIRE((arena_bases % PA_ALIGN_BASES) == 0, "%s: arena_bases %llu is not a multiple of %u", who,
+             (unsigned long long)arena_bases, PA_ALIGN_BASES);
+  PA_REQUIRE(k >= 1 && k <= PA_MAX_K, "%s: k=%u outside [1,%u]", who, k, PA_MAX_K);
+  PA_REQUIRE(h_genome_start[n_genomes] == arena_bases, "%s: genome_start[n] must equal arena_bases", who);
+  plan->n_blocks = arena_bases / PA_ALIGN_BASES;
+  plan->frac = (max_hash == UINT64_MAX) ? 1.0 : ((double)max_hash + 1.0) / 18446744073709551616.0;
+  plan->blk.assign((size_t)n_genomes + 1, 0);
+  plan->region_off.assign((size_t)n_genomes + 1, 0);
+  plan->longest_region = 0;
+  for (uint32_t g = 0; g <= n_genomes; ++g) {
+    const uint64_t s = h_genome_start[g];
+    PA_REQUIRE((s % PA_ALIGN_BASES) == 0 && (g == 0 || s >= h_genome_start[g - 1]) && s <= arena_bases,
+               "%s: genome_start[%u]=%llu must be an ascending multiple of %u inside the arena", who, g,
+               (unsigned long long)s, PA_ALIGN_BASES);
+    plan->blk[g] = (uint32_t)(s / PA_ALIGN_BASES);
+    if (g < n_genomes) {
+      const uint64_t room = (uint64_t)((double)(h_genome_start[g + 1] - s) * plan->frac * 1.25) + 128;
+      plan->longest_region = std::max(plan->longest_region, room);
+      plan->region_off[g + 1] = plan->region_off[g] + room;
+    }
+  }
+  PA_REQUIRE(plan->n_blocks < (1ULL << 32), "%s: arena too large", who);
+  return PA_OK;
+}
+// capi.hip.  Region mode begins: the plan's two tables go up to genome_blk and region_off (the caller waits on
+// c->stream while the plan is alive), cand_keys[0] holds all regions, the cursors and kRegionOverflow are zeroed.
+int pa_regions_begin(pa_ctx *c, const SketchPlan &plan);
+CandSink pa_region_sink(pa_ctx *c, uint32_t n_genomes);  // the sink over those buffers
+// pa_sketch behind its argument checks: the arena is on the device, the plan made
+int pa_sketch_resident(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty_in,
+                       const SketchPlan &plan, uint32_t k, uint64_t max_hash, uint64_t *d_hashes, uint64_t cap_hashes,
+                       uint64_t *d_off, uint64_t *h_total);
 
 // Dirty bitmap of an arena (sketch_stream.hip): bit b of word w <-> block 64*w + b holds an invalid position, or
 // the 32 positions before it do, or it is block 0.  ceil(n_blocks64 / 64) words.

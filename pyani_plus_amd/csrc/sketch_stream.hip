@@ -119,62 +119,38 @@ int pa_sketch_streamed(pa_ctx *c, const uint32_t *h_packed, const uint64_t *h_ru
                        uint32_t k, uint64_t max_hash, uint32_t *d_packed, uint32_t *d_mask, uint64_t *d_dirty,
                        uint64_t *d_hashes, uint64_t cap_hashes, uint64_t *d_off, uint64_t *h_total) {
   PA_REQUIRE(c && d_off && h_total && h_genome_start, "pa_sketch_streamed: null argument");
-  PA_REQUIRE((arena_bases % PA_ALIGN_BASES) == 0, "pa_sketch_streamed: arena_bases %llu is not a multiple of %u",
-             (unsigned long long)arena_bases, PA_ALIGN_BASES);
   PA_REQUIRE(arena_bases == 0 || (h_packed && d_packed && d_mask), "pa_sketch_streamed: null arena");
-  PA_REQUIRE(k >= 1 && k <= PA_MAX_K, "pa_sketch_streamed: k=%u outside [1,%u]", k, PA_MAX_K);
-  PA_REQUIRE(h_genome_start[n_genomes] == arena_bases, "pa_sketch_streamed: genome_start[n] must equal arena_bases");
+  SketchPlan plan;
+  PA_TRY(pa_sketch_plan(h_genome_start, n_genomes, arena_bases, k, max_hash, "pa_sketch_streamed", &plan));
   PA_HIP(hipSetDevice(c->device));
   *h_total = 0;
   PA_TRY(pa_mask_from_runs(c, h_run_start, h_run_len, n_runs, d_mask, arena_bases));
 
-  const uint64_t n_blocks = arena_bases / PA_ALIGN_BASES;
+  const uint64_t n_blocks = plan.n_blocks;
   if (!d_dirty) {
     PA_TRY(c->dirty.reserve(((n_blocks + 63) / 64 + 1) * 8));
     d_dirty = c->dirty.as<uint64_t>();
   }
   PA_TRY(pa_build_dirty(c, d_mask, n_blocks, d_dirty));
-  PA_REQUIRE(n_blocks < (1ULL << 32), "pa_sketch_streamed: arena too large");
-  const double frac = (max_hash == UINT64_MAX) ? 1.0 : ((double)max_hash + 1.0) / 18446744073709551616.0;
-  std::vector<uint64_t> region_off(n_genomes + 1, 0);
-  std::vector<uint32_t> blk(n_genomes + 1);
-  uint64_t longest_region = 0;
-  for (uint32_t g = 0; g <= n_genomes; ++g) {
-    const uint64_t s = h_genome_start[g];
-    PA_REQUIRE((s % PA_ALIGN_BASES) == 0 && (g == 0 || s >= h_genome_start[g - 1]) && s <= arena_bases,
-               "pa_sketch_streamed: genome_start[%u]=%llu must be an ascending multiple of %u inside the arena", g,
-               (unsigned long long)s, PA_ALIGN_BASES);
-    blk[g] = (uint32_t)(s / PA_ALIGN_BASES);
-    if (g < n_genomes) {
-      const uint64_t room = (uint64_t)((double)(h_genome_start[g + 1] - s) * frac * 1.25) + 128;
-      longest_region = std::max(longest_region, room);
-      region_off[g + 1] = region_off[g] + room;
-    }
-  }
-  const bool overlap = n_genomes > 0 && longest_region <= kLdsSortMax && arena_bases > 0;
+  const bool overlap = n_genomes > 0 && plan.longest_region <= kLdsSortMax && arena_bases > 0;
   if (!overlap) {  // long genomes / tiny scaled: plain upload, general sketch path
     PA_HIP(hipMemcpyAsync(d_packed, h_packed, arena_bases / 4, hipMemcpyHostToDevice, c->stream));
-    return pa_sketch(c, d_packed, d_mask, d_dirty, arena_bases, h_genome_start, n_genomes, k, max_hash, d_hashes, cap_hashes,
-                     d_off, h_total);
+    return pa_sketch_resident(c, d_packed, d_mask, d_dirty, plan, k, max_hash, d_hashes, cap_hashes, d_off, h_total);
   }
   if (!c->copy_stream) PA_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  PA_TRY(c->genome_blk.reserve((uint64_t)(n_genomes + 1) * sizeof(uint32_t)));
-  PA_TRY(c->region_off.reserve((uint64_t)(n_genomes + 1) * sizeof(uint64_t)));
-  PA_TRY(c->region_cursor.reserve((uint64_t)n_genomes * sizeof(uint32_t)));
-  PA_TRY(c->cand_keys[0].reserve(region_off[n_genomes] * sizeof(uint64_t)));
-  PA_HIP(hipMemcpyAsync(c->genome_blk.p, blk.data(), (uint64_t)(n_genomes + 1) * sizeof(uint32_t), hipMemcpyHostToDevice,
-                        c->stream));
-  PA_HIP(hipMemcpyAsync(c->region_off.p, region_off.data(), (uint64_t)(n_genomes + 1) * sizeof(uint64_t),
-                        hipMemcpyHostToDevice, c->stream));
-  uint32_t *d_overflow = c->slot(kRegionOverflow);
-  PA_HIP(hipMemsetAsync(c->region_cursor.p, 0, (uint64_t)n_genomes * sizeof(uint32_t), c->stream));
-  PA_HIP(hipMemsetAsync(d_overflow, 0, kRegionOverflow.bytes(), c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));  // blk / region_off are stack-owned; the copy stream starts after this
+  PA_TRY(pa_regions_begin(c, plan));
+  PA_HIP(hipStreamSynchronize(c->stream));  // the copy stream starts after this
 
   // 64 MB of packed bases (2.7e8 positions) per chunk: ~1.2 ms on the bus, ~0.7 ms of hashing
   uint64_t chunk_blocks = (64ull << 20) / 16;
   if (const char *v = PA_TOOL_ENV("PA_STREAM_CHUNK_BLOCKS"))  // tests: small chunks, so that windows cross chunk boundaries
     chunk_blocks = std::max<uint64_t>(64, (strtoull(v, nullptr, 10) + 63) / 64 * 64);
+  KmerHashArgs hash;  // one launch per chunk: blocks [blk0, n_blocks64) of the arena as far as it has arrived
+  hash.arena = {d_packed, d_mask, d_dirty, 0};
+  hash.k = k;
+  hash.max_hash = max_hash;
+  hash.sink = pa_region_sink(c, n_genomes);
+  hash.stream = c->stream;
   std::vector<hipEvent_t> arrived;
   int status = PA_OK;
   {
@@ -190,17 +166,16 @@ int pa_sketch_streamed(pa_ctx *c, const uint32_t *h_packed, const uint64_t *h_ru
         pa_set_error("pa_sketch_streamed: chunk upload failed");
         break;
       }
-      status = pa_launch_kmer_hash(c, d_packed, d_mask, d_dirty, b1, c->genome_blk.as<uint32_t>(), n_genomes, k, max_hash,
-                                   c->cand_keys[0].as<uint64_t>(), nullptr, 0, nullptr, c->region_off.as<uint64_t>(),
-                                   c->region_cursor.as<uint32_t>(), d_overflow, b0, c->stream);
+      hash.arena.n_blocks64 = b1;
+      hash.blk0 = b0;
+      status = pa_launch_kmer_hash(c, hash);
     }
   }
   bool overflow = false;
   if (status == PA_OK) {
     ProfScope prof(c, PA_PROF_SKETCH_SORT);
-    status = pa_sketch_from_regions(c, c->cand_keys[0].as<uint64_t>(), c->region_off.as<uint64_t>(),
-                                    c->region_cursor.as<uint32_t>(), d_overflow, n_genomes, (uint32_t)longest_region,
-                                    max_hash, d_hashes, cap_hashes, d_off, h_total, &overflow);
+    status = pa_sketch_from_regions(c, hash.sink.cand_hash, hash.sink.region_off, hash.sink.cursor, hash.sink.overflow, n_genomes,
+                                    (uint32_t)plan.longest_region, max_hash, d_hashes, cap_hashes, d_off, h_total, &overflow);
   } else {
     (void)hipStreamSynchronize(c->copy_stream);
     (void)hipStreamSynchronize(c->stream);
@@ -209,8 +184,7 @@ int pa_sketch_streamed(pa_ctx *c, const uint32_t *h_packed, const uint64_t *h_ru
   if (status != PA_OK) return status;
   if (!overflow) return PA_OK;
   // a region overflowed (repeats, low-complexity sequence): the arena is resident now, take the general path
-  return pa_sketch(c, d_packed, d_mask, d_dirty, arena_bases, h_genome_start, n_genomes, k, max_hash, d_hashes, cap_hashes,
-                   d_off, h_total);
+  return pa_sketch_resident(c, d_packed, d_mask, d_dirty, plan, k, max_hash, d_hashes, cap_hashes, d_off, h_total);
 }
 
 }  // extern "C"

@@ -386,6 +386,34 @@ def test_streamed_sketch_equals_resident_sketch(engine):
         assert engine.torch.equal(dev2.packed[: arena.packed.size], dev.packed)
 
 
+@pytest.mark.parametrize("k", [31, 51])
+def test_region_overflow_falls_back_resident_and_streamed(engine, k):
+    """A genome whose candidates overrun its region (400 copies of one surviving k-mer against a region of 143 slots at
+    k = 31, 153 at k = 51) sends pa_sketch and pa_sketch_streamed from the per-genome regions to the general path."""
+    from pyani_plus_amd.engine import pack_genomes
+
+    rng = np.random.default_rng(100 + k)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    thresh = oracle.max_hash(1000)
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    while True:  # a k-mer whose canonical hash passes scaled=1000
+        kmer = rng.choice(acgt, size=k).tobytes()
+        canon = min(kmer, kmer.translate(comp)[::-1])
+        if oracle.murmur3_h1(canon, 42) <= thresh:
+            break
+    repeat = kmer * 400
+    rand = rng.choice(acgt, size=20_000).tobytes()
+    want = [oracle.sketch_seq(repeat, k, 1000), oracle.sketch_seq(rand, k, 1000)]
+    assert want[0].size >= 1 and oracle.murmur3_h1(canon, 42) in want[0]
+    arena = pack_genomes([repeat, rand], fasta=False)
+    resident = engine.sketch(engine.upload(arena), k, 1000).to_host()
+    _dev, streamed = engine.sketch_streamed(engine.pin_arena(arena), k, 1000)
+    streamed = streamed.to_host()
+    for g in range(2):
+        assert np.array_equal(resident[g], want[g]) and np.array_equal(streamed[g], want[g]), (k, g)
+    assert resident[0].size >= 1
+
+
 @pytest.mark.parametrize("k", [31, 51, 64])
 def test_streamed_sketch_windows_across_chunk_boundaries(tools_engine, k, monkeypatch):
     """The hash kernel of chunk c looks back into chunk c - 1 (up to k - 1 positions, 63 for the long-k form): with
