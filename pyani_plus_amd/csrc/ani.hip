@@ -68,8 +68,6 @@ int pa_launch_ani(pa_ctx *c, const uint32_t *d_counts, const uint64_t *d_off, ui
   const uint64_t total = (uint64_t)nq * ns;
   if (total == 0) return PA_OK;
   ProfScope prof(c, PA_PROF_ANI);
-  hipLaunchKernelGGL(ani_kernel, dim3(ceil_div_u64((ns + 1u) / 2u, kThreads), nq < 65535u ? nq : 65535u), dim3(kThreads), 0, c->stream, d_counts,
-                     d_off, q0, nq, s0, ns, 1.0 / (double)k, d_identity, d_cov_query);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return PA_LAUNCH(c, ani_kernel, LaunchDim(ceil_div((ns + 1u) / 2u, kThreads), nq < 65535u ? nq : 65535u), kThreads, 0, d_counts, d_off, q0,
+                   nq, s0, ns, 1.0 / (double)k, d_identity, d_cov_query);
 }

@@ -225,18 +225,17 @@ int pa_sketch_bottom(pa_ctx *c, const uint32_t *d_packed, const uint32_t *d_mask
       if (st == PA_E_CAPACITY) cap = total;
     }
     if (st != PA_OK) return st;
-    PA_HIP(hipMemcpyAsync(h_off.data(), tmp_off.p, (uint64_t)(n_genomes + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    PA_HIP(hipStreamSynchronize(c->stream));
+    PA_TRY(pa_copy_to_host(c, h_off.data(), tmp_off.p, (uint64_t)(n_genomes + 1) * 8));
     bool short_sketch = false;
     for (uint32_t g = 0; g < n_genomes && !short_sketch; ++g) short_sketch = h_off[g + 1] - h_off[g] < m;
     if (!short_sketch || max_hash == ~0ULL) break;  // with the threshold at its maximum a short sketch is simply all there is
     frac *= 8.0;
   }
-  hipLaunchKernelGGL(truncated_sizes_kernel, dim3(ceil_div_u64(n_genomes, kThreads)), dim3(kThreads), 0, c->stream,
-                     tmp_off.as<uint64_t>(), n_genomes, (uint64_t)m, sizes.as<uint32_t>());
+  PA_TRY(PA_LAUNCH(c, truncated_sizes_kernel, ceil_div(n_genomes, kThreads), kThreads, 0, tmp_off.as<uint64_t>(), n_genomes, (uint64_t)m,
+                   sizes.as<uint32_t>()));
   PA_TRY(pa_exclusive_scan_u32(c, sizes.as<uint32_t>(), pos.as<uint32_t>(), n_genomes, c->slot<uint64_t>(kSketchTotal)));
-  hipLaunchKernelGGL(truncate_copy_kernel, dim3(n_genomes), dim3(kThreads), 0, c->stream, tmp_hashes.as<uint64_t>(),
-                     tmp_off.as<uint64_t>(), pos.as<uint32_t>(), n_genomes, (uint64_t)m, d_hashes, d_off);
+  PA_TRY(PA_LAUNCH(c, truncate_copy_kernel, n_genomes, kThreads, 0, tmp_hashes.as<uint64_t>(), tmp_off.as<uint64_t>(), pos.as<uint32_t>(),
+                   n_genomes, (uint64_t)m, d_hashes, d_off));
   return pa_read_back(c, c->slot<uint64_t>(kSketchTotal), h_total);
 }
 
@@ -252,8 +251,7 @@ int pa_pair_mash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_off, uin
              (unsigned long long)pairs);
   // lengths on the host: the longest staged list decides whether a tile of lists fits in LDS
   std::vector<uint64_t> h_off(n + 1);
-  PA_HIP(hipMemcpyAsync(h_off.data(), d_off, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));
+  PA_TRY(pa_copy_to_host(c, h_off.data(), d_off, (uint64_t)(n + 1) * 8));
   uint64_t longest = 0;
   for (uint32_t g = q0; g < q1; ++g) longest = std::max(longest, std::min<uint64_t>(m, h_off[g + 1] - h_off[g]));
   for (uint32_t g = s0; g < s1; ++g) longest = std::max(longest, std::min<uint64_t>(m, h_off[g + 1] - h_off[g]));
@@ -272,18 +270,12 @@ int pa_pair_mash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_off, uin
                (unsigned long long)tiles_q * tiles_s);
     const uint32_t threads = ((tq * ts + 63u) / 64u) * 64u;
     const uint32_t lds_bytes = (tq + ts) * stride * 4u;
-    PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mash_tile_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(mash_tile_kernel, dim3(tiles_q * tiles_s), dim3(threads), lds_bytes, c->stream,
-                       c->ids.as<uint32_t>(), d_off, q0, nq, s0, ns, m, tq, ts, stride, tiles_s, d_common, d_denom);
-    PA_HIP(hipGetLastError());
-    return PA_OK;
+    return PA_LAUNCH_RAISE_LDS(c, mash_tile_kernel, tiles_q * tiles_s, threads, lds_bytes, c->ids.as<uint32_t>(), d_off, q0, nq, s0, ns, m, tq,
+                               ts, stride, tiles_s, d_common, d_denom);
   }
   ProfScope prof(c, PA_PROF_PAIR_COUNT);
-  hipLaunchKernelGGL(mash_pair_kernel, dim3(ceil_div_u64(pairs, kWavesPerBlock)), dim3(kThreads), 0, c->stream, d_hashes,
-                     d_off, q0, q1 - q0, s0, s1 - s0, m, d_common, d_denom);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return PA_LAUNCH(c, mash_pair_kernel, ceil_div(pairs, kWavesPerBlock), kThreads, 0, d_hashes, d_off, q0, q1 - q0, s0, s1 - s0, m, d_common,
+                   d_denom);
 }
 
 int pa_ani_mash(pa_ctx *c, const uint32_t *d_common, const uint32_t *d_denom, uint64_t n_pairs, uint32_t k,
@@ -293,10 +285,7 @@ int pa_ani_mash(pa_ctx *c, const uint32_t *d_common, const uint32_t *d_denom, ui
   PA_REQUIRE(d_common && d_denom && d_ani, "pa_ani_mash: null buffer");
   PA_HIP(hipSetDevice(c->device));
   ProfScope prof(c, PA_PROF_ANI);
-  hipLaunchKernelGGL(mash_ani_kernel, dim3(ceil_div_u64(n_pairs, kThreads)), dim3(kThreads), 0, c->stream, d_common,
-                     d_denom, n_pairs, 1.0 / (double)k, d_ani);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return PA_LAUNCH(c, mash_ani_kernel, ceil_div(n_pairs, kThreads), kThreads, 0, d_common, d_denom, n_pairs, 1.0 / (double)k, d_ani);
 }
 
 }  // extern "C"

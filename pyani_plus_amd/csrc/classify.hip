@@ -157,10 +157,9 @@ extern "C" int pa_classify_edges(pa_ctx *c, const double *d_score, const double 
     uint32_t *d_counts = c->flags.as<uint32_t>();
     // the tiles below the diagonal are not evaluated: their counts are zero
     PA_HIP(hipMemsetAsync(d_counts, 0, n_counts * sizeof(uint32_t), c->stream));
-    const dim3 grid(nt, nt);
-    hipLaunchKernelGGL(cls_edges_kernel<false>, grid, dim3(kThreads), 0, c->stream, d_score, d_cov, n, nt, agg_score, agg_cov, cov_min,
-                       d_counts, 0ULL, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    PA_HIP(hipGetLastError());
+    const LaunchDim grid(nt, nt);
+    PA_TRY(PA_LAUNCH(c, cls_edges_kernel<false>, grid, kThreads, 0, d_score, d_cov, n, nt, agg_score, agg_cov, cov_min, d_counts, 0ULL, nullptr,
+                     nullptr, nullptr, nullptr, nullptr, nullptr));
     PA_TRY(pa_scan_total_u32(c, d_counts, d_counts, n_counts, c->slot<uint64_t>(kCompactTotal), &E));
     *n_edges = E;
     if (E > cap_edges) {
@@ -177,19 +176,15 @@ extern "C" int pa_classify_edges(pa_ctx *c, const double *d_score, const double 
       PA_TRY(c->cand_keys[b].reserve(E * sizeof(uint64_t)));
       PA_TRY(c->cand_vals[b].reserve(E * sizeof(uint32_t)));
     }
-    hipLaunchKernelGGL(cls_edges_kernel<true>, grid, dim3(kThreads), 0, c->stream, d_score, d_cov, n, nt, agg_score, agg_cov, cov_min,
-                       d_counts, E, c->cls_i.as<uint32_t>(), c->cls_j.as<uint32_t>(), c->cls_score.as<double>(), c->cls_cov.as<double>(),
-                       c->cand_keys[0].as<uint64_t>(), c->cand_vals[0].as<uint32_t>());
-    PA_HIP(hipGetLastError());
+    PA_TRY(PA_LAUNCH(c, cls_edges_kernel<true>, grid, kThreads, 0, d_score, d_cov, n, nt, agg_score, agg_cov, cov_min, d_counts, E,
+                     c->cls_i.as<uint32_t>(), c->cls_j.as<uint32_t>(), c->cls_score.as<double>(), c->cls_cov.as<double>(),
+                     c->cand_keys[0].as<uint64_t>(), c->cand_vals[0].as<uint32_t>()));
   }
   ProfScope prof(c, PA_PROF_CLS_SORT);
   uint64_t *keys[2] = {c->cand_keys[0].as<uint64_t>(), c->cand_keys[1].as<uint64_t>()};
   uint32_t *vals[2] = {c->cand_vals[0].as<uint32_t>(), c->cand_vals[1].as<uint32_t>()};
   int which = 0;
   PA_TRY(pa_radix_sort_pairs(c, keys, vals, E, 0, 64, false, &which));
-  hipLaunchKernelGGL(cls_gather_kernel, dim3(ceil_div_u64(E, kThreads)), dim3(kThreads), 0, c->stream, vals[which], E,
-                     c->cls_i.as<uint32_t>(), c->cls_j.as<uint32_t>(), c->cls_score.as<double>(), c->cls_cov.as<double>(), d_i, d_j,
-                     d_edge_score, d_edge_cov);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return PA_LAUNCH(c, cls_gather_kernel, ceil_div(E, kThreads), kThreads, 0, vals[which], E, c->cls_i.as<uint32_t>(), c->cls_j.as<uint32_t>(),
+                   c->cls_score.as<double>(), c->cls_cov.as<double>(), d_i, d_j, d_edge_score, d_edge_cov);
 }

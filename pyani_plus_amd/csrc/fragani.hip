@@ -316,22 +316,21 @@ int cut_frequent_postings(pa_ctx *c, FragWork &W, const uint32_t *d_heads, const
     PA_HIP(hipMemsetAsync(d_hist, 0, hist_words * 4, c->stream));
     // the runs numbered: flags in scratch_a, runs before each posting in scratch_b, the runs' first postings in idx_spare
     // (m + 1 words: every buffer here was reserved with room to spare)
-    const uint32_t gm0 = ceil_div_u64(m, kThreads);
-    hipLaunchKernelGGL(posting_run_flags_kernel, dim3(gm0), dim3(kThreads), 0, c->stream, d_heads, W.post_g.as<uint16_t>(), m, scratch_a);
+    const uint64_t gm0 = ceil_div(m, kThreads);
+    PA_TRY(PA_LAUNCH(c, posting_run_flags_kernel, gm0, kThreads, 0, d_heads, W.post_g.as<uint16_t>(), m, scratch_a));
     PA_TRY(pa_exclusive_scan_u32(c, scratch_a, scratch_b, m, nullptr));
-    hipLaunchKernelGGL(posting_run_starts_kernel, dim3(gm0), dim3(kThreads), 0, c->stream, scratch_a, scratch_b, m, d_idx_spare);
-    hipLaunchKernelGGL(posting_run_hist_kernel, dim3(gm0), dim3(kThreads), 0, c->stream, scratch_a, scratch_b, d_idx_spare,
-                       W.post_g.as<uint16_t>(), m, d_hist, d_dups, W.long_runs.as<uint2>(), kOverCap, d_over_n);
+    PA_TRY(PA_LAUNCH(c, posting_run_starts_kernel, gm0, kThreads, 0, scratch_a, scratch_b, m, d_idx_spare));
+    PA_TRY(PA_LAUNCH(c, posting_run_hist_kernel, gm0, kThreads, 0, scratch_a, scratch_b, d_idx_spare, W.post_g.as<uint16_t>(), m, d_hist, d_dups,
+                     W.long_runs.as<uint2>(), kOverCap, d_over_n));
     std::vector<uint32_t> h((size_t)hist_words);
-    PA_HIP(hipMemcpyAsync(h.data(), d_hist, hist_words * 4, hipMemcpyDeviceToHost, c->stream));
-    PA_HIP(hipStreamSynchronize(c->stream));
+    PA_TRY(pa_copy_to_host(c, h.data(), d_hist, hist_words * 4));
     const uint32_t n_over = h[hist_words - 1];
     PA_REQUIRE(n_over <= kOverCap, "pa_fragani: %u (minimizer, genome) pairs with %u or more occurrences", n_over, kFreqBins - 1);
     std::vector<uint2> h_over(n_over);
-    if (n_over) PA_HIP(hipMemcpy(h_over.data(), W.long_runs.p, (size_t)n_over * 8, hipMemcpyDeviceToHost));
+    if (n_over) PA_TRY(pa_copy_to_host(c, h_over.data(), W.long_runs.p, (size_t)n_over * 8));
     // minimizers per genome: its contigs' shares of the minimizer array
     std::vector<uint32_t> cmo(n_contigs + 1);
-    PA_HIP(hipMemcpy(cmo.data(), W.contig_mini_off.p, (size_t)(n_contigs + 1) * 4, hipMemcpyDeviceToHost));
+    PA_TRY(pa_copy_to_host(c, cmo.data(), W.contig_mini_off.p, (size_t)(n_contigs + 1) * 4));
     std::vector<uint64_t> n_min(n_genomes, 0);
     for (uint32_t ci = 0; ci < n_contigs; ++ci) n_min[h_contig_genome[ci]] += cmo[ci + 1] - cmo[ci];
     std::vector<std::vector<uint32_t>> long_runs(n_genomes);
@@ -362,19 +361,19 @@ int cut_frequent_postings(pa_ctx *c, FragWork &W, const uint32_t *d_heads, const
   PA_TRY(upload(c, W.run_hist, threshold));  // (the histograms are on the host by now)
   PA_TRY(W.post_cw2.reserve((uint64_t)m * 8));
   PA_TRY(W.post_g2.reserve((uint64_t)m * 2 + 16));
-  const uint32_t gm = ceil_div_u64(m, kThreads);
-  hipLaunchKernelGGL(posting_cut_flags_kernel, dim3(gm), dim3(kThreads), 0, c->stream, d_heads, d_ids_before, scratch_b, d_idx_spare,
-                     W.post_g.as<uint16_t>(), m, W.run_hist.as<uint32_t>(), scratch_a, W.hash_cut.as<uint32_t>());
-  hipLaunchKernelGGL(mark_cut_minimizers_kernel, dim3(gm), dim3(kThreads), 0, c->stream, d_heads, d_ids_before, d_sorted_idx, m,
-                     W.hash_cut.as<uint32_t>(), W.mini_id.as<uint32_t>());
+  const uint64_t gm = ceil_div(m, kThreads);
+  PA_TRY(PA_LAUNCH(c, posting_cut_flags_kernel, gm, kThreads, 0, d_heads, d_ids_before, scratch_b, d_idx_spare, W.post_g.as<uint16_t>(), m,
+                   W.run_hist.as<uint32_t>(), scratch_a, W.hash_cut.as<uint32_t>()));
+  PA_TRY(PA_LAUNCH(c, mark_cut_minimizers_kernel, gm, kThreads, 0, d_heads, d_ids_before, d_sorted_idx, m, W.hash_cut.as<uint32_t>(),
+                   W.mini_id.as<uint32_t>()));
   uint64_t kept64 = 0;
   PA_TRY(pa_scan_total_u32(c, scratch_a, scratch_b, m, W.slot<uint64_t>(kScanTotal), &kept64));
   const uint32_t kept = (uint32_t)kept64;
   if (kept != m) {
-    hipLaunchKernelGGL(posting_compact_kernel, dim3(gm), dim3(kThreads), 0, c->stream, scratch_a, scratch_b, W.post_cw.as<uint64_t>(),
-                       W.post_g.as<uint16_t>(), d_sorted_idx, m, W.post_cw2.as<uint64_t>(), W.post_g2.as<uint16_t>(), d_idx_spare);
-    hipLaunchKernelGGL(posting_starts_kernel, dim3(ceil_div_u64((uint64_t)n_ids + 1, kThreads)), dim3(kThreads), 0, c->stream,
-                       W.post_start.as<uint32_t>(), n_ids, scratch_b, m, kept);
+    PA_TRY(PA_LAUNCH(c, posting_compact_kernel, gm, kThreads, 0, scratch_a, scratch_b, W.post_cw.as<uint64_t>(), W.post_g.as<uint16_t>(),
+                     d_sorted_idx, m, W.post_cw2.as<uint64_t>(), W.post_g2.as<uint16_t>(), d_idx_spare));
+    PA_TRY(PA_LAUNCH(c, posting_starts_kernel, ceil_div((uint64_t)n_ids + 1, kThreads), kThreads, 0, W.post_start.as<uint32_t>(), n_ids, scratch_b,
+                     m, kept));
     std::swap(W.post_cw, W.post_cw2);
     std::swap(W.post_g, W.post_g2);
     // (the postings' minimizer indices -- what the path for more than 8 192 genomes reads -- go back where they are looked for)
@@ -386,12 +385,14 @@ int cut_frequent_postings(pa_ctx *c, FragWork &W, const uint32_t *d_heads, const
 template <int K>
 int run_minimizers(pa_ctx *c, FragWork &W, const uint32_t *d_packed, const uint32_t *d_mask, uint64_t arena_bases,
                    uint32_t n_contigs, int w, uint32_t *m_out, const std::function<void()> *meanwhile) {
-  const uint32_t blocks = ceil_div_u64(arena_bases, kOwn);
+  PA_REQUIRE(ceil_div(arena_bases, kOwn) < (1ULL << 32), "fragment ANI: an arena of %llu bases has too many tiles for the minimizer scan",
+             (unsigned long long)arena_bases);
+  const uint32_t blocks = (uint32_t)ceil_div(arena_bases, kOwn);
   PA_TRY(W.block_counts.reserve((uint64_t)blocks * 8));  // the look-back words of minimizer_kernel
   PA_TRY(W.scalars.reserve(kMiniScalars.bytes()));
   PA_TRY(W.block_offsets.reserve((uint64_t)blocks * 4 + 16));  // the contig of every tile's first position
-  hipLaunchKernelGGL(tile_contig_kernel, dim3(ceil_div_u64(blocks, kThreads)), dim3(kThreads), 0, c->stream, W.contig_start.as<uint64_t>(), n_contigs,
-                     blocks, W.block_offsets.as<uint32_t>());
+  PA_TRY(PA_LAUNCH(c, tile_contig_kernel, ceil_div(blocks, kThreads), kThreads, 0, W.contig_start.as<uint64_t>(), n_contigs, blocks,
+                   W.block_offsets.as<uint32_t>()));
   // expected density of winnowed minimizers is 2 / (w + 1); the arrays are sized a quarter above that and the run is
   // repeated with the exact size should a low-complexity data set need more
   uint64_t cap = (uint64_t)((double)arena_bases * 2.5 / (double)(w + 1)) + (1u << 20);
@@ -407,12 +408,10 @@ int run_minimizers(pa_ctx *c, FragWork &W, const uint32_t *d_packed, const uint3
     PA_TRY(W.mini_contig.reserve(cap * 4 + 16));
     PA_HIP(hipMemsetAsync(W.block_counts.p, 0, (uint64_t)blocks * 8, c->stream));
     PA_HIP(hipMemsetAsync(W.slot(kMiniScalars), 0, kMiniScalars.bytes(), c->stream));
-    hipLaunchKernelGGL((minimizer_kernel<K>), dim3(blocks), dim3(kMiniThreads), 0, c->stream,
-                       d_packed, d_mask, arena_bases, W.contig_start.as<uint64_t>(), W.contig_len.as<uint32_t>(), n_contigs, w,
-                       W.block_counts.as<unsigned long long>(), W.slot(kMiniScalars), (uint32_t)cap,
-                       W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(), W.mini_contig.as<uint32_t>(), blocks, W.ambiguous(d_packed), ticket_mode,
-                       W.block_offsets.as<uint32_t>());
-    PA_HIP(hipGetLastError());
+    PA_TRY(PA_LAUNCH(c, minimizer_kernel<K>, blocks, kMiniThreads, 0, d_packed, d_mask, arena_bases, W.contig_start.as<uint64_t>(),
+                     W.contig_len.as<uint32_t>(), n_contigs, w, W.block_counts.as<unsigned long long>(), W.slot(kMiniScalars), (uint32_t)cap,
+                     W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(), W.mini_contig.as<uint32_t>(), blocks, W.ambiguous(d_packed), ticket_mode,
+                     W.block_offsets.as<uint32_t>()));
     uint32_t h[kMiniResult.words];
     ReadBack rb(c);
     PA_TRY(rb.queue(W.slot(kMiniResult), h, kMiniResult.words));
@@ -442,20 +441,10 @@ int run_minimizers(pa_ctx *c, FragWork &W, const uint32_t *d_packed, const uint3
 
 int dispatch_minimizers(pa_ctx *c, FragWork &W, const uint32_t *d_packed, const uint32_t *d_mask, uint64_t arena_bases,
                         uint32_t n_contigs, uint32_t k, int w, uint32_t *m_out, const std::function<void()> *meanwhile = nullptr) {
-  switch (k) {
-    case 8: return run_minimizers<8>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile);
-    case 9: return run_minimizers<9>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile);
-    case 10: return run_minimizers<10>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile);
-    case 11: return run_minimizers<11>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile);
-    case 12: return run_minimizers<12>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile);
-    case 13: return run_minimizers<13>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile);
-    case 14: return run_minimizers<14>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile);
-    case 15: return run_minimizers<15>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile);
-    case 16: return run_minimizers<16>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile);
-    default:
-      pa_set_error("fragment ANI: k=%u outside [8,16] (fastANI itself stops at 16)", k);
-      return PA_E_INVALID;
-  }
+  int status = PA_E_INVALID;
+  if (!dispatch_value(k, value_list<8, 9>{}, [&](auto kk) { status = run_minimizers<kk()>(c, W, d_packed, d_mask, arena_bases, n_contigs, w, m_out, meanwhile); }))
+    pa_set_error("fragment ANI: k=%u outside [8,16] (fastANI itself stops at 16)", k);
+  return status;
 }
 
 int stage_contigs(pa_ctx *c, FragWork &W, const uint64_t *h_contig_start, const uint32_t *h_contig_len,
@@ -607,17 +596,16 @@ int build_minimizers(pa_ctx *c, FragWork &W, const FragCall &a, FragLayout &L, u
   uint32_t m = 0;
   PA_TRY(dispatch_minimizers(c, W, a.d_packed, a.d_mask, a.arena_bases, a.n_contigs, a.k, a.w, &m, &meanwhile));
   PA_TRY(W.contig_mini_off.reserve((uint64_t)(a.n_contigs + 2) * 4));
-  hipLaunchKernelGGL(contig_offsets_kernel, dim3(ceil_div_u64(a.n_contigs + 1, kThreads)), dim3(kThreads), 0, c->stream,
-                     W.mini_contig.as<uint32_t>(), m, a.n_contigs, W.contig_mini_off.as<uint32_t>());
+  PA_TRY(PA_LAUNCH(c, contig_offsets_kernel, ceil_div(a.n_contigs + 1, kThreads), kThreads, 0, W.mini_contig.as<uint32_t>(), m, a.n_contigs,
+                   W.contig_mini_off.as<uint32_t>()));
   std::vector<uint32_t> cbo(a.n_contigs + 1, 0);
   for (uint32_t ci = 0; ci < a.n_contigs; ++ci) cbo[ci + 1] = cbo[ci] + (a.h_contig_len[ci] >> kBucketShift) + 2;
   PA_REQUIRE((uint64_t)cbo[a.n_contigs] < (1ULL << 31), "pa_fragani: bucket index too large");
   PA_TRY(upload(c, W.contig_bucket_off, cbo));
   PA_HIP(hipStreamSynchronize(c->stream));
   PA_TRY(W.bucket_first.reserve((uint64_t)cbo[a.n_contigs] * 4 + 16));
-  hipLaunchKernelGGL(bucket_index_kernel, dim3(ceil_div_u64(cbo[a.n_contigs], kThreads)), dim3(kThreads), 0, c->stream,
-                     W.mini_wpos.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(),
-                     a.n_contigs, cbo[a.n_contigs], W.bucket_first.as<uint32_t>());
+  PA_TRY(PA_LAUNCH(c, bucket_index_kernel, ceil_div(cbo[a.n_contigs], kThreads), kThreads, 0, W.mini_wpos.as<uint32_t>(),
+                   W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(), a.n_contigs, cbo[a.n_contigs], W.bucket_first.as<uint32_t>()));
   *m_out = m;
   return PA_OK;
 }
@@ -635,8 +623,8 @@ int build_dictionary(pa_ctx *c, FragWork &W, const FragCall &a, uint32_t m, int 
     while (c_lo < a.n_contigs && a.h_contig_genome[c_lo] < a.ref0) ++c_lo;
     c_hi = c_lo;
     while (c_hi < a.n_contigs && a.h_contig_genome[c_hi] < a.ref1) ++c_hi;
-    PA_HIP(hipMemcpy(&m_lo, W.contig_mini_off.as<uint32_t>() + c_lo, 4, hipMemcpyDeviceToHost));
-    PA_HIP(hipMemcpy(&m_hi, W.contig_mini_off.as<uint32_t>() + c_hi, 4, hipMemcpyDeviceToHost));
+    PA_TRY(pa_copy_to_host(c, &m_lo, W.contig_mini_off.as<uint32_t>() + c_lo, 4));
+    PA_TRY(pa_copy_to_host(c, &m_hi, W.contig_mini_off.as<uint32_t>() + c_hi, 4));
   }
   const uint32_t md = m_hi - m_lo;  // minimizers in the dictionary
   const uint64_t md_room = std::max<uint32_t>(md, 1u);
@@ -656,12 +644,11 @@ int build_dictionary(pa_ctx *c, FragWork &W, const FragCall &a, uint32_t m, int 
   PA_HIP(hipMemsetAsync(W.prev_same.p, 0xff, (uint64_t)m * 4, c->stream));  // -1: no earlier occurrence
   uint32_t n_ids = 0;
   if (md) {
-    const uint32_t gm = ceil_div_u64(md, kThreads);
-    hipLaunchKernelGGL(mini_keys_kernel, dim3(gm), dim3(kThreads), 0, c->stream, W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
-                       m_lo, md, keys[0], vals[0]);
+    const uint64_t gm = ceil_div(md, kThreads);
+    PA_TRY(PA_LAUNCH(c, mini_keys_kernel, gm, kThreads, 0, W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(), m_lo, md, keys[0], vals[0]));
     PA_TRY(pa_radix_sort_pairs(c, keys, vals, md, 0, 32, false, &which));
     uint32_t *d_flags = W.flags.as<uint32_t>(), *d_pos = d_flags + md;
-    hipLaunchKernelGGL(key_heads_kernel, dim3(gm), dim3(kThreads), 0, c->stream, keys[which], md, d_flags);
+    PA_TRY(PA_LAUNCH(c, key_heads_kernel, gm, kThreads, 0, keys[which], md, d_flags));
     uint64_t n_ids64 = 0;
     PA_TRY(pa_scan_total_u32(c, d_flags, d_pos, md, W.slot<uint64_t>(kScanTotal), &n_ids64));
     n_ids = (uint32_t)n_ids64;
@@ -671,13 +658,11 @@ int build_dictionary(pa_ctx *c, FragWork &W, const FragCall &a, uint32_t m, int 
     // (the contig of every block of minimizers: the look-back words of minimizer_kernel are free again)
     const uint32_t n_blocks = (uint32_t)(((uint64_t)m + (1u << kContigBlockShift) - 1u) >> kContigBlockShift);
     PA_TRY(W.block_counts.reserve((uint64_t)n_blocks * 4 + 16));
-    hipLaunchKernelGGL(block_contig_kernel, dim3(ceil_div_u64(n_blocks, kThreads)), dim3(kThreads), 0, c->stream, W.mini_contig.as<uint32_t>(), m,
-                       W.block_counts.as<uint32_t>());
-    hipLaunchKernelGGL(postings_kernel, dim3(gm), dim3(kThreads), 0, c->stream, keys[which], vals[which], d_flags, d_pos, md,
-                       n_ids, W.mini_contig.as<uint32_t>(), W.mini_id.as<uint32_t>(), W.post_start.as<uint32_t>(),
-                       W.prev_same.as<int32_t>(), W.mini_wpos.as<uint32_t>(), W.contig_genome.as<uint32_t>(),
-                       W.post_cw.as<uint64_t>(), W.post_g.as<uint16_t>(), W.contig_mini_off.as<uint32_t>(), a.n_contigs,
-                       W.uniq_hash.as<uint32_t>(), W.block_counts.as<uint32_t>());
+    PA_TRY(PA_LAUNCH(c, block_contig_kernel, ceil_div(n_blocks, kThreads), kThreads, 0, W.mini_contig.as<uint32_t>(), m, W.block_counts.as<uint32_t>()));
+    PA_TRY(PA_LAUNCH(c, postings_kernel, gm, kThreads, 0, keys[which], vals[which], d_flags, d_pos, md, n_ids, W.mini_contig.as<uint32_t>(),
+                     W.mini_id.as<uint32_t>(), W.post_start.as<uint32_t>(), W.prev_same.as<int32_t>(), W.mini_wpos.as<uint32_t>(),
+                     W.contig_genome.as<uint32_t>(), W.post_cw.as<uint64_t>(), W.post_g.as<uint16_t>(), W.contig_mini_off.as<uint32_t>(), a.n_contigs,
+                     W.uniq_hash.as<uint32_t>(), W.block_counts.as<uint32_t>()));
     PA_TRY(cut_frequent_postings(c, W, d_flags, d_pos, vals[which], vals[1 - which], reinterpret_cast<uint32_t *>(keys[1 - which]), md, n_ids,
                                  a.h_contig_genome, a.n_contigs, a.n_genomes));
   } else {  // the reference genomes hold no minimizer: an empty dictionary
@@ -694,9 +679,8 @@ int build_dictionary(pa_ctx *c, FragWork &W, const FragCall &a, uint32_t m, int 
     W.index_lookup_bits = bits;
     PA_TRY(W.lookup_at.reserve((16ull << bits) + 16));
     PA_HIP(hipMemsetAsync(W.lookup_at.p, 0xff, 16ull << bits, c->stream));
-    if (n_ids)
-      hipLaunchKernelGGL(lookup_insert_kernel, dim3(ceil_div_u64(n_ids, kThreads)), dim3(kThreads), 0, c->stream, W.uniq_hash.as<uint32_t>(),
-                         W.post_start.as<uint32_t>(), W.hash_cut.as<uint32_t>(), n_ids, bits, W.lookup_at.as<uint4>());
+    PA_TRY(PA_LAUNCH(c, lookup_insert_kernel, ceil_div(n_ids, kThreads), kThreads, 0, W.uniq_hash.as<uint32_t>(), W.post_start.as<uint32_t>(),
+                     W.hash_cut.as<uint32_t>(), n_ids, bits, W.lookup_at.as<uint4>()));
   }
   *which_out = which;
   return PA_OK;
@@ -824,15 +808,15 @@ int stage_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragLayout &L, 
 int seed_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, FragBatch &B) {
   const uint32_t nf = B.nf;
   PA_TRY(W.frag_d.reserve((uint64_t)nf * 4));
-  hipLaunchKernelGGL(windows_without_selection_kernel, dim3(ceil_div_u64(nf, kThreads)), dim3(kThreads), 0, c->stream, a.d_packed, a.d_mask,
-                     a.arena_bases, W.contig_start.as<uint64_t>(), a.k, (uint32_t)a.w, W.frag_contig.as<uint32_t>(), W.frag_no.as<uint32_t>(),
-                     nf, a.frag_len, a.count_windows, W.frag_d.as<uint32_t>(), W.ambiguous(a.d_packed));
-  hipLaunchKernelGGL(query_sketch_kernel, dim3(ceil_div_u64(nf, kThreads / 64)), dim3(kThreads), 0, c->stream, W.frag_d.as<uint32_t>(),
-                     W.frag_contig.as<uint32_t>(), W.frag_no.as<uint32_t>(), nf, a.frag_len, a.count_windows, W.contig_mini_off.as<uint32_t>(),
-                     W.contig_bucket_off.as<uint32_t>(), W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
-                     W.mini_id.as<uint32_t>(), W.post_start.as<uint32_t>(), B.q_hash, B.q_pos, B.q_id, W.q_s.as<uint32_t>(),
-                     W.hit_count.as<uint32_t>(), W.slot(kSketchOverflow), W.slot(kMaxHits), W.q_cut.as<uint32_t>(),
-                     R.restricted ? W.lookup_at.as<uint4>() : nullptr, W.index_lookup_bits, W.q_tab.as<uint32_t>());
+  PA_TRY(PA_LAUNCH(c, windows_without_selection_kernel, ceil_div(nf, kThreads), kThreads, 0, a.d_packed, a.d_mask, a.arena_bases,
+                   W.contig_start.as<uint64_t>(), a.k, (uint32_t)a.w, W.frag_contig.as<uint32_t>(), W.frag_no.as<uint32_t>(), nf, a.frag_len,
+                   a.count_windows, W.frag_d.as<uint32_t>(), W.ambiguous(a.d_packed)));
+  PA_TRY(PA_LAUNCH(c, query_sketch_kernel, ceil_div(nf, kThreads / 64), kThreads, 0, W.frag_d.as<uint32_t>(), W.frag_contig.as<uint32_t>(),
+                   W.frag_no.as<uint32_t>(), nf, a.frag_len, a.count_windows, W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(),
+                   W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(), W.mini_id.as<uint32_t>(),
+                   W.post_start.as<uint32_t>(), B.q_hash, B.q_pos, B.q_id, W.q_s.as<uint32_t>(), W.hit_count.as<uint32_t>(),
+                   W.slot(kSketchOverflow), W.slot(kMaxHits), W.q_cut.as<uint32_t>(), R.restricted ? W.lookup_at.as<uint4>() : nullptr,
+                   W.index_lookup_bits, W.q_tab.as<uint32_t>()));
   PA_TRY(pa_exclusive_scan_u32(c, W.hit_count.as<uint32_t>(), W.hit_off.as<uint32_t>(), nf, W.slot<uint64_t>(kScanTotal)));
   uint32_t longest[kMaxHits.words];  // [0] most seed hits of one fragment, [1] the longest sketch
   ReadBack rb(c);
@@ -893,17 +877,15 @@ int bucket_pass(pa_ctx *c, FragWork &W, const FragCall &a, const FragBatch &B, S
   PA_HIP(hipMemsetAsync(d_seg_counters, 0, kSegCounters.bytes(), c->stream));
   PA_HIP(hipMemsetAsync(d_cursor64, 0, kSegCursor.bytes(), c->stream));
   if (P.stage_hits && !write_all)
-    hipLaunchKernelGGL(bucket_hits_staged_kernel, dim3(B.nf), dim3(kStageWaves * 64), P.stage_lds, c->stream, B.nf, B.q_pos, B.q_id,
-                       W.q_s.as<uint32_t>(), W.hit_off.as<uint32_t>(), W.post_g.as<uint16_t>(),
-                       W.post_cw.as<uint64_t>(), a.n_genomes, W.tab_min_hits.as<uint32_t>(), S.hk[0], W.seg_a0.as<uint32_t>(),
-                       W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), P.seg_cap, d_seg_counters, d_cursor64, a.ref0, a.ref1, P.stage_cap);
+    PA_TRY(PA_LAUNCH_RAISE_LDS(c, bucket_hits_staged_kernel, B.nf, kStageWaves * 64, P.stage_lds, B.nf, B.q_pos, B.q_id, W.q_s.as<uint32_t>(),
+                               W.hit_off.as<uint32_t>(), W.post_g.as<uint16_t>(), W.post_cw.as<uint64_t>(), a.n_genomes,
+                               W.tab_min_hits.as<uint32_t>(), S.hk[0], W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(),
+                               P.seg_cap, d_seg_counters, d_cursor64, a.ref0, a.ref1, P.stage_cap));
   else
-    hipLaunchKernelGGL(bucket_hits_kernel, dim3(ceil_div_u64(B.nf, kBucketWaves)), dim3(kBucketWaves * 64), P.lds_bytes,
-                       c->stream, B.nf, B.q_pos, B.q_id, W.q_s.as<uint32_t>(),
-                       W.hit_off.as<uint32_t>(), W.post_g.as<uint16_t>(), W.post_cw.as<uint64_t>(), a.n_genomes,
-                       W.tab_min_hits.as<uint32_t>(), S.hk[0], S.hv[0],
-                       W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), P.seg_cap, d_seg_counters,
-                       d_cursor64, a.ref0, a.ref1, write_all);
+    PA_TRY(PA_LAUNCH_RAISE_LDS(c, bucket_hits_kernel, ceil_div(B.nf, kBucketWaves), kBucketWaves * 64, P.lds_bytes, B.nf, B.q_pos, B.q_id,
+                               W.q_s.as<uint32_t>(), W.hit_off.as<uint32_t>(), W.post_g.as<uint16_t>(), W.post_cw.as<uint64_t>(), a.n_genomes,
+                               W.tab_min_hits.as<uint32_t>(), S.hk[0], S.hv[0], W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(),
+                               W.seg_f.as<uint32_t>(), P.seg_cap, d_seg_counters, d_cursor64, a.ref0, a.ref1, write_all));
   uint32_t hc32[kSegCounters.words];
   unsigned long long cursor64 = 0;
   ReadBack rb(c);
@@ -931,8 +913,6 @@ int list_segments_bucketed(pa_ctx *c, FragWork &W, const FragCall &a, const Frag
   PA_TRY(W.seg_nh.reserve((uint64_t)P.seg_cap * 4 + 16));
   PA_TRY(W.seg_f.reserve((uint64_t)P.seg_cap * 4 + 16));
   P.lds_bytes = (uint32_t)kBucketWaves * n_genomes * 4u;
-  PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bucket_hits_kernel),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_bytes));
   // one fragment per workgroup with the listed pairs' hits staged in LDS (whole-sector writes) when the two per-genome
   // arrays leave room for a staging area; the batch that is about to be ordered as a whole (write_all) keeps the
   // wave-per-fragment form, which writes every slot
@@ -941,9 +921,6 @@ int list_segments_bucketed(pa_ctx *c, FragWork &W, const FragCall &a, const Frag
   P.stage_cap = n_genomes * 8u + 8192u <= lds_room ? ((lds_room - n_genomes * 8u) / 8u) & ~63u : 0u;
   P.stage_lds = P.stage_cap * 8u + n_genomes * 8u;
   P.stage_hits = P.stage_cap >= 1024u;
-  if (P.stage_hits)
-    PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bucket_hits_staged_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.stage_lds));
   PA_TRY(bucket_pass(c, W, a, B, S, P, false));
   S.presorted = false;
   uint32_t frag_sort_max = kFragSortMax;  // tests: PA_FRAGANI_SORT_MAX=600 sends a 60-copy repeat family down this path
@@ -961,16 +938,14 @@ int list_segments_bucketed(pa_ctx *c, FragWork &W, const FragCall &a, const Frag
     PA_TRY(W.seg_list.reserve((uint64_t)n_big * 8 + 16));
     uint32_t *big_a0 = W.seg_list.as<uint32_t>(), *big_nh = big_a0 + n_big;
     PA_HIP(hipMemsetAsync(W.slot(kBigCursor), 0, kBigCursor.bytes(), c->stream));
-    hipLaunchKernelGGL(big_segments_kernel, dim3(ceil_div_u64(S.n_large, kThreads)), dim3(kThreads), 0, c->stream,
-                       W.seg_a0.as<uint32_t>() + S.large_at, W.seg_nh.as<uint32_t>() + S.large_at, S.n_large, big_a0,
-                       big_nh, W.slot(kBigCursor));
+    PA_TRY(PA_LAUNCH(c, big_segments_kernel, ceil_div(S.n_large, kThreads), kThreads, 0, W.seg_a0.as<uint32_t>() + S.large_at,
+                     W.seg_nh.as<uint32_t>() + S.large_at, S.n_large, big_a0, big_nh, W.slot(kBigCursor)));
     uint32_t np2_max = 2;
     while (np2_max < P.max_big) np2_max <<= 1;
     const uint32_t sort_lds = np2_max * 12u;
-    PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(frag_sort_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
-    hipLaunchKernelGGL(frag_sort_kernel, dim3(n_big), dim3(kFragSortThreads), sort_lds, c->stream, S.hk[0], S.hv[0],
-                       big_a0, big_nh, np2_max, 64u - kHitRankShift + 11u);  // (contig, window id) to the top, the rank below
+    // (contig, window id) to the top, the rank below
+    PA_TRY(PA_LAUNCH_RAISE_LDS(c, frag_sort_kernel, n_big, kFragSortThreads, sort_lds, S.hk[0], S.hv[0], big_a0, big_nh, np2_max,
+                               64u - kHitRankShift + 11u));
   }
   return PA_OK;
 }
@@ -979,65 +954,45 @@ int list_segments_bucketed(pa_ctx *c, FragWork &W, const FragCall &a, const Frag
 int list_segments_sorted(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, const FragBatch &B, SegLists &S) {
   PA_TRY(begin_hits(W, B, S));
   const uint64_t n_hits = B.n_hits;
-  hipLaunchKernelGGL(fill_hits_kernel, dim3(ceil_div_u64(B.nf, kThreads / 64)), dim3(kThreads), 0, c->stream, B.nf, B.q_pos,
-                     B.q_id, W.q_s.as<uint32_t>(), W.hit_off.as<uint32_t>(),
-                     W.post_start.as<uint32_t>(), W.vals[R.which].as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
-                     W.mini_contig.as<uint32_t>(), S.hk[0], S.hv[0]);
+  PA_TRY(PA_LAUNCH(c, fill_hits_kernel, ceil_div(B.nf, kThreads / 64), kThreads, 0, B.nf, B.q_pos, B.q_id, W.q_s.as<uint32_t>(),
+                   W.hit_off.as<uint32_t>(), W.post_start.as<uint32_t>(), W.vals[R.which].as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
+                   W.mini_contig.as<uint32_t>(), S.hk[0], S.hv[0]));
   if (B.max_hits <= kFragSortMax) {  // every fragment's hits fit one LDS sort
     uint32_t np2_max = 2;
     while (np2_max < B.max_hits) np2_max <<= 1;
     const uint32_t lds_bytes = np2_max * 12u;
-    PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(frag_sort_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(frag_sort_kernel, dim3(B.nf), dim3(kFragSortThreads), lds_bytes, c->stream, S.hk[0], S.hv[0],
-                       W.hit_off.as<uint32_t>(), W.hit_count.as<uint32_t>(), np2_max, 0u);
+    PA_TRY(PA_LAUNCH_RAISE_LDS(c, frag_sort_kernel, B.nf, kFragSortThreads, lds_bytes, S.hk[0], S.hv[0], W.hit_off.as<uint32_t>(),
+                               W.hit_count.as<uint32_t>(), np2_max, 0u));
   } else {
     PA_TRY(sort_all_hits(c, W, B, S));
   }
   PA_TRY(W.flags.reserve(n_hits * 8 + 64));
   uint32_t *hf = W.flags.as<uint32_t>(), *hp = hf + n_hits;
-  const uint32_t gh = ceil_div_u64(n_hits, kThreads);
-  hipLaunchKernelGGL(segment_heads_kernel, dim3(gh), dim3(kThreads), 0, c->stream, S.hk[S.hw], (uint32_t)n_hits,
-                     W.contig_genome.as<uint32_t>(), hf);
+  const uint64_t gh = ceil_div(n_hits, kThreads);
+  PA_TRY(PA_LAUNCH(c, segment_heads_kernel, gh, kThreads, 0, S.hk[S.hw], (uint32_t)n_hits, W.contig_genome.as<uint32_t>(), hf));
   uint64_t total = 0;
   PA_TRY(pa_scan_total_u32(c, hf, hp, n_hits, W.slot<uint64_t>(kScanTotal), &total));
   const uint32_t n_segs = (uint32_t)total;
   PA_TRY(W.seg_start.reserve((uint64_t)(n_segs + 2) * 4));
-  hipLaunchKernelGGL(segment_starts_kernel, dim3(gh), dim3(kThreads), 0, c->stream, hf, hp, (uint32_t)n_hits,
-                     W.seg_start.as<uint32_t>());
+  PA_TRY(PA_LAUNCH(c, segment_starts_kernel, gh, kThreads, 0, hf, hp, (uint32_t)n_hits, W.seg_start.as<uint32_t>()));
   // most segments are chance hits of unrelated genomes (fewer hits than any L1 run needs): drop them
   // here, one thread each, instead of spending a workgroup launch on each in the mapping kernel
-  const uint32_t gs = ceil_div_u64(n_segs, kThreads);
-  hipLaunchKernelGGL(segment_keep_kernel, dim3(gs), dim3(kThreads), 0, c->stream, S.hk[S.hw],
-                     W.seg_start.as<uint32_t>(), n_segs, W.q_s.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(),
-                     W.contig_genome.as<uint32_t>(), a.ref0, a.ref1, hf);
+  const uint64_t gs = ceil_div(n_segs, kThreads);
+  PA_TRY(PA_LAUNCH(c, segment_keep_kernel, gs, kThreads, 0, S.hk[S.hw], W.seg_start.as<uint32_t>(), n_segs, W.q_s.as<uint32_t>(),
+                   W.tab_min_hits.as<uint32_t>(), W.contig_genome.as<uint32_t>(), a.ref0, a.ref1, hf));
   PA_TRY(pa_scan_total_u32(c, hf, hp, n_segs, W.slot<uint64_t>(kScanTotal), &total));
   S.n_keep = (uint32_t)total;
   PA_TRY(W.seg_list.reserve((uint64_t)(S.n_keep + 1) * 4));
   PA_TRY(W.seg_a0.reserve((uint64_t)S.n_keep * 4 + 16));
   PA_TRY(W.seg_nh.reserve((uint64_t)S.n_keep * 4 + 16));
-  hipLaunchKernelGGL(segment_list_kernel, dim3(gs), dim3(kThreads), 0, c->stream, hf, hp, n_segs,
-                     W.seg_list.as<uint32_t>());
-  if (S.n_keep)
-    hipLaunchKernelGGL(segments_from_list_kernel, dim3(ceil_div_u64(S.n_keep, kThreads)), dim3(kThreads), 0, c->stream,
-                       W.seg_start.as<uint32_t>(), W.seg_list.as<uint32_t>(), S.n_keep, W.seg_a0.as<uint32_t>(),
-                       W.seg_nh.as<uint32_t>());
-  return PA_OK;
+  PA_TRY(PA_LAUNCH(c, segment_list_kernel, gs, kThreads, 0, hf, hp, n_segs, W.seg_list.as<uint32_t>()));
+  return PA_LAUNCH(c, segments_from_list_kernel, ceil_div(S.n_keep, kThreads), kThreads, 0, W.seg_start.as<uint32_t>(), W.seg_list.as<uint32_t>(),
+                   S.n_keep, W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>());
 }
 
 // ---- 4. (continued) mapping
 // One list of segments through segment_records_kernel and the general mapping kernel.  kAll: every segment's hits fit the
 // smaller LDS footprint.
-#define PA_MAP_CASE(CAP)                                                                                                  \
-  case CAP:                                                                                                               \
-    hipLaunchKernelGGL((map_segments_kernel<CAP, kAll>), dim3(count), dim3(64), eval_lds_bytes(B.s_cap, hit_cap, CAP) + PA_MAP_LDS_PAD, c->stream,  \
-                       S.hk[S.hw], S.hv[S.hw], W.seg_rec.as<uint4>(), count, S.presorted, B.q_hash, W.q_tab.as<uint32_t>(), \
-                       W.frag_genome_local.as<uint32_t>(), a.frag_len, a.count_windows,                                    \
-                       W.tab_min_shared.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(),                                  \
-                       W.contig_bucket_off.as<uint32_t>(), W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(),      \
-                       W.mini_wpos.as<uint32_t>(), W.prev_same.as<int32_t>(), W.contig_bin_off.as<uint32_t>(), R.range_bins, \
-                       B.table, W.run_g.as<uint32_t>(), B.s_cap, hit_cap PA_MAP_CUT_ARG);                                  \
-    break;
 template <bool kAll>
 int launch_map(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, const FragBatch &B, const SegLists &S,
                const uint32_t *list_a0, const uint32_t *list_nh, const uint32_t *list_f, uint32_t count, uint32_t hit_cap) {
@@ -1047,17 +1002,22 @@ int launch_map(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, cons
   const uint32_t map_cut = cut_env ? (uint32_t)atoi(cut_env) : 0xffffffffu;
 #endif
   PA_TRY(W.seg_rec.reserve((uint64_t)count * 48));
-  hipLaunchKernelGGL(segment_records_kernel, dim3(ceil_div_u64(count, kThreads)), dim3(kThreads), 0, c->stream, S.hk[S.hw],
-                     list_a0, list_nh, list_f, count, W.q_s.as<uint32_t>(), W.q_cut.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(),
-                     W.tab_min_shared.as<uint32_t>(), W.contig_genome.as<uint32_t>(), W.genome_first_contig.as<uint32_t>(),
-                     W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(), W.frag_genome_local.as<uint32_t>(), W.seg_rec.as<uint4>());
-  switch (R.ref_cap) {
-    PA_MAP_CASE(256) PA_MAP_CASE(320) PA_MAP_CASE(384) PA_MAP_CASE(448)
-    default: PA_MAP_CASE(512)
-  }
-  return PA_OK;
+  PA_TRY(PA_LAUNCH(c, segment_records_kernel, ceil_div(count, kThreads), kThreads, 0, S.hk[S.hw], list_a0, list_nh, list_f, count,
+                   W.q_s.as<uint32_t>(), W.q_cut.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(), W.tab_min_shared.as<uint32_t>(),
+                   W.contig_genome.as<uint32_t>(), W.genome_first_contig.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(),
+                   W.contig_bucket_off.as<uint32_t>(), W.frag_genome_local.as<uint32_t>(), W.seg_rec.as<uint4>()));
+  int status = PA_OK;
+  auto launch = [&](auto cap) {
+    status = PA_LAUNCH(c, (map_segments_kernel<cap(), kAll>), count, 64, eval_lds_bytes(B.s_cap, hit_cap, cap()) + PA_MAP_LDS_PAD, S.hk[S.hw],
+                       S.hv[S.hw], W.seg_rec.as<uint4>(), count, S.presorted, B.q_hash, W.q_tab.as<uint32_t>(),
+                       W.frag_genome_local.as<uint32_t>(), a.frag_len, a.count_windows, W.tab_min_shared.as<uint32_t>(),
+                       W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(), W.bucket_first.as<uint32_t>(),
+                       W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(), W.prev_same.as<int32_t>(), W.contig_bin_off.as<uint32_t>(),
+                       R.range_bins, B.table, W.run_g.as<uint32_t>(), B.s_cap, hit_cap PA_MAP_CUT_ARG);
+  };
+  if (!dispatch_value(R.ref_cap, value_list<256, 5, 64>{}, launch)) launch(std::integral_constant<int, 512>{});  // the longest stretch
+  return status;
 }
-#undef PA_MAP_CASE
 
 // The bucketed lists' short segments: the tiny-segment filter, then those of at most kSparseHits hits through
 // map_sparse_kernel and the rest -- and what the sparse kernel hands on -- through the general kernel
@@ -1074,10 +1034,10 @@ int map_short_segments(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun 
   if (const char *v = PA_TOOL_ENV("PA_FRAGANI_SPARSE")) sparse_max = (atoi(v) && !S.presorted) ? kSparseHits : 0u;
   unsigned long long *d_pre_cursor = W.slot<unsigned long long>(kPreCursor);
   PA_HIP(hipMemsetAsync(d_pre_cursor, 0, kPreCursor.bytes(), c->stream));
-  hipLaunchKernelGGL(prefilter_segments_kernel, dim3(ceil_div_u64(n_keep, kThreads)), dim3(kThreads), 0, c->stream,
-                     S.hk[S.hw], W.seg_a0.as<uint32_t>(), W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), n_keep,
-                     W.q_s.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(), W.q_cut.as<uint32_t>(), a.frag_len, W.seg2_a0.as<uint32_t>(),
-                     W.seg2_nh.as<uint32_t>(), W.seg2_f.as<uint32_t>(), d_pre_cursor, sparse_max);
+  PA_TRY(PA_LAUNCH(c, prefilter_segments_kernel, ceil_div(n_keep, kThreads), kThreads, 0, S.hk[S.hw], W.seg_a0.as<uint32_t>(),
+                   W.seg_nh.as<uint32_t>(), W.seg_f.as<uint32_t>(), n_keep, W.q_s.as<uint32_t>(), W.tab_min_hits.as<uint32_t>(),
+                   W.q_cut.as<uint32_t>(), a.frag_len, W.seg2_a0.as<uint32_t>(), W.seg2_nh.as<uint32_t>(), W.seg2_f.as<uint32_t>(), d_pre_cursor,
+                   sparse_max));
   unsigned long long pre_cursor = 0;
   PA_TRY(pa_read_back(c, d_pre_cursor, &pre_cursor));
   const uint32_t n_small = (uint32_t)pre_cursor, n_sparse = (uint32_t)(pre_cursor >> 32);
@@ -1092,17 +1052,18 @@ int map_short_segments(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun 
   uint32_t *over_a0 = W.seg_over.as<uint32_t>(), *over_nh = over_a0 + n_sparse, *over_f = over_nh + n_sparse;
   uint32_t *d_over_n = W.slot(kSparseOver);
   PA_HIP(hipMemsetAsync(d_over_n, 0, kSparseOver.bytes(), c->stream));
-  hipLaunchKernelGGL(map_sparse_kernel, dim3(n_sparse), dim3(64), 0, c->stream, S.hk[S.hw], W.seg2_a0.as<uint32_t>() + at,
-                     W.seg2_nh.as<uint32_t>() + at, W.seg2_f.as<uint32_t>() + at, n_sparse, W.q_s.as<uint32_t>(), B.q_hash,
-                     W.frag_genome_local.as<uint32_t>(), a.frag_len, a.count_windows, W.tab_min_hits.as<uint32_t>(),
-                     W.tab_min_shared.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(), W.contig_bucket_off.as<uint32_t>(),
-                     W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
-                     W.prev_same.as<int32_t>(), W.contig_bin_off.as<uint32_t>(), R.range_bins, B.table, over_a0, over_nh, over_f,
-                     d_over_n
 #ifdef PA_MAP_STATS
-                     , W.run_g.as<uint32_t>()
+#define PA_SPARSE_STATS_ARG , W.run_g.as<uint32_t>()
+#else
+#define PA_SPARSE_STATS_ARG
 #endif
-  );
+  PA_TRY(PA_LAUNCH(c, map_sparse_kernel, n_sparse, 64, 0, S.hk[S.hw], W.seg2_a0.as<uint32_t>() + at, W.seg2_nh.as<uint32_t>() + at,
+                   W.seg2_f.as<uint32_t>() + at, n_sparse, W.q_s.as<uint32_t>(), B.q_hash, W.frag_genome_local.as<uint32_t>(), a.frag_len,
+                   a.count_windows, W.tab_min_hits.as<uint32_t>(), W.tab_min_shared.as<uint32_t>(), W.contig_mini_off.as<uint32_t>(),
+                   W.contig_bucket_off.as<uint32_t>(), W.bucket_first.as<uint32_t>(), W.mini_hash.as<uint32_t>(), W.mini_wpos.as<uint32_t>(),
+                   W.prev_same.as<int32_t>(), W.contig_bin_off.as<uint32_t>(), R.range_bins, B.table, over_a0, over_nh, over_f,
+                   d_over_n PA_SPARSE_STATS_ARG));
+#undef PA_SPARSE_STATS_ARG
   uint32_t n_over = 0;
   PA_TRY(pa_read_back(c, d_over_n, &n_over));
   if (R.trace) fprintf(stderr, "pa_fragani: %u segments of at most %u hits in the sparse kernel, %u of them handed on\n", n_sparse, kSparseHits, n_over);
@@ -1123,9 +1084,9 @@ int map_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, const
 
 #ifdef PA_MAP_STATS
 // the event counters of the two mapping kernels (PA_FRAGANI_TRACE)
-int print_map_stats(const FragWork &W) {
+int print_map_stats(pa_ctx *c, const FragWork &W) {
   uint32_t st[64];
-  PA_HIP(hipMemcpy(st, W.run_g.p, 256, hipMemcpyDeviceToHost));
+  PA_TRY(pa_copy_to_host(c, st, W.run_g.p, 256));
   fprintf(stderr, "pa_fragani: map stats: %u segments at L1 with %u hits, %u candidates, %u groups, %u begins past the bound, "
                   "%u rounds, %u stretch entries, %u windows evaluated, %u fine passes, %u cooperative, %u begins in rounds, "
                   "%u begins finished, %u rounds without items, %u second passes, %u windows with an exact value, %u of them at or above the bar, "
@@ -1145,11 +1106,8 @@ int print_map_stats(const FragWork &W) {
 int reduce_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragRun &R, const FragBatch &B) {
   PA_TRY(W.matched.reserve((uint64_t)B.nq * a.n_genomes * 4));
   PA_TRY(W.ident_sum.reserve((uint64_t)B.nq * a.n_genomes * 8));
-  hipLaunchKernelGGL(reduce_pairs_kernel, dim3(B.nq * a.n_genomes), dim3(64), 0, c->stream,
-                     B.table, R.range_bins, W.genome_bin_off.as<uint32_t>(), a.n_genomes,
-                     W.ident_tab.as<float>(), W.matched.as<uint32_t>(), W.ident_sum.as<double>());
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return PA_LAUNCH(c, reduce_pairs_kernel, B.nq * a.n_genomes, 64, 0, B.table, R.range_bins, W.genome_bin_off.as<uint32_t>(), a.n_genomes,
+                   W.ident_tab.as<float>(), W.matched.as<uint32_t>(), W.ident_sum.as<double>());
 }
 // the batch's rows of the two result matrices to the host: whole, or the columns of the reference range only
 int copy_out_batch(pa_ctx *c, FragWork &W, const FragCall &a, const FragBatch &B) {
@@ -1228,7 +1186,7 @@ int fragani_ex_impl(pa_ctx *c, FragCall &a) {
       prof.emplace(c, PA_PROF_FRAG_MAP);
       PA_TRY(map_batch(c, W, a, R, B, S));
 #ifdef PA_MAP_STATS
-      if (R.trace) PA_TRY(print_map_stats(W));
+      if (R.trace) PA_TRY(print_map_stats(c, W));
 #endif
     }
     PA_TRY(reduce_batch(c, W, a, R, B));
@@ -1237,7 +1195,7 @@ int fragani_ex_impl(pa_ctx *c, FragCall &a) {
     g0 = B.g1;
   }
   uint32_t h_over[2] = {0, 0};
-  PA_HIP(hipMemcpy(h_over, W.slot(kSketchOverflow), kSketchOverflow.bytes(), hipMemcpyDeviceToHost));
+  PA_TRY(pa_copy_to_host(c, h_over, W.slot(kSketchOverflow), kSketchOverflow.bytes()));
   if (h_over[0]) {
     pa_set_error("pa_fragani: %u fragment sketches exceeded %d minimizers (fragLen too long for this window); "
                  "those sketches were truncated", h_over[0], kQMax);

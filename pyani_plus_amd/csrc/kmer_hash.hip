@@ -473,41 +473,29 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_long_kernel(
 // ---- launch ----------------------------------------------------------------------------------------------------------
 // one thread per arena block from a.blk0 on: the two streaming kernels
 template <class Kernel>
-int launch_blocks(pa_ctx *c, Kernel kernel, const KmerHashArgs &a) {
+int launch_blocks(pa_ctx *c, const char *name, Kernel kernel, const KmerHashArgs &a) {
   const ArenaView &v = a.arena;
   const CandSink &s = a.sink;
-  const uint32_t grid = ceil_div_u64(v.n_blocks64 - a.blk0, kThreads);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, a.stream ? a.stream : c->stream,
-                     reinterpret_cast<const uint4 *>(v.packed), reinterpret_cast<const uint2 *>(v.mask), v.dirty,
-                     (uint32_t)v.n_blocks64, s.genome_blk, s.n_genomes, a.max_hash, s.cand_hash, s.cand_genome, s.cap,
-                     reinterpret_cast<unsigned long long *>(s.count), s.region_off, s.cursor, s.overflow, (uint32_t)a.blk0);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return pa_launch(c, name, kernel, false, ceil_div(v.n_blocks64 - a.blk0, kThreads), kThreads, 0, a.stream,
+                   reinterpret_cast<const uint4 *>(v.packed), reinterpret_cast<const uint2 *>(v.mask), v.dirty,
+                   (uint32_t)v.n_blocks64, s.genome_blk, s.n_genomes, a.max_hash, s.cand_hash, s.cand_genome, s.cap,
+                   reinterpret_cast<unsigned long long *>(s.count), s.region_off, s.cursor, s.overflow, (uint32_t)a.blk0);
 }
 
 template <int K>
 int launch_k(pa_ctx *c, const KmerHashArgs &a) {
   if constexpr (K > 32) {
-    return launch_blocks(c, kmer_hash_wide_kernel<K>, a);
+    return launch_blocks(c, "kmer_hash_wide_kernel", kmer_hash_wide_kernel<K>, a);
   } else {
     if constexpr (K == 31) {  // the ablation build exists for the benchmarked k only
       static const bool arithmetic = [] {
         const char *v = PA_TOOL_ENV("PA_KMER_VARIANT");
         return v && v[0] == '0';
       }();
-      if (arithmetic) return launch_blocks(c, kmer_hash_kernel<K, false>, a);
+      if (arithmetic) return launch_blocks(c, "kmer_hash_kernel<31, false>", kmer_hash_kernel<K, false>, a);
     }
-    return launch_blocks(c, kmer_hash_kernel<K, true>, a);
+    return launch_blocks(c, "kmer_hash_kernel", kmer_hash_kernel<K, true>, a);
   }
-}
-
-// the kernel of a.k, which is one of KMinus1 + 1 ..., or an error
-template <int... KMinus1>
-int launch_for_k(pa_ctx *c, const KmerHashArgs &a, std::integer_sequence<int, KMinus1...>) {
-  int status = PA_E_INVALID;
-  const bool found = ((a.k == (uint32_t)(KMinus1 + 1) && ((status = launch_k<KMinus1 + 1>(c, a)), true)) || ...);
-  if (!found) pa_set_error("k=%u outside [1,64]", a.k);
-  return status;
 }
 
 }  // namespace
@@ -524,12 +512,12 @@ int pa_launch_kmer_hash(pa_ctx *c, const KmerHashArgs &a) {
     const uint64_t n_wg = (pos1 - pos0 + per_wg - 1) / per_wg;
     const uint32_t gx = (uint32_t)std::min<uint64_t>(n_wg, 1u << 20), gy = (uint32_t)((n_wg + gx - 1) / gx);
     PA_REQUIRE(gy <= 65535u, "arena too large for one launch of the long k-mer kernel: %llu positions", (unsigned long long)(pos1 - pos0));
-    hipLaunchKernelGGL(kmer_hash_long_kernel, dim3(gx, gy), dim3(kThreads), 0, a.stream ? a.stream : c->stream, a.arena.packed,
-                       a.arena.mask, pos0, pos1, a.k, s.genome_blk, s.n_genomes, a.max_hash, s.cand_hash, s.cand_genome, s.cap,
-                       reinterpret_cast<unsigned long long *>(s.count), s.region_off, s.cursor, s.overflow);
-    PA_HIP(hipGetLastError());
-    return PA_OK;
+    return PA_LAUNCH_ON(c, a.stream, kmer_hash_long_kernel, LaunchDim(gx, gy), kThreads, 0, a.arena.packed, a.arena.mask, pos0, pos1, a.k,
+                        s.genome_blk, s.n_genomes, a.max_hash, s.cand_hash, s.cand_genome, s.cap,
+                        reinterpret_cast<unsigned long long *>(s.count), s.region_off, s.cursor, s.overflow);
   }
   PA_REQUIRE((a.blk0 & 63u) == 0, "k-mer hash launch must start at a multiple of 64 blocks, not %llu", (unsigned long long)a.blk0);
-  return launch_for_k(c, a, std::make_integer_sequence<int, 64>{});
+  int status = PA_E_INVALID;
+  if (!dispatch_value(a.k, value_list<1, 64>{}, [&](auto k) { status = launch_k<k()>(c, a); })) pa_set_error("k=%u outside [1,64]", a.k);
+  return status;
 }

@@ -171,14 +171,6 @@ __global__ __launch_bounds__(kThreads) void msa_mirror_kernel(uint32_t n, uint32
   }
 }
 
-template <int P>
-void launch_pairs(dim3 grid, hipStream_t st, const uint32_t *planes, uint32_t n_pad, uint32_t n_words, uint32_t wps, uint32_t q0,
-                  uint32_t nq, uint32_t s0, uint32_t ns, uint32_t n_tiles_s, int symmetric, int accumulate, uint32_t *match,
-                  uint32_t *both) {
-  hipLaunchKernelGGL(msa_pairs_kernel<P>, grid, dim3(kThreads), 0, st, planes, n_pad, n_words, wps, q0, nq, s0, ns, n_tiles_s, symmetric,
-                     accumulate, match, both);
-}
-
 inline uint32_t n_pad_of(uint32_t n_rows) { return (n_rows + kTile - 1u) / kTile * kTile; }
 inline uint64_t n_words_of(uint64_t n_cols) { return (n_cols + 31u) / 32u; }
 
@@ -217,10 +209,8 @@ int pa_msa_pack(pa_ctx *c, const uint8_t *d_rows, uint64_t row_stride, uint32_t 
   splits = std::max<uint64_t>(1, std::min<uint64_t>({splits, (n_words + 15) / 16, 65535}));
   const uint32_t wpb = (uint32_t)((n_words + splits - 1) / splits);
   splits = (n_words + wpb - 1) / wpb;
-  hipLaunchKernelGGL(msa_pack_kernel, dim3(row_blocks, (uint32_t)splits), dim3(kThreads), 0, c->stream, d_rows, row_stride, row0, n_chunk_rows,
-                     n_pad_of(n_rows), n_cols, (uint32_t)n_words, wpb, table, bits, d_planes, d_nongap);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return PA_LAUNCH(c, msa_pack_kernel, LaunchDim(row_blocks, splits), kThreads, 0, d_rows, row_stride, row0, n_chunk_rows, n_pad_of(n_rows), n_cols,
+                   (uint32_t)n_words, wpb, table, bits, d_planes, d_nongap);
 }
 
 int pa_msa_pair_counts(pa_ctx *c, const uint32_t *d_planes, uint32_t n_rows, uint64_t n_cols, uint32_t bits, uint32_t q0, uint32_t q1,
@@ -255,25 +245,18 @@ int pa_msa_pair_counts(pa_ctx *c, const uint32_t *d_planes, uint32_t n_rows, uin
     PA_HIP(hipMemsetAsync(d_both, 0, (uint64_t)nq * ns * 4u, c->stream));
   }
   if (n_words) {
-    const dim3 grid((uint32_t)tiles, (uint32_t)splits);
+    const LaunchDim grid(tiles, splits);
     const uint32_t np = n_pad_of(n_rows);
-    switch (bits + 1) {
-      case 2: launch_pairs<2>(grid, c->stream, d_planes, np, n_words, wps, q0, nq, s0, ns, symmetric ? tq : ts, symmetric, accumulate, d_match, d_both); break;
-      case 3: launch_pairs<3>(grid, c->stream, d_planes, np, n_words, wps, q0, nq, s0, ns, symmetric ? tq : ts, symmetric, accumulate, d_match, d_both); break;
-      case 4: launch_pairs<4>(grid, c->stream, d_planes, np, n_words, wps, q0, nq, s0, ns, symmetric ? tq : ts, symmetric, accumulate, d_match, d_both); break;
-      case 5: launch_pairs<5>(grid, c->stream, d_planes, np, n_words, wps, q0, nq, s0, ns, symmetric ? tq : ts, symmetric, accumulate, d_match, d_both); break;
-      case 6: launch_pairs<6>(grid, c->stream, d_planes, np, n_words, wps, q0, nq, s0, ns, symmetric ? tq : ts, symmetric, accumulate, d_match, d_both); break;
-      case 7: launch_pairs<7>(grid, c->stream, d_planes, np, n_words, wps, q0, nq, s0, ns, symmetric ? tq : ts, symmetric, accumulate, d_match, d_both); break;
-      case 8: launch_pairs<8>(grid, c->stream, d_planes, np, n_words, wps, q0, nq, s0, ns, symmetric ? tq : ts, symmetric, accumulate, d_match, d_both); break;
-      default: launch_pairs<9>(grid, c->stream, d_planes, np, n_words, wps, q0, nq, s0, ns, symmetric ? tq : ts, symmetric, accumulate, d_match, d_both); break;
-    }
-    PA_HIP(hipGetLastError());
+    int status = PA_OK;
+    auto launch_pairs = [&](auto planes) {
+      status = PA_LAUNCH(c, msa_pairs_kernel<planes()>, grid, kThreads, 0, d_planes, np, n_words, wps, q0, nq, s0, ns, symmetric ? tq : ts, symmetric,
+                         accumulate, d_match, d_both);
+    };
+    if (!dispatch_value(bits + 1, value_list<2, 7>{}, launch_pairs)) launch_pairs(std::integral_constant<int, 9>{});
+    PA_TRY(status);
   }
-  if (symmetric && tq > 1) {
-    hipLaunchKernelGGL(msa_mirror_kernel, dim3((nq + kThreads - 1) / kThreads, nq < 65535u ? nq : 65535u), dim3(kThreads), 0, c->stream, nq,
-                       d_match, d_both);
-    PA_HIP(hipGetLastError());
-  }
+  if (symmetric && tq > 1)
+    PA_TRY(PA_LAUNCH(c, msa_mirror_kernel, LaunchDim((nq + kThreads - 1) / kThreads, nq < 65535u ? nq : 65535u), kThreads, 0, nq, d_match, d_both));
   return PA_OK;
 }
 

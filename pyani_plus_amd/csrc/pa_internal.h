@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/pyani_hip.h"
+#include "pa_launch_geom.h"
 
 // ---- error plumbing -------------------------------------------------------
 void pa_set_error(const char *fmt, ...);
@@ -255,8 +256,49 @@ struct ProfScope {
   ~ProfScope();
 };
 
-// ---- launch geometry helpers ----------------------------------------------
-static inline uint32_t ceil_div_u64(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+// Bulk copy to the host on the context's stream, and the wait for it.
+inline int pa_copy_to_host(pa_ctx *c, void *h_dst, const void *d_src, size_t bytes) {
+  PA_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+  PA_HIP(hipStreamSynchronize(c->stream));
+  return PA_OK;
+}
+
+// ---- kernel launches ---------------------------------------------------------
+// Every kernel is launched through PA_LAUNCH (on the context's stream), PA_LAUNCH_ON (on a stream of the caller's;
+// nullptr: the context's) or PA_LAUNCH_RAISE_LDS (the kernel's dynamic LDS limit is raised to this launch's bytes
+// first).  grid and block are LaunchDim: a 64-bit count for the 1-D form, LaunchDim(x, y) otherwise.  An empty grid
+// launches nothing and is PA_OK; a grid or block beyond the device's limits is PA_E_INVALID; what the runtime refuses
+// is PA_E_HIP, reported at once with the kernel's name and sizes.  The launcher keeps no state.
+inline int pa_launch_refused(const char *name, LaunchDim g, LaunchDim b, size_t lds_bytes, const char *why, int status) {
+  pa_set_error("launch of %s, grid (%llu, %llu, %llu), block (%llu, %llu, %llu), %zu bytes of dynamic LDS: %s", name, (unsigned long long)g.x,
+               (unsigned long long)g.y, (unsigned long long)g.z, (unsigned long long)b.x, (unsigned long long)b.y, (unsigned long long)b.z,
+               lds_bytes, why);
+  return status;
+}
+template <class... Params, class... Args>
+int pa_launch(pa_ctx *c, const char *name, void (*kernel)(Params...), bool raise_lds, LaunchDim grid, LaunchDim block, size_t lds_bytes,
+              hipStream_t stream, Args &&...args) {
+  const hipDeviceProp_t &p = c->prop;
+  const LaunchLimits lim{{(uint64_t)p.maxGridSize[0], (uint64_t)p.maxGridSize[1], (uint64_t)p.maxGridSize[2]},
+                         {(uint64_t)p.maxThreadsDim[0], (uint64_t)p.maxThreadsDim[1], (uint64_t)p.maxThreadsDim[2]},
+                         (uint64_t)p.maxThreadsPerBlock};
+  switch (launch_verdict(grid, block, lim)) {
+    case LaunchVerdict::kEmptyGrid: return PA_OK;
+    case LaunchVerdict::kOutsideLimits: return pa_launch_refused(name, grid, block, lds_bytes, "beyond the device's limits", PA_E_INVALID);
+    case LaunchVerdict::kGo: break;
+  }
+  if (raise_lds)
+    PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  kernel<<<dim3((uint32_t)grid.x, (uint32_t)grid.y, (uint32_t)grid.z), dim3((uint32_t)block.x, (uint32_t)block.y, (uint32_t)block.z), lds_bytes,
+           stream ? stream : c->stream>>>(std::forward<Args>(args)...);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PA_OK : pa_launch_refused(name, grid, block, lds_bytes, hipGetErrorString(e), PA_E_HIP);
+}
+#define PA_LAUNCH_ON(c, stream, kernel, grid, block, lds_bytes, ...) \
+  pa_launch(c, #kernel, kernel, false, grid, block, lds_bytes, stream, __VA_ARGS__)
+#define PA_LAUNCH(c, kernel, grid, block, lds_bytes, ...) PA_LAUNCH_ON(c, nullptr, kernel, grid, block, lds_bytes, __VA_ARGS__)
+#define PA_LAUNCH_RAISE_LDS(c, kernel, grid, block, lds_bytes, ...) \
+  pa_launch(c, #kernel, kernel, true, grid, block, lds_bytes, nullptr, __VA_ARGS__)
 
 // ---- device primitives implemented in the .hip files -----------------------
 // radix_sort.hip

@@ -351,26 +351,14 @@ __global__ __launch_bounds__(256) void mirror_lower_kernel(uint32_t *__restrict_
   }
 }
 
-template <int TPR>
-void launch_row_sum(pa_ctx *c, uint32_t nq, const uint32_t *ids, const uint64_t *off, uint32_t q0,
-                    const uint32_t *rows, uint32_t tile_cols, uint32_t *counts, uint32_t ns, uint32_t col0) {
-  hipLaunchKernelGGL(row_sum_kernel<TPR>, dim3(nq), dim3(kThreads), 0, c->stream, ids, off, q0, rows, tile_cols,
-                     counts, ns, col0);
-}
-
 int dispatch_row_sum(pa_ctx *c, int tpr, uint32_t nq, const uint32_t *ids, const uint64_t *off, uint32_t q0,
                      const uint32_t *rows, uint32_t tile_cols, uint32_t *counts, uint32_t ns, uint32_t col0) {
-#define PA_ROW_CASE(T) \
-  case T: launch_row_sum<T>(c, nq, ids, off, q0, rows, tile_cols, counts, ns, col0); return PA_OK;
-  switch (tpr) {
-    PA_ROW_CASE(1) PA_ROW_CASE(2) PA_ROW_CASE(3) PA_ROW_CASE(4) PA_ROW_CASE(5) PA_ROW_CASE(6) PA_ROW_CASE(7)
-    PA_ROW_CASE(8) PA_ROW_CASE(9) PA_ROW_CASE(10) PA_ROW_CASE(11) PA_ROW_CASE(12) PA_ROW_CASE(13) PA_ROW_CASE(14)
-    PA_ROW_CASE(15) PA_ROW_CASE(16)
-    default:
-      pa_set_error("pair phase: %d threads per bit row (tile wider than %u subjects)", tpr, kMaxTileSubjects);
-      return PA_E_INVALID;
-  }
-#undef PA_ROW_CASE
+  int status = PA_E_INVALID;
+  if (!dispatch_value(tpr, value_list<1, 16>{}, [&](auto t) {
+        status = PA_LAUNCH(c, row_sum_kernel<t()>, nq, kThreads, 0, ids, off, q0, rows, tile_cols, counts, ns, col0);
+      }))
+    pa_set_error("pair phase: %d threads per bit row (tile wider than %u subjects)", tpr, kMaxTileSubjects);
+  return status;
 }
 
 }  // namespace
@@ -396,22 +384,20 @@ int pa_dense_ids_sorted(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_o
   uint32_t *d_flags = c->flags.as<uint32_t>(), *d_pos = d_flags + P;
   uint64_t *d_or = c->slot<uint64_t>(kDenseIds) + kDenseOr, *d_distinct = c->slot<uint64_t>(kDenseIds) + kDenseDistinct;
 
-  const uint32_t grid = ceil_div_u64(P, kThreads);
+  const uint64_t grid = ceil_div(P, kThreads);
   PA_HIP(hipMemcpyAsync(keys[0], d_hashes, P * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
   PA_HIP(hipMemsetAsync(c->slot(kDenseIds), 0, kDenseIds.bytes(), c->stream));
-  hipLaunchKernelGGL(iota_kernel, dim3(grid), dim3(kThreads), 0, c->stream, vals[0], P);
-  hipLaunchKernelGGL(last_or_kernel, dim3(ceil_div_u64(n, kThreads)), dim3(kThreads), 0, c->stream, d_hashes, d_off,
-                     n, reinterpret_cast<unsigned long long *>(d_or));
+  PA_TRY(PA_LAUNCH(c, iota_kernel, grid, kThreads, 0, vals[0], P));
+  PA_TRY(PA_LAUNCH(c, last_or_kernel, ceil_div(n, kThreads), kThreads, 0, d_hashes, d_off, n, reinterpret_cast<unsigned long long *>(d_or)));
   uint64_t all_or = 0;
   PA_TRY(pa_read_back(c, d_or, &all_or));
   int bit_hi = all_or ? 64 - __builtin_clzll(all_or) : 0;
   bit_hi = (bit_hi + 7) & ~7;
   int which = 0;
   PA_TRY(pa_radix_sort_pairs(c, keys, vals, P, 0, bit_hi, false, &which));
-  hipLaunchKernelGGL(key_heads_kernel, dim3(grid), dim3(kThreads), 0, c->stream, keys[which], P, d_flags);
+  PA_TRY(PA_LAUNCH(c, key_heads_kernel, grid, kThreads, 0, keys[which], P, d_flags));
   PA_TRY(pa_exclusive_scan_u32(c, d_flags, d_pos, P, d_distinct));
-  hipLaunchKernelGGL(assign_ids_kernel, dim3(grid), dim3(kThreads), 0, c->stream, vals[which], d_flags, d_pos, P,
-                     d_off, n, d_ids, d_id_sorted, d_genome_sorted);
+  PA_TRY(PA_LAUNCH(c, assign_ids_kernel, grid, kThreads, 0, vals[which], d_flags, d_pos, P, d_off, n, d_ids, d_id_sorted, d_genome_sorted));
   return pa_read_back(c, d_distinct, n_distinct);
 }
 
@@ -442,15 +428,14 @@ int pa_pairs_bitrow(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_off, 
       ProfScope prof(c, PA_PROF_PAIR_DICT);
       PA_TRY(c->bitrows.reserve(row_bytes));
       PA_HIP(hipMemsetAsync(c->bitrows.p, 0, row_bytes, c->stream));
-      hipLaunchKernelGGL(build_rows_kernel, dim3(ceil_div_u64(P, kThreads)), dim3(kThreads), 0, c->stream,
-                         d_id_sorted, d_genome_sorted, P, t0, t1, w32, c->bitrows.as<uint32_t>());
+      PA_TRY(PA_LAUNCH(c, build_rows_kernel, ceil_div(P, kThreads), kThreads, 0, d_id_sorted, d_genome_sorted, P, t0, t1, w32,
+                       c->bitrows.as<uint32_t>()));
     }
     {
       ProfScope prof(c, PA_PROF_PAIR_COUNT);
       const uint32_t *rows = c->bitrows.as<uint32_t>();
       PA_TRY(dispatch_row_sum(c, tpr, nq, d_ids, d_off, q0, rows, cols, d_counts, ns, t0 - s0));
     }
-    PA_HIP(hipGetLastError());
   }
   return PA_OK;
 }
@@ -467,11 +452,8 @@ static int dict_insert(pa_ctx *c, const uint64_t *d_postings, uint64_t n_post, u
   PA_HIP(hipMemsetAsync(c->dict_keys[0].p, 0xff, cap64 * sizeof(DictEntry), c->stream));
   PA_HIP(hipMemsetAsync(d_counter, 0, 4, c->stream));
   PA_HIP(hipMemsetAsync(d_special, 0xff, 4, c->stream));
-  if (n_post)
-    hipLaunchKernelGGL(table_insert_kernel, dim3(ceil_div_u64(n_post, kThreads * kInsertPerThread)), dim3(kThreads), 0,
-                       c->stream, d_postings, (uint64_t)0, n_post, c->dict_keys[0].as<DictEntry>(), (uint32_t)cap64,
-                       d_counter, d_special);
-  PA_HIP(hipGetLastError());
+  PA_TRY(PA_LAUNCH(c, table_insert_kernel, ceil_div(n_post, kThreads * kInsertPerThread), kThreads, 0, d_postings, (uint64_t)0, n_post,
+                   c->dict_keys[0].as<DictEntry>(), (uint32_t)cap64, d_counter, d_special));
   *cap_out = (uint32_t)cap64;
   return PA_OK;
 }
@@ -488,10 +470,8 @@ int pa_pair_dict_prepare_impl(pa_ctx *c, const uint64_t *d_subject_hashes, uint6
   // what the dictionary was built from, for the call that consumes it
   unsigned long long *d_fp = c->dict_slot<unsigned long long>(kDictPreparedFp);
   PA_HIP(hipMemsetAsync(d_fp, 0, kDictPreparedFp.bytes(), c->stream));
-  if (n_postings)
-    hipLaunchKernelGGL(postings_fingerprint_kernel, dim3(std::min<uint32_t>(1024u, ceil_div_u64(n_postings, kThreads))),
-                       dim3(kThreads), 0, c->stream, d_subject_hashes, n_postings, d_fp);
-  PA_HIP(hipGetLastError());
+  PA_TRY(PA_LAUNCH(c, postings_fingerprint_kernel, std::min<uint64_t>(1024u, ceil_div(n_postings, kThreads)), kThreads, 0, d_subject_hashes,
+                   n_postings, d_fp));
   c->dict_prepared = true;
   c->dict_prepared_postings = n_postings;
   c->dict_prepared_cap = cap;
@@ -516,8 +496,7 @@ int pa_pairs_bitrow_hash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_
   const uint64_t *h_off = h_off_in;
   if (!h_off) {
     h_off_own.resize(n + 1);
-    PA_HIP(hipMemcpyAsync(h_off_own.data(), d_off, (uint64_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    PA_HIP(hipStreamSynchronize(c->stream));
+    PA_TRY(pa_copy_to_host(c, h_off_own.data(), d_off, (uint64_t)(n + 1) * 8));
     h_off = h_off_own.data();
   }
   PA_TRY(c->ids.reserve(total * sizeof(uint32_t)));
@@ -547,9 +526,8 @@ int pa_pairs_bitrow_hash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_
         // the lookups below are then enqueued a few microseconds later than they could have been)
         unsigned long long *d_tile_fp = c->dict_slot<unsigned long long>(kDictTileFp);
         PA_HIP(hipMemsetAsync(d_tile_fp, 0, kDictTileFp.bytes(), c->stream));
-        if (pt1 > pt0)
-          hipLaunchKernelGGL(postings_fingerprint_kernel, dim3(std::min<uint32_t>(1024u, ceil_div_u64(pt1 - pt0, kThreads))),
-                             dim3(kThreads), 0, c->stream, d_hashes + pt0, pt1 - pt0, d_tile_fp);
+        PA_TRY(PA_LAUNCH(c, postings_fingerprint_kernel, std::min<uint64_t>(1024u, ceil_div(pt1 - pt0, kThreads)), kThreads, 0, d_hashes + pt0,
+                         pt1 - pt0, d_tile_fp));
         unsigned long long fp_prepared[2], fp_tile[2];
         ReadBack rb(c);
         PA_TRY(rb.queue(c->dict_slot<unsigned long long>(kDictPreparedFp), fp_prepared, 2));
@@ -574,41 +552,35 @@ int pa_pairs_bitrow_hash(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_
         row_bound = std::max<uint64_t>(1, std::min<uint64_t>(row_bound, distinct));
       }
       PA_TRY(c->bitrows.reserve(row_bound * w32 * sizeof(uint32_t)));
-      hipLaunchKernelGGL(zero_rows_kernel, dim3(ceil_div_u64(row_bound * w32 / 4u, kThreads)), dim3(kThreads), 0,
-                         c->stream, c->bitrows.as<uint4>(), d_counter, w32);
+      PA_TRY(PA_LAUNCH(c, zero_rows_kernel, ceil_div(row_bound * w32 / 4u, kThreads), kThreads, 0, c->bitrows.as<uint4>(), d_counter, w32));
       const DictEntry *table = c->dict_keys[0].as<DictEntry>();
       if (pt1 > pt0) {
         uint64_t longest = 0;
         for (uint32_t g = t0; g < t1; ++g) longest = std::max(longest, h_off[g + 1] - h_off[g]);
-        hipLaunchKernelGGL(table_lookup_kernel<true>, dim3(ceil_div_u64(longest, kThreads), cols), dim3(kThreads), 0,
-                           c->stream, d_hashes, pt0, pt1, table, cap, d_special, d_ids, d_off, n, t0, w32,
-                           c->bitrows.as<uint32_t>());
+        PA_TRY(PA_LAUNCH(c, table_lookup_kernel<true>, LaunchDim(ceil_div(longest, kThreads), cols), kThreads, 0, d_hashes, pt0, pt1, table, cap,
+                         d_special, d_ids, d_off, n, t0, w32, c->bitrows.as<uint32_t>()));
       }
       // query postings outside the tile's own range
       const uint64_t a0 = pq0, a1 = pq1 < pt0 ? pq1 : pt0;  // part before the tile
       const uint64_t b0 = pq0 > pt1 ? pq0 : pt1, b1 = pq1;  // part after the tile
       if (a1 > a0)
-        hipLaunchKernelGGL(table_lookup_kernel<false>, dim3(ceil_div_u64(a1 - a0, kThreads)), dim3(kThreads), 0,
-                           c->stream, d_hashes, a0, a1, table, cap, d_special, d_ids, d_off, n, t0, w32,
-                           (uint32_t *)nullptr);
+        PA_TRY(PA_LAUNCH(c, table_lookup_kernel<false>, ceil_div(a1 - a0, kThreads), kThreads, 0, d_hashes, a0, a1, table, cap, d_special, d_ids,
+                         d_off, n, t0, w32, nullptr));
       if (b1 > b0)
-        hipLaunchKernelGGL(table_lookup_kernel<false>, dim3(ceil_div_u64(b1 - b0, kThreads)), dim3(kThreads), 0,
-                           c->stream, d_hashes, b0, b1, table, cap, d_special, d_ids, d_off, n, t0, w32,
-                           (uint32_t *)nullptr);
+        PA_TRY(PA_LAUNCH(c, table_lookup_kernel<false>, ceil_div(b1 - b0, kThreads), kThreads, 0, d_hashes, b0, b1, table, cap, d_special, d_ids,
+                         d_off, n, t0, w32, nullptr));
     }
     {
       ProfScope prof(c, PA_PROF_PAIR_COUNT);
       const uint32_t *rows = c->bitrows.as<uint32_t>();
       PA_TRY(dispatch_row_sum(c, tpr, tq1 - q0, d_ids, d_off, q0, rows, cols, d_counts, ns, t0 - s0));
     }
-    PA_HIP(hipGetLastError());
   }
   if (symmetric) {
     ProfScope prof(c, PA_PROF_PAIR_COUNT);
     static_assert(kMaxTileSubjects % 32u == 0, "mirror pieces must not straddle a tile edge");
     const uint32_t g = (ns + 31u) / 32u;
-    hipLaunchKernelGGL(mirror_lower_kernel, dim3(g, g), dim3(256), 0, c->stream, d_counts, ns, kMaxTileSubjects);
-    PA_HIP(hipGetLastError());
+    PA_TRY(PA_LAUNCH(c, mirror_lower_kernel, LaunchDim(g, g), 256, 0, d_counts, ns, kMaxTileSubjects));
   }
   return PA_OK;
 }

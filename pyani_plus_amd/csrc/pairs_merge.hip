@@ -76,8 +76,5 @@ int pa_pairs_merge(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_off, u
   PA_REQUIRE(pairs / kWavesPerBlock < (1ULL << 31), "pa_pairs_merge: tile of %llu pairs is too large for one launch",
              (unsigned long long)pairs);
   ProfScope prof(c, PA_PROF_PAIR_COUNT);
-  hipLaunchKernelGGL(merge_count_kernel, dim3(ceil_div_u64(pairs, kWavesPerBlock)), dim3(kThreads), 0, c->stream,
-                     d_hashes, d_off, q0, nq, s0, ns, d_counts);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return PA_LAUNCH(c, merge_count_kernel, ceil_div(pairs, kWavesPerBlock), kThreads, 0, d_hashes, d_off, q0, nq, s0, ns, d_counts);
 }

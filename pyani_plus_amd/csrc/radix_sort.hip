@@ -235,43 +235,31 @@ int pa_exclusive_scan_u32(pa_ctx *c, const uint32_t *d_in, uint32_t *d_out, uint
     if (d_total_u64) PA_HIP(hipMemsetAsync(d_total_u64, 0, sizeof(uint64_t), c->stream));
     return PA_OK;
   }
-  const uint32_t tiles = ceil_div_u64(n, kScanTile);
-  PA_TRY(c->scan_tmp.reserve((uint64_t)tiles * sizeof(uint32_t)));
+  const uint64_t tiles = ceil_div(n, kScanTile);  // the first launch refuses a count that does not fit the grid
+  PA_TRY(c->scan_tmp.reserve(tiles * sizeof(uint32_t)));
   uint32_t *d_sums = c->scan_tmp.as<uint32_t>();
-  hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(tiles), dim3(kScanThreads), 0, c->stream, d_in, n, d_sums);
-  hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanThreads), 0, c->stream, d_sums, tiles,
-                     reinterpret_cast<unsigned long long *>(d_total_u64));
-  hipLaunchKernelGGL(scan_apply_kernel, dim3(tiles), dim3(kScanThreads), 0, c->stream, d_in, d_out, n, d_sums);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  PA_TRY(PA_LAUNCH(c, scan_tile_sums_kernel, tiles, kScanThreads, 0, d_in, n, d_sums));
+  PA_TRY(PA_LAUNCH(c, scan_sums_kernel, 1, kScanThreads, 0, d_sums, (uint32_t)tiles, reinterpret_cast<unsigned long long *>(d_total_u64)));
+  return PA_LAUNCH(c, scan_apply_kernel, tiles, kScanThreads, 0, d_in, d_out, n, d_sums);
 }
 
 int pa_radix_sort_pairs(pa_ctx *c, uint64_t *keys[2], uint32_t *vals[2], uint64_t n, int bit_lo, int bit_hi,
                         bool by_val, int *which) {
   if (n <= 1 || bit_hi <= bit_lo) return PA_OK;
   PA_REQUIRE(n < (1ULL << 32), "radix sort: %llu elements exceed the 32-bit index space", (unsigned long long)n);
-  const uint32_t tiles = ceil_div_u64(n, kTile);
+  const uint32_t tiles = (uint32_t)ceil_div(n, kTile);  // n < 2^32
   const uint64_t hist_n = (uint64_t)kRadix * tiles;
   PA_TRY(c->hist.reserve(hist_n * sizeof(uint32_t)));
   uint32_t *d_hist = c->hist.as<uint32_t>();
   int cur = *which;
   for (int shift = bit_lo; shift < bit_hi; shift += 8) {
-    if (by_val)
-      hipLaunchKernelGGL(rs_hist_kernel<true>, dim3(tiles), dim3(kSortThreads), 0, c->stream, keys[cur], vals[cur],
-                         n, shift, tiles, d_hist);
-    else
-      hipLaunchKernelGGL(rs_hist_kernel<false>, dim3(tiles), dim3(kSortThreads), 0, c->stream, keys[cur], vals[cur],
-                         n, shift, tiles, d_hist);
+    PA_TRY(pa_launch(c, "rs_hist_kernel", by_val ? rs_hist_kernel<true> : rs_hist_kernel<false>, false, tiles, kSortThreads, 0, nullptr,
+                     keys[cur], vals[cur], n, shift, tiles, d_hist));
     PA_TRY(pa_exclusive_scan_u32(c, d_hist, d_hist, hist_n, nullptr));
-    if (by_val)
-      hipLaunchKernelGGL(rs_scatter_kernel<true>, dim3(tiles), dim3(kSortThreads), 0, c->stream, keys[cur],
-                         vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, tiles, d_hist);
-    else
-      hipLaunchKernelGGL(rs_scatter_kernel<false>, dim3(tiles), dim3(kSortThreads), 0, c->stream, keys[cur],
-                         vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, tiles, d_hist);
+    PA_TRY(pa_launch(c, "rs_scatter_kernel", by_val ? rs_scatter_kernel<true> : rs_scatter_kernel<false>, false, tiles, kSortThreads, 0, nullptr,
+                     keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, tiles, d_hist));
     cur ^= 1;
   }
-  PA_HIP(hipGetLastError());
   *which = cur;
   return PA_OK;
 }

@@ -140,7 +140,5 @@ extern "C" int pa_rowdist_euclid(pa_ctx *c, const double *d_x, uint32_t n, uint3
   PA_HIP(hipSetDevice(c->device));
   ProfScope prof(c, PA_PROF_ROWDIST);
   const uint32_t nt = (n + kTile - 1) / kTile;
-  hipLaunchKernelGGL(rowdist_euclid_kernel, dim3(nt, nt), dim3(kThreads), 0, c->stream, d_x, n, m, d_out);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return PA_LAUNCH(c, rowdist_euclid_kernel, LaunchDim(nt, nt), kThreads, 0, d_x, n, m, d_out);
 }

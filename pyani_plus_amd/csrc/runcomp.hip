@@ -215,18 +215,13 @@ extern "C" int pa_runcomp_join(pa_ctx *c, const double *d_ref, uint32_t n_ref, c
   const uint64_t n_groups = (n_rows + 63) / 64;
   PA_TRY(c->flags.reserve(n_groups * sizeof(uint32_t)));
   uint32_t *d_counts = c->flags.as<uint32_t>();
-  const dim3 grid(ceil_div_u64(n_rows, kRowsPerWg));
-  hipLaunchKernelGGL(rc_join_kernel<false>, grid, dim3(kThreads), 0, c->stream, d_ref, n_ref, d_q, d_s, d_y, n_rows, d_counts, 0ULL, nullptr,
-                     nullptr, nullptr);
-  PA_HIP(hipGetLastError());
+  const uint64_t grid = ceil_div(n_rows, kRowsPerWg);
+  PA_TRY(PA_LAUNCH(c, rc_join_kernel<false>, grid, kThreads, 0, d_ref, n_ref, d_q, d_s, d_y, n_rows, d_counts, 0ULL, nullptr, nullptr, nullptr));
   uint64_t total = 0;
   PA_TRY(pa_scan_total_u32(c, d_counts, d_counts, n_groups, c->slot<uint64_t>(kCompactTotal), &total));
   *n_common = total;
   if (total == 0) return PA_OK;
-  hipLaunchKernelGGL(rc_join_kernel<true>, grid, dim3(kThreads), 0, c->stream, d_ref, n_ref, d_q, d_s, d_y, n_rows, d_counts, total, d_x,
-                     d_y_out, d_diff);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  return PA_LAUNCH(c, rc_join_kernel<true>, grid, kThreads, 0, d_ref, n_ref, d_q, d_s, d_y, n_rows, d_counts, total, d_x, d_y_out, d_diff);
 }
 
 extern "C" int pa_minmax_f64(pa_ctx *c, const double *d_v, uint64_t n, double *out, uint64_t *n_valid) {
@@ -239,9 +234,8 @@ extern "C" int pa_minmax_f64(pa_ctx *c, const double *d_v, uint64_t n, double *o
   PA_TRY(c->hist.reserve(((uint64_t)blocks + 1) * 3 * sizeof(double)));
   double *d_partial = c->hist.as<double>();
   double *d_result = d_partial + 3 * (uint64_t)blocks;
-  hipLaunchKernelGGL(rc_minmax_kernel, dim3(blocks), dim3(kThreads), 0, c->stream, d_v, n, d_partial);
-  hipLaunchKernelGGL(rc_minmax_final_kernel, dim3(1), dim3(kThreads), 0, c->stream, d_partial, blocks, d_result);
-  PA_HIP(hipGetLastError());
+  PA_TRY(PA_LAUNCH(c, rc_minmax_kernel, blocks, kThreads, 0, d_v, n, d_partial));
+  PA_TRY(PA_LAUNCH(c, rc_minmax_final_kernel, 1, kThreads, 0, d_partial, blocks, d_result));
   double result[3];  // min, max, the count's bits
   PA_TRY(pa_read_back(c, d_result, result, 3));
   uint64_t valid;
@@ -274,9 +268,6 @@ extern "C" int pa_hist_uniform_f64(pa_ctx *c, const double *d_v, uint64_t n, con
   double *d_edges = reinterpret_cast<double *>(d_counts + bins);
   PA_HIP(hipMemsetAsync(d_counts, 0, (uint64_t)bins * 8, c->stream));
   PA_HIP(hipMemcpyAsync(d_edges, h_edges, ((uint64_t)bins + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(rc_hist_kernel, dim3(stride_blocks(n)), dim3(kThreads), 0, c->stream, d_v, n, d_edges, bins, d_counts);
-  PA_HIP(hipGetLastError());
-  PA_HIP(hipMemcpyAsync(h_counts, d_counts, (uint64_t)bins * 8, hipMemcpyDeviceToHost, c->stream));
-  PA_HIP(hipStreamSynchronize(c->stream));  // the caller's edges and counts are not touched after the return
-  return PA_OK;
+  PA_TRY(PA_LAUNCH(c, rc_hist_kernel, stride_blocks(n), kThreads, 0, d_v, n, d_edges, bins, d_counts));
+  return pa_copy_to_host(c, h_counts, d_counts, (uint64_t)bins * 8);  // the caller's edges and counts are not touched after the return
 }

@@ -53,14 +53,12 @@ int pa_build_sketch_csr(pa_ctx *c, const uint64_t *d_sorted_hash, const uint32_t
   PA_TRY(c->flags.reserve(2 * n_cand * sizeof(uint32_t)));
   uint32_t *d_flags = c->flags.as<uint32_t>();
   uint32_t *d_pos = d_flags + n_cand;
-  const uint32_t grid = ceil_div_u64(n_cand, kThreads);
-  hipLaunchKernelGGL(head_flags_kernel, dim3(grid), dim3(kThreads), 0, c->stream, d_sorted_hash, d_sorted_genome,
-                     n_cand, d_flags);
+  const uint64_t grid = ceil_div(n_cand, kThreads);
+  PA_TRY(PA_LAUNCH(c, head_flags_kernel, grid, kThreads, 0, d_sorted_hash, d_sorted_genome, n_cand, d_flags));
   PA_TRY(pa_scan_total_u32(c, d_flags, d_pos, n_cand, c->slot<uint64_t>(kSketchTotal), h_total));
   // offsets are always produced (they are valid even when the payload does not fit)
-  hipLaunchKernelGGL(compact_csr_kernel, dim3(grid), dim3(kThreads), 0, c->stream, d_sorted_hash, d_sorted_genome,
-                     d_flags, d_pos, n_cand, n_genomes, *h_total <= cap_hashes ? cap_hashes : 0ULL, d_hashes, d_off);
-  PA_HIP(hipGetLastError());
+  PA_TRY(PA_LAUNCH(c, compact_csr_kernel, grid, kThreads, 0, d_sorted_hash, d_sorted_genome, d_flags, d_pos, n_cand, n_genomes,
+                   *h_total <= cap_hashes ? cap_hashes : 0ULL, d_hashes, d_off));
   if (*h_total > cap_hashes) {
     pa_set_error("sketch output needs %llu hashes, caller gave room for %llu", (unsigned long long)*h_total,
                  (unsigned long long)cap_hashes);

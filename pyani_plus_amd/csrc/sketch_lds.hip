@@ -195,17 +195,14 @@ int pa_sketch_from_regions(pa_ctx *c, uint64_t *d_regions, const uint64_t *d_reg
   PA_TRY(c->flags.reserve((uint64_t)n_genomes * sizeof(uint32_t)));
   uint32_t *d_uniq = c->flags.as<uint32_t>();
   uint64_t *d_total = c->slot<uint64_t>(kSketchTotal);
-  PA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(genome_sort_kernel),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   // value ranges of the bucket sort: equal shares of [0, max_hash]
   const int key_bits = max_hash ? 64 - __builtin_clzll(max_hash) : 1;
   const uint32_t key_shift = key_bits > 32 ? (uint32_t)key_bits - 32u : 0u;
   const uint64_t top = (max_hash >> key_shift) + 1;  // (key >> shift) < top <= 2^32
   const uint32_t key_mult = (uint32_t)std::min<uint64_t>(((uint64_t)kBuckets << 32) / top, 0xffffffffull);
-  hipLaunchKernelGGL(genome_sort_kernel, dim3(n_genomes), dim3(kSortThreads), lds_bytes, c->stream, d_regions,
-                     d_region_off, d_cursor, d_uniq, key_shift, key_mult);
-  hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(kSortThreads), 0, c->stream, d_uniq, n_genomes, d_off, d_total);
-  PA_HIP(hipGetLastError());
+  PA_TRY(PA_LAUNCH_RAISE_LDS(c, genome_sort_kernel, n_genomes, kSortThreads, lds_bytes, d_regions, d_region_off, d_cursor, d_uniq, key_shift,
+                             key_mult));
+  PA_TRY(PA_LAUNCH(c, offsets_kernel, 1, kSortThreads, 0, d_uniq, n_genomes, d_off, d_total));
   // one round trip for both scalars: the total and the overflow flag
   uint64_t total = 0;
   uint32_t overflow = 0;
@@ -221,9 +218,6 @@ int pa_sketch_from_regions(pa_ctx *c, uint64_t *d_regions, const uint64_t *d_reg
                  (unsigned long long)cap_hashes);
     return PA_E_CAPACITY;
   }
-  if (*h_total)
-    hipLaunchKernelGGL(gather_kernel, dim3(n_genomes), dim3(256), 0, c->stream, d_regions, d_region_off, d_off,
-                       d_hashes);
-  PA_HIP(hipGetLastError());
+  if (*h_total) PA_TRY(PA_LAUNCH(c, gather_kernel, n_genomes, 256, 0, d_regions, d_region_off, d_off, d_hashes));
   return PA_OK;
 }

@@ -62,12 +62,9 @@ __global__ __launch_bounds__(kThreads) void dirty_kernel(const uint2 *__restrict
 }  // namespace
 
 int pa_build_dirty(pa_ctx *c, const uint32_t *d_mask, uint64_t n_blocks64, uint64_t *d_dirty, hipStream_t stream) {
-  if (n_blocks64 == 0) return PA_OK;
-  const uint64_t words = (n_blocks64 + 63) / 64;
-  hipLaunchKernelGGL(dirty_kernel, dim3(ceil_div_u64(words * 64, kThreads)), dim3(kThreads), 0, stream ? stream : c->stream,
-                     reinterpret_cast<const uint2 *>(d_mask), n_blocks64, d_dirty);
-  PA_HIP(hipGetLastError());
-  return PA_OK;
+  const uint64_t words = (n_blocks64 + 63) / 64;  // an empty arena: an empty grid
+  return PA_LAUNCH_ON(c, stream, dirty_kernel, ceil_div(words * 64, kThreads), kThreads, 0, reinterpret_cast<const uint2 *>(d_mask),
+                      n_blocks64, d_dirty);
 }
 
 int pa_dirty_or_build(pa_ctx *c, const uint32_t *d_mask, uint64_t n_blocks64, const uint64_t *d_dirty, const uint64_t **out) {
@@ -107,9 +104,7 @@ int pa_mask_from_runs(pa_ctx *c, const uint64_t *h_run_start, const uint64_t *h_
     PA_HIP(hipMemcpyAsync(d_len, h_run_len, (uint64_t)n_runs * 8, hipMemcpyHostToDevice, c->stream));
   }
   const uint64_t n_words = arena_bases / 32;
-  hipLaunchKernelGGL(mask_from_runs_kernel, dim3(ceil_div_u64(n_words, kThreads)), dim3(kThreads), 0, c->stream, d_start,
-                     d_len, n_runs, d_mask, n_words);
-  PA_HIP(hipGetLastError());
+  PA_TRY(PA_LAUNCH(c, mask_from_runs_kernel, ceil_div(n_words, kThreads), kThreads, 0, d_start, d_len, n_runs, d_mask, n_words));
   PA_HIP(hipStreamSynchronize(c->stream));  // the caller's run arrays may go away
   return PA_OK;
 }

@@ -1197,3 +1197,35 @@ def test_bench_dump_outputs_budget_sample_and_exact_hashes(tmp_path):
     got = (a["sketch_sample_hash_hi"].astype(np.uint64) << np.uint64(32)) | a["sketch_sample_hash_lo"].astype(np.uint64)
     want = np.concatenate([hashes[off[g] : off[g + 1]] for g in a["sketch_sample_genomes"].astype(np.int64)]).view(np.uint64)
     assert np.array_equal(got, want)
+
+
+# ------------------------------------------------------------------ kernel launches
+def test_launch_arithmetic_and_value_dispatch_under_sanitizers():
+    """AddressSanitizer + UBSan over ``pa_launch_geom.h`` in a stand-alone CPU program: block counts at 0, 1, the limit and
+    the limit + 1 in each dimension, a 64-bit count that 32 bits would have wrapped, and the value dispatch (each listed
+    value reaches its own case once, a value off the list reports a miss)."""
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("no host compiler")
+    script = Path(__file__).resolve().parent / "tools" / "sanitize" / "run_launch_geom.sh"
+    done = subprocess.run(["bash", str(script)], capture_output=True, text=True, timeout=600)
+    assert done.returncode == 0 and "sanitizer runs clean" in done.stdout, done.stdout[-2000:] + done.stderr[-2000:]
+    assert "MISMATCH" not in done.stdout
+
+
+def test_kernels_are_launched_through_the_launcher_only():
+    """The library's sources launch, raise a kernel's LDS limit and read the runtime's last error in ``pa_internal.h``
+    alone (``DevBuf::reserve`` clears a failed allocation's error there too); no blocking copy, no truncating grid helper
+    and no dispatch macro is left."""
+    csrc = Path(_capi.__file__).resolve().parent / "csrc"
+    found = {}
+    for path in sorted(csrc.iterdir()):
+        if path.suffix not in {".hip", ".inc", ".h", ".cpp"}:
+            continue
+        text = path.read_text()
+        for word in ("hipLaunchKernelGGL", "<<<", "hipFuncSetAttribute", "hipGetLastError", "hipMemcpy(", "_CASE(", "ceil_div_u64"):
+            if text.count(word):
+                found[path.name, word] = text.count(word)
+    assert found == {("pa_internal.h", "<<<"): 1, ("pa_internal.h", "hipFuncSetAttribute"): 1, ("pa_internal.h", "hipGetLastError"): 3}, found
