@@ -366,9 +366,12 @@ int dispatch_row_sum(pa_ctx *c, int tpr, uint32_t nq, const uint32_t *ids, const
 // Dense ids in ascending hash order for all P postings (id order == hash order): sort (hash, posting),
 // flag the first posting of every distinct hash, scan.  Leaves ids in CSR order in c->ids and the
 // (id, genome) pairs in sorted order in c->post_genome[0..P) / [P..2P).
+// The sort's key buffers are c->dict_keys[]: dict_keys[0] is also where a dictionary built ahead
+// (pa_pair_dict_prepare) keeps its hash table, so this call overwrites that table and drops the preparation.
 int pa_dense_ids_sorted(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_off, uint32_t n, uint64_t P,
                         uint64_t *n_distinct) {
   ProfScope prof(c, PA_PROF_PAIR_DICT);
+  c->dict_prepared = false;
   for (int b = 0; b < 2; ++b) {
     PA_TRY(c->dict_keys[b].reserve(P * sizeof(uint64_t)));
     PA_TRY(c->dict_vals[b].reserve(P * sizeof(uint32_t)));
