@@ -576,6 +576,48 @@ PA_API int pa_minmax_f64_host(const double *h_v, uint64_t n, double *out, uint64
 PA_API int pa_hist_uniform_f64_host(const double *h_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts);
 PA_API int pa_write_pairs_tsv(const char *path, const char *header, const double *h_x, const double *h_y, uint64_t n);
 
+/* ---- plot-run: score distributions ----
+ * What the reference's plot_distribution (pyani_plus/plot_run.py:153-215) has seaborn compute from all N^2 cells of a
+ * score matrix: the order statistics numpy's automatic bin rule needs, the moments behind Scott's bandwidth, scipy's
+ * gaussian_kde on a grid, and numpy.histogram's counts for the many bins the automatic rule can ask for.  v is a
+ * vector of n doubles; NaN means no value and is skipped everywhere.
+ *
+ *   pa_select_f64            (device) h_out[r] = the element at zero-based rank h_ranks[r] of the non-NaN elements of
+ *        d_v[n] in ascending order of value, for up to PA_SELECT_MAX_RANKS ranks in any order, repeats allowed: the value
+ *        numpy.sort(v)[rank] has (when -0.0 and 0.0 both occur, which of the two comes back is not defined).  An MSB
+ *        radix select over order-preserving u64 keys, a byte a pass, all ranks in the same eight passes; integer
+ *        counters only, no sort and no copy of the data; one host synchronisation per pass.  PA_E_INVALID for
+ *        n_ranks > PA_SELECT_MAX_RANKS, for a rank >= the number of non-NaN elements (so for every rank when there is
+ *        none) and for n >= 2^40; n_ranks = 0 is valid and does nothing.
+ *   pa_moments_f64           (device) out[0] = the mean of the non-NaN elements, out[1] = the sum of their squared
+ *        deviations from it, in two passes (the mean first); without such an element out is untouched.  A fixed
+ *        reduction tree whose shape depends on n alone, no floating-point atomics: two runs give the same bits.  The
+ *        host twin adds in index order, so the two agree to rounding, not in bits.  One host synchronisation.
+ *   pa_kde_gauss_f64         (device) h_density[j] = 1 / (m bw sqrt(2 pi)) * sum over the m non-NaN elements of
+ *        exp(-0.5 ((h_grid[j] - v_i) / bw)^2) for n_grid <= 1024 grid points: scipy's gaussian_kde(v)(grid) when bw is
+ *        Scott's factor times the standard deviation.  The quotient is the correctly rounded one, the exponent the
+ *        library's exp of a double.  A run of at most PA_KDE_CHAIN additions one after the other, then a fixed binary
+ *        tree over the partial sums, no floating-point atomics: the same bits run to run; the terms are non-negative, so
+ *        the sum's relative error is at most (PA_KDE_CHAIN + the tree's depth) * 2^-53.  PA_E_INVALID for n_grid outside
+ *        1 .. 1024, a grid point that is not finite, bw that is not positive and finite, an infinite element and no
+ *        non-NaN element.
+ *   pa_hist_uniform_f64_wide (device) pa_hist_uniform_f64's rule, the same division and the same corrections, for
+ *        1 .. 2^20 bins: counters in LDS up to PA_HIST_WIDE_LDS_BINS bins, 64-bit integer atomics on the counters in
+ *        global memory above.  The same errors as pa_hist_uniform_f64, with this range of bins.
+ *   pa_select_f64_host, pa_moments_f64_host, pa_kde_gauss_f64_host, pa_hist_uniform_f64_wide_host   the same from host
+ *        arrays, plain loops.  The density's sum is kept in a long double.  The histogram takes 1 .. 2^28 bins. */
+#define PA_SELECT_MAX_RANKS 8
+#define PA_KDE_CHAIN 2048
+#define PA_HIST_WIDE_LDS_BINS 8192
+PA_API int pa_select_f64(pa_ctx *ctx, const double *d_v, uint64_t n, const uint64_t *h_ranks, uint32_t n_ranks, double *h_out);
+PA_API int pa_moments_f64(pa_ctx *ctx, const double *d_v, uint64_t n, double *out);
+PA_API int pa_kde_gauss_f64(pa_ctx *ctx, const double *d_v, uint64_t n, const double *h_grid, uint32_t n_grid, double bw, double *h_density);
+PA_API int pa_hist_uniform_f64_wide(pa_ctx *ctx, const double *d_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts);
+PA_API int pa_select_f64_host(const double *h_v, uint64_t n, const uint64_t *h_ranks, uint32_t n_ranks, double *h_out);
+PA_API int pa_moments_f64_host(const double *h_v, uint64_t n, double *out);
+PA_API int pa_kde_gauss_f64_host(const double *h_v, uint64_t n, const double *h_grid, uint32_t n_grid, double bw, double *h_density);
+PA_API int pa_hist_uniform_f64_wide_host(const double *h_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */

@@ -29,6 +29,9 @@ PA_FRAGANI_REUSE_INDEX = 1
 PA_FRAGANI_COLUMNS_ONLY = 2
 PA_PAIRS_AUTO, PA_PAIRS_BITROW, PA_PAIRS_MERGE, PA_PAIRS_BITROW_HASH = 0, 1, 2, 3
 PA_ALIGN_BASES = 64
+PA_SELECT_MAX_RANKS = 8
+PA_KDE_CHAIN = 2048  # the longest run of sequential additions of pa_kde_gauss_f64 (the c of DESIGN.md section 7e)
+PA_HIST_WIDE_LDS_BINS = 8192  # pa_hist_uniform_f64_wide counts in LDS up to this many bins
 PROF_PHASES = {"kmer_hash": 0, "sketch_sort": 1, "pair_dict": 2, "pair_count": 3, "ani": 4, "frag_index": 5, "frag_seed": 6, "frag_map": 7,
                "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11, "rowdist": 12}
 PA_AGG = {"min": 0, "max": 1, "mean": 2}
@@ -177,6 +180,14 @@ SIGNATURES: dict[str, tuple] = {
     "pa_minmax_f64_host": (C.c_int, [_vp, C.c_uint64, _vp, _u64p]),
     "pa_hist_uniform_f64_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint32, _vp]),
     "pa_write_pairs_tsv": (C.c_int, [C.c_char_p, C.c_char_p, _vp, _vp, C.c_uint64]),
+    "pa_select_f64": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "pa_moments_f64": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "pa_kde_gauss_f64": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_double, _vp]),
+    "pa_hist_uniform_f64_wide": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "pa_select_f64_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "pa_moments_f64_host": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "pa_kde_gauss_f64_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint32, C.c_double, _vp]),
+    "pa_hist_uniform_f64_wide_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint32, _vp]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),
     "pa_prof_get": (C.c_int, [_vp, C.c_int, _f64p, _u64p]),

@@ -760,6 +760,49 @@ class HipEngine:
         )
         return counts
 
+    # -- plot-run's distributions
+    def select(self, values, ranks) -> np.ndarray:
+        """``pa_select_f64``: the values at the zero-based ``ranks`` (at most 8, in any order) among the non-NaN
+        elements of ``values`` in ascending order, ``numpy.sort(v)[ranks]``; ``values`` is a host array or a float64
+        tensor on this device, which is neither copied nor sorted."""
+        d_v = self._f64_on_device(values).reshape(-1)
+        h_ranks = np.ascontiguousarray(ranks, dtype=np.uint64).reshape(-1)
+        out = np.empty(len(h_ranks), dtype=np.float64)
+        self._check(self.lib.pa_select_f64(self.ctx, d_v.data_ptr(), d_v.numel(), h_ranks.ctypes.data, len(h_ranks), out.ctypes.data), "pa_select_f64")
+        return out
+
+    def moments(self, values) -> tuple[float, float]:
+        """``pa_moments_f64``: the mean of the non-NaN elements of ``values`` and the sum of their squared deviations
+        from it, the same bits every run; ``(nan, nan)`` when there is none."""
+        d_v = self._f64_on_device(values).reshape(-1)
+        out = (C.c_double * 2)(float("nan"), float("nan"))
+        self._check(self.lib.pa_moments_f64(self.ctx, d_v.data_ptr(), d_v.numel(), out), "pa_moments_f64")
+        return float(out[0]), float(out[1])
+
+    def kde_gauss(self, values, grid, bw: float) -> np.ndarray:
+        """``pa_kde_gauss_f64``: the Gaussian kernel density of the non-NaN elements of ``values`` with bandwidth ``bw``
+        at the ``grid`` points (at most 1024), the same bits every run."""
+        d_v = self._f64_on_device(values).reshape(-1)
+        h_grid = np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)
+        density = np.empty(len(h_grid), dtype=np.float64)
+        self._check(
+            self.lib.pa_kde_gauss_f64(self.ctx, d_v.data_ptr(), d_v.numel(), h_grid.ctypes.data, len(h_grid), float(bw), density.ctypes.data), "pa_kde_gauss_f64"
+        )
+        return density
+
+    def hist_uniform_wide(self, values, edges) -> np.ndarray:
+        """``pa_hist_uniform_f64_wide``: ``hist_uniform`` for up to 2^20 bins."""
+        d_v = self._f64_on_device(values).reshape(-1)
+        h_edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if h_edges.ndim != 1 or len(h_edges) < 2:
+            raise ValueError(f"edges of shape {h_edges.shape}, expected at least two in one dimension")
+        counts = np.zeros(len(h_edges) - 1, dtype=np.uint64)
+        self._check(
+            self.lib.pa_hist_uniform_f64_wide(self.ctx, d_v.data_ptr(), d_v.numel(), h_edges.ctypes.data, len(counts), counts.ctypes.data),
+            "pa_hist_uniform_f64_wide",
+        )
+        return counts
+
     # -- profiling
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")

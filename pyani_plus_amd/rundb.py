@@ -51,7 +51,8 @@ import numpy as np
 from . import _capi, launch, wire
 from . import classify as classify_mod
 from . import cluster as cluster_mod
-from . import heatmap_figure, run_comp_figure
+from . import distribution as distribution_mod
+from . import distribution_figure, heatmap_figure, run_comp_figure
 from . import run_comp as run_comp_mod
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
@@ -1434,7 +1435,7 @@ def _write_scatter_tables(logger, conn, run: Run, outdir: Path) -> list[Path]:
 
 
 def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", formats: tuple[str, ...] = ("tsv",),  # noqa: PLR0913
-             engine=None, logger: logging.Logger | None = None) -> list[Path]:
+             engine=None, logger: logging.Logger | None = None, distributions: bool = False) -> list[Path]:
     """Write what the reference's ``plot-run`` computes for a complete run: the clustered heatmap tables
     ``<method>_{identity,query_cov,hadamard,tANI}_heatmap.tsv`` and the scatter tables
     ``<method>_{query_cov,tANI}_scatter.tsv``, byte for byte what the reference writes from the same database, with its
@@ -1447,10 +1448,18 @@ def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     ``pyani_plus_amd.cluster`` with the same bits.  Every matrix is clustered on its own.
 
     ``formats``: ``tsv`` writes the tables; any other format (``png``, ``pdf``, ``svg``, ``jpg``) adds the heatmap figure
-    with its row dendrogram, drawn with matplotlib alone.  The reference's distribution and scatter figures are not made.
+    with its row dendrogram, drawn with matplotlib alone.  The reference's scatter figures are not made.
     A comparison with a zero Hadamard product is written to the tANI scatter table as ``inf``, where the reference raises.
 
-    ``engine``: a ``HipEngine`` computes the row distances on the GPU; None on the host.  Returns the written paths."""
+    ``distributions``: also the score distribution of each matrix that is plotted (``pyani_plus_amd.distribution``):
+    with ``tsv`` the tables ``<method>_<score>_dist_hist.tsv`` (``#left TAB right TAB count``, the bins of
+    ``numpy.histogram(cells, "auto")``) and ``<method>_<score>_dist_kde.tsv`` (``#x TAB density``, scipy's
+    ``gaussian_kde`` on seaborn's 200-point grid; the header alone for fewer than two cells or cells that are all
+    equal), floats as ``repr``; with an image format the reference's ``<method>_<score>_dist.<ext>``, histogram, density
+    and rug.  The reference writes no table for a distribution: the two are this project's.  Off by default.
+
+    ``engine``: a ``HipEngine`` computes the row distances and the distributions on the GPU; None on the host.  Returns
+    the written paths."""
     logger = logger or logging.getLogger("pyani_plus_amd")
     if str(database) == ":memory:" or not Path(database).is_file():
         sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
@@ -1501,6 +1510,22 @@ def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
                 table.to_csv(written[-1], sep="\t")
             else:
                 heatmap_figure.draw_heatmap(table, tree, leaves, name, color_scheme, written[-1])
+        if distributions:
+            try:
+                cells = np.ascontiguousarray(matrix.to_numpy(dtype=float))
+                values = engine.torch.from_numpy(cells).to(engine.device) if engine is not None else cells  # uploaded once
+                dist = distribution_mod.describe(values, engine, logger)
+                rug = distribution_mod.rug_counts(values, name, dist, engine) if images else None
+            except HipBackendError as err:
+                sourmash_hip.backend_failure(logger, f"plot-run distribution of {name}", err)
+            if "tsv" in formats:
+                written.append(outdir / f"{method}_{name}_dist_hist.tsv")
+                distribution_mod.write_hist_tsv(written[-1], dist)
+                written.append(outdir / f"{method}_{name}_dist_kde.tsv")
+                distribution_mod.write_kde_tsv(written[-1], dist)
+            for ext in images:
+                written.append(outdir / f"{method}_{name}_dist.{ext}")
+                distribution_figure.draw_distribution(dist, rug, name, written[-1])
     logger.info("Wrote %d images to %s/%s_*.*", len(written), outdir, method)
     return written
 
@@ -1673,7 +1698,8 @@ def main(argv: list[str] | None = None) -> int:
     p_p.add_argument("--run-id", type=int, default=None)
     p_p.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
     p_p.add_argument("--formats", default="tsv", help="comma separated: tsv for the tables, png, pdf, svg or jpg for the heatmap figures (matplotlib)")
-    p_p.add_argument("--device", type=int, default=None, help="compute the row distances on this GPU (default: on the host)")
+    p_p.add_argument("--distributions", action="store_true", help="also each score's distribution: histogram and density tables, and the figure with an image format")
+    p_p.add_argument("--device", type=int, default=None, help="compute the row distances and the distributions on this GPU (default: on the host)")
     p_p.add_argument("--verbose", "-v", action="store_true")
     p_pc = sub.add_parser("plot-run-comp", help="the identities of further runs against a reference run's, pair by pair")
     p_pc.add_argument("--database", "-d", required=True, type=Path)
@@ -1716,7 +1742,8 @@ def main(argv: list[str] | None = None) -> int:
                         print(path)
                 else:
                     formats = tuple(f for f in args.formats.split(",") if f)
-                    for path in plot_run(args.database, args.outdir, run_id=args.run_id, label=args.label, formats=formats, engine=engine, logger=logger):
+                    for path in plot_run(args.database, args.outdir, run_id=args.run_id, label=args.label, formats=formats, engine=engine, logger=logger,
+                                         distributions=args.distributions):
                         print(path)
             finally:
                 if engine is not None:
