@@ -618,6 +618,36 @@ PA_API int pa_moments_f64_host(const double *h_v, uint64_t n, double *out);
 PA_API int pa_kde_gauss_f64_host(const double *h_v, uint64_t n, const double *h_grid, uint32_t n_grid, double bw, double *h_density);
 PA_API int pa_hist_uniform_f64_wide_host(const double *h_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts);
 
+/* ---- plot-run: scatter figures ----
+ * What the reference's plot_scatter (pyani_plus/plot_run.py:218-299) hands seaborn.jointplot as one marker per
+ * comparison, restated as a raster over the joint panel: N^2 points (x[t], y[t]), t = 0 .. n - 1, binned into
+ * bins_x x bins_y cells; per cell the number of points and the index of the last one, whose colour an overdrawn stack
+ * of markers shows.
+ *
+ *   pa_bin2d_f64             (device) point t counts iff x[t] >= xedges[0] && x[t] <= xedges[bins_x] and the same holds
+ *        for y[t] and the y edges (NaN fails).  Its bin on each axis is exactly pa_hist_uniform_f64's: the correctly
+ *        rounded division, the rounded multiplication, the clamp to bins - 1 and the two corrections against the edges.
+ *        h_counts and h_last are u64[bins_x * bins_y] with cell (ix, iy) at ix * bins_y + iy, numpy.histogram2d's
+ *        layout: h_counts = histogram2d(x, y, (xedges, yedges))[0]; h_last = the largest t among the cell's points,
+ *        PA_BIN2D_NONE for an empty cell.  One grid-stride pass; a wave first merges the points that share its leading
+ *        cell into one update; grids of up to PA_BIN2D_LDS_CELLS cells are counted wholly in LDS, larger ones through
+ *        a direct-mapped cache of PA_BIN2D_SLOTS slots in LDS, the slot of a cell being cell % PA_BIN2D_SLOTS: the
+ *        first cell to claim a slot in a workgroup keeps it, the other cells of that slot go to 32-bit integer atomics
+ *        in global memory.  Sums and maxima of integers only, no floating-point atomics: the same bits run to run and
+ *        as the host twin.  One host synchronisation.  PA_E_INVALID, checked before any array is touched: bins_x or
+ *        bins_y outside 1 .. PA_BIN2D_MAX_BINS; n >= 2^32 - 1 (a cell holds t + 1 in 32 bits on the device); on either
+ *        axis, named in the message, an edge that is not finite or lies below the one before it, and a last edge minus
+ *        the first that is not positive and finite.  n = 0 is valid: every cell empty.
+ *   pa_bin2d_f64_host        the same from host arrays, one plain loop, the same bits, the same checks. */
+#define PA_BIN2D_MAX_BINS 1024
+#define PA_BIN2D_LDS_CELLS 4096
+#define PA_BIN2D_SLOTS 2048
+#define PA_BIN2D_NONE 0xFFFFFFFFFFFFFFFFULL
+PA_API int pa_bin2d_f64(pa_ctx *ctx, const double *d_x, const double *d_y, uint64_t n, const double *h_xedges, uint32_t bins_x,
+                        const double *h_yedges, uint32_t bins_y, uint64_t *h_counts, uint64_t *h_last);
+PA_API int pa_bin2d_f64_host(const double *h_x, const double *h_y, uint64_t n, const double *h_xedges, uint32_t bins_x,
+                             const double *h_yedges, uint32_t bins_y, uint64_t *h_counts, uint64_t *h_last);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */

@@ -32,6 +32,10 @@ PA_ALIGN_BASES = 64
 PA_SELECT_MAX_RANKS = 8
 PA_KDE_CHAIN = 2048  # the longest run of sequential additions of pa_kde_gauss_f64 (the c of DESIGN.md section 7e)
 PA_HIST_WIDE_LDS_BINS = 8192  # pa_hist_uniform_f64_wide counts in LDS up to this many bins
+PA_BIN2D_MAX_BINS = 1024  # pa_bin2d_f64: bins per axis, at most
+PA_BIN2D_LDS_CELLS = 4096  # ... counts grids of up to this many cells wholly in LDS
+PA_BIN2D_SLOTS = 2048  # ... and larger ones through this many direct-mapped slots: the slot of a cell is cell % PA_BIN2D_SLOTS
+PA_BIN2D_NONE = 0xFFFFFFFFFFFFFFFF  # the `last` of an empty cell
 PROF_PHASES = {"kmer_hash": 0, "sketch_sort": 1, "pair_dict": 2, "pair_count": 3, "ani": 4, "frag_index": 5, "frag_seed": 6, "frag_map": 7,
                "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11, "rowdist": 12}
 PA_AGG = {"min": 0, "max": 1, "mean": 2}
@@ -188,6 +192,8 @@ SIGNATURES: dict[str, tuple] = {
     "pa_moments_f64_host": (C.c_int, [_vp, C.c_uint64, _vp]),
     "pa_kde_gauss_f64_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint32, C.c_double, _vp]),
     "pa_hist_uniform_f64_wide_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "pa_bin2d_f64": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    "pa_bin2d_f64_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),
     "pa_prof_get": (C.c_int, [_vp, C.c_int, _f64p, _u64p]),

@@ -1,0 +1,36 @@
+// scatter_common.h -- what scatter.hip (device) and scatter_host.cpp (host twin) share: the bin of a value among
+// uniform edges, which is pa_hist_uniform_f64's rule restated once for both, and the argument check of pa_bin2d_f64 and
+// pa_bin2d_f64_host.  rc_hist_kernel (runcomp.hip) and dist_hist_wide_kernel (dist.hip) keep their own copies of the rule.
+// Both translation units are built with -ffp-contract=off: the bin index is a rounded division, then a rounded
+// multiplication, and must not become a fused one.
+#ifndef PA_SCATTER_COMMON_H
+#define PA_SCATTER_COMMON_H
+#include <cstdint>
+
+#ifdef __HIPCC__
+#define PA_HD __host__ __device__ __forceinline__
+#else
+#define PA_HD inline
+#endif
+
+#pragma clang fp contract(off)
+
+// The bin of x among `bins` uniform bins with these bins + 1 edges; the caller has checked first <= x <= last, where
+// first = edges[0], last = edges[bins], span = last - first and nb = (double)bins.  numpy/lib/_histograms_impl.py, the
+// uniform-bins branch.
+PA_HD uint32_t pa_uniform_bin(double x, double first, double span, double nb, uint32_t bins, const double *edges) {
+  const double t = (x - first) / span;  // in [0, 1]: both differences are rounded the same way
+  uint32_t b = (uint32_t)(t * nb);      // in [0, bins]
+  if (b >= bins) b = bins - 1;          // the last edge belongs to the last bin
+  if (x < edges[b]) --b;                // never at b = 0: x >= first
+  if (x >= edges[b + 1] && b != bins - 1) ++b;
+  return b;
+}
+
+// PA_OK, or PA_E_INVALID with the message set (`who` names the entry point): a null argument, bins outside
+// 1 .. PA_BIN2D_MAX_BINS on either axis, n >= 2^32 - 1, and the edge errors of pa_hist_uniform_f64 with the axis named.
+// Reads the edges and nothing else.  scatter_host.cpp
+int pa_bin2d_validate(const char *who, const void *x, const void *y, uint64_t n, const double *h_xedges, uint32_t bins_x,
+                      const double *h_yedges, uint32_t bins_y, const uint64_t *h_counts, const uint64_t *h_last);
+
+#endif  // PA_SCATTER_COMMON_H

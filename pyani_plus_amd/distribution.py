@@ -160,9 +160,22 @@ class Distribution:
     density: np.ndarray | None
 
 
-def describe(values, engine=None, logger: logging.Logger | None = None) -> Distribution:
-    """The histogram and the density of the non-NaN elements of ``values``: a host array, or with an ``engine`` a
-    float64 tensor on its device, which is read in place.  Both backends take the same steps."""
+@dataclass
+class Histogram:
+    """``n`` values from ``lo`` to ``hi`` and their automatic histogram: ``edges`` and uint64 ``counts``."""
+
+    n: int
+    lo: float
+    hi: float
+    edges: np.ndarray
+    counts: np.ndarray
+
+
+def auto_histogram(values, engine=None, logger: logging.Logger | None = None) -> Histogram:
+    """``numpy.histogram(v, "auto")`` of the non-NaN elements ``v`` of ``values`` (a host array, or with an ``engine`` a
+    float64 tensor on its device, which is read in place): the range, the four order statistics of the automatic rule,
+    ``auto_bin_edges`` and the uniform-bin counts; above ``WIDE_MAX_BINS`` bins the device's values are counted on the
+    host.  ``ValueError`` when every element is NaN."""
     on_device = engine is not None
     lo, hi, n = engine.minmax(values) if on_device else run_comp.minmax_host(values)
     if not n:
@@ -177,6 +190,15 @@ def describe(values, engine=None, logger: logging.Logger | None = None) -> Distr
         counts = hist_uniform_wide_host(values.cpu().numpy() if hasattr(values, "cpu") else values, edges)
     else:
         counts = engine.hist_uniform_wide(values, edges) if on_device else hist_uniform_wide_host(values, edges)
+    return Histogram(n, lo, hi, edges, counts)
+
+
+def describe(values, engine=None, logger: logging.Logger | None = None) -> Distribution:
+    """The histogram and the density of the non-NaN elements of ``values``: a host array, or with an ``engine`` a
+    float64 tensor on its device, which is read in place.  Both backends take the same steps."""
+    on_device = engine is not None
+    hist = auto_histogram(values, engine, logger)
+    n, lo, hi, edges, counts = hist.n, hist.lo, hist.hi, hist.edges, hist.counts
     if n < 2 or lo == hi:  # noqa: PLR2004
         return Distribution(n, lo, hi, edges, counts, None, None, None)
     _mean, squares = engine.moments(values) if on_device else moments_host(values)
@@ -194,7 +216,7 @@ def rug_counts(values, name: str, dist: Distribution, engine=None) -> tuple[np.n
     return edges, (engine.hist_uniform(values, edges) if engine is not None else run_comp.hist_uniform_host(values, edges))
 
 
-def write_hist_tsv(path, dist: Distribution) -> None:
+def write_hist_tsv(path, dist: Distribution | Histogram) -> None:
     """``#left TAB right TAB count`` and a line per bin, the floats as ``repr``."""
     with open(path, "w") as handle:
         handle.write("#left\tright\tcount\n")

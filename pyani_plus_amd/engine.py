@@ -803,6 +803,29 @@ class HipEngine:
         )
         return counts
 
+    # -- plot-run's scatter figures
+    def bin2d(self, x, y, xedges, yedges) -> tuple[np.ndarray, np.ndarray]:
+        """``pa_bin2d_f64``: ``(counts, last)``, uint64 arrays of shape ``(len(xedges) - 1, len(yedges) - 1)``:
+        ``numpy.histogram2d``'s counts of the points ``(x, y)`` over the uniform edges the caller made
+        (``run_comp.hist_edges``, at most 1024 bins an axis) and the largest index among each cell's points
+        (``scatter.NONE`` for an empty cell), the same bits every run.  ``x`` and ``y`` are host arrays or float64 tensors
+        on this device, which are read in place."""
+        d_x, d_y = self._f64_on_device(x).reshape(-1), self._f64_on_device(y).reshape(-1)
+        if d_x.shape != d_y.shape:
+            raise ValueError(f"{d_x.numel()} x values and {d_y.numel()} y values")
+        h_xe, h_ye = np.ascontiguousarray(xedges, dtype=np.float64), np.ascontiguousarray(yedges, dtype=np.float64)
+        for h_edges in (h_xe, h_ye):
+            if h_edges.ndim != 1 or len(h_edges) < 2:
+                raise ValueError(f"edges of shape {h_edges.shape}, expected at least two in one dimension")
+        shape = (len(h_xe) - 1, len(h_ye) - 1)
+        counts, last = np.empty(shape, dtype=np.uint64), np.empty(shape, dtype=np.uint64)
+        self._check(
+            self.lib.pa_bin2d_f64(self.ctx, d_x.data_ptr(), d_y.data_ptr(), d_x.numel(), h_xe.ctypes.data, shape[0], h_ye.ctypes.data, shape[1],
+                                  counts.ctypes.data, last.ctypes.data),
+            "pa_bin2d_f64",
+        )  # fmt: skip
+        return counts, last
+
     # -- profiling
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")

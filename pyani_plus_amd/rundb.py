@@ -52,8 +52,9 @@ from . import _capi, launch, wire
 from . import classify as classify_mod
 from . import cluster as cluster_mod
 from . import distribution as distribution_mod
-from . import distribution_figure, heatmap_figure, run_comp_figure
+from . import distribution_figure, heatmap_figure, run_comp_figure, scatter_figure
 from . import run_comp as run_comp_mod
+from . import scatter as scatter_mod
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
 from .engine import load_fasta_files
@@ -1434,8 +1435,47 @@ def _write_scatter_tables(logger, conn, run: Run, outdir: Path) -> list[Path]:
     return written
 
 
+def _run_label(genome, label: str) -> str:
+    """The label ``_relabelled`` gives a genome of the run."""
+    return {"md5": genome.genome_hash, "filename": genome.fasta_filename}.get(label) or filename_stem(genome.fasta_filename)
+
+
+def _write_scatter_figures(logger, method: str, frames: dict, lengths: np.ndarray, outdir: Path, formats: tuple[str, ...], bins: int,  # noqa: PLR0913
+                           engine, warned: int | None) -> list[Path]:
+    """The scatter figures of ``plot_run(scatter=True)`` and their tables (``pyani_plus_amd.scatter``), from the
+    relabelled identity, query coverage and Hadamard frames; ``lengths``: the query length of each row.  ``warned``: the
+    position of the score the scatter tables have already logged the no-valid-values warning for, or None."""
+    n = len(lengths)
+    cells = {name: np.ascontiguousarray(frames[name].to_numpy(dtype=float)) for name in ("identity", "query_cov")}
+    cells["tANI"] = -classify_mod.tani_scores(frames["hadamard"].to_numpy(dtype=float))  # -log(h) if h else nan
+    written: list[Path] = []
+    try:
+        if engine is not None:
+            cells = {name: engine.torch.from_numpy(np.ascontiguousarray(v)).to(engine.device) for name, v in cells.items()}  # uploaded once
+        for position, (caption, name) in enumerate((("Query coverage", "query_cov"), ("tANI", "tANI"))):
+            data = scatter_mod.describe(cells["identity"], cells[name], lengths, n, engine, bins, logger)
+            if data is None:
+                if warned != position:
+                    logger.warning("No valid identity, %s values from %s run", caption, method)
+                return written
+            if "tsv" in formats:
+                written.append(outdir / f"{method}_{name}_scatter_grid.tsv")
+                scatter_mod.write_grid_tsv(written[-1], data)
+                for axis, hist in (("x", data.x_hist), ("y", data.y_hist)):
+                    written.append(outdir / f"{method}_{name}_scatter_{axis}_hist.tsv")
+                    distribution_mod.write_hist_tsv(written[-1], hist)
+            for ext in formats:
+                if ext != "tsv":
+                    written.append(outdir / f"{method}_{name}_scatter.{ext}")
+                    scatter_figure.draw_scatter(data, caption, written[-1])
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, "plot-run scatter figures", err)
+    return written
+
+
 def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", formats: tuple[str, ...] = ("tsv",),  # noqa: PLR0913
-             engine=None, logger: logging.Logger | None = None, distributions: bool = False) -> list[Path]:
+             engine=None, logger: logging.Logger | None = None, distributions: bool = False, scatter: bool = False,
+             scatter_bins: int = scatter_mod.GRID) -> list[Path]:
     """Write what the reference's ``plot-run`` computes for a complete run: the clustered heatmap tables
     ``<method>_{identity,query_cov,hadamard,tANI}_heatmap.tsv`` and the scatter tables
     ``<method>_{query_cov,tANI}_scatter.tsv``, byte for byte what the reference writes from the same database, with its
@@ -1448,7 +1488,7 @@ def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     ``pyani_plus_amd.cluster`` with the same bits.  Every matrix is clustered on its own.
 
     ``formats``: ``tsv`` writes the tables; any other format (``png``, ``pdf``, ``svg``, ``jpg``) adds the heatmap figure
-    with its row dendrogram, drawn with matplotlib alone.  The reference's scatter figures are not made.
+    with its row dendrogram, drawn with matplotlib alone.  The reference's scatter figures are made with ``scatter``.
     A comparison with a zero Hadamard product is written to the tANI scatter table as ``inf``, where the reference raises.
 
     ``distributions``: also the score distribution of each matrix that is plotted (``pyani_plus_amd.distribution``):
@@ -1458,8 +1498,22 @@ def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     equal), floats as ``repr``; with an image format the reference's ``<method>_<score>_dist.<ext>``, histogram, density
     and rug.  The reference writes no table for a distribution: the two are this project's.  Off by default.
 
-    ``engine``: a ``HipEngine`` computes the row distances and the distributions on the GPU; None on the host.  Returns
-    the written paths."""
+    ``scatter``: also the reference's two scatter figures, identity against query coverage and against tANI
+    (``pyani_plus_amd.scatter``), after everything else and in that order.  The reference draws a marker per comparison,
+    coloured by the query's length, with automatic histograms on the margins; here the joint panel is a raster of
+    ``scatter_bins`` x ``scatter_bins`` cells (1 to 1024, 256 by default) over the ranges of the valid points, a cell in
+    the colour of the last point that falls into it, which is what overdrawn markers show.  The points are the cells of
+    the matrices above in row-major order (rows = query); a point is valid iff neither value is NaN, so a zero Hadamard
+    product (tANI NaN) drops out.  Two things are this project's choices: "last" is by that row-major order of the
+    label-sorted matrix, where the reference's is ``comparison_id`` order, and for runs that fit the cache the values are
+    the cached 10-decimal ones, as for the distributions.  With ``tsv``: ``<method>_<y>_scatter_grid.tsv``
+    (``#x_left x_right y_left y_right count query_length``, a line per non-empty cell, x-major) and the margins
+    ``<method>_<y>_scatter_x_hist.tsv`` and ``<method>_<y>_scatter_y_hist.tsv`` (as ``_dist_hist.tsv``); with an image
+    format the reference's ``<method>_<y>_scatter.<ext>``.  Without a valid point the reference's warning is logged and
+    neither this figure nor the next is made.  Off by default.
+
+    ``engine``: a ``HipEngine`` computes the row distances, the distributions and the scatter rasters on the GPU; None on
+    the host.  Returns the written paths."""
     logger = logger or logging.getLogger("pyani_plus_amd")
     if str(database) == ":memory:" or not Path(database).is_file():
         sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
@@ -1470,6 +1524,8 @@ def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
             importlib.import_module("matplotlib")
         except ImportError:
             sourmash_hip.log_sys_exit(logger, f"Image formats ({', '.join(images)}) need matplotlib, which cannot be imported; only tsv is available")
+    if scatter and not 1 <= int(scatter_bins) <= scatter_mod.MAX_BINS:
+        sourmash_hip.log_sys_exit(logger, f"--scatter-bins {scatter_bins}: expected 1 to {scatter_mod.MAX_BINS}")
     outdir = Path(outdir)
     if not outdir.is_dir():
         logger.warning("Output directory %s does not exist, making it.", outdir)
@@ -1485,6 +1541,8 @@ def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     method = run.configuration.method
     frames = dict(zip(("identity", "query_cov", "hadamard"), _relabelled(logger, run, _score_frames(logger, conn, run), label)))
     written = _write_scatter_tables(logger, conn, run, outdir) if "tsv" in formats else []
+    scatter_tables = len(written)
+    genome_lengths = dict(conn.execute("SELECT genome_hash, length FROM genomes")) if scatter else {}
     conn.close()
     for name, color_scheme, na_fill in _PLOT_SCORES:
         if name == "tANI":
@@ -1526,6 +1584,12 @@ def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
             for ext in images:
                 written.append(outdir / f"{method}_{name}_dist.{ext}")
                 distribution_figure.draw_distribution(dist, rug, name, written[-1])
+    if scatter:
+        by_label = {_run_label(a, label): genome_lengths[a.genome_hash] for a in run.fasta_hashes}
+        lengths = np.array([by_label[q] for q in frames["identity"].index], dtype=np.int64)
+        # the scatter tables have logged the warning for the first score they found no comparison for
+        warned = scatter_tables if "tsv" in formats else None
+        written += _write_scatter_figures(logger, method, frames, lengths, outdir, formats, int(scatter_bins), engine, warned)
     logger.info("Wrote %d images to %s/%s_*.*", len(written), outdir, method)
     return written
 
@@ -1699,7 +1763,9 @@ def main(argv: list[str] | None = None) -> int:
     p_p.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
     p_p.add_argument("--formats", default="tsv", help="comma separated: tsv for the tables, png, pdf, svg or jpg for the heatmap figures (matplotlib)")
     p_p.add_argument("--distributions", action="store_true", help="also each score's distribution: histogram and density tables, and the figure with an image format")
-    p_p.add_argument("--device", type=int, default=None, help="compute the row distances and the distributions on this GPU (default: on the host)")
+    p_p.add_argument("--scatter", action="store_true", help="also the two scatter figures (identity against query coverage and tANI) as rasters: their grid and margin tables, and the figure with an image format")
+    p_p.add_argument("--scatter-bins", type=int, default=scatter_mod.GRID, help="cells per axis of a scatter figure's raster, 1 to 1024 (default 256)")
+    p_p.add_argument("--device", type=int, default=None, help="compute the row distances, the distributions and the scatter rasters on this GPU (default: on the host)")
     p_p.add_argument("--verbose", "-v", action="store_true")
     p_pc = sub.add_parser("plot-run-comp", help="the identities of further runs against a reference run's, pair by pair")
     p_pc.add_argument("--database", "-d", required=True, type=Path)
@@ -1743,7 +1809,7 @@ def main(argv: list[str] | None = None) -> int:
                 else:
                     formats = tuple(f for f in args.formats.split(",") if f)
                     for path in plot_run(args.database, args.outdir, run_id=args.run_id, label=args.label, formats=formats, engine=engine, logger=logger,
-                                         distributions=args.distributions):
+                                         distributions=args.distributions, scatter=args.scatter, scatter_bins=args.scatter_bins):
                         print(path)
             finally:
                 if engine is not None:
