@@ -561,7 +561,10 @@ PA_API int pa_linkage_average(uint32_t n, const double *h_condensed, double *h_Z
  *        multiplication, two roundings -- set to bins - 1 where it came out bins, decremented where v < edges[i], then
  *        incremented where v >= edges[i + 1] and i != bins - 1 (numpy/lib/_histograms_impl.py, the uniform-bins branch).
  *        PA_E_INVALID for bins outside 1 .. 1024, an edge that is not finite or lies below the one before it, and
- *        edges[bins] - edges[0] not positive and finite.  One host synchronisation.
+ *        edges[bins] - edges[0] not positive and finite.  One host synchronisation.  The rule is pa_uniform_bin
+ *        (csrc/uniform_bins.h), the one statement of it for this function, its wide form and pa_bin2d_f64, on the device
+ *        and on the host; the edge check is pa_check_uniform_edges (csrc/hist_host.cpp), the same for all of them; the
+ *        kernel and the host loop are csrc/hist.hip and csrc/hist_host.cpp.
  *   pa_runcomp_join_host, pa_minmax_f64_host, pa_hist_uniform_f64_host   the same from host arrays into host arrays,
  *        plain loops, the same bits.
  *   pa_write_pairs_tsv       (host) `header` and a newline, then n lines repr(x) TAB repr(y) with Python's
@@ -601,9 +604,10 @@ PA_API int pa_write_pairs_tsv(const char *path, const char *header, const double
  *        the sum's relative error is at most (PA_KDE_CHAIN + the tree's depth) * 2^-53.  PA_E_INVALID for n_grid outside
  *        1 .. 1024, a grid point that is not finite, bw that is not positive and finite, an infinite element and no
  *        non-NaN element.
- *   pa_hist_uniform_f64_wide (device) pa_hist_uniform_f64's rule, the same division and the same corrections, for
- *        1 .. 2^20 bins: counters in LDS up to PA_HIST_WIDE_LDS_BINS bins, 64-bit integer atomics on the counters in
- *        global memory above.  The same errors as pa_hist_uniform_f64, with this range of bins.
+ *   pa_hist_uniform_f64_wide (device) pa_hist_uniform_f64 with another limit, 1 .. 2^20 bins: the same function
+ *        (csrc/hist.hip), which chooses by the number of bins: edges and counters in LDS up to 1024 bins, counters in
+ *        LDS up to PA_HIST_WIDE_LDS_BINS bins, 64-bit integer atomics on the counters in global memory above.  The
+ *        same errors as pa_hist_uniform_f64, with this range of bins.
  *   pa_select_f64_host, pa_moments_f64_host, pa_kde_gauss_f64_host, pa_hist_uniform_f64_wide_host   the same from host
  *        arrays, plain loops.  The density's sum is kept in a long double.  The histogram takes 1 .. 2^28 bins. */
 #define PA_SELECT_MAX_RANKS 8

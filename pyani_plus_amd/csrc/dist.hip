@@ -1,6 +1,6 @@
 // dist.hip -- plot-run's score distributions on the device (gfx950, wave64): the order statistics the automatic bin
-// rule needs, the moments behind Scott's bandwidth, the Gaussian kernel density on a grid, and numpy's uniform-bin
-// histogram for up to 2^20 bins.  DESIGN.md section 7e has the definitions and the error bound.
+// rule needs, the moments behind Scott's bandwidth and the Gaussian kernel density on a grid.  The histogram itself is
+// hist.hip's.  DESIGN.md section 7e has the definitions and the error bound.
 //
 // pa_select_f64: an MSB radix select.  A double becomes a u64 key whose unsigned order is the order of the values (the
 // sign bit flipped for positive values, all bits for negative ones; -0.0 sorts directly below 0.0, which is the same
@@ -24,33 +24,22 @@
 // nothing.  The S slices of a grid point are added by halving in LDS, the workgroups' sums by halving in global memory
 // (one small launch per level): a fixed tree, no atomics, the same bits run to run.  The division and the exponent
 // are the definition's: (g - v) / bw correctly rounded, its square, times -0.5 (contraction is off for this file).
-//
-// pa_hist_uniform_f64_wide: the rule of pa_hist_uniform_f64 (runcomp.hip) with the edges read from global memory.
-// Up to kWideLdsBins bins a workgroup counts in u32 LDS counters and adds them once to the u64 counters in global
-// memory; above that every value is one u64 integer atomic on the global counters.
 #include <cmath>
 #include <cstring>
 
+#include "block_reduce_dev.h"
 #include "pa_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kMaxBlocks = 1024;  // grid-stride passes: four workgroups for each of the 256 CUs
+constexpr int kThreads = kStrideThreads;
 constexpr uint32_t kMaxRanks = PA_SELECT_MAX_RANKS;
 constexpr uint32_t kKdeChain = PA_KDE_CHAIN;  // c: the longest run of sequential additions of the density sum
 constexpr uint32_t kKdeAcc = 4;               // accumulators (grid point, slice) per lane
 constexpr uint32_t kKdeSlots = kThreads * kKdeAcc;  // 1024: accumulators per workgroup, and data staged at a time
-constexpr uint32_t kWideLdsBins = PA_HIST_WIDE_LDS_BINS;
-constexpr uint32_t kWideMaxBins = 1u << 20;
 static_assert(kKdeSlots == 1024 && kKdeChain % kKdeSlots == 0, "a slice of every S <= 1024 takes whole staged blocks");
-
-inline uint32_t stride_blocks(uint64_t n) {
-  const uint64_t want = (n + kThreads - 1) / kThreads;
-  return (uint32_t)(want < kMaxBlocks ? want : kMaxBlocks);
-}
 
 // ---- select -------------------------------------------------------------------
 __device__ __forceinline__ uint64_t order_key(double x) {
@@ -91,28 +80,10 @@ __global__ __launch_bounds__(kThreads) void dist_select_kernel(const double *__r
 }
 
 // ---- moments ------------------------------------------------------------------
-// the sum of the workgroup's `x` in thread 0, by halving: a fixed tree
-__device__ __forceinline__ double block_sum(double x, double *s_x) {
-  s_x[threadIdx.x] = x;
-  __syncthreads();
-  for (uint32_t step = kThreads / 2; step > 0; step >>= 1) {
-    if (threadIdx.x < step) s_x[threadIdx.x] += s_x[threadIdx.x + step];
-    __syncthreads();
-  }
-  const double total = s_x[0];
-  __syncthreads();
-  return total;
-}
-__device__ __forceinline__ unsigned long long block_count(unsigned long long x, unsigned long long *s_x) {
-  s_x[threadIdx.x] = x;
-  __syncthreads();
-  for (uint32_t step = kThreads / 2; step > 0; step >>= 1) {
-    if (threadIdx.x < step) s_x[threadIdx.x] += s_x[threadIdx.x + step];
-    __syncthreads();
-  }
-  const unsigned long long total = s_x[0];
-  __syncthreads();
-  return total;
+// the sum of the workgroup's `x`, by halving: a fixed tree
+template <typename T>
+__device__ __forceinline__ T block_sum(T x, T *s_x) {
+  return pa_dev::block_reduce<kThreads>(x, s_x, [](T a, T b) { return a + b; });
 }
 
 // SQUARES false: partial[2 b] = the sum of workgroup b's non-NaN elements, partial[2 b + 1] = the bits of their number.
@@ -134,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void dist_moments_kernel(const double *__
     }
   }
   sum = block_sum(sum, s_sum);
-  if (!SQUARES) cnt = block_count(cnt, s_cnt);
+  if (!SQUARES) cnt = block_sum(cnt, s_cnt);
   if (threadIdx.x == 0) {
     partial[2 * (uint64_t)blockIdx.x] = sum;
     if (!SQUARES) partial[2 * (uint64_t)blockIdx.x + 1] = __longlong_as_double((long long)cnt);
@@ -154,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void dist_moments_final_kernel(const doub
     if (!SQUARES) cnt += (unsigned long long)__double_as_longlong(partial[2 * (uint64_t)b + 1]);
   }
   sum = block_sum(sum, s_sum);
-  if (!SQUARES) cnt = block_count(cnt, s_cnt);
+  if (!SQUARES) cnt = block_sum(cnt, s_cnt);
   if (threadIdx.x == 0) {
     if (SQUARES) {
       result[1] = sum;
@@ -218,38 +189,6 @@ __global__ __launch_bounds__(kThreads) void dist_kde_fold_kernel(double *__restr
   const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
   const uint64_t w = i / n_grid;
   if (w < step && w + step < rows) partial[i] += partial[i + (uint64_t)step * n_grid];
-}
-
-// ---- wide histogram -------------------------------------------------------------
-template <bool LDS>
-__global__ __launch_bounds__(kThreads) void dist_hist_wide_kernel(const double *__restrict__ v, uint64_t n, const double *__restrict__ edges /*[bins + 1]*/,
-                                                                  uint32_t bins, unsigned long long *__restrict__ counts /*[bins]*/) {
-  __shared__ uint32_t s_counts[LDS ? kWideLdsBins : 1];
-  if (LDS) {
-    for (uint32_t b = threadIdx.x; b < bins; b += kThreads) s_counts[b] = 0;
-    __syncthreads();
-  }
-  const double first = edges[0], last = edges[bins];
-  const double span = last - first, nb = (double)bins;
-  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads) {
-    const double x = v[i];
-    if (x >= first && x <= last) {  // false for NaN
-      const double t = (x - first) / span;  // in [0, 1]
-      uint32_t b = (uint32_t)(t * nb);      // in [0, bins]
-      if (b >= bins) b = bins - 1;          // the last edge belongs to the last bin
-      if (x < edges[b]) --b;                // never at b = 0: x >= first
-      if (x >= edges[b + 1] && b != bins - 1) ++b;
-      if (LDS)
-        atomicAdd(&s_counts[b], 1u);
-      else
-        atomicAdd(&counts[b], 1ULL);
-    }
-  }
-  if (LDS) {
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < bins; b += kThreads)
-      if (s_counts[b]) atomicAdd(&counts[b], (unsigned long long)s_counts[b]);
-  }
 }
 
 }  // namespace
@@ -356,31 +295,4 @@ extern "C" int pa_kde_gauss_f64(pa_ctx *c, const double *d_v, uint64_t n, const 
   const double norm = 1.0 / ((double)valid * bw * sqrt(2.0 * M_PI));
   for (uint32_t j = 0; j < n_grid; ++j) h_density[j] *= norm;
   return PA_OK;
-}
-
-extern "C" int pa_hist_uniform_f64_wide(pa_ctx *c, const double *d_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts) {
-  PA_REQUIRE(c != nullptr && h_edges != nullptr && h_counts != nullptr, "pa_hist_uniform_f64_wide: null argument");
-  PA_REQUIRE(bins >= 1 && bins <= kWideMaxBins, "pa_hist_uniform_f64_wide: %u bins; 1 to 1048576", bins);
-  PA_REQUIRE(n < (1ULL << 40), "pa_hist_uniform_f64_wide: %llu values; a workgroup's counters are 32-bit", (unsigned long long)n);
-  for (uint32_t b = 0; b <= bins; ++b) {
-    const double e = h_edges[b];
-    PA_REQUIRE(e - e == 0.0, "pa_hist_uniform_f64_wide: edge %u is not finite", b);
-    PA_REQUIRE(b == 0 || h_edges[b - 1] <= e, "pa_hist_uniform_f64_wide: edge %u is below edge %u", b, b - 1);
-  }
-  const double span = h_edges[bins] - h_edges[0];
-  PA_REQUIRE(span > 0.0 && span - span == 0.0, "pa_hist_uniform_f64_wide: the last edge must be above the first and their difference finite");
-  for (uint32_t b = 0; b < bins; ++b) h_counts[b] = 0;
-  if (n == 0) return PA_OK;
-  PA_REQUIRE(d_v != nullptr, "pa_hist_uniform_f64_wide: null array");
-  PA_HIP(hipSetDevice(c->device));
-  PA_TRY(c->hist.reserve((2 * (uint64_t)bins + 1) * 8));
-  unsigned long long *d_counts = c->hist.as<unsigned long long>();
-  double *d_edges = reinterpret_cast<double *>(d_counts + bins);
-  PA_HIP(hipMemsetAsync(d_counts, 0, (uint64_t)bins * 8, c->stream));
-  PA_HIP(hipMemcpyAsync(d_edges, h_edges, ((uint64_t)bins + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (bins <= kWideLdsBins)
-    PA_TRY(PA_LAUNCH(c, dist_hist_wide_kernel<true>, stride_blocks(n), kThreads, 0, d_v, n, (const double *)d_edges, bins, d_counts));
-  else
-    PA_TRY(PA_LAUNCH(c, dist_hist_wide_kernel<false>, stride_blocks(n), kThreads, 0, d_v, n, (const double *)d_edges, bins, d_counts));
-  return pa_copy_to_host(c, h_counts, d_counts, (uint64_t)bins * 8);  // the caller's edges and counts are not touched after the return
 }

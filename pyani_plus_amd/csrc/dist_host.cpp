@@ -1,9 +1,8 @@
-// dist_host.cpp -- host twins of dist.hip: the order statistics, the moments, the Gaussian kernel density on a grid and
-// numpy's uniform-bin histogram for many bins, as plain loops.  They are what plot-run's distributions use without a
-// GPU and what the device kernels are compared with.  The select and the histogram give the same values and counts as
-// the device; the moments and the density add in another order and agree within the bound of DESIGN.md section 7e.
-// Built with -ffp-contract=off: the bin index is a rounded division followed by a rounded multiplication, and the
-// density's exponent is a rounded division, a rounded square and a halving.
+// dist_host.cpp -- host twins of dist.hip: the order statistics, the moments and the Gaussian kernel density on a grid,
+// as plain loops.  They are what plot-run's distributions use without a GPU and what the device kernels are compared
+// with; the histogram's twin is hist_host.cpp.  The select gives the same values as the device; the moments and the
+// density add in another order and agree within the bound of DESIGN.md section 7e.
+// Built with -ffp-contract=off: the density's exponent is a rounded division, a rounded square and a halving.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -88,33 +87,6 @@ int pa_kde_gauss_f64_host(const double *h_v, uint64_t n, const double *h_grid, u
       sum += (long double)exp(-0.5 * (z * z));
     }
     h_density[j] = (double)sum * norm;
-  }
-  return PA_OK;
-}
-
-int pa_hist_uniform_f64_wide_host(const double *h_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts) {
-  if (!h_edges || !h_counts || (n && !h_v)) { pa_set_error("pa_hist_uniform_f64_wide_host: null argument"); return PA_E_INVALID; }
-  if (bins < 1 || bins > (1u << 28)) { pa_set_error("pa_hist_uniform_f64_wide_host: %u bins; 1 to 268435456", bins); return PA_E_INVALID; }
-  for (uint32_t b = 0; b <= bins; ++b) {
-    if (!std::isfinite(h_edges[b])) { pa_set_error("pa_hist_uniform_f64_wide_host: edge %u is not finite", b); return PA_E_INVALID; }
-    if (b && h_edges[b - 1] > h_edges[b]) { pa_set_error("pa_hist_uniform_f64_wide_host: edge %u is below edge %u", b, b - 1); return PA_E_INVALID; }
-  }
-  const double first = h_edges[0], last = h_edges[bins];
-  const double span = last - first, nb = (double)bins;
-  if (!(span > 0.0) || !std::isfinite(span)) {
-    pa_set_error("pa_hist_uniform_f64_wide_host: the last edge must be above the first and their difference finite");
-    return PA_E_INVALID;
-  }
-  for (uint32_t b = 0; b < bins; ++b) h_counts[b] = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    const double x = h_v[i];
-    if (!(x >= first && x <= last)) continue;  // NaN too
-    const double t = (x - first) / span;
-    uint32_t b = (uint32_t)(t * nb);
-    if (b >= bins) b = bins - 1;
-    if (x < h_edges[b]) --b;  // never at b = 0: x >= first
-    if (x >= h_edges[b + 1] && b != bins - 1) ++b;
-    ++h_counts[b];
   }
   return PA_OK;
 }

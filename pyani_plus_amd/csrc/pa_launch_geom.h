@@ -33,6 +33,14 @@ constexpr LaunchVerdict launch_verdict(LaunchDim grid, LaunchDim block, const La
   return threads <= lim.threads_per_block ? LaunchVerdict::kGo : LaunchVerdict::kOutsideLimits;
 }
 
+// The grid of a grid-stride pass of 256-lane workgroups over n elements: ceil(n / 256) workgroups, at most 1024 (four
+// for each of the 256 CUs); workgroup b takes the elements 256 b + lane, then every 256 * grid further on.
+constexpr uint32_t kStrideThreads = 256, kStrideMaxBlocks = 1024;
+constexpr uint32_t stride_blocks(uint64_t n) {
+  const uint64_t want = ceil_div(n, kStrideThreads);
+  return (uint32_t)(want < kStrideMaxBlocks ? want : kStrideMaxBlocks);
+}
+
 // ---- run-time value to template argument --------------------------------------------------------------------------
 // Calls fn(std::integral_constant<int, V>{}) for the V of the list that equals v; false if none does, for the caller
 // to set its own error or take its own default.

@@ -1,12 +1,13 @@
-// runcomp.hip -- plot-run-comp on the device (gfx950, wave64): two runs joined pair by pair, the minimum and maximum
-// of a vector, and numpy's uniform-bin histogram of it.
+// runcomp.hip -- plot-run-comp on the device (gfx950, wave64): two runs joined pair by pair and the minimum and maximum
+// of a vector.  The histograms of the joined values are hist.hip's.
 //
 // The reference keeps one Python dictionary per run, keyed by (query_hash, subject_hash) tuples, looks every pair of
 // the other run up in the reference run's dictionary and hands the joined lists to Axes.hist
 // (pyani_plus/plot_run.py:404-575).  Here the reference run R is its n_ref x n_ref identity matrix (NaN: no value) and
 // the other run O is three arrays in database order: the row and the column of each of its comparisons in R's matrix,
 // and its own identity.  The join is then a gather and a stream compaction, and the histograms are reductions.
-// DESIGN.md section 7d has the definition and the measurements.
+// DESIGN.md section 7d has the definition and the measurements.  Contraction is off for this file, by the pragma below
+// and by the Makefile, as it is for the host twin.
 //
 // pa_runcomp_join, the shape of classify.hip:
 //   1. rc_join_kernel<false>: a lane per row.  A row survives iff q < n_ref, s < n_ref, y is not NaN and ref[q, s] is
@@ -36,28 +37,19 @@
 //
 // pa_minmax_f64: a grid-stride pass, at most 1024 workgroups, each reduces its share through LDS to one (min, max,
 // count) triple; a one-workgroup second pass reduces the triples.  No atomics; values are compared as values.
-//
-// pa_hist_uniform_f64: numpy.histogram's uniform-bin rule (numpy/lib/_histograms_impl.py): the bin of v is
-// ((v - first) / (last - first)) * bins truncated, with the three corrections against the edges.  The division is
-// the IEEE one (v_div_scale / v_div_fmas / v_div_fixup, correctly rounded) and the product is rounded on its own:
-// contraction is off for this file, by the pragma below and by the Makefile.  The edges are the caller's (numpy's
-// linspace in the driver), staged in LDS; the counters of a workgroup are u32 in LDS (a workgroup sees at most
-// n / 1024 + 256 values) and are added once to the u64 counters in global memory, which decides no position.  All
-// loads are 8 bytes per lane: the callers pass slices of tensors, which promise no wider alignment.
 #include <cstring>
 
+#include "block_reduce_dev.h"
 #include "pa_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kStrideThreads;
 constexpr int kGroups = 4;                                      // 64-row groups per wave
 constexpr uint32_t kRowsPerWg = (uint32_t)kThreads * kGroups;  // T
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr uint32_t kMaxBlocks = 1024;  // grid-stride passes: four workgroups for each of the 256 CUs
-constexpr uint32_t kMaxBins = 1024;
 
 template <bool SCATTER>
 __global__ __launch_bounds__(kThreads) void rc_join_kernel(const double *__restrict__ ref, uint32_t n_ref, const uint32_t *__restrict__ q,
@@ -103,31 +95,20 @@ __global__ __launch_bounds__(kThreads) void rc_join_kernel(const double *__restr
   }
 }
 
-// the workgroup's (min, max, count) in thread 0; s_* hold kThreads elements each
-__device__ __forceinline__ void block_minmax(double &lo, double &hi, unsigned long long &cnt, double *s_lo, double *s_hi,
-                                             unsigned long long *s_cnt) {
-  s_lo[threadIdx.x] = lo;
-  s_hi[threadIdx.x] = hi;
-  s_cnt[threadIdx.x] = cnt;
-  __syncthreads();
-  for (uint32_t step = kThreads / 2; step > 0; step >>= 1) {
-    if (threadIdx.x < step) {
-      const double a = s_lo[threadIdx.x + step], b = s_hi[threadIdx.x + step];
-      if (a < s_lo[threadIdx.x]) s_lo[threadIdx.x] = a;
-      if (b > s_hi[threadIdx.x]) s_hi[threadIdx.x] = b;
-      s_cnt[threadIdx.x] += s_cnt[threadIdx.x + step];
-    }
-    __syncthreads();
-  }
-  lo = s_lo[0];
-  hi = s_hi[0];
-  cnt = s_cnt[0];
+// (min, max, count) of the non-NaN values seen so far; the identities compare correctly with every value
+struct MinMax {
+  double lo, hi;
+  unsigned long long cnt;
+};
+__device__ __forceinline__ MinMax block_minmax(MinMax mine, MinMax *s) {
+  return pa_dev::block_reduce<kThreads>(mine, s, [](MinMax a, MinMax b) {
+    return MinMax{b.lo < a.lo ? b.lo : a.lo, b.hi > a.hi ? b.hi : a.hi, a.cnt + b.cnt};
+  });
 }
 
 // partial[3 b .. 3 b + 2] = min, max and (as its bits) the count of the non-NaN values of workgroup b's share
 __global__ __launch_bounds__(kThreads) void rc_minmax_kernel(const double *__restrict__ v, uint64_t n, double *__restrict__ partial) {
-  __shared__ double s_lo[kThreads], s_hi[kThreads];
-  __shared__ unsigned long long s_cnt[kThreads];
+  __shared__ MinMax s_mm[kThreads];
   double lo = __builtin_inf(), hi = -__builtin_inf();
   unsigned long long cnt = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads) {
@@ -138,19 +119,18 @@ __global__ __launch_bounds__(kThreads) void rc_minmax_kernel(const double *__res
       ++cnt;
     }
   }
-  block_minmax(lo, hi, cnt, s_lo, s_hi, s_cnt);
+  const MinMax all = block_minmax(MinMax{lo, hi, cnt}, s_mm);
   if (threadIdx.x == 0) {
-    partial[3 * (uint64_t)blockIdx.x] = lo;
-    partial[3 * (uint64_t)blockIdx.x + 1] = hi;
-    partial[3 * (uint64_t)blockIdx.x + 2] = __longlong_as_double((long long)cnt);
+    partial[3 * (uint64_t)blockIdx.x] = all.lo;
+    partial[3 * (uint64_t)blockIdx.x + 1] = all.hi;
+    partial[3 * (uint64_t)blockIdx.x + 2] = __longlong_as_double((long long)all.cnt);
   }
 }
 
 // one workgroup: the n_partial triples -> result[0 .. 2] (min, max, the count's bits)
 __global__ __launch_bounds__(kThreads) void rc_minmax_final_kernel(const double *__restrict__ partial, uint32_t n_partial,
                                                                   double *__restrict__ result) {
-  __shared__ double s_lo[kThreads], s_hi[kThreads];
-  __shared__ unsigned long long s_cnt[kThreads];
+  __shared__ MinMax s_mm[kThreads];
   double lo = __builtin_inf(), hi = -__builtin_inf();
   unsigned long long cnt = 0;
   for (uint32_t b = threadIdx.x; b < n_partial; b += kThreads) {
@@ -162,42 +142,12 @@ __global__ __launch_bounds__(kThreads) void rc_minmax_final_kernel(const double 
       cnt += c;
     }
   }
-  block_minmax(lo, hi, cnt, s_lo, s_hi, s_cnt);
+  const MinMax all = block_minmax(MinMax{lo, hi, cnt}, s_mm);
   if (threadIdx.x == 0) {
-    result[0] = lo;
-    result[1] = hi;
-    result[2] = __longlong_as_double((long long)cnt);
+    result[0] = all.lo;
+    result[1] = all.hi;
+    result[2] = __longlong_as_double((long long)all.cnt);
   }
-}
-
-__global__ __launch_bounds__(kThreads) void rc_hist_kernel(const double *__restrict__ v, uint64_t n, const double *__restrict__ edges /*[bins + 1]*/,
-                                                           uint32_t bins, unsigned long long *__restrict__ counts /*[bins]*/) {
-  __shared__ double s_edges[kMaxBins + 1];
-  __shared__ uint32_t s_counts[kMaxBins];
-  for (uint32_t b = threadIdx.x; b <= bins; b += kThreads) s_edges[b] = edges[b];
-  for (uint32_t b = threadIdx.x; b < bins; b += kThreads) s_counts[b] = 0;
-  __syncthreads();
-  const double first = s_edges[0], last = s_edges[bins];
-  const double span = last - first, nb = (double)bins;
-  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads) {
-    const double x = v[i];
-    if (x >= first && x <= last) {  // false for NaN
-      const double t = (x - first) / span;  // in [0, 1]: both differences are rounded the same way
-      uint32_t b = (uint32_t)(t * nb);      // in [0, bins]
-      if (b >= bins) b = bins - 1;          // the last edge belongs to the last bin
-      if (x < s_edges[b]) --b;              // never at b = 0: x >= first
-      if (x >= s_edges[b + 1] && b != bins - 1) ++b;
-      atomicAdd(&s_counts[b], 1u);
-    }
-  }
-  __syncthreads();
-  for (uint32_t b = threadIdx.x; b < bins; b += kThreads)
-    if (s_counts[b]) atomicAdd(&counts[b], (unsigned long long)s_counts[b]);
-}
-
-inline uint32_t stride_blocks(uint64_t n) {
-  const uint64_t want = (n + kThreads - 1) / kThreads;
-  return (uint32_t)(want < kMaxBlocks ? want : kMaxBlocks);
 }
 
 }  // namespace
@@ -246,28 +196,4 @@ extern "C" int pa_minmax_f64(pa_ctx *c, const double *d_v, uint64_t n, double *o
     out[1] = result[1];
   }
   return PA_OK;
-}
-
-extern "C" int pa_hist_uniform_f64(pa_ctx *c, const double *d_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts) {
-  PA_REQUIRE(c != nullptr && h_edges != nullptr && h_counts != nullptr, "pa_hist_uniform_f64: null argument");
-  PA_REQUIRE(bins >= 1 && bins <= kMaxBins, "pa_hist_uniform_f64: %u bins; 1 to 1024", bins);
-  PA_REQUIRE(n < (1ULL << 40), "pa_hist_uniform_f64: %llu values; a workgroup's counters are 32-bit", (unsigned long long)n);
-  for (uint32_t b = 0; b <= bins; ++b) {
-    const double e = h_edges[b];
-    PA_REQUIRE(e - e == 0.0, "pa_hist_uniform_f64: edge %u is not finite", b);
-    PA_REQUIRE(b == 0 || h_edges[b - 1] <= e, "pa_hist_uniform_f64: edge %u is below edge %u", b, b - 1);
-  }
-  const double span = h_edges[bins] - h_edges[0];
-  PA_REQUIRE(span > 0.0 && span - span == 0.0, "pa_hist_uniform_f64: the last edge must be above the first and their difference finite");
-  for (uint32_t b = 0; b < bins; ++b) h_counts[b] = 0;
-  if (n == 0) return PA_OK;
-  PA_REQUIRE(d_v != nullptr, "pa_hist_uniform_f64: null array");
-  PA_HIP(hipSetDevice(c->device));
-  PA_TRY(c->hist.reserve((2 * (uint64_t)bins + 1) * 8));
-  unsigned long long *d_counts = c->hist.as<unsigned long long>();
-  double *d_edges = reinterpret_cast<double *>(d_counts + bins);
-  PA_HIP(hipMemsetAsync(d_counts, 0, (uint64_t)bins * 8, c->stream));
-  PA_HIP(hipMemcpyAsync(d_edges, h_edges, ((uint64_t)bins + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  PA_TRY(PA_LAUNCH(c, rc_hist_kernel, stride_blocks(n), kThreads, 0, d_v, n, d_edges, bins, d_counts));
-  return pa_copy_to_host(c, h_counts, d_counts, (uint64_t)bins * 8);  // the caller's edges and counts are not touched after the return
 }

@@ -1,7 +1,7 @@
-// runcomp_host.cpp -- host twins of runcomp.hip: the join of two runs, the minimum and maximum of a vector and
-// numpy's uniform-bin histogram, as plain loops with the same results bit for bit.  They are what plot-run-comp uses
-// without a GPU and what the device kernels are compared with.  Built with -ffp-contract=off: the bin index is a
-// rounded division followed by a rounded multiplication.
+// runcomp_host.cpp -- host twins of runcomp.hip: the join of two runs and the minimum and maximum of a vector, as plain
+// loops with the same results bit for bit.  They are what plot-run-comp uses without a GPU and what the device kernels
+// are compared with; the histogram's twin is hist_host.cpp.  Built with -ffp-contract=off, as runcomp.hip is: the
+// join's y - x stays a difference of its own on both sides.
 #include <cmath>
 #include <cstdint>
 
@@ -52,33 +52,6 @@ int pa_minmax_f64_host(const double *h_v, uint64_t n, double *out, uint64_t *n_v
   if (valid) {
     out[0] = lo;
     out[1] = hi;
-  }
-  return PA_OK;
-}
-
-int pa_hist_uniform_f64_host(const double *h_v, uint64_t n, const double *h_edges, uint32_t bins, uint64_t *h_counts) {
-  if (!h_edges || !h_counts || (n && !h_v)) { pa_set_error("pa_hist_uniform_f64_host: null argument"); return PA_E_INVALID; }
-  if (bins < 1 || bins > 1024) { pa_set_error("pa_hist_uniform_f64_host: %u bins; 1 to 1024", bins); return PA_E_INVALID; }
-  for (uint32_t b = 0; b <= bins; ++b) {
-    if (!std::isfinite(h_edges[b])) { pa_set_error("pa_hist_uniform_f64_host: edge %u is not finite", b); return PA_E_INVALID; }
-    if (b && h_edges[b - 1] > h_edges[b]) { pa_set_error("pa_hist_uniform_f64_host: edge %u is below edge %u", b, b - 1); return PA_E_INVALID; }
-  }
-  const double first = h_edges[0], last = h_edges[bins];
-  const double span = last - first, nb = (double)bins;
-  if (!(span > 0.0) || !std::isfinite(span)) {
-    pa_set_error("pa_hist_uniform_f64_host: the last edge must be above the first and their difference finite");
-    return PA_E_INVALID;
-  }
-  for (uint32_t b = 0; b < bins; ++b) h_counts[b] = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    const double x = h_v[i];
-    if (!(x >= first && x <= last)) continue;  // NaN too
-    const double t = (x - first) / span;
-    uint32_t b = (uint32_t)(t * nb);
-    if (b >= bins) b = bins - 1;
-    if (x < h_edges[b]) --b;  // never at b = 0: x >= first
-    if (x >= h_edges[b + 1] && b != bins - 1) ++b;
-    ++h_counts[b];
   }
   return PA_OK;
 }

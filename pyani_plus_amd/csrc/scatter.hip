@@ -3,12 +3,12 @@
 // 7f has the definition and the measurements.
 //
 // pa_bin2d_f64: point t counts iff x[t] and y[t] lie within their edges (NaN does not); its bin on each axis is
-// pa_hist_uniform_f64's (scatter_common.h; contraction is off for this file, by the pragma there and by the Makefile);
+// pa_hist_uniform_f64's (uniform_bins.h; contraction is off for this file, by the pragma there and by the Makefile);
 // its cell is ix * bins_y + iy.  A cell holds two u32 words in two arrays, `count` and `last + 1` (0: no point), and
 // not one packed u64: the count is a sum and the index a maximum, which one 64-bit atomic cannot do together, and the
 // 32-bit LDS atomics are the native ones.  n < 2^32 - 1, so both fit; the host widens them to u64.
 //
-// One grid-stride pass, at most kMaxBlocks workgroups of 256 lanes, 8-byte loads (the callers pass slices of tensors),
+// One grid-stride pass, at most kStrideMaxBlocks workgroups of 256 lanes, 8-byte loads (the callers pass slices of tensors),
 // both edge arrays staged in LDS.  ANI points are as contended as points get -- the self comparisons all sit on
 // (1, 1), a species cluster fills a handful of cells -- so three things keep a point off the global atomics:
 //   1. the wave peels its leading cell: the lanes whose cell is that of the wave's first valid lane are counted with
@@ -25,14 +25,13 @@
 #include <vector>
 
 #include "pa_internal.h"
-#include "scatter_common.h"
+#include "uniform_bins.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kMaxBlocks = 1024;  // the grid-stride pass: four workgroups for each of the 256 CUs
+constexpr int kThreads = kStrideThreads;
 constexpr uint32_t kLdsCells = PA_BIN2D_LDS_CELLS;
 constexpr uint32_t kSlots = PA_BIN2D_SLOTS;
 static_assert((kSlots & (kSlots - 1)) == 0, "the slot of a cell is taken with a mask");
@@ -41,10 +40,6 @@ static_assert((kSlots & (kSlots - 1)) == 0, "the slot of a cell is taken with a 
 static_assert(2 * (PA_BIN2D_MAX_BINS + 1) * 8 + 3 * kSlots * 4 <= 65536 && 2 * (PA_BIN2D_MAX_BINS + 1) * 8 + 2 * kLdsCells * 4 <= 65536,
               "the workgroup's LDS");
 
-inline uint32_t stride_blocks(uint64_t n) {
-  const uint64_t want = (n + kThreads - 1) / kThreads;
-  return (uint32_t)(want < kMaxBlocks ? want : kMaxBlocks);
-}
 inline size_t lds_bytes(uint32_t bins_x, uint32_t bins_y, bool full) {
   return ((size_t)bins_x + bins_y + 2) * 8 + (full ? 2 * (size_t)bins_x * bins_y : 3 * (size_t)kSlots) * 4;
 }

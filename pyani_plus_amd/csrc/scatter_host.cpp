@@ -6,28 +6,11 @@
 #include <cstdint>
 
 #include "../../include/pyani_hip.h"
-#include "scatter_common.h"
+#include "uniform_bins.h"
 
 void pa_set_error(const char *fmt, ...);
 
 #pragma STDC FP_CONTRACT OFF
-
-namespace {
-
-int check_edges(const char *who, const char *axis, const double *e, uint32_t bins) {
-  for (uint32_t b = 0; b <= bins; ++b) {
-    if (!std::isfinite(e[b])) { pa_set_error("%s: %s edge %u is not finite", who, axis, b); return PA_E_INVALID; }
-    if (b && e[b - 1] > e[b]) { pa_set_error("%s: %s edge %u is below edge %u", who, axis, b, b - 1); return PA_E_INVALID; }
-  }
-  const double span = e[bins] - e[0];
-  if (!(span > 0.0) || !std::isfinite(span)) {
-    pa_set_error("%s: the last %s edge must be above the first and their difference finite", who, axis);
-    return PA_E_INVALID;
-  }
-  return PA_OK;
-}
-
-}  // namespace
 
 int pa_bin2d_validate(const char *who, const void *x, const void *y, uint64_t n, const double *h_xedges, uint32_t bins_x,
                       const double *h_yedges, uint32_t bins_y, const uint64_t *h_counts, const uint64_t *h_last) {
@@ -35,8 +18,8 @@ int pa_bin2d_validate(const char *who, const void *x, const void *y, uint64_t n,
   if (bins_x < 1 || bins_x > PA_BIN2D_MAX_BINS) { pa_set_error("%s: %u x bins; 1 to %u", who, bins_x, PA_BIN2D_MAX_BINS); return PA_E_INVALID; }
   if (bins_y < 1 || bins_y > PA_BIN2D_MAX_BINS) { pa_set_error("%s: %u y bins; 1 to %u", who, bins_y, PA_BIN2D_MAX_BINS); return PA_E_INVALID; }
   if (n >= 0xFFFFFFFFULL) { pa_set_error("%s: %llu points; at most 2^32 - 2 (a cell holds the index of its last point in 32 bits)", who, (unsigned long long)n); return PA_E_INVALID; }
-  if (int s = check_edges(who, "x", h_xedges, bins_x)) return s;
-  return check_edges(who, "y", h_yedges, bins_y);
+  if (int s = pa_check_uniform_edges(who, "x ", h_xedges, bins_x)) return s;
+  return pa_check_uniform_edges(who, "y ", h_yedges, bins_y);
 }
 
 extern "C" int pa_bin2d_f64_host(const double *h_x, const double *h_y, uint64_t n, const double *h_xedges, uint32_t bins_x, const double *h_yedges,

@@ -1,10 +1,10 @@
-// scatter_common.h -- what scatter.hip (device) and scatter_host.cpp (host twin) share: the bin of a value among
-// uniform edges, which is pa_hist_uniform_f64's rule restated once for both, and the argument check of pa_bin2d_f64 and
-// pa_bin2d_f64_host.  rc_hist_kernel (runcomp.hip) and dist_hist_wide_kernel (dist.hip) keep their own copies of the rule.
-// Both translation units are built with -ffp-contract=off: the bin index is a rounded division, then a rounded
-// multiplication, and must not become a fused one.
-#ifndef PA_SCATTER_COMMON_H
-#define PA_SCATTER_COMMON_H
+// uniform_bins.h -- numpy's uniform-bin rule, stated once for every histogram of the library: the bin of a value among
+// uniform edges (device and host: hist.hip, scatter.hip, hist_host.cpp, scatter_host.cpp), the check of an edge array
+// that the 1-D and the 2-D entry points share, and the argument check of pa_bin2d_f64 and pa_bin2d_f64_host.
+// Every translation unit that includes this is built with -ffp-contract=off: the bin index is a rounded division, then
+// a rounded multiplication, and must not become a fused one.
+#ifndef PA_UNIFORM_BINS_H
+#define PA_UNIFORM_BINS_H
 #include <cstdint>
 
 #ifdef __HIPCC__
@@ -27,10 +27,15 @@ PA_HD uint32_t pa_uniform_bin(double x, double first, double span, double nb, ui
   return b;
 }
 
+// PA_OK, or PA_E_INVALID with the message set: one of the bins + 1 edges is infinite or NaN or lies below the one
+// before it, or the last edge is not above the first by a finite difference.  `who` names the entry point and `axis` is
+// "", "x " or "y ".  hist_host.cpp
+int pa_check_uniform_edges(const char *who, const char *axis, const double *edges, uint32_t bins);
+
 // PA_OK, or PA_E_INVALID with the message set (`who` names the entry point): a null argument, bins outside
-// 1 .. PA_BIN2D_MAX_BINS on either axis, n >= 2^32 - 1, and the edge errors of pa_hist_uniform_f64 with the axis named.
+// 1 .. PA_BIN2D_MAX_BINS on either axis, n >= 2^32 - 1, and the edge errors above with the axis named.
 // Reads the edges and nothing else.  scatter_host.cpp
 int pa_bin2d_validate(const char *who, const void *x, const void *y, uint64_t n, const double *h_xedges, uint32_t bins_x,
                       const double *h_yedges, uint32_t bins_y, const uint64_t *h_counts, const uint64_t *h_last);
 
-#endif  // PA_SCATTER_COMMON_H
+#endif  // PA_UNIFORM_BINS_H

@@ -122,14 +122,7 @@ def kde_gauss_host(values, grid, bw: float) -> np.ndarray:
 
 def hist_uniform_wide_host(values, edges) -> np.ndarray:
     """``pa_hist_uniform_f64_wide_host``: ``numpy.histogram``'s uint64 counts over the uniform bins with these edges."""
-    v = _vector(values)
-    h_edges = np.ascontiguousarray(edges, dtype=np.float64)
-    if h_edges.ndim != 1 or len(h_edges) < 2:  # noqa: PLR2004
-        msg = f"edges of shape {h_edges.shape}, expected at least two in one dimension"
-        raise ValueError(msg)
-    counts = np.zeros(len(h_edges) - 1, dtype=np.uint64)
-    check(_capi.load_library().pa_hist_uniform_f64_wide_host(v.ctypes.data, len(v), h_edges.ctypes.data, len(counts), counts.ctypes.data), "pa_hist_uniform_f64_wide_host")
-    return counts
+    return run_comp._hist_uniform_host("pa_hist_uniform_f64_wide_host", values, edges)  # noqa: SLF001
 
 
 def kde_tree_depth(n: int, n_grid: int) -> int:

@@ -746,19 +746,20 @@ class HipEngine:
         self._check(self.lib.pa_minmax_f64(self.ctx, d_v.data_ptr(), d_v.numel(), out, C.byref(valid)), "pa_minmax_f64")
         return float(out[0]), float(out[1]), int(valid.value)
 
-    def hist_uniform(self, values, edges) -> np.ndarray:
-        """``pa_hist_uniform_f64``: the uint64 counts of ``numpy.histogram`` over the uniform bins whose ascending
-        ``edges`` the caller made (``run_comp.hist_edges``); ``values`` is a host array or a float64 tensor on this
-        device, which is not copied.  NaN and values outside the edges are not counted."""
+    def _hist_uniform(self, symbol: str, values, edges) -> np.ndarray:
         d_v = self._f64_on_device(values).reshape(-1)
         h_edges = np.ascontiguousarray(edges, dtype=np.float64)
         if h_edges.ndim != 1 or len(h_edges) < 2:
             raise ValueError(f"edges of shape {h_edges.shape}, expected at least two in one dimension")
         counts = np.zeros(len(h_edges) - 1, dtype=np.uint64)
-        self._check(
-            self.lib.pa_hist_uniform_f64(self.ctx, d_v.data_ptr(), d_v.numel(), h_edges.ctypes.data, len(counts), counts.ctypes.data), "pa_hist_uniform_f64"
-        )
+        self._check(getattr(self.lib, symbol)(self.ctx, d_v.data_ptr(), d_v.numel(), h_edges.ctypes.data, len(counts), counts.ctypes.data), symbol)
         return counts
+
+    def hist_uniform(self, values, edges) -> np.ndarray:
+        """``pa_hist_uniform_f64``: the uint64 counts of ``numpy.histogram`` over the uniform bins whose ascending
+        ``edges`` the caller made (``run_comp.hist_edges``); ``values`` is a host array or a float64 tensor on this
+        device, which is not copied.  NaN and values outside the edges are not counted."""
+        return self._hist_uniform("pa_hist_uniform_f64", values, edges)
 
     # -- plot-run's distributions
     def select(self, values, ranks) -> np.ndarray:
@@ -792,16 +793,7 @@ class HipEngine:
 
     def hist_uniform_wide(self, values, edges) -> np.ndarray:
         """``pa_hist_uniform_f64_wide``: ``hist_uniform`` for up to 2^20 bins."""
-        d_v = self._f64_on_device(values).reshape(-1)
-        h_edges = np.ascontiguousarray(edges, dtype=np.float64)
-        if h_edges.ndim != 1 or len(h_edges) < 2:
-            raise ValueError(f"edges of shape {h_edges.shape}, expected at least two in one dimension")
-        counts = np.zeros(len(h_edges) - 1, dtype=np.uint64)
-        self._check(
-            self.lib.pa_hist_uniform_f64_wide(self.ctx, d_v.data_ptr(), d_v.numel(), h_edges.ctypes.data, len(counts), counts.ctypes.data),
-            "pa_hist_uniform_f64_wide",
-        )
-        return counts
+        return self._hist_uniform("pa_hist_uniform_f64_wide", values, edges)
 
     # -- plot-run's scatter figures
     def bin2d(self, x, y, xedges, yedges) -> tuple[np.ndarray, np.ndarray]:

@@ -89,16 +89,20 @@ def minmax_host(values) -> tuple[float, float, int]:
     return float(out[0]), float(out[1]), int(valid.value)
 
 
-def hist_uniform_host(values, edges) -> np.ndarray:
-    """``pa_hist_uniform_f64_host``: ``numpy.histogram``'s uint64 counts over the uniform bins with these edges."""
+def _hist_uniform_host(symbol: str, values, edges) -> np.ndarray:
     v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
     h_edges = np.ascontiguousarray(edges, dtype=np.float64)
-    if h_edges.ndim != 1 or len(h_edges) < 2:
+    if h_edges.ndim != 1 or len(h_edges) < 2:  # noqa: PLR2004
         msg = f"edges of shape {h_edges.shape}, expected at least two in one dimension"
         raise ValueError(msg)
     counts = np.zeros(len(h_edges) - 1, dtype=np.uint64)
-    check(_capi.load_library().pa_hist_uniform_f64_host(v.ctypes.data, len(v), h_edges.ctypes.data, len(counts), counts.ctypes.data), "pa_hist_uniform_f64_host")
+    check(getattr(_capi.load_library(), symbol)(v.ctypes.data, len(v), h_edges.ctypes.data, len(counts), counts.ctypes.data), symbol)
     return counts
+
+
+def hist_uniform_host(values, edges) -> np.ndarray:
+    """``pa_hist_uniform_f64_host``: ``numpy.histogram``'s uint64 counts over the uniform bins with these edges."""
+    return _hist_uniform_host("pa_hist_uniform_f64_host", values, edges)
 
 
 def range_and_counts(values, engine=None, bins: int = BINS) -> tuple[tuple[float, float] | None, np.ndarray]:

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from pyani_plus_amd import run_comp, rundb
+from pyani_plus_amd import distribution, run_comp, rundb
 from tests.run_comp_cases import (
     HIST_BINS,
     HIST_FAMILIES,
@@ -18,6 +18,7 @@ from tests.run_comp_cases import (
     JOIN_REFS,
     JOIN_ROWS,
     NONE,
+    adversarial_values,
     hist_inputs,
     join_inputs,
     join_reference,
@@ -124,6 +125,33 @@ def test_histogram_arguments(engine):
     edges = run_comp.hist_edges(v.min(), v.max(), 1024)
     assert np.array_equal(engine.hist_uniform(v, edges), numpy_hist(v, edges))
     assert engine.hist_uniform([], [0.0, 1.0]).tolist() == [0]
+
+
+@pytest.mark.parametrize("bins", [1, 2, 1024])
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 262_145])  # the last: one past 1024 workgroups of 256, where the grid starts to stride
+def test_both_entry_points_and_both_host_twins_count_alike(engine, n, bins):
+    """One device vector and one set of edges through ``pa_hist_uniform_f64`` and ``pa_hist_uniform_f64_wide``: every
+    edge, its neighbouring doubles (one of them outside at each end), the midpoints and NaN."""
+    edges = run_comp.hist_edges(0.1, 0.7, bins)
+    rest = np.random.default_rng(n + bins).permutation(np.concatenate([adversarial_values(edges), [np.nan, edges[0] - 0.25, edges[-1] + 0.25]]))
+    v = np.resize(np.concatenate([edges[-1:], rest]), n)  # the last edge, which belongs to the last bin, is in every size
+    d_v = engine.torch.from_numpy(v).to(engine.device)
+    narrow, wide = engine.hist_uniform(d_v, edges), engine.hist_uniform_wide(d_v, edges)
+    want = numpy_hist(v, edges)
+    assert narrow.dtype == wide.dtype == np.uint64 and want[-1] >= 1
+    assert np.array_equal(narrow, wide) and np.array_equal(narrow, want)
+    assert np.array_equal(narrow, run_comp.hist_uniform_host(v, edges)) and np.array_equal(narrow, distribution.hist_uniform_wide_host(v, edges))
+
+
+def test_the_2d_binning_summed_over_y_is_the_histogram_of_x(engine):
+    """The 1-D and the 2-D use of the one bin rule: with a y range that holds every point, the cells of a column add up
+    to the histogram of x."""
+    xedges, yedges = run_comp.hist_edges(0.1, 0.7, 3), run_comp.hist_edges(-1.0, 2.0, 2)
+    x = np.resize(np.concatenate([adversarial_values(xedges), [np.nan, -3.0, 3.0]]), 257)
+    y = np.random.default_rng(257).random(257)
+    cells, _last = engine.bin2d(x, y, xedges, yedges)
+    assert cells.shape == (3, 2) and cells.min() > 0
+    assert np.array_equal(cells.sum(axis=1), engine.hist_uniform(x, xedges)) and np.array_equal(cells.sum(axis=1), numpy_hist(x, xedges))
 
 
 # ------------------------------------------------------------------ minimum and maximum

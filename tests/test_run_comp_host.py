@@ -113,6 +113,79 @@ def test_hist_edges_and_arguments():
     assert none is None and zeros.tolist() == [0] * 30
 
 
+# the bad arguments of test_messages_of_the_entry_points_that_take_edges: three edges for two bins, then bin counts
+BAD_EDGES = ([0.0, np.inf, 1.0], [0.0, 0.5, np.nan], [0.0, 0.75, 0.5], [0.5, 0.5, 0.5], [-1e308, 0.0, 1e308])
+# what each entry point says to the five edge arrays, then to 0 bins and to one bin past its limit
+EDGE_MESSAGES = {
+    ("pa_hist_uniform_f64_host", ""): (
+        "pa_hist_uniform_f64_host: edge 1 is not finite",
+        "pa_hist_uniform_f64_host: edge 2 is not finite",
+        "pa_hist_uniform_f64_host: edge 2 is below edge 1",
+        "pa_hist_uniform_f64_host: the last edge must be above the first and their difference finite",
+        "pa_hist_uniform_f64_host: the last edge must be above the first and their difference finite",
+        "pa_hist_uniform_f64_host: 0 bins; 1 to 1024",
+        "pa_hist_uniform_f64_host: 1025 bins; 1 to 1024",
+    ),
+    ("pa_hist_uniform_f64_wide_host", ""): (
+        "pa_hist_uniform_f64_wide_host: edge 1 is not finite",
+        "pa_hist_uniform_f64_wide_host: edge 2 is not finite",
+        "pa_hist_uniform_f64_wide_host: edge 2 is below edge 1",
+        "pa_hist_uniform_f64_wide_host: the last edge must be above the first and their difference finite",
+        "pa_hist_uniform_f64_wide_host: the last edge must be above the first and their difference finite",
+        "pa_hist_uniform_f64_wide_host: 0 bins; 1 to 268435456",
+        "pa_hist_uniform_f64_wide_host: 268435457 bins; 1 to 268435456",
+    ),
+    ("pa_bin2d_f64_host", "x"): (
+        "pa_bin2d_f64_host: x edge 1 is not finite",
+        "pa_bin2d_f64_host: x edge 2 is not finite",
+        "pa_bin2d_f64_host: x edge 2 is below edge 1",
+        "pa_bin2d_f64_host: the last x edge must be above the first and their difference finite",
+        "pa_bin2d_f64_host: the last x edge must be above the first and their difference finite",
+        "pa_bin2d_f64_host: 0 x bins; 1 to 1024",
+        "pa_bin2d_f64_host: 1025 x bins; 1 to 1024",
+    ),
+    ("pa_bin2d_f64_host", "y"): (
+        "pa_bin2d_f64_host: y edge 1 is not finite",
+        "pa_bin2d_f64_host: y edge 2 is not finite",
+        "pa_bin2d_f64_host: y edge 2 is below edge 1",
+        "pa_bin2d_f64_host: the last y edge must be above the first and their difference finite",
+        "pa_bin2d_f64_host: the last y edge must be above the first and their difference finite",
+        "pa_bin2d_f64_host: 0 y bins; 1 to 1024",
+        "pa_bin2d_f64_host: 1025 y bins; 1 to 1024",
+    ),
+}
+
+
+def test_messages_of_the_entry_points_that_take_edges():
+    """The whole message of every host entry point with edges (the 1-D histogram under its two names and the 2-D binning
+    on each axis, all through the one edge check) for a non-finite edge, a descending edge, a zero span, an infinite span,
+    0 bins and one bin past the limit.  The device entry points build theirs with the same check and formats."""
+    lib = _capi.load_library()
+    ok, v = np.array([0.0, 0.5, 1.0]), np.array([0.5])
+    counts, last = np.full(4, 7, dtype=np.uint64), np.full(4, 7, dtype=np.uint64)
+
+    def call(who, axis, edges, bins):
+        if axis == "":
+            return getattr(lib, who)(v.ctypes.data, 1, edges.ctypes.data, bins, counts.ctypes.data)
+        (xe, bx), (ye, by) = ((edges, bins), (ok, 2)) if axis == "x" else ((ok, 2), (edges, bins))
+        return lib.pa_bin2d_f64_host(v.ctypes.data, v.ctypes.data, 1, xe.ctypes.data, bx, ye.ctypes.data, by, counts.ctypes.data, last.ctypes.data)
+
+    for (who, axis), messages in EDGE_MESSAGES.items():
+        limit = int(messages[-1].split()[-1])
+        # the bin counts are refused before an edge is read: the array holds three
+        cases = [(np.array(edges), 2) for edges in BAD_EDGES] + [(ok, 0), (ok, limit + 1)]
+        for (edges, bins), message in zip(cases, messages, strict=True):
+            assert call(who, axis, edges, bins) == -1 and _capi.last_error() == message  # PA_E_INVALID
+            assert counts.tolist() == last.tolist() == [7] * 4  # refused before anything was written
+    # two things wrong: the bin range is reported before an edge, the x axis before the y axis
+    assert call("pa_hist_uniform_f64_host", "", np.array([np.nan, 0.0]), 0) == -1 and _capi.last_error() == "pa_hist_uniform_f64_host: 0 bins; 1 to 1024"
+    nan_edge = np.array([0.0, np.nan, 1.0])
+    assert lib.pa_bin2d_f64_host(v.ctypes.data, v.ctypes.data, 1, np.full(3, 0.5).ctypes.data, 2, nan_edge.ctypes.data, 2, counts.ctypes.data, last.ctypes.data) == -1
+    assert _capi.last_error() == "pa_bin2d_f64_host: the last x edge must be above the first and their difference finite"
+    assert lib.pa_bin2d_f64_host(v.ctypes.data, v.ctypes.data, 1, nan_edge.ctypes.data, 2, ok.ctypes.data, 0, counts.ctypes.data, last.ctypes.data) == -1
+    assert _capi.last_error() == "pa_bin2d_f64_host: 0 y bins; 1 to 1024"
+
+
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 100_003])
 def test_host_minmax_equals_numpy(n):
     rng = np.random.default_rng(n)

@@ -10,11 +10,12 @@ import sqlite3
 import numpy as np
 import pytest
 
-from pyani_plus_amd import _capi, classify, distribution, rundb, scatter
+from pyani_plus_amd import _capi, classify, distribution, run_comp, rundb, scatter
 from pyani_plus_amd._capi import HipBackendError
 from tests.distribution_cases import EDGE_FAMILIES, edge_values, kde_values, same_bits
 from tests.fake_engine import OracleEngine
 from tests.helpers import FIXTURE_SETS, GOLDEN
+from tests.run_comp_cases import adversarial_values, numpy_hist
 from tests.scatter_cases import GRIDS, LDS_CELLS, NONE, SLOTS, ani_like, assert_cells, edge_points, grid_edges, oracle, random_points
 
 DEFAULT_NAMES = ["sourmash-hip_query_cov_scatter.tsv", "sourmash-hip_tANI_scatter.tsv"] + [
@@ -82,6 +83,17 @@ def test_host_bin2d_of_no_points_and_arguments():
         assert f"{n} points; at most 2^32 - 2" in _capi.last_error() and status
     assert lib.pa_bin2d_f64_host(None, None, 1, ok.ctypes.data, 4, ok.ctypes.data, 4, cells[0].ctypes.data, cells[1].ctypes.data) != _capi.PA_OK
     assert "null argument" in _capi.last_error()
+
+
+def test_host_bin2d_summed_over_y_is_the_histogram_of_x():
+    """The 1-D and the 2-D use of the one bin rule: with a y range that holds every point, the cells of a column add up
+    to the histogram of x."""
+    xedges, yedges = run_comp.hist_edges(0.1, 0.7, 3), run_comp.hist_edges(-1.0, 2.0, 2)
+    x = np.resize(np.concatenate([adversarial_values(xedges), [np.nan, -3.0, 3.0]]), 257)
+    y = np.random.default_rng(257).random(257)
+    cells, _last = scatter.bin2d_host(x, y, xedges, yedges)
+    assert cells.shape == (3, 2) and cells.min() > 0
+    assert np.array_equal(cells.sum(axis=1), run_comp.hist_uniform_host(x, xedges)) and np.array_equal(cells.sum(axis=1), numpy_hist(x, xedges))
 
 
 def test_the_binding_states_the_library_constants():

@@ -6,6 +6,7 @@
 #include <cstdio>
 void pa_set_error(const char *fmt, ...) {}
 #include "../../../pyani_plus_amd/csrc/dist_host.cpp"
+#include "../../../pyani_plus_amd/csrc/hist_host.cpp"
 #include <random>
 int main(int argc, char **argv) {
   const int trials = argc > 1 ? atoi(argv[1]) : 2000;

@@ -1,4 +1,4 @@
-// The launcher's arithmetic (pa_launch_geom.h: ceil_div, launch_verdict, dispatch_value) under AddressSanitizer / UBSan:
+// The launcher's arithmetic (pa_launch_geom.h: ceil_div, stride_blocks, launch_verdict, dispatch_value) under AddressSanitizer / UBSan:
 // a stand-alone CPU program, no HIP runtime.
 //   usage: launch_geom
 #include <cstdio>
@@ -55,6 +55,10 @@ int main() {
   // ceil_div at its edges: no a + b - 1 that wraps
   CHECK(ceil_div(0, 256) == 0 && ceil_div(1, 256) == 1 && ceil_div(256, 256) == 1 && ceil_div(257, 256) == 2);
   CHECK(ceil_div(~0ull, 1) == ~0ull && ceil_div(~0ull, 2) == (1ull << 63) && ceil_div(~0ull, ~0ull) == 1 && ceil_div(~0ull - 1, ~0ull) == 1);
+  // the grid of a grid-stride pass: a workgroup per 256 elements up to 1024 of them, then it stays
+  CHECK(stride_blocks(0) == 0 && stride_blocks(1) == 1 && stride_blocks(256) == 1 && stride_blocks(257) == 2);
+  CHECK(stride_blocks(1024 * 256 - 1) == 1024 && stride_blocks(1024 * 256) == 1024 && stride_blocks(1024 * 256 + 1) == 1024);
+  CHECK(stride_blocks(1023 * 256) == 1023 && stride_blocks(1023 * 256 + 1) == 1024 && stride_blocks((1ull << 40) - 1) == 1024 && stride_blocks(~0ull) == 1024);
 
   // the value dispatch: each listed value reaches its own case once and no other, a value off the list reports a miss
   static_assert(std::is_same<value_list<1, 4>, std::integer_sequence<int, 1, 2, 3, 4>>::value, "consecutive values");

@@ -7,6 +7,7 @@
 void pa_set_error(const char *fmt, ...) {}
 #include "../../../pyani_plus_amd/csrc/json_writer.cpp"
 #include "../../../pyani_plus_amd/csrc/runcomp_host.cpp"
+#include "../../../pyani_plus_amd/csrc/hist_host.cpp"
 #include <random>
 int main(int argc, char **argv) {
   if (argc < 2) { printf("usage: runcomp_host <scratch file> [trials]\n"); return 2; }

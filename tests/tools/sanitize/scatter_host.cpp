@@ -6,6 +6,7 @@
 #include <cstdlib>
 void pa_set_error(const char *fmt, ...) {}
 #include "../../../pyani_plus_amd/csrc/scatter_host.cpp"
+#include "../../../pyani_plus_amd/csrc/hist_host.cpp"
 #include <random>
 static uint32_t search(const double *e, uint32_t bins, double v) {  // the last edge <= v, the last bin for the last edge
   uint32_t b = 0;
