@@ -652,6 +652,58 @@ PA_API int pa_bin2d_f64(pa_ctx *ctx, const double *d_x, const double *d_y, uint6
 PA_API int pa_bin2d_f64_host(const double *h_x, const double *h_y, uint64_t n, const double *h_xedges, uint32_t bins_x,
                              const double *h_yedges, uint32_t bins_y, uint64_t *h_counts, uint64_t *h_last);
 
+/* ---- TETRA-hip: tetranucleotide Z-score correlations of all genome pairs ----
+ * Replaces nothing in the reference: pyani-plus has no TETRA method.  The definition below is this project's own
+ * contract (after Teeling et al. 2004, the TETRA of pyani and JSpecies); it is pinned by an independent restatement in
+ * tests/tetra_cases.py, and no bit parity with pyani or JSpecies is claimed.  DESIGN.md section 7g.
+ *
+ * Windows and counts.  For k = 2, 3, 4 a window starts at arena position p when the mask bits p .. p + k - 1 are all 0
+ * (pa_sketch's rule: k valid bases inside one record; separators, non-ACGT residues and padding end windows); it
+ * belongs to genome g when genome_start[g] <= p and p + k <= genome_start[g + 1].  The index of a word is
+ * sum b_i 4^(k - 1 - i) with A=0 C=1 G=2 T=3, the first base most significant.  F[g] is PA_TETRA_BINS = 336 u64 per
+ * genome, forward strand only: [0, 256) tetra-, [256, 320) tri-, [320, 336) dinucleotides.
+ *
+ * Z-scores (host, from the integers).  C_k[w] = F_k[w] + F_k[rc_k(w)], rc_k reversing the k digits and replacing each
+ * digit d by 3 - d.  For w = n1 n2 n3 n4, each step one IEEE double operation: N = C_4[w], L = C_3[n1 n2 n3],
+ * R = C_3[n2 n3 n4], M = C_2[n2 n3]; E = (L * R) / M; V = (E * ((M - L) * (M - R))) / (M * M); Z = (N - E) / sqrt(V);
+ * Z = 0.0 when M == 0 or V is not > 0.
+ *
+ * Unit rows.  mean = (Z[0] + ... + Z[255], added in this order) / 256; d = Z - mean; ss = the sum of d * d in this order,
+ * each product rounded before it is added (no FMA); U = d / sqrt(ss).  ss == 0 (a genome without a window, or one
+ * like ACGT alone whose every Z is 0): the genome is degenerate and its U is all NaN.
+ *
+ * Correlation.  acc = acc + U_a[k] * U_b[k] for k = 0 .. 255 ascending, one accumulator per pair, the product rounded
+ * before the addition; r = min(1, max(-1, acc)); exactly 1.0 where a and b are the same genome index; NaN where either
+ * genome is degenerate.  r(a, b) and r(b, a) have the same bits.
+ *
+ *   pa_tetra_counts        (device) d_counts[n_genomes][336] from an arena as pa_sketch takes it (d_dirty may be NULL:
+ *        the bitmap is then built into a buffer of the context).  One pass over the packed bases; the mask is read only
+ *        for the blocks the dirty bitmap flags and for each genome's first and last block.  Integer sums: the same
+ *        counts run to run.  Zeroes d_counts itself; one host synchronisation.
+ *   pa_tetra_counts_host   the same from a host arena, one rolling loop per genome on n_threads host threads (0: as many
+ *        as the process may use).
+ *   pa_tetra_zscores_host  h_counts[n][336] -> h_Z[n][256] and h_U[n][256] as above.  There is no device form.
+ *   pa_tetra_corr          (device) d_U[n][256] -> d_out[q1 - q0][s1 - s0], r of genome q0 + i with genome s0 + j.
+ *        symmetric != 0 needs q0 == s0 and q1 == s1 (PA_E_INVALID otherwise): only the tiles on and above the diagonal
+ *        are evaluated and the rest is mirrored.  64 x 64 pairs per workgroup, register-tiled vector arithmetic, no
+ *        atomics.  Allocates nothing, does not synchronise, runs on the context's stream.
+ *   pa_tetra_corr_host     the same from host arrays, the same bits.
+ *   pa_append_identity_json  pa_append_comparisons_json for a method without coverage: the same rows with
+ *        "cov_query": null in every one, "identity": null where is_null. */
+#define PA_TETRA_BINS 336
+#define PA_TETRA_WORDS 256
+PA_API int pa_tetra_counts(pa_ctx *ctx, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty, uint64_t arena_bases,
+                           const uint64_t *h_genome_start, uint32_t n_genomes, uint64_t *d_counts);
+PA_API int pa_tetra_counts_host(const uint32_t *h_packed, const uint32_t *h_mask, uint64_t arena_bases, const uint64_t *h_genome_start,
+                                uint32_t n_genomes, uint64_t *h_counts, uint32_t n_threads);
+PA_API int pa_tetra_zscores_host(const uint64_t *h_counts, uint32_t n_genomes, double *h_Z, double *h_U);
+PA_API int pa_tetra_corr(pa_ctx *ctx, const double *d_U, uint32_t n, uint32_t q0, uint32_t q1, uint32_t s0, uint32_t s1, int symmetric,
+                         double *d_out);
+PA_API int pa_tetra_corr_host(const double *h_U, uint32_t n, uint32_t q0, uint32_t q1, uint32_t s0, uint32_t s1, int symmetric,
+                              double *h_out, uint32_t n_threads);
+PA_API int pa_append_identity_json(const char *path, const char *suffix, int file_has_rows, const char *const *q_hashes, uint32_t nq,
+                                   const char *const *s_hashes, uint32_t ns, const double *identity, const uint8_t *is_null);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */

@@ -36,6 +36,8 @@ PA_BIN2D_MAX_BINS = 1024  # pa_bin2d_f64: bins per axis, at most
 PA_BIN2D_LDS_CELLS = 4096  # ... counts grids of up to this many cells wholly in LDS
 PA_BIN2D_SLOTS = 2048  # ... and larger ones through this many direct-mapped slots: the slot of a cell is cell % PA_BIN2D_SLOTS
 PA_BIN2D_NONE = 0xFFFFFFFFFFFFFFFF  # the `last` of an empty cell
+PA_TETRA_BINS = 336  # pa_tetra_counts: u64 per genome, 256 tetra-, 64 tri- and 16 dinucleotides
+PA_TETRA_WORDS = 256  # columns of a Z-score row and of a unit row
 PROF_PHASES = {"kmer_hash": 0, "sketch_sort": 1, "pair_dict": 2, "pair_count": 3, "ani": 4, "frag_index": 5, "frag_seed": 6, "frag_map": 7,
                "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11, "rowdist": 12}
 PA_AGG = {"min": 0, "max": 1, "mean": 2}
@@ -194,6 +196,12 @@ SIGNATURES: dict[str, tuple] = {
     "pa_hist_uniform_f64_wide_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint32, _vp]),
     "pa_bin2d_f64": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "pa_bin2d_f64_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    "pa_tetra_counts": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "pa_tetra_counts_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32]),
+    "pa_tetra_zscores_host": (C.c_int, [_vp, C.c_uint32, _vp, _vp]),
+    "pa_tetra_corr": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp]),
+    "pa_tetra_corr_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp, C.c_uint32]),
+    "pa_append_identity_json": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, _vp, _vp]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),
     "pa_prof_get": (C.c_int, [_vp, C.c_int, _f64p, _u64p]),

@@ -98,7 +98,7 @@ void format_rows(std::vector<char> &out, bool first, const char *const *q_hashes
         if (is_null[idx]) { memcpy(p, "null", 4); p += 4; } else p = std::to_chars(p, end, sim_errors[idx]).ptr;
       }
       memcpy(p, ", \"cov_query\": ", 15); p += 15;
-      if (is_null[idx]) { memcpy(p, "null", 4); p += 4; } else p = put_double(p, end, cov_query[idx]);
+      if (is_null[idx] || !cov_query) { memcpy(p, "null", 4); p += 4; } else p = put_double(p, end, cov_query[idx]);  // no cov_query: a method without coverage
       *p++ = '}';
       fill = (size_t)(p - out.data());
     }
@@ -162,8 +162,9 @@ static int append_comparisons_json(const char *path, const char *suffix, int fil
                                    const char *const *q_hashes, uint32_t nq, const char *const *s_hashes,
                                    uint32_t ns, const double *identity, const double *cov_query,
                                    const uint8_t *is_null, const int64_t *aln_length = nullptr,
-                                   const int64_t *sim_errors = nullptr) {
-  if (!path || !suffix || (nq && !q_hashes) || (ns && !s_hashes) || ((uint64_t)nq * ns && (!identity || !cov_query || !is_null))) {
+                                   const int64_t *sim_errors = nullptr, bool identity_only = false) {
+  if (!path || !suffix || (nq && !q_hashes) || (ns && !s_hashes) ||
+      ((uint64_t)nq * ns && (!identity || (!cov_query && !identity_only) || !is_null))) {
     pa_set_error("pa_append_comparisons_json: null argument");
     return PA_E_INVALID;
   }
@@ -213,6 +214,15 @@ extern "C" int pa_append_comparisons_json_ex(const char *path, const char *suffi
   return pa_host_guard("pa_append_comparisons_json_ex", pa_set_error, [&] {
     return append_comparisons_json(path, suffix, file_has_rows, q_hashes, nq, s_hashes, ns, identity, cov_query, is_null, aln_length,
                                    sim_errors);
+  });
+}
+
+// TETRA-hip rows: an identity beside a NULL coverage (the method has none), which the entry points above cannot say --
+// their is_null stands for both columns.  Same keys, "cov_query": null in every row.
+extern "C" int pa_append_identity_json(const char *path, const char *suffix, int file_has_rows, const char *const *q_hashes, uint32_t nq,
+                                       const char *const *s_hashes, uint32_t ns, const double *identity, const uint8_t *is_null) {
+  return pa_host_guard("pa_append_identity_json", pa_set_error, [&] {
+    return append_comparisons_json(path, suffix, file_has_rows, q_hashes, nq, s_hashes, ns, identity, nullptr, is_null, nullptr, nullptr, true);
   });
 }
 

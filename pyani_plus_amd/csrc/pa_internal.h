@@ -163,10 +163,11 @@ constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of
 //   pair phase: dict_keys / dict_vals, ids, post_genome, bitrows; dict_scalars, the hash dictionary's scalars above
 //   classify (classify.hip): cls_i, cls_j, cls_score, cls_cov, the edges in (i, j) order, before the sort
 //   plot-run's scatter figures (scatter.hip): bin2d, the two edge arrays, then the cells' counts and last indices
+//   TETRA-hip (tetra.hip): tetra_tab, the genomes' first blocks and first chunks (u32[2 (n + 1)])
 #define PA_CTX_BUFFERS(ONE, PAIR)                                                                                   \
   PAIR(cand_keys) PAIR(cand_vals) ONE(genome_blk) ONE(counters) ONE(hist) ONE(flags) ONE(scan_tmp) ONE(region_off) \
   ONE(region_cursor) ONE(dirty) PAIR(dict_keys) PAIR(dict_vals) ONE(ids) ONE(post_genome) ONE(bitrows)             \
-  ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d)
+  ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d) ONE(tetra_tab)
 
 struct pa_ctx {
   int device = 0;

@@ -818,6 +818,45 @@ class HipEngine:
         )  # fmt: skip
         return counts, last
 
+    # -- TETRA-hip
+    def tetra_counts(self, arena, *, use_dirty: bool = True) -> np.ndarray:
+        """``pa_tetra_counts``: the forward di-, tri- and tetranucleotide counts of every genome of ``arena`` (a
+        ``DeviceArena``, or a ``HostArena`` that is uploaded first) as a host uint64 array ``[n_genomes, 336]``.
+        ``use_dirty`` False hands the library no dirty bitmap (it then builds its own)."""
+        t = self.torch
+        if isinstance(arena, HostArena):
+            arena = self.upload(arena)
+        n = arena.n_genomes
+        counts = t.empty((max(n, 1), _capi.PA_TETRA_BINS), dtype=t.int64, device=self.device)
+        gs = np.ascontiguousarray(arena.genome_start, dtype=np.uint64)
+        dirty = self.arena_dirty(arena).data_ptr() if use_dirty and arena.arena_bases else None
+        self._check(
+            self.lib.pa_tetra_counts(self.ctx, arena.packed.data_ptr(), arena.mask.data_ptr(), dirty, arena.arena_bases, gs.ctypes.data, n,
+                                     counts.data_ptr()),
+            "pa_tetra_counts",
+        )  # fmt: skip
+        return counts[:n].cpu().numpy().view(np.uint64)
+
+    def tetra_correlations_device(self, U, q_range=None, s_range=None):
+        """``pa_tetra_corr``: the correlations of the unit rows ``U`` (``[n, 256]`` float64, a host array or a tensor on
+        this device), queries ``q_range`` against subjects ``s_range`` (default: all), as a device tensor; a square block
+        on the diagonal is evaluated above the diagonal and mirrored."""
+        t = self.torch
+        d_u = self._f64_on_device(U)
+        if d_u.dim() != 2 or d_u.shape[1] != _capi.PA_TETRA_WORDS:
+            raise ValueError(f"U has shape {tuple(d_u.shape)}, expected (n, {_capi.PA_TETRA_WORDS})")
+        n = d_u.shape[0]
+        (q0, q1), (s0, s1) = q_range or (0, n), s_range or (0, n)
+        if not (0 <= q0 <= q1 <= n and 0 <= s0 <= s1 <= n):
+            raise ValueError(f"ranges [{q0}, {q1}) x [{s0}, {s1}) outside the {n} genomes")
+        out = t.empty((q1 - q0, s1 - s0), dtype=t.float64, device=self.device)
+        self._check(self.lib.pa_tetra_corr(self.ctx, d_u.data_ptr(), n, q0, q1, s0, s1, int((q0, q1) == (s0, s1)), out.data_ptr()), "pa_tetra_corr")
+        return out
+
+    def tetra_correlations(self, U, q_range=None, s_range=None) -> np.ndarray:
+        """``tetra_correlations_device`` copied back: the same bits as ``tetra_correlations_host``."""
+        return self.tetra_correlations_device(U, q_range, s_range).cpu().numpy()
+
     # -- profiling
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")
@@ -859,6 +898,52 @@ def ani_host(counts: np.ndarray, q_sizes, s_sizes, k: int, *, symmetric: bool = 
         "pa_ani_host",
     )
     return ident, cov, null.view(np.bool_) if null.dtype == np.uint8 else null
+
+
+# ------------------------------------------------------------------ TETRA-hip: the host forms (no GPU needed)
+def tetra_counts_host(arena: HostArena, threads: int = 0) -> np.ndarray:
+    """``pa_tetra_counts_host``: what ``HipEngine.tetra_counts`` returns, from a host arena on host threads."""
+    n = arena.n_genomes
+    counts = np.zeros((n, _capi.PA_TETRA_BINS), dtype=np.uint64)
+    packed = np.ascontiguousarray(arena.packed, dtype=np.uint32)
+    mask = np.ascontiguousarray(arena.mask, dtype=np.uint32)
+    gs = np.ascontiguousarray(arena.genome_start, dtype=np.uint64)
+    check(
+        _capi.load_library().pa_tetra_counts_host(packed.ctypes.data, mask.ctypes.data, arena.arena_bases, gs.ctypes.data, n, counts.ctypes.data,
+                                                  int(threads)),
+        "pa_tetra_counts_host",
+    )  # fmt: skip
+    return counts
+
+
+def tetra_zscores(counts) -> tuple[np.ndarray, np.ndarray]:
+    """``pa_tetra_zscores_host``: ``(Z, U)``, the tetranucleotide Z-scores and their unit rows (``[n, 256]`` float64 each;
+    a degenerate genome's U is all NaN) from the forward counts ``[n, 336]``.  Host only: 256 values per genome."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    if counts.ndim != 2 or counts.shape[1] != _capi.PA_TETRA_BINS:
+        raise ValueError(f"counts have shape {counts.shape}, expected (n, {_capi.PA_TETRA_BINS})")
+    n = counts.shape[0]
+    z = np.zeros((n, _capi.PA_TETRA_WORDS), dtype=np.float64)
+    u = np.zeros((n, _capi.PA_TETRA_WORDS), dtype=np.float64)
+    check(_capi.load_library().pa_tetra_zscores_host(counts.ctypes.data, n, z.ctypes.data, u.ctypes.data), "pa_tetra_zscores_host")
+    return z, u
+
+
+def tetra_correlations_host(U, q_range=None, s_range=None, threads: int = 0) -> np.ndarray:
+    """``pa_tetra_corr_host``: what ``HipEngine.tetra_correlations`` returns, the same bits, on host threads."""
+    u = np.ascontiguousarray(U, dtype=np.float64)
+    if u.ndim != 2 or u.shape[1] != _capi.PA_TETRA_WORDS:
+        raise ValueError(f"U has shape {u.shape}, expected (n, {_capi.PA_TETRA_WORDS})")
+    n = u.shape[0]
+    (q0, q1), (s0, s1) = q_range or (0, n), s_range or (0, n)
+    if not (0 <= q0 <= q1 <= n and 0 <= s0 <= s1 <= n):
+        raise ValueError(f"ranges [{q0}, {q1}) x [{s0}, {s1}) outside the {n} genomes")
+    out = np.empty((q1 - q0, s1 - s0), dtype=np.float64)
+    check(
+        _capi.load_library().pa_tetra_corr_host(u.ctypes.data, n, q0, q1, s0, s1, int((q0, q1) == (s0, s1)), out.ctypes.data, int(threads)),
+        "pa_tetra_corr_host",
+    )
+    return out
 
 
 # ------------------------------------------------------------------ external alignment (external-alignment-hip)

@@ -1,5 +1,5 @@
-"""Run driver and persistence for the three methods ``sourmash-hip``, ``fastANI-hip`` and ``external-alignment-hip``
-(stdlib ``sqlite3``).
+"""Run driver and persistence for the four methods ``sourmash-hip``, ``fastANI-hip``, ``external-alignment-hip`` and
+``TETRA-hip`` (stdlib ``sqlite3``).
 
 The reference's Python (Typer CLI, SQLAlchemy ORM, snakemake) does not travel to the GPU
 box, so this module is the build's own counterpart of ``cli_sourmash`` / ``fastani`` / ``external_alignment`` +
@@ -58,7 +58,7 @@ from . import scatter as scatter_mod
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
 from .engine import load_fasta_files
-from .methods import external_alignment_hip, fastani_hip, sourmash_hip
+from .methods import external_alignment_hip, fastani_hip, sourmash_hip, tetra_hip
 from .methods.external_alignment_hip import filename_stem  # also reached as ``rundb.filename_stem``
 
 FASTA_EXTENSIONS = {".fasta", ".fas", ".fna", ".fa"}  # pyani_plus/__init__.py:48
@@ -1186,10 +1186,75 @@ def run_external_alignment_hip(  # noqa: PLR0913
     return _finish_run(state, _compute_missing_external_alignment(state))
 
 
+# ------------------------------------------------------------------ TETRA-hip (no counterpart in the reference)
+def _tetra_one_gpu_only(logger, gpus: int) -> None:
+    if int(gpus) != 1:
+        sourmash_hip.log_sys_exit(logger, f"{tetra_hip.METHOD} runs on the host or on one GPU; --gpus {gpus} is not supported")
+
+
+def _compute_missing_tetra(state: _RunState, *, precounted: dict | None = None) -> None:
+    """The subject columns the database does not complete yet, through the column worker and its JSON file: the count
+    files first (only those the cache lacks), then all columns in one file for a new run, the incomplete ones otherwise."""
+    _tetra_one_gpu_only(state.logger, state.gpus)
+    missing = _begin_missing(state)
+    if missing is None:
+        return
+    state.cache_dir = _work_dir(state.cache_dir, "pyani_hip_cache_")
+    for _ in tetra_hip.prepare_genomes(state.logger, state.run, state.cache_dir, engine=state.engine, precounted=precounted):
+        pass
+    state.mark("count_files")
+    query_hashes = {a.genome_hash: 0 for a in state.run.fasta_hashes}
+    _json_columns(state, tetra_hip.compute_tetra_hip, query_hashes, missing[1], cache=state.cache_dir)
+
+
+def run_tetra_hip(  # noqa: PLR0913
+    fasta: Path,
+    database: Path | str,
+    *,
+    cache: Path | None = None,
+    name: str | None = None,
+    temp: Path | None = None,
+    logger: logging.Logger | None = None,
+    engine=None,
+    timings: dict | None = None,
+    gpus: int = 1,
+) -> Run:
+    """FASTA directory -> database with all N^2 TETRA-hip comparisons and cached matrices.  The reference has no such
+    command; the method's definition is this project's own (``methods/tetra_hip.py``).  ``engine`` None computes on the
+    host, a ``HipEngine`` on its device, with the same rows.  The configuration records method, program and version
+    only; every row has an identity (NULL for a degenerate genome) and NULL coverage.  ``gpus`` > 1 is refused."""
+    mark = _phase_clock(timings)
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    _tetra_one_gpu_only(logger, gpus)
+    fasta = Path(fasta)
+    fasta_names = check_fasta(logger, fasta)
+    tool = tetra_hip.get_tetra_hip()
+    conn = connect_to_db(database)
+    config = db_configuration(conn, tetra_hip.METHOD, tool.exe_path.stem, tool.version)
+    # one pass over the files: checksum, length, title and -- from the same arena -- the counts
+    infos, arena = load_fasta_files(fasta_names)
+    md5_to_filename: dict[str, Path] = {}
+    for filename, info in zip(fasta_names, infos):
+        if info.status != 0:
+            sourmash_hip.log_sys_exit(logger, info.message)
+        _record_genome(logger, conn, md5_to_filename, filename, info.md5, info.length, info.description)
+    mark("register_genomes")
+    try:
+        counts = tetra_hip.count_arena(arena, engine)
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, f"{tetra_hip.METHOD} counting", err)
+    del arena
+    mark("counts")
+    state = _RunState(logger, conn, _work_dir(temp), _work_dir(cache, "pyani_hip_cache_"), engine, gpus, None, "json", mark)
+    _record_run(state, config, fasta, "Initialising", name, md5_to_filename)
+    return _finish_run(state, _compute_missing_tetra(state, precounted={info.md5: row for info, row in zip(infos, counts)}))
+
+
 _METHODS = {  # method name -> (its tool, its "compute what is missing"): what ``resume`` needs to know of a method
     sourmash_hip.METHOD: (sourmash_hip.get_sourmash_hip, _compute_missing_sourmash),
     fastani_hip.METHOD: (fastani_hip.get_fastani_hip, _compute_missing_fastani),
     external_alignment_hip.METHOD: (external_alignment_hip.get_external_alignment_hip, _compute_missing_external_alignment),
+    tetra_hip.METHOD: (tetra_hip.get_tetra_hip, _compute_missing_tetra),
 }
 
 
@@ -1701,7 +1766,7 @@ def plot_run_comp(database: Path | str, outdir: Path, run_ids, *, columns: int =
 
 # ------------------------------------------------------------------ the driver as a process
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,resume,export-run,classify,plot-run,plot-run-comp} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -1735,6 +1800,10 @@ def main(argv: list[str] | None = None) -> int:
     common(p_x, run_options=True)
     p_x.add_argument("--alignment", required=True, type=Path, help="FASTA MSA of the genomes, one row per genome")
     p_x.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
+    p_t = sub.add_parser("tetra", help="FASTA directory -> all N^2 TETRA-hip comparisons (tetranucleotide Z-score correlations)")
+    common(p_t, run_options=True)
+    p_t.add_argument("--cache", type=Path, default=None)
+    p_t.add_argument("--device", type=int, default=None, help="count and correlate on this GPU (default: on the host)")
     p_r = sub.add_parser("resume", help="complete a partial run")
     common(p_r, run_options=False)
     p_r.add_argument("--run-id", type=int, default=None)
@@ -1789,6 +1858,18 @@ def main(argv: list[str] | None = None) -> int:
         elif args.command == "external-alignment":
             run = run_external_alignment_hip(args.fasta, args.database, alignment=args.alignment, label=args.label, name=args.name,
                                              temp=args.temp, logger=logger, gpus=args.gpus)
+        elif args.command == "tetra":
+            engine = None
+            if args.device is not None:
+                from .engine import HipEngine
+
+                engine = HipEngine(args.device)
+            try:
+                run = run_tetra_hip(args.fasta, args.database, cache=args.cache, name=args.name, temp=args.temp, logger=logger, engine=engine,
+                                    gpus=args.gpus)
+            finally:
+                if engine is not None:
+                    engine.close()
         elif args.command == "resume":
             run = resume(args.database, run_id=args.run_id, cache=args.cache, temp=args.temp, logger=logger, ingest=args.ingest,
                          gpus=args.gpus, engine_factory=args.engine_factory)

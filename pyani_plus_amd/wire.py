@@ -171,6 +171,32 @@ class ColumnFileWriter:
         self.rows += nq * ns
         self.logger.debug("Saved %d comparisons to %s", self.rows, self.path)
 
+    def append_identity(self, queries: list[str], subjects: list[str], identity) -> None:
+        """One more block of comparisons of a method without coverage (TETRA-hip): ``identity`` (NaN: NULL) beside a
+        NULL ``cov_query`` in every row (native ``pa_append_identity_json``; ``append``'s ``is_null`` stands for both)."""
+        import ctypes as C
+
+        import numpy as np
+
+        from . import _capi
+
+        nq, ns = len(queries), len(subjects)
+        if nq == 0 or ns == 0:
+            return
+        identity = np.ascontiguousarray(identity, dtype=np.float64)
+        assert identity.shape == (nq, ns)
+        null = np.ascontiguousarray(np.isnan(identity), dtype=np.uint8)
+        q_arr = (C.c_char_p * nq)(*[q.encode() for q in queries])
+        s_arr = (C.c_char_p * ns)(*[s.encode() for s in subjects])
+        _capi.check(
+            _capi.load_library().pa_append_identity_json(
+                str(self.path).encode(), self.SUFFIX.encode(), int(self.rows > 0), q_arr, nq, s_arr, ns, identity.ctypes.data, null.ctypes.data
+            ),
+            "pa_append_identity_json",
+        )
+        self.rows += nq * ns
+        self.logger.debug("Saved %d comparisons to %s", self.rows, self.path)
+
 
 def _empty(dtype=float):
     import numpy as np
