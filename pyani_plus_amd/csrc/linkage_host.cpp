@@ -27,6 +27,8 @@
 #pragma GCC optimize("fp-contract=off")
 #endif
 
+#include "pairs_f64_host.h"  // after the pragma: its loop is compiled with contraction off
+
 void pa_set_error(const char *fmt, ...);
 
 namespace {
@@ -49,38 +51,12 @@ int pa_rowdist_euclid_host(const double *h_x, uint32_t n, uint32_t m, double *h_
     const uint32_t nt = pa_host_threads(steps, 1u << 20, n_threads);
     std::atomic<uint32_t> next{0};
     HostPool::get().run(nt, [&](uint32_t, uint32_t) {
-      // rows are handed out one at a time (row i has n - 1 - i pairs); eight pairs of one row run side by side so that
-      // the eight dependent chains of additions overlap -- each chain keeps its own order
-      constexpr uint32_t kSide = 8;
-      for (;;) {
+      for (;;) {  // rows are handed out one at a time (row i has n - 1 - i pairs)
         const uint32_t i = next.fetch_add(1, std::memory_order_relaxed);
         if (i + 1 >= n) break;
-        const double *a = h_x + (uint64_t)i * m;
         double *out = h_out + condensed_index(n, i, i + 1);
-        uint32_t j = i + 1;
-        for (; j + kSide <= n; j += kSide) {
-          double s[kSide] = {0, 0, 0, 0, 0, 0, 0, 0};
-          const double *b = h_x + (uint64_t)j * m;
-          for (uint32_t c = 0; c < m; ++c) {
-            const double ac = a[c];
-            for (uint32_t u = 0; u < kSide; ++u) {
-              const double d = ac - b[(uint64_t)u * m + c];
-              const double sq = d * d;
-              s[u] = s[u] + sq;
-            }
-          }
-          for (uint32_t u = 0; u < kSide; ++u) out[j - i - 1 + u] = std::sqrt(s[u]);
-        }
-        for (; j < n; ++j) {
-          const double *b = h_x + (uint64_t)j * m;
-          double s = 0.0;
-          for (uint32_t c = 0; c < m; ++c) {
-            const double d = a[c] - b[c];
-            const double sq = d * d;
-            s = s + sq;
-          }
-          out[j - i - 1] = std::sqrt(s);
-        }
+        pairs_f64::pair_row_accumulate<pairs_f64::EuclidTerm>(h_x + (uint64_t)i * m, h_x + (uint64_t)(i + 1) * m, n - 1 - i, m,
+                                                              [out](uint32_t u, double s) { out[u] = std::sqrt(s); });
       }
     });
     return PA_OK;

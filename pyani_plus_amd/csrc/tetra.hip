@@ -31,8 +31,8 @@
 // vector global atomic.  Integer sums: the result does not depend on the order, two runs give the same counts.
 //
 // ---- tetra_corr_kernel ----------------------------------------------------------------------------------------------
-// rowdist.hip's tiling with a product in place of the squared difference: 64 x 64 pairs per 256-thread workgroup, 4 x 4
-// pairs per lane, the two 64-row panels staged transposed through LDS 16 columns at a time, double-buffered.  Bit
+// The tile skeleton of pairs_f64_tile.h (which has the layout) with a product as its term and the 256 columns known at
+// compile time: 64 x 64 pairs per 256-thread workgroup, 4 x 4 pairs per lane.  Bit
 // contract: one accumulator per pair, acc = acc + U_a[k] * U_b[k] for k = 0 .. 255 ascending, the product rounded before
 // the addition (contraction is off for this file, and the Makefile passes -ffp-contract=off), no split over k, no
 // atomics; r = min(1, max(-1, acc)), NaN kept; the diagonal (same genome index) is exactly 1.0 unless NaN.  The f64 matrix
@@ -41,6 +41,8 @@
 #include "pa_internal.h"
 
 #pragma clang fp contract(off)
+
+#include "pairs_f64_tile.h"
 
 namespace {
 
@@ -183,38 +185,16 @@ static_assert(kThreads == 256, "the flush takes one tetranucleotide per lane");
 static_assert(kBins == 336, "256 tetra-, 64 tri- and 16 dinucleotides");
 
 // ---- correlations -----------------------------------------------------------------------------------------------------
-constexpr int kTile = 64;
+constexpr int kTile = 64;              // rows of queries and of subjects per workgroup: the launch grid's step
 constexpr int kCols = PA_TETRA_WORDS;  // 256 columns per row
-constexpr int kStage = 16;             // columns per stage
-constexpr int kStride = kTile + 2;     // doubles per LDS column: 16-byte aligned rows of four (rowdist.hip)
-constexpr int kLoads = kTile * kStage / kThreads;
+static_assert(kTile == pairs_f64::kTile && kThreads == pairs_f64::kThreads, "the correlation kernel is launched with the skeleton's tile and workgroup");
 
-struct Staged {
-  double a[kLoads], b[kLoads];
+struct DotTerm {
+  static __device__ __forceinline__ double add(double acc, double a, double b) {
+    const double p = a * b;  // rounded here: contraction is off for this file
+    return acc + p;
+  }
 };
-
-// the lane's share of columns [c0, c0 + kStage) of the two panels: element f = tid + 256 e is (row f / 16, column f % 16);
-// rows past the ranges are staged as 0.0 and their pairs are never written
-__device__ __forceinline__ void load_stage(const double *__restrict__ u, uint32_t i0, uint32_t i_end, uint32_t j0, uint32_t j_end, uint32_t c0,
-                                           Staged &st) {
-#pragma unroll
-  for (int e = 0; e < kLoads; ++e) {
-    const uint32_t f = threadIdx.x + kThreads * e;
-    const uint32_t r = f / kStage, c = c0 + f % kStage;
-    const uint32_t ia = i0 + r, jb = j0 + r;
-    st.a[e] = ia < i_end ? u[(uint64_t)ia * kCols + c] : 0.0;
-    st.b[e] = jb < j_end ? u[(uint64_t)jb * kCols + c] : 0.0;
-  }
-}
-
-__device__ __forceinline__ void store_stage(double (*pa)[kStride], double (*pb)[kStride], const Staged &st) {
-#pragma unroll
-  for (int e = 0; e < kLoads; ++e) {
-    const uint32_t f = threadIdx.x + kThreads * e;
-    pa[f % kStage][f / kStage] = st.a[e];
-    pb[f % kStage][f / kStage] = st.b[e];
-  }
-}
 
 __device__ __forceinline__ double finish_r(double acc, bool same) {
   if (acc != acc) return acc;  // a degenerate genome: NaN (min and max would drop it)
@@ -228,44 +208,10 @@ __global__ __launch_bounds__(kThreads, 4) void tetra_corr_kernel(const double *_
                                                               int symmetric, double *__restrict__ out) {
   const uint32_t tj = blockIdx.x, ti = blockIdx.y;
   if (symmetric && tj < ti) return;
-  __shared__ __attribute__((aligned(16))) double pa[2][kStage][kStride];
-  __shared__ __attribute__((aligned(16))) double pb[2][kStage][kStride];
   const uint32_t i0 = q0 + ti * kTile, j0 = s0 + tj * kTile;
   const uint32_t ty = threadIdx.x / 16, tx = threadIdx.x % 16;
   double acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
-
-  constexpr uint32_t n_stages = kCols / kStage;
-  Staged st;
-  load_stage(u, i0, q1, j0, s1, 0, st);
-  store_stage(pa[0], pb[0], st);
-  __syncthreads();
-  for (uint32_t k = 0; k < n_stages; ++k) {
-    const int cur = (int)(k & 1u);
-    const bool more = k + 1 < n_stages;
-    if (more) load_stage(u, i0, q1, j0, s1, (k + 1) * kStage, st);
-#pragma unroll 4
-    for (int c = 0; c < kStage; ++c) {
-      const double2 a01 = *reinterpret_cast<const double2 *>(&pa[cur][c][4 * ty]);
-      const double2 a23 = *reinterpret_cast<const double2 *>(&pa[cur][c][4 * ty + 2]);
-      const double2 b01 = *reinterpret_cast<const double2 *>(&pb[cur][c][4 * tx]);
-      const double2 b23 = *reinterpret_cast<const double2 *>(&pb[cur][c][4 * tx + 2]);
-      const double av[4] = {a01.x, a01.y, a23.x, a23.y};
-      const double bv[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const double p = av[a] * bv[b];  // rounded here: contraction is off for this file
-          acc[a][b] = acc[a][b] + p;
-        }
-    }
-    if (more) store_stage(pa[cur ^ 1], pb[cur ^ 1], st);
-    __syncthreads();
-  }
+  pairs_f64::pair_tile_accumulate<kCols, DotTerm>(u, kCols, i0, q1, j0, s1, ty, tx, acc);
 
   const uint64_t ns = s1 - s0;
 #pragma unroll

@@ -25,6 +25,8 @@
 #pragma GCC optimize("fp-contract=off")
 #endif
 
+#include "pairs_f64_host.h"  // after the pragma: its loop is compiled with contraction off
+
 void pa_set_error(const char *fmt, ...);
 
 namespace {
@@ -169,30 +171,18 @@ int pa_tetra_corr_host(const double *h_U, uint32_t n, uint32_t q0, uint32_t q1, 
     const uint32_t nt = pa_host_threads((uint64_t)(q1 - q0) * ns * kWords, 1u << 20, n_threads);
     std::atomic<uint32_t> next{q0};
     HostPool::get().run(nt, [&](uint32_t, uint32_t) {
-      constexpr uint32_t kSide = 8;  // eight pairs of one row side by side: eight chains of additions, each in its own order
       for (;;) {
         const uint32_t i = next.fetch_add(1, std::memory_order_relaxed);
         if (i >= q1) break;
-        const double *a = h_U + (uint64_t)i * kWords;
         double *out = h_out + (uint64_t)(i - q0) * ns;
         const uint32_t j_first = symmetric ? i : s0;  // symmetric: row i from the diagonal on, mirrored
-        for (uint32_t j = j_first; j < s1; j += kSide) {
-          const uint32_t side = std::min(kSide, s1 - j);
-          double acc[kSide] = {0, 0, 0, 0, 0, 0, 0, 0};
-          const double *b = h_U + (uint64_t)j * kWords;
-          for (uint32_t k = 0; k < kWords; ++k) {
-            const double ak = a[k];
-            for (uint32_t u = 0; u < side; ++u) {
-              const double p = ak * b[(uint64_t)u * kWords + k];
-              acc[u] = acc[u] + p;
-            }
-          }
-          for (uint32_t u = 0; u < side; ++u) {
-            const double r = finish_r(acc[u], i == j + u);
-            out[j + u - s0] = r;
-            if (symmetric) h_out[(uint64_t)(j + u - q0) * ns + (i - s0)] = r;
-          }
-        }
+        auto finish = [&](uint32_t u, double acc) {
+          const uint32_t j = j_first + u;
+          const double r = finish_r(acc, i == j);
+          out[j - s0] = r;
+          if (symmetric) h_out[(uint64_t)(j - q0) * ns + (i - s0)] = r;
+        };
+        pairs_f64::pair_row_accumulate<pairs_f64::DotTerm>(h_U + (uint64_t)i * kWords, h_U + (uint64_t)j_first * kWords, s1 - j_first, kWords, finish);
       }
     });
     return PA_OK;

@@ -290,6 +290,16 @@ class DeviceSketches:
         return [flat[int(off[g]) : int(off[g + 1])].copy() for g in range(self.n)]
 
 
+def _pair_ranges(n: int, q_range, s_range, *, tetra: bool = False) -> tuple[int, int, int, int]:
+    """``(q0, q1, s0, s1)`` of an all-pairs call: the query and the subject range, each all ``n`` unless given.
+    ``tetra``: checked against the ``n`` genomes of a TETRA-hip call, before the output is allocated."""
+    q0, q1 = q_range or (0, n)
+    s0, s1 = s_range or (0, n)
+    if tetra and not (0 <= q0 <= q1 <= n and 0 <= s0 <= s1 <= n):
+        raise ValueError(f"ranges [{q0}, {q1}) x [{s0}, {s1}) outside the {n} genomes")
+    return q0, q1, s0, s1
+
+
 class HipEngine:
     """One HIP context on one GPU.  Raises ``HipBackendError`` when no MI355X is usable."""
 
@@ -453,8 +463,7 @@ class HipEngine:
     def pair_counts(self, sk: DeviceSketches, q_range=None, s_range=None, algo: int = _capi.PA_PAIRS_AUTO):
         """uint32 |S_q n S_s| for q in q_range, s in s_range -> torch.int32 [nq, ns] on the GPU."""
         t = self.torch
-        q0, q1 = q_range or (0, sk.n)
-        s0, s1 = s_range or (0, sk.n)
+        q0, q1, s0, s1 = _pair_ranges(sk.n, q_range, s_range)
         counts = t.empty((q1 - q0, s1 - s0), dtype=t.int32, device=self.device)
         h_off = sk.offsets_host()  # one small copy per sketch set, cached; the pair phase itself then never waits for the host
         assert h_off.dtype == np.uint64 and len(h_off) == sk.n + 1
@@ -474,8 +483,7 @@ class HipEngine:
     def ani(self, counts, sk: DeviceSketches, k: int, q_range=None, s_range=None):
         """Device f64 (identity, cov_query); NaN marks the reference's NULL."""
         t = self.torch
-        q0, q1 = q_range or (0, sk.n)
-        s0, s1 = s_range or (0, sk.n)
+        q0, q1, s0, s1 = _pair_ranges(sk.n, q_range, s_range)
         ident = t.empty((q1 - q0, s1 - s0), dtype=t.float64, device=self.device)
         cov = t.empty_like(ident)
         self._check(
@@ -504,8 +512,7 @@ class HipEngine:
     def pair_mash(self, sk: DeviceSketches, m: int, q_range=None, s_range=None):
         """(common, denom) int32 tensors [nq, ns] of the Mash Jaccard estimator."""
         t = self.torch
-        q0, q1 = q_range or (0, sk.n)
-        s0, s1 = s_range or (0, sk.n)
+        q0, q1, s0, s1 = _pair_ranges(sk.n, q_range, s_range)
         common = t.empty((q1 - q0, s1 - s0), dtype=t.int32, device=self.device)
         denom = t.empty_like(common)
         self._check(
@@ -615,8 +622,7 @@ class HipEngine:
     def msa_pair_counts(self, dm: "DeviceMSA", q_range=None, s_range=None, *, symmetric: bool = False):
         """(M, B) as torch.int32 [nq, ns] on the device for rows q_range x s_range (uint32 values)."""
         t = self.torch
-        q0, q1 = q_range or (0, dm.n_rows)
-        s0, s1 = s_range or (0, dm.n_rows)
+        q0, q1, s0, s1 = _pair_ranges(dm.n_rows, q_range, s_range)
         match = t.empty((q1 - q0, s1 - s0), dtype=t.int32, device=self.device)
         both = t.empty((q1 - q0, s1 - s0), dtype=t.int32, device=self.device)
         if match.numel() == 0:
@@ -635,13 +641,7 @@ class HipEngine:
         (int32 views of uint32, float64), trimmed to the number of edges.  ``score`` and ``cov`` are N x N float64,
         host arrays or tensors on this device."""
         t = self.torch
-
-        def on_device(m):
-            if not isinstance(m, t.Tensor):
-                m = t.from_numpy(np.ascontiguousarray(m, dtype=np.float64))
-            return m.to(device=self.device, dtype=t.float64).contiguous()
-
-        d_score, d_cov = on_device(score), on_device(cov)
+        d_score, d_cov = self._f64_on_device(score), self._f64_on_device(cov)
         n = d_score.shape[0]
         if d_score.shape != (n, n) or d_cov.shape != (n, n):
             raise ValueError(f"score {tuple(d_score.shape)} and coverage {tuple(d_cov.shape)} must be square and equal")
@@ -674,9 +674,7 @@ class HipEngine:
         """``pa_rowdist_euclid``: the condensed Euclidean distances between the rows of ``matrix`` (n x m float64, a
         host array or a tensor on this device; finite values) as a device tensor of n (n - 1) / 2 float64."""
         t = self.torch
-        if not isinstance(matrix, t.Tensor):
-            matrix = t.from_numpy(np.ascontiguousarray(matrix, dtype=np.float64))
-        d_x = matrix.to(device=self.device, dtype=t.float64).contiguous()
+        d_x = self._f64_on_device(matrix)
         if d_x.dim() != 2:
             raise ValueError(f"matrix has shape {tuple(d_x.shape)}, expected two dimensions")
         n, m = d_x.shape
@@ -846,9 +844,7 @@ class HipEngine:
         if d_u.dim() != 2 or d_u.shape[1] != _capi.PA_TETRA_WORDS:
             raise ValueError(f"U has shape {tuple(d_u.shape)}, expected (n, {_capi.PA_TETRA_WORDS})")
         n = d_u.shape[0]
-        (q0, q1), (s0, s1) = q_range or (0, n), s_range or (0, n)
-        if not (0 <= q0 <= q1 <= n and 0 <= s0 <= s1 <= n):
-            raise ValueError(f"ranges [{q0}, {q1}) x [{s0}, {s1}) outside the {n} genomes")
+        q0, q1, s0, s1 = _pair_ranges(n, q_range, s_range, tetra=True)
         out = t.empty((q1 - q0, s1 - s0), dtype=t.float64, device=self.device)
         self._check(self.lib.pa_tetra_corr(self.ctx, d_u.data_ptr(), n, q0, q1, s0, s1, int((q0, q1) == (s0, s1)), out.data_ptr()), "pa_tetra_corr")
         return out
@@ -935,9 +931,7 @@ def tetra_correlations_host(U, q_range=None, s_range=None, threads: int = 0) -> 
     if u.ndim != 2 or u.shape[1] != _capi.PA_TETRA_WORDS:
         raise ValueError(f"U has shape {u.shape}, expected (n, {_capi.PA_TETRA_WORDS})")
     n = u.shape[0]
-    (q0, q1), (s0, s1) = q_range or (0, n), s_range or (0, n)
-    if not (0 <= q0 <= q1 <= n and 0 <= s0 <= s1 <= n):
-        raise ValueError(f"ranges [{q0}, {q1}) x [{s0}, {s1}) outside the {n} genomes")
+    q0, q1, s0, s1 = _pair_ranges(n, q_range, s_range, tetra=True)
     out = np.empty((q1 - q0, s1 - s0), dtype=np.float64)
     check(
         _capi.load_library().pa_tetra_corr_host(u.ctypes.data, n, q0, q1, s0, s1, int((q0, q1) == (s0, s1)), out.ctypes.data, int(threads)),

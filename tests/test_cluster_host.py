@@ -37,6 +37,17 @@ def test_host_distances_equal_the_numpy_restatement(shape):
             assert got[0] == 0.0 and not np.signbit(got[0])  # rows 0 and 1 are equal: +0.0
 
 
+@pytest.mark.parametrize("n", (7, 8, 9, 17))
+def test_host_distances_around_the_eight_pairs_side_by_side(n):
+    """A row's pairs run eight at a time: fewer than eight, exactly eight, one more, and two groups and one, with one
+    column, sixteen and seventeen."""
+    for m in (1, 16, 17):
+        for _name, x in distance_inputs(n, m):
+            got = cluster.row_distances(x)
+            same_bits(got, numpy_distances(x))
+            same_bits(cluster.row_distances(x, threads=1), got)
+
+
 def test_host_distances_small_inputs_and_arguments():
     assert cluster.row_distances(np.zeros((0, 4))).shape == (0,)
     assert cluster.row_distances(np.zeros((1, 4))).shape == (0,)

@@ -15,8 +15,10 @@ from tests.plot_run_cases import case_matrix, distance_inputs, filled, load_case
 pytestmark = pytest.mark.gpu
 
 # the tile edges (63, 64, 65), a ragged last column chunk and more than one chunk (257 and 130 columns of 16), more tiles
-# than one wave of workgroups (1000 rows: 136 tiles of 64 x 64)
-SHAPES = ((2, 2), (3, 3), (63, 63), (64, 64), (65, 65), (130, 257), (257, 130), (1000, 1000))
+# than one wave of workgroups (1000 rows: 136 tiles of 64 x 64); then the run-time column count at the 256 that the
+# correlation kernel fixes at compile time and one below it, exactly one stage, a single column, and one column past a
+# stage on the smallest matrix
+SHAPES = ((2, 2), (3, 3), (63, 63), (64, 64), (65, 65), (130, 257), (257, 130), (1000, 1000), (65, 256), (65, 255), (70, 16), (70, 1), (2, 17))
 CASES = load_cases()
 PLOTS = GOLDEN / "viral_example" / "plots"
 

@@ -9,7 +9,7 @@ import sqlite3
 import numpy as np
 import pytest
 
-from pyani_plus_amd import rundb
+from pyani_plus_amd import cluster, rundb
 from pyani_plus_amd.engine import HipEngine, tetra_correlations_host
 from tests import tetra_cases as tc
 from tests.helpers import GOLDEN
@@ -74,6 +74,24 @@ def test_correlation_ranges_off_the_tile_grid(engine):
     tc.same_bits(engine.tetra_correlations(unit, (17, 82), (17, 82)), full[17:82, 17:82])  # a square range: mirrored, same cells
     small = [tc.unit_row(tc.zscores(tc.forward_counts(tc.fasta(tc.random_bases(np.random.default_rng(s), 2000))))) for s in range(3)]
     tc.same_bits(engine.tetra_correlations(np.array(small)), tc.correlation_matrix(small))  # and the plain-Python restatement
+
+
+def test_both_tile_instantiations_back_to_back(engine):
+    """The tile skeleton's two instantiations (run-time columns in the row distances, 256 fixed here) alternate in one
+    context; each result has its host twin's bits and the second distance call repeats the first."""
+    unit = tc.unit_rows(130)
+    finite = unit.copy()
+    finite[1] = 0.0  # the distances take finite rows
+    assert np.isnan(unit[1]).all() and np.isfinite(finite).all()
+    first = engine.row_distances(finite)
+    whole = engine.tetra_correlations(unit)
+    second = engine.row_distances(finite)
+    part = engine.tetra_correlations(unit, (3, 70), (60, 129))
+    tc.same_bits(first, cluster.row_distances(finite))
+    tc.same_bits(whole, tetra_correlations_host(unit))
+    tc.same_bits(second, cluster.row_distances(finite))
+    tc.same_bits(part, tetra_correlations_host(unit, (3, 70), (60, 129)))
+    assert np.array_equal(first.view(np.uint64), second.view(np.uint64))
 
 
 def _rows(database):

@@ -66,6 +66,21 @@ def test_zscores_unit_rows_and_r_bit_for_bit(genomes):
     tc.same_bits(tetra_correlations_host(u, (2, 3), (2, 3), threads=1), tc.correlation_matrix(want_u, (2, 3), (2, 3)))
 
 
+@pytest.mark.parametrize("n", (7, 8, 9, 17))
+def test_r_around_the_eight_pairs_side_by_side(n):
+    """A row's pairs run eight at a time: the whole matrix (row i from the diagonal on: n - i pairs), a rectangle of
+    three subjects, and a square range off zero against the same cells of the whole matrix; row 1 is all NaN."""
+    unit = tc.unit_rows(n)
+    assert np.isnan(unit[1]).all() and not np.isnan(np.delete(unit, 1, axis=0)).any()
+    rows = unit.tolist()
+    whole = tetra_correlations_host(unit)
+    tc.same_bits(whole, tc.correlation_matrix(rows))
+    tc.same_bits(tetra_correlations_host(unit, threads=1), whole)
+    tc.same_bits(tetra_correlations_host(unit, (1, n), (0, 3)), tc.correlation_matrix(rows, (1, n), (0, 3)))
+    tc.same_bits(tetra_correlations_host(unit, (2, n), (2, n)), whole[2:, 2:])
+    tc.same_bits(tetra_correlations_host(unit, (2, n), (2, n)), tc.correlation_matrix(rows, (2, n), (2, n)))
+
+
 def test_r_is_numpy_corrcoef(genomes):
     """Each computation's error on unit vectors is bounded by about 256 * 2^-53 = 3e-14; the bound asked is 1e-12."""
     _texts, _counts, z, u = genomes

@@ -9,8 +9,8 @@ Two layers, neither of which goes through the library:
 
 The definition is this project's own (after Teeling et al. 2004); nothing here is taken from pyani or JSpecies.
 
-The case builders read the chunk and tile constants from ``csrc/tetra.hip``, so that the seam cases sit on the kernel's
-seams whatever those constants are.  Used by tests/test_tetra_host.py (no GPU) and tests/test_gpu_tetra.py."""
+The case builders read the chunk constants from ``csrc/tetra.hip`` and the tile from ``csrc/pairs_f64_tile.h``, so that
+the seam cases sit on the kernel's seams whatever those constants are.  Used by tests/test_tetra_host.py (no GPU) and tests/test_gpu_tetra.py."""
 
 from __future__ import annotations
 
@@ -30,13 +30,15 @@ for _i, _c in enumerate("ACGT"):
 
 @lru_cache(maxsize=None)
 def kernel_constants() -> dict[str, int]:
-    """kThreads, kBlocksPerLane, kCopies and kTile as csrc/tetra.hip states them."""
-    text = (ROOT / "pyani_plus_amd" / "csrc" / "tetra.hip").read_text()
+    """kThreads, kBlocksPerLane and kCopies as csrc/tetra.hip states them, kTile as csrc/pairs_f64_tile.h does."""
+    csrc = ROOT / "pyani_plus_amd" / "csrc"
     out = {}
-    for name in ("kThreads", "kBlocksPerLane", "kCopies", "kTile"):
-        found = re.search(rf"constexpr int {name} = (\d+);", text)
-        assert found, f"{name} not found in tetra.hip"
-        out[name] = int(found.group(1))
+    for file, names in (("tetra.hip", ("kThreads", "kBlocksPerLane", "kCopies")), ("pairs_f64_tile.h", ("kTile",))):
+        text = (csrc / file).read_text()
+        for name in names:
+            found = re.search(rf"constexpr int {name} = (\d+);", text)
+            assert found, f"{name} not found in {file}"
+            out[name] = int(found.group(1))
     return out
 
 
