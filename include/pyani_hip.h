@@ -704,6 +704,40 @@ PA_API int pa_tetra_corr_host(const double *h_U, uint32_t n, uint32_t q0, uint32
 PA_API int pa_append_identity_json(const char *path, const char *suffix, int file_has_rows, const char *const *q_hashes, uint32_t nq,
                                    const char *const *s_hashes, uint32_t ns, const double *identity, const uint8_t *is_null);
 
+/* ---- tree-run: the neighbour-joining tree of a distance matrix ----
+ * Replaces nothing in the reference: pyani-plus writes no tree.  The definition below is this project's own contract
+ * (canonical neighbour joining, Saitou & Nei 1987 in Studier & Keppler's form); it is pinned by an independent
+ * restatement in tests/tree_cases.py, and no parity with any other program is claimed.  DESIGN.md section 7h.
+ *
+ * Input.  D, n x n f64 row-major: finite, >= 0, bitwise symmetric, zero diagonal; 1 <= n <= 65535.  Otherwise
+ * PA_E_INVALID, and pa_last_error() names the first offending cell in row-major order as D[i,j].
+ * Node ids.  Leaves 0 .. n - 1; the node made by join t (t = 0, 1, ...) is n + t.
+ * Set-up.  r[i] = D[i, 0] + ... + D[i, n - 1], added in this order into one accumulator; m = n live nodes.
+ * While m > 2, every step one IEEE double operation (no FMA):
+ *   score of a live pair with ids lo < hi   q = ((double)(m - 2) * d(lo, hi) - r[lo]) - r[hi];
+ *   choice   the pair with the smallest q; among equal q (== on doubles: -0.0 ties with 0.0) the smallest lo, then the
+ *            smallest hi.  Ties go by node id, not by where a node is stored: the storage layout is free;
+ *   join     d = d(lo, hi); len_lo = 0.5 * d + (r[lo] - r[hi]) / (2.0 * (double)(m - 2)); len_hi = d - len_lo;
+ *            negative lengths are kept as they come; the record of join t is (lo, hi, len_lo, len_hi);
+ *   new node u   for every other live k: d(u, k) = 0.5 * ((d(lo, k) + d(hi, k)) - d);
+ *            r[k] = ((r[k] - d(lo, k)) - d(hi, k)) + d(u, k); r[u] = 0.5 * ((r[lo] + r[hi]) - (double)m * d); m -= 1.
+ * When m = 2 the two remaining nodes a < b and d(a, b) are the last edge.  n = 2: no join, the last edge is
+ * (0, 1, D[0, 1]); n = 1: no join and no edge, nothing is written.  Distances so large that a score overflows are
+ * outside the contract (every access stays in bounds; the tree is what IEEE arithmetic gives).
+ * Outputs (host).  child[2 (n - 2)] u32 and len[2 (n - 2)] f64: join t is child[2t] = lo, child[2t + 1] = hi with
+ * len[2t], len[2t + 1]; last[2] = (a, b) and *last_len.
+ *
+ *   pa_nj        (device) d_D is device memory and is overwritten as workspace; the other workspace is the context's.
+ *        Three launches per join on the context's stream (scan of the live pairs, choice and record, update), enqueued
+ *        without a host round trip; one read-back for the check's count and one at the end for the join table.  Integer
+ *        atomics in the check only, no floating-point atomics: the same bits run to run and as the host twin.
+ *   pa_nj_host   the same from a host matrix, which it does not modify (it works on a copy; PA_E_NOMEM when that cannot
+ *        be made); the scan runs on n_threads host threads (0: as many as the process may use) and the result does not
+ *        depend on their number. */
+PA_API int pa_nj(pa_ctx *ctx, double *d_D, uint32_t n, uint32_t *h_child, double *h_len, uint32_t *h_last, double *h_last_len);
+PA_API int pa_nj_host(const double *h_D, uint32_t n, uint32_t *h_child, double *h_len, uint32_t *h_last, double *h_last_len,
+                      uint32_t n_threads);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */
@@ -719,7 +753,10 @@ PA_API int pa_append_identity_json(const char *path, const char *suffix, int fil
 #define PA_PROF_CLS_EDGES 10  /* classify: pair evaluation, counts, scan, compaction (cls_edges_kernel) */
 #define PA_PROF_CLS_SORT 11   /* classify: radix sort of the edges by score + gather */
 #define PA_PROF_ROWDIST 12   /* plot-run: all-pairs row distances (rowdist_euclid_kernel) */
-#define PA_PROF_NPHASES 13
+#define PA_PROF_NJ_SCAN 13   /* tree-run: the scan of the live pairs before each join (nj_scan_kernel) */
+#define PA_PROF_NJ_JOIN 14   /* tree-run: the choice among the tiles' candidates and the record (nj_join_kernel) */
+#define PA_PROF_NJ_UPDATE 15 /* tree-run: the new node's row and column, the row sums, the swap-remove (nj_update_kernel) */
+#define PA_PROF_NPHASES 16
 PA_API int pa_prof_enable(pa_ctx *ctx, int on);
 PA_API int pa_prof_reset(pa_ctx *ctx);
 /* total milliseconds and number of timed launches of a phase (syncs the stream) */

@@ -21,6 +21,7 @@ TOOLS_LIB_PATH = _PKG / "_lib" / "libpyani_hip_tools.so"
 
 ABI_VERSION = 5
 PA_OK = 0
+PA_E_INVALID = -1
 PA_E_NOMEM = -3
 PA_E_CAPACITY = -4
 PA_E_IO = -6
@@ -39,7 +40,7 @@ PA_BIN2D_NONE = 0xFFFFFFFFFFFFFFFF  # the `last` of an empty cell
 PA_TETRA_BINS = 336  # pa_tetra_counts: u64 per genome, 256 tetra-, 64 tri- and 16 dinucleotides
 PA_TETRA_WORDS = 256  # columns of a Z-score row and of a unit row
 PROF_PHASES = {"kmer_hash": 0, "sketch_sort": 1, "pair_dict": 2, "pair_count": 3, "ani": 4, "frag_index": 5, "frag_seed": 6, "frag_map": 7,
-               "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11, "rowdist": 12}
+               "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11, "rowdist": 12, "nj_scan": 13, "nj_join": 14, "nj_update": 15}
 PA_AGG = {"min": 0, "max": 1, "mean": 2}
 
 _u8p = C.POINTER(C.c_uint8)
@@ -201,6 +202,8 @@ SIGNATURES: dict[str, tuple] = {
     "pa_tetra_zscores_host": (C.c_int, [_vp, C.c_uint32, _vp, _vp]),
     "pa_tetra_corr": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp]),
     "pa_tetra_corr_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp, C.c_uint32]),
+    "pa_nj": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "pa_nj_host": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32]),
     "pa_append_identity_json": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, _vp, _vp]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),

@@ -133,14 +133,16 @@ constexpr bool slots_apart(uint32_t region_bytes, std::initializer_list<ScalarSl
 }
 
 // The words of pa_ctx::counters (pa_ctx::slot).  A new feature that needs a device scalar adds its slot here.
-constexpr uint32_t kCtxScalarBytes = 64;       // what pa_ctx_create reserves
+constexpr uint32_t kCtxScalarBytes = 128;      // what pa_ctx_create reserves
 constexpr ScalarSlot kCandCount{0, 2};         // pa_sketch, general path: candidates of the k-mer hash kernel, 64-bit; zeroed and read per attempt
 constexpr ScalarSlot kSketchTotal{2, 2};       // pa_build_sketch_csr, pa_sketch_from_regions, pa_sketch_bottom: the 64-bit total of their scan (written, never zeroed)
 constexpr ScalarSlot kDenseIds{4, 4};          // pa_dense_ids_sorted, two 64-bit words zeroed as one: [0] OR of the keys, [1] distinct keys (its scan's total)
 constexpr uint32_t kDenseOr = 0, kDenseDistinct = 1;  // 64-bit words within kDenseIds
 constexpr ScalarSlot kCompactTotal{8, 2};      // pa_classify_edges, pa_runcomp_join: the 64-bit total of their scan (written, never zeroed)
 constexpr ScalarSlot kRegionOverflow{12, 1};   // pa_sketch, pa_sketch_streamed: a region was too small; zeroed there, read by pa_sketch_from_regions
-static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow}),
+constexpr ScalarSlot kNjPick{16, 8};           // pa_nj: the pair a join chose, written by its join kernel and read by its update kernel (NjPick, nj.hip)
+constexpr ScalarSlot kNjBad{24, 4};            // pa_nj: two 64-bit words zeroed / set as one: [0] cells that break the contract, [1] the first of them
+static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow, kNjPick, kNjBad}),
               "two slots of pa_ctx::counters overlap or leave the block");
 
 // The words of pa_ctx::dict_scalars (pa_ctx::dict_slot), the hash dictionary's own block, touched by no other phase
@@ -164,10 +166,11 @@ constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of
 //   classify (classify.hip): cls_i, cls_j, cls_score, cls_cov, the edges in (i, j) order, before the sort
 //   plot-run's scatter figures (scatter.hip): bin2d, the two edge arrays, then the cells' counts and last indices
 //   TETRA-hip (tetra.hip): tetra_tab, the genomes' first blocks and first chunks (u32[2 (n + 1)])
+//   tree-run (nj.hip): nj_work, the row sums, the slots' node ids, the scan's candidates and the join table
 #define PA_CTX_BUFFERS(ONE, PAIR)                                                                                   \
   PAIR(cand_keys) PAIR(cand_vals) ONE(genome_blk) ONE(counters) ONE(hist) ONE(flags) ONE(scan_tmp) ONE(region_off) \
   ONE(region_cursor) ONE(dirty) PAIR(dict_keys) PAIR(dict_vals) ONE(ids) ONE(post_genome) ONE(bitrows)             \
-  ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d) ONE(tetra_tab)
+  ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d) ONE(tetra_tab) ONE(nj_work)
 
 struct pa_ctx {
   int device = 0;

@@ -854,6 +854,26 @@ class HipEngine:
         return self.tetra_correlations_device(U, q_range, s_range).cpu().numpy()
 
     # -- profiling
+    # -- tree-run
+    def nj_tree(self, D) -> tuple[np.ndarray, np.ndarray, np.ndarray, float]:
+        """``pa_nj``: the neighbour-joining tree of the n x n float64 distance matrix ``D`` (a host array or a tensor on
+        this device; finite, >= 0, bitwise symmetric, zero diagonal) as ``(child, length, last, last_len)``: join t makes
+        node n + t from ``child[t]`` (uint32, (n - 2) x 2) with the branch lengths ``length[t]``; ``last`` is the edge
+        between the two nodes that remain and ``last_len`` its length.  The library works on a copy of ``D``."""
+        t = self.torch
+        if isinstance(D, np.ndarray) and not D.flags.writeable:
+            D = D.copy()  # torch wraps writable arrays only
+        d = self._f64_on_device(D)
+        if d.dim() != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError(f"distance matrix of shape {tuple(d.shape)}, expected a square one")
+        n = d.shape[0]
+        if n > 65535:  # the library's limit, checked before a copy of n^2 doubles is made for it to refuse
+            raise ValueError(f"{n} nodes; at most 65535")
+        work = d.clone() if isinstance(D, t.Tensor) and d.data_ptr() == D.data_ptr() else d  # the call overwrites its matrix
+        out = _nj_outputs(n)
+        self._check(self.lib.pa_nj(self.ctx, work.data_ptr(), n, *(a.ctypes.data for a in out)), "pa_nj")
+        return out[0], out[1], out[2], float(out[3][0])
+
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")
 
@@ -897,6 +917,25 @@ def ani_host(counts: np.ndarray, q_sizes, s_sizes, k: int, *, symmetric: bool = 
 
 
 # ------------------------------------------------------------------ TETRA-hip: the host forms (no GPU needed)
+def _nj_outputs(n: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    joins = max(n - 2, 0)
+    return np.zeros((joins, 2), dtype=np.uint32), np.zeros((joins, 2), dtype=np.float64), np.zeros(2, dtype=np.uint32), np.zeros(1, dtype=np.float64)
+
+
+def nj_tree_host(D, threads: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray, float]:
+    """``pa_nj_host``: what ``HipEngine.nj_tree`` returns, bit for bit, from plain loops on ``threads`` host threads (0: as
+    many as the process may use); ``D`` is not modified."""
+    d = np.ascontiguousarray(D, dtype=np.float64)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise ValueError(f"distance matrix of shape {d.shape}, expected a square one")
+    n = d.shape[0]
+    if n > 65535:
+        raise ValueError(f"{n} nodes; at most 65535")
+    out = _nj_outputs(n)
+    check(_capi.load_library().pa_nj_host(d.ctypes.data, n, *(a.ctypes.data for a in out), int(threads)), "pa_nj_host")
+    return out[0], out[1], out[2], float(out[3][0])
+
+
 def tetra_counts_host(arena: HostArena, threads: int = 0) -> np.ndarray:
     """``pa_tetra_counts_host``: what ``HipEngine.tetra_counts`` returns, from a host arena on host threads."""
     n = arena.n_genomes

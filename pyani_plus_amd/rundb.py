@@ -55,6 +55,7 @@ from . import distribution as distribution_mod
 from . import distribution_figure, heatmap_figure, run_comp_figure, scatter_figure
 from . import run_comp as run_comp_mod
 from . import scatter as scatter_mod
+from . import tree as tree_mod
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
 from .engine import load_fasta_files
@@ -1465,6 +1466,52 @@ def classify(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     return written
 
 
+# ------------------------------------------------------------------ tree-run (this project's own: the reference writes no tree)
+def tree_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", method: str = "nj", missing: float = 1.0,  # noqa: PLR0913
+             engine=None, logger: logging.Logger | None = None) -> Path:
+    """Write ``<method>_identity_<nj|upgma>.nwk``: the tree of a complete run's genomes as one line of Newick text, from
+    the distances ``1 - identity`` (``tree.run_distances``: the two directions averaged; ``missing`` where a pair has no
+    identity either way).  ``method`` "nj" is canonical neighbour joining (unrooted, written with a
+    trifurcation at the last join), "upgma" the average-linkage tree of the same distances.  The matrices and labels are
+    the ones ``classify`` and ``plot-run`` read, with the reference's messages for a missing database, an incomplete run,
+    duplicate stems and an unknown label.
+
+    ``engine``: a ``HipEngine`` makes the joins of "nj" on the GPU; None makes them on the host, with the same bits.
+    UPGMA runs on the host either way."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    if str(database) == ":memory:" or not Path(database).is_file():
+        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
+    if method not in tree_mod.METHODS:
+        sourmash_hip.log_sys_exit(logger, f"Unknown tree method {method!r}: expected one of {', '.join(tree_mod.METHODS)}")
+    if not (math.isfinite(missing) and missing >= 0):
+        sourmash_hip.log_sys_exit(logger, f"The distance of a pair without identity must be finite and not negative, not {missing!r}")
+    outdir = Path(outdir)
+    if not outdir.is_dir():
+        logger.warning("Output directory %s does not exist, making it.", outdir)
+        outdir.mkdir()
+    conn, run = _open_run(logger, database, run_id, "Exporting")
+    run_id = run.run_id
+    n = len(run.fasta_hashes)
+    done = count_run_comparisons(conn, run)
+    if not n:
+        sourmash_hip.log_sys_exit(logger, f"Run-id {run_id} has no genomes")
+    if done != n * n:  # db_orm.load_run(check_complete=True)
+        sourmash_hip.log_sys_exit(logger, f"run-id {run_id} has {done} of {n}^2={n * n} comparisons, {n * n - done} needed")
+    run_method = run.configuration.method
+    frames = _score_frames(logger, conn, run)
+    conn.close()
+    logger.info("Run %d has %d comparisons across %d genomes.", run_id, done, n)
+    identity = _relabelled(logger, run, frames, label)[0]
+    distances = tree_mod.run_distances(identity, missing, logger)
+    if (distances < 0).any():
+        sourmash_hip.log_sys_exit(logger, "An identity above 1 gives a negative distance: no tree is defined")
+    table = tree_mod.neighbour_joining(distances, engine=engine) if method == "nj" else tree_mod.upgma(distances)
+    written = outdir / f"{run_method}_identity_{method}.nwk"
+    written.write_text(tree_mod.newick(table, [str(x) for x in identity.columns]) + "\n")
+    logger.info("Wrote %s tree to %s", method, written)
+    return written
+
+
 # ------------------------------------------------------------------ plot-run (pyani_plus/public_cli.py:1095-1136)
 # score, colour map, what a NaN cell counts as when the rows are clustered (pyani_plus/plot_run.py:320-325)
 _PLOT_SCORES = (("identity", "spbnd_BuRd", 0), ("query_cov", "BuRd", 0), ("hadamard", "viridis", 0), ("tANI", "viridis_r", -5))
@@ -1766,7 +1813,7 @@ def plot_run_comp(database: Path | str, outdir: Path, run_ids, *, columns: int =
 
 # ------------------------------------------------------------------ the driver as a process
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -1844,6 +1891,15 @@ def main(argv: list[str] | None = None) -> int:
     p_pc.add_argument("--formats", default="tsv", help="comma separated: tsv for the tables, png, pdf, svg or jpg for the two figures (matplotlib)")
     p_pc.add_argument("--device", type=int, default=None, help="join the runs and take the histograms on this GPU (default: on the host)")
     p_pc.add_argument("--verbose", "-v", action="store_true")
+    p_tr = sub.add_parser("tree-run", help="the neighbour-joining or UPGMA tree of a complete run as <method>_identity_<nj|upgma>.nwk")
+    p_tr.add_argument("--database", "-d", required=True, type=Path)
+    p_tr.add_argument("--outdir", "-o", required=True, type=Path)
+    p_tr.add_argument("--run-id", type=int, default=None)
+    p_tr.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
+    p_tr.add_argument("--method", choices=tree_mod.METHODS, default="nj")
+    p_tr.add_argument("--missing", type=float, default=1.0, help="distance of a pair with no identity in either direction (default 1.0)")
+    p_tr.add_argument("--device", type=int, default=None, help="make the joins of neighbour joining on this GPU (default: on the host)")
+    p_tr.add_argument("--verbose", "-v", action="store_true")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
     logger = logging.getLogger("pyani_plus_amd")
@@ -1873,7 +1929,7 @@ def main(argv: list[str] | None = None) -> int:
         elif args.command == "resume":
             run = resume(args.database, run_id=args.run_id, cache=args.cache, temp=args.temp, logger=logger, ingest=args.ingest,
                          gpus=args.gpus, engine_factory=args.engine_factory)
-        elif args.command in {"classify", "plot-run", "plot-run-comp"}:
+        elif args.command in {"classify", "plot-run", "plot-run-comp", "tree-run"}:
             engine = None
             if args.device is not None:
                 from .engine import HipEngine
@@ -1883,6 +1939,9 @@ def main(argv: list[str] | None = None) -> int:
                 if args.command == "classify":
                     print(classify(args.database, args.outdir, run_id=args.run_id, label=args.label, coverage_edges=args.coverage_edges,
                                    score_edges=args.score_edges, cov_min=args.cov_min, mode=args.mode, engine=engine, logger=logger))
+                elif args.command == "tree-run":
+                    print(tree_run(args.database, args.outdir, run_id=args.run_id, label=args.label, method=args.method, missing=args.missing,
+                                   engine=engine, logger=logger))
                 elif args.command == "plot-run-comp":
                     formats = tuple(f for f in args.formats.split(",") if f)
                     for path in plot_run_comp(args.database, args.outdir, args.run_ids, columns=args.columns, formats=formats, engine=engine, logger=logger):
