@@ -13,7 +13,7 @@
 // packed bases and nothing else.
 // The kernel is integer-VALU bound (8 arithmetic 64-bit multiplies + ~60 other
 // VALU per window against 0.25 byte of HBM input; VALUBusy 105 % by counters), so
-// there is no LDS tiling of the input; LDS holds the first-multiply tables and
+// there is no LDS tiling of the input; LDS holds the tables of the murmur words and
 // stages the rare survivors (1 in `scaled`) so that the global append is one
 // atomic per workgroup and the stores are coalesced.
 #include <cstdlib>
@@ -29,6 +29,9 @@ using namespace pa_dev;
 
 constexpr int kThreads = 256;
 constexpr uint32_t kStageCap = 1024;  // LDS staging slots per workgroup
+// kmer_hash_kernel with the second-product tables (20 KB against 12 KB) stages half as many, so that six workgroups
+// stay resident per CU; at scaled = 1000 a workgroup's 16 384 windows leave about 16 survivors
+constexpr uint32_t kStageCapSecond = 512;
 
 constexpr int pow2_floor(int k) { int c = 1; while (2 * c <= k) c *= 2; return c; }
 
@@ -62,13 +65,14 @@ __device__ __forceinline__ void append_candidate(const CandSink &s, uint32_t g, 
   }
 }
 
-// One candidate of arena block t into the workgroup's LDS staging (kStageCap slots, s_n counts them); with the staging
+// One candidate of arena block t into the workgroup's LDS staging (Cap slots, s_n counts them); with the staging
 // full (tiny `scaled`) it goes out directly.  Not through append_candidate: there the genome is looked up before the
 // slot is known to exist, here -- inside the window loop -- only after.
-__device__ __forceinline__ void stage_candidate(const CandSink &s, uint64_t (&s_hash)[kStageCap], uint32_t (&s_blk)[kStageCap],
+template <uint32_t Cap>
+__device__ __forceinline__ void stage_candidate(const CandSink &s, uint64_t (&s_hash)[Cap], uint32_t (&s_blk)[Cap],
                                                 uint32_t &s_n, uint32_t t, uint64_t h) {
   const uint32_t slot = atomicAdd(&s_n, 1u);
-  if (slot < kStageCap) {
+  if (slot < Cap) {
     s_hash[slot] = h;
     s_blk[slot] = t;
   } else if (s.region_off) {
@@ -84,11 +88,12 @@ __device__ __forceinline__ void stage_candidate(const CandSink &s, uint64_t (&s_
 
 // The end of a streaming kernel, reached by every thread of the workgroup: the staged candidates go out with one
 // atomic per workgroup and coalesced stores.  The workgroup holds blocks blk0 + blockIdx.x * kThreads onwards.
-__device__ __forceinline__ void flush_staged(const CandSink &s, const uint64_t (&s_hash)[kStageCap], const uint32_t (&s_blk)[kStageCap],
+template <uint32_t Cap>
+__device__ __forceinline__ void flush_staged(const CandSink &s, const uint64_t (&s_hash)[Cap], const uint32_t (&s_blk)[Cap],
                                              const uint32_t &s_n, unsigned long long &s_base, uint32_t blk0, uint32_t n_blocks64) {
   const uint32_t tid = threadIdx.x;
   __syncthreads();
-  const uint32_t n = min(s_n, kStageCap);
+  const uint32_t n = min(s_n, Cap);
   if (n == 0) return;
   if (s.region_off) {
     // per-genome regions (see sketch_lds.hip): a workgroup that lies inside one genome -- all but the
@@ -128,9 +133,12 @@ __device__ __forceinline__ uint32_t rev_groups32(uint32_t x) {  // the sixteen 2
   return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
 }
 
-// LUT = true (default): the first multiply of every murmur word is looked up (murmur_dev.h).
-// LUT = false keeps the arithmetic form (ablation / cross-check, PA_KMER_VARIANT=0).
-template <int K, bool LUT>
+// How a murmur word gets to its second product (murmur_dev.h):
+//   kSecondTables (default): T and A.hi of the lo group and B of the hi group are looked up, then one 32 x 64 bit product;
+//   kFirstTables: the first product is looked up, rotated and multiplied (cross-check / A-B, PA_KMER_VARIANT=1);
+//   kArithmetic: nothing is looked up (ablation / cross-check, PA_KMER_VARIANT=0).
+enum WordForm { kArithmetic = 0, kFirstTables = 1, kSecondTables = 2 };
+template <int K, WordForm FORM>
 __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
     const uint4 *__restrict__ packed, const uint2 *__restrict__ mask, const uint64_t *__restrict__ dirty, uint32_t n_blocks64,
     const uint32_t *__restrict__ genome_blk, uint32_t n_genomes, uint64_t max_hash,
@@ -138,13 +146,15 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
     unsigned long long *__restrict__ count, const uint64_t *__restrict__ region_off, uint32_t *__restrict__ cursor,
     uint32_t *__restrict__ overflow, uint32_t blk0) {
   static_assert(K >= 1 && K <= 32, "a k-mer is one 64-bit register pair");
-  __shared__ uint64_t s_hash[kStageCap];
-  __shared__ uint32_t s_blk[kStageCap];
+  constexpr uint32_t kCap = FORM == kSecondTables ? kStageCapSecond : kStageCap;
+  __shared__ uint64_t s_hash[kCap];
+  __shared__ uint32_t s_blk[kCap];
   __shared__ uint32_t s_n;
   __shared__ unsigned long long s_base;
   constexpr int kWords = (K + 7) / 8;
-  __shared__ uint64_t s_lo[LUT ? kWords : 1][256];
-  __shared__ uint32_t s_hi[LUT ? kWords : 1][256];
+  __shared__ uint64_t s_lo[FORM == kFirstTables ? kWords : 1][256];
+  __shared__ uint4 s_w[FORM == kSecondTables ? kWords : 1][256];
+  __shared__ uint32_t s_hi[FORM != kArithmetic ? kWords : 1][256];
 
   const uint32_t tid = threadIdx.x;
   const CandSink sink{cand_hash, cand_genome, cap, reinterpret_cast<uint64_t *>(count), region_off, cursor, overflow, genome_blk, n_genomes};
@@ -152,7 +162,8 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
   const bool take_all = max_hi == 0xffffffffu;  // scaled = 1: no screen
   const uint32_t screen_hi = max_hi + 1u;
   if (tid == 0) s_n = 0;
-  if constexpr (LUT) fill_first_products(s_lo, s_hi, tid, std::integral_constant<int, K>{});
+  if constexpr (FORM == kFirstTables) fill_first_products(s_lo, s_hi, tid, std::integral_constant<int, K>{});
+  if constexpr (FORM == kSecondTables) fill_second_products(s_w, s_hi, tid, K);
   __syncthreads();
 
   const uint32_t t = blk0 + blockIdx.x * kThreads + tid;  // blk0: first arena block of this launch (streamed uploads)
@@ -232,11 +243,13 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
           uint32_t clo, chi;
           asm("s_nop 1\n\tv_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(clo) : "v"((uint32_t)r_lsb), "v"((uint32_t)f_lsb), "s"(fwd));
           asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(chi) : "v"((uint32_t)(r_lsb >> 32)), "v"((uint32_t)(f_lsb >> 32)), "s"(fwd), "v"(clo));
-          uint64_t P[4] = {0, 0, 0, 0};
+          uint64_t P[4] = {0, 0, 0, 0};  // the first products of the words, or with kSecondTables the second ones
 #pragma unroll
           for (int j = 0; j < kWords; ++j) {
             const uint32_t src = j < 2 ? clo : chi;
-            if constexpr (LUT) {
+            if constexpr (FORM == kSecondTables) {
+              P[j] = second_product(s_w, s_hi, j, src);
+            } else if constexpr (FORM == kFirstTables) {
               P[j] = first_product(s_lo, s_hi, j, src);
             } else {
               const uint32_t glo = (src >> (16 * (j & 1))) & 0xffu, ghi = (src >> (16 * (j & 1) + 8)) & 0xffu;
@@ -247,7 +260,7 @@ __global__ __launch_bounds__(kThreads) void kmer_hash_kernel(
           (void)kMaskHi;
           // the 999 in 1000 windows that the screen drops never form the last products (passes_screen, murmur_dev.h)
           uint64_t U, V;
-          murmur3_pre_last_mul<K>(P, U, V);
+          if constexpr (FORM == kSecondTables) murmur3_pre_last_mul_of_seconds<K>(P, U, V); else murmur3_pre_last_mul<K>(P, U, V);
           if (passes_screen(U, V, take_all, screen_hi)) {
             const uint64_t h = last_mul_and_fold(U, V);
             if (h > max_hash || ((bad[wi >> 1] >> (16 * (wi & 1) + i)) & 1u)) continue;  // validity is only looked at for the 1 in 1000
@@ -487,14 +500,14 @@ int launch_k(pa_ctx *c, const KmerHashArgs &a) {
   if constexpr (K > 32) {
     return launch_blocks(c, "kmer_hash_wide_kernel", kmer_hash_wide_kernel<K>, a);
   } else {
-    if constexpr (K == 31) {  // the ablation build exists for the benchmarked k only
-      static const bool arithmetic = [] {
-        const char *v = PA_TOOL_ENV("PA_KMER_VARIANT");
-        return v && v[0] == '0';
-      }();
-      if (arithmetic) return launch_blocks(c, "kmer_hash_kernel<31, false>", kmer_hash_kernel<K, false>, a);
+#ifdef PA_TOOLS  // the other two forms exist for the benchmarked k and in the tools build only
+    if constexpr (K == 31) {
+      const char *v = PA_TOOL_ENV("PA_KMER_VARIANT");  // read per launch: one process can compare the forms
+      if (v && v[0] == '0') return launch_blocks(c, "kmer_hash_kernel<31, kArithmetic>", kmer_hash_kernel<K, kArithmetic>, a);
+      if (v && v[0] == '1') return launch_blocks(c, "kmer_hash_kernel<31, kFirstTables>", kmer_hash_kernel<K, kFirstTables>, a);
     }
-    return launch_blocks(c, "kmer_hash_kernel", kmer_hash_kernel<K, true>, a);
+#endif
+    return launch_blocks(c, "kmer_hash_kernel", kmer_hash_kernel<K, kSecondTables>, a);
   }
 }
 

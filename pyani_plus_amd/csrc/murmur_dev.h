@@ -10,19 +10,12 @@
 
 #include <cstdint>
 
+#include "murmur_words.h"  // kC1, kC2, ascii4, ascii_group and the entries of the second-product tables: device and host
+
 namespace pa_dev {
 
 __device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh) {
   return __builtin_amdgcn_alignbit(hi, lo, sh);
-}
-
-// 4 bases (8 bits, base j at bits 2j) -> 4 ASCII bytes (base j in byte j).
-// spread the 2-bit codes to one per byte, then use v_perm_b32 as a 4-entry LUT.
-__device__ __forceinline__ uint32_t ascii4(uint32_t b8) {
-  uint32_t u = (b8 | (b8 << 12)) & 0x000F000Fu;
-  uint32_t v = (u | (u << 6)) & 0x03030303u;
-  // selector byte value 0..3 picks that byte of the second source: "ACGT" little-endian
-  return __builtin_amdgcn_perm(0u, 0x54474341u, v);
 }
 
 __device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
@@ -48,8 +41,7 @@ __device__ __forceinline__ uint64_t fmix64(uint64_t k) {
 // The K ASCII bytes form up to four little-endian 64-bit words; word j is a "k1" word
 // (j even: k*c1, rotl 31, *c2, xor into h1) or a "k2" word (j odd: k*c2, rotl 33, *c1,
 // xor into h2), in the 16-byte blocks and in the tail alike.  P[j] is the FIRST product
-// (word * c1 or c2); everything after it is computed here.
-constexpr uint64_t kC1 = 0x87c37b91114253d5ULL, kC2 = 0x4cf5ad432745937fULL;
+// (word * c1 or c2), Kw[j] the second one (rotated first product * c2 or c1); everything after it is computed here.
 
 // h*5 + c.  Left to itself hipcc turns this into two v_mad_u64_u32 plus fix-ups; gfx950 has a 64-bit
 // shift-and-add (v_lshl_add_u64, shift 0..4), so (h << 2) + h is one instruction and + c a second.
@@ -91,6 +83,39 @@ __device__ __forceinline__ void murmur3_pre_last_mul(const uint64_t (&P)[N], uin
   }
   if constexpr (tail > 8) h2 ^= rotl64(P[2 * nblocks + 1], 33) * kC1;
   if constexpr (tail > 0) h1 ^= rotl64(P[2 * nblocks], 31) * kC2;
+  h1 ^= (uint64_t)K; h2 ^= (uint64_t)K;
+  h1 += h2; h2 += h1;
+  h1 ^= h1 >> 33; h1 *= kF1; h1 ^= h1 >> 33;
+  h2 ^= h2 >> 33; h2 *= kF1; h2 ^= h2 >> 33;
+  U = h1;
+  V = h2;
+}
+
+// the same from the second products Kw[j] (second_product below): the four rotates and 64 x 64 multiplies are gone
+template <int K, int N>
+__device__ __forceinline__ void murmur3_pre_last_mul_of_seconds(const uint64_t (&Kw)[N], uint64_t &U, uint64_t &V) {
+  static_assert(N >= (K + 7) / 8, "one second product per 8-byte word of the k-mer");
+  uint64_t h1 = 42, h2 = 42;
+  constexpr int nblocks = K / 16;
+  constexpr int tail = K % 16;
+#pragma unroll
+  for (int i = 0; i < nblocks; ++i) {
+    h1 ^= Kw[2 * i];
+    if (i == 0) {
+      h1 = times5_plus(rotl64(h1, 27), 5ULL * 42ULL + 0x52dce729ULL);
+    } else {
+      h1 = rotl64(h1, 27) + h2;
+      h1 = times5_plus(h1, 0x52dce729ULL);
+    }
+    h2 ^= Kw[2 * i + 1];
+    // the rotated value as one register pair: left to itself hipcc adds its two halves to h1 one by one, each paired
+    // with a zero (a v_mov and two v_lshl_add_u64 where one 64-bit add does)
+    uint64_t r2 = rotl64(h2, 31);
+    asm("" : "+v"(r2));
+    h2 = times5_plus(r2 + h1, 0x38495ab5ULL);
+  }
+  if constexpr (tail > 8) h2 ^= Kw[2 * nblocks + 1];
+  if constexpr (tail > 0) h1 ^= Kw[2 * nblocks];
   h1 ^= (uint64_t)K; h2 ^= (uint64_t)K;
   h1 += h2; h2 += h1;
   h1 ^= h1 >> 33; h1 *= kF1; h1 ^= h1 >> 33;
@@ -158,12 +183,6 @@ __device__ __forceinline__ uint64_t murmur3_from_products(const uint64_t (&P)[N]
   return last_mul_and_fold(U, V);
 }
 
-// the 4-base group `b8` (base j at bits 2j) as ASCII, keeping only its first `nv` bytes
-__device__ __forceinline__ uint32_t ascii_group(uint32_t b8, int nv) {
-  const uint32_t a = ascii4(b8);
-  return nv >= 4 ? a : (nv <= 0 ? 0u : (a & ((1u << (8 * nv)) - 1u)));
-}
-
 // ---- the first multiply of every murmur word, looked up -----------------------------
 // Word j of the k-mer (bases 8j .. 8j+7, the last one partial) is two 4-base groups (lo, hi), and
 //   word*c_j = (ascii(lo) + ascii(hi)*2^32)*c_j = s_lo[j][lo] + (s_hi[j][hi] << 32)   (mod 2^64)
@@ -189,6 +208,47 @@ __device__ __forceinline__ uint64_t first_product(const uint64_t (&s_lo)[W][256]
   const uint32_t glo = (src >> (16u * (j & 1u))) & 0xffu, ghi = (src >> (16u * (j & 1u) + 8u)) & 0xffu;
   const uint64_t lo = s_lo[j][glo];
   return u64_of((uint32_t)lo, (uint32_t)(lo >> 32) + s_hi[j][ghi]);
+}
+
+// ---- the second multiply of every murmur word, from tables and one 32 x 64 bit product ------------------------------
+// murmur_words.h has the identity and the entries.  s_w[j][lo group] = {T, A.hi} (16 bytes, one ds_read_b128),
+// s_b[j][hi group] = B; thread `tid` of 256 fills one entry of each.  The caller puts a barrier between this and the
+// first look-up.
+template <int W>
+__device__ __forceinline__ void fill_second_products(uint4 (&s_w)[W][256], uint32_t (&s_b)[W][256], uint32_t tid, int k) {
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    const WordLoEntry e = word_lo_entry(j, k, tid);
+    s_w[j][tid] = make_uint4(e.t_lo, e.t_hi, e.a_hi, e.pad);
+    s_b[j][tid] = word_hi_entry(j, k, tid);
+  }
+}
+
+// byte `byte` of src, times 2^SH: the byte offset of a table entry, one SDWA shift whichever byte it is (left to
+// itself hipcc spends a shift and an `and` on byte 0)
+template <uint32_t SH>
+__device__ __forceinline__ uint32_t byte_offset(uint32_t src, uint32_t byte) {
+  uint32_t r;
+  const uint32_t sh = SH;
+  switch (byte) {
+    case 0: asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "v"(sh), "v"(src)); break;
+    case 1: asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "v"(sh), "v"(src)); break;
+    case 2: asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "v"(sh), "v"(src)); break;
+    default: asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "v"(sh), "v"(src)); break;
+  }
+  return r;
+}
+
+// k_j from the tables; src is the 32-bit word j/2 of the k-mer (base i at bits 2i), which holds word j's two groups
+template <int W>
+__device__ __forceinline__ uint64_t second_product(const uint4 (&s_w)[W][256], const uint32_t (&s_b)[W][256], int j, uint32_t src) {
+  const uint32_t off_w = byte_offset<4>(src, 2u * (j & 1)), off_b = byte_offset<2>(src, 2u * (j & 1) + 1u);
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 e = *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(&s_w[j][0]) + off_w);
+  // the whole entry in one aligned register quad: without this hipcc drops the pad and reads the rest in two pieces
+  asm("" : "+v"(e));
+  const uint32_t b = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(&s_b[j][0]) + off_b);
+  return second_product_of(j, e.x, e.y, e.z, b);
 }
 
 }  // namespace pa_dev

@@ -29,7 +29,7 @@ cycles = mean("GRBM_GUI_ACTIVE") / 8.0
 clock = cycles / (dur["sq_valu"] * 1e-3) / 1e9
 out = {
     "label": label,
-    "kernel": "kmer_hash_kernel<31,true>, 1000 x 5 Mb (tools/pmc_hash.py), profiled dispatch",
+    "kernel": "kmer_hash_kernel<31, kSecondTables>, 1000 x 5 Mb (tools/pmc_hash.py), profiled dispatch",
     "traffic_source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes ({label}); FETCH_SIZE x2 per the gfx950 correction; not measured inside this run",
     "hbm_bytes_per_launch": mean("FETCH_SIZE") * 1024 * 2 + mean("WRITE_SIZE") * 1024,
     "fetch_size_kib_raw": mean("FETCH_SIZE"),
@@ -46,5 +46,8 @@ out = {
     "valu_instr_per_wave_window": mean("SQ_INSTS_VALU") / (1000 * 5_000_064 / 64.0),
     "valu_instr_per_wave_window_note": "SQ_INSTS_VALU / (arena positions / 64); tools/pmc_hash.py hashes 1000 genomes of 5 000 064 arena positions",
 }
+if "SQ_LDS_BANK_CONFLICT" in vals and "SQ_LDS_IDX_ACTIVE" in vals:
+    out["lds_bank_conflict_share"] = mean("SQ_LDS_BANK_CONFLICT") / mean("SQ_LDS_IDX_ACTIVE")
+    out["lds_bank_conflict_note"] = "SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE: the extra LDS-array cycles of bank conflicts over all LDS-array cycles"
 dst.write_text(json.dumps(out, indent=1) + "\n")
 print(json.dumps(out, indent=1))

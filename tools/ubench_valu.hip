@@ -194,6 +194,44 @@ __global__ __launch_bounds__(256) void k_lds_b32(uint32_t *out, uint32_t seed) {
   }
   out[blockIdx.x * 256 + threadIdx.x] = acc;
 }
+// the same with 16-byte entries: one ds_read_b128, and one ds_read_b96 of an entry's first three dwords (the empty asm
+// keeps the whole vector in one register tuple, so that the read is not split)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+__global__ __launch_bounds__(256) void k_lds_b128(uint32_t *out, uint32_t seed) {
+  __shared__ u32x4 tab[4][256];
+  for (int j = 0; j < 4; ++j) tab[j][threadIdx.x] = u32x4{threadIdx.x * 0x9e3779b9u + j, threadIdx.x, seed, 1u};
+  __syncthreads();
+  uint32_t x = threadIdx.x * 2654435761u + seed;
+  uint32_t acc = 0;
+  for (int it = 0; it < ITERS; ++it) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      u32x4 e = tab[j & 3][(x >> (j * 3)) & 255];
+      asm("" : "+v"(e));
+      acc += e.x + e.z;
+    }
+    x = x * 1664525u + 1013904223u;
+  }
+  out[blockIdx.x * 256 + threadIdx.x] = acc;
+}
+__global__ __launch_bounds__(256) void k_lds_b96(uint32_t *out, uint32_t seed) {
+  __shared__ u32x4 tab[4][256];
+  for (int j = 0; j < 4; ++j) tab[j][threadIdx.x] = u32x4{threadIdx.x * 0x9e3779b9u + j, threadIdx.x, seed, 1u};
+  __syncthreads();
+  uint32_t x = threadIdx.x * 2654435761u + seed;
+  uint32_t acc = 0;
+  for (int it = 0; it < ITERS; ++it) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      u32x3 e = *reinterpret_cast<const u32x3 *>(&tab[j & 3][(x >> (j * 3)) & 255]);
+      asm("" : "+v"(e));
+      acc += e.x + e.z;
+    }
+    x = x * 1664525u + 1013904223u;
+  }
+  out[blockIdx.x * 256 + threadIdx.x] = acc;
+}
 
 typedef void (*kern_t)(uint32_t *, uint32_t);
 struct Entry { const char *name; kern_t fn; int ops_per_iter; };
@@ -212,7 +250,8 @@ int main() {
       {"v_cndmask_b32", k_cndmask, 8}, {"v_mad_u64_u32", k_mad64, 8}, {"v_lshlrev_b64", k_shl64, 8},
       {"v_lshrrev_b64", k_shr64, 8}, {"v_lshl_add_u64", k_lshladd64, 8}, {"v_cmp_gt_u64", k_cmp64, 8},
       {"v_add_co+v_addc pair", k_addco_pair, 8}, {"ds_read_b64 random(+add64)", k_lds_b64, 8},
-      {"ds_read_b32 random(+add)", k_lds_b32, 8},
+      {"ds_read_b32 random(+add)", k_lds_b32, 8}, {"ds_read_b128 random(+2 add)", k_lds_b128, 8},
+      {"ds_read_b96 random(+2 add)", k_lds_b96, 8},
       {"v_lshlrev_b32 (imm)", k_shl32, 8}, {"v_lshrrev_b32 (imm)", k_shr32, 8}, {"v_lshlrev_b32 (vgpr)", k_shlv32, 8},
       {"v_and_b32", k_and, 8}, {"v_or_b32", k_or, 8}, {"v_sub_u32", k_sub, 8}, {"v_mov_b32", k_mov, 8},
       {"v_lshl_add_u32", k_lshladd32, 8}, {"v_add_lshl_u32", k_addlshl32, 8}, {"v_xad_u32", k_xad, 8},
