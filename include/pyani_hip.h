@@ -53,7 +53,8 @@ typedef enum pa_status {
   PA_E_NOMEM = -3,     /* host or device allocation failed */
   PA_E_CAPACITY = -4,  /* caller buffer too small; required size reported */
   PA_E_NODEVICE = -5,  /* no usable gfx950 device */
-  PA_E_IO = -6         /* database I/O failed (pa_sqlite_insert_comparisons) */
+  PA_E_IO = -6,        /* database I/O failed (pa_sqlite_insert_comparisons) */
+  PA_E_NOCONVERGE = -7 /* an iteration used up its max_iter (pa_symm_top_eigs); nothing partial is returned */
 } pa_status;
 
 typedef struct pa_ctx pa_ctx;
@@ -737,6 +738,66 @@ PA_API int pa_append_identity_json(const char *path, const char *suffix, int fil
 PA_API int pa_nj(pa_ctx *ctx, double *d_D, uint32_t n, uint32_t *h_child, double *h_len, uint32_t *h_last, double *h_last_len);
 PA_API int pa_nj_host(const double *h_D, uint32_t n, uint32_t *h_child, double *h_len, uint32_t *h_last, double *h_last_len,
                       uint32_t n_threads);
+
+/* ---- ordinate-run: principal coordinates (classical scaling) of a distance matrix ----
+ * Replaces nothing in the reference: pyani-plus writes no ordination.  The definitions below are this project's own
+ * contract, pinned by an independent restatement in tests/pcoa_cases.py; no parity with any other program is claimed.
+ * DESIGN.md section 7i.  Every step is one IEEE double operation (no FMA), no floating-point atomics: a device entry
+ * point gives the same bits run to run and the same bits as its host twin, and a host twin's result does not depend on
+ * n_threads (0: as many as the process may use).  pcoa_rule.h states the constants and formulas once for both.
+ *
+ *   pa_mul_tall_f64   Y = A Q.  A is n x n, Q and Y are n x p, all f64 row-major; 1 <= n <= 65535, 1 <= p <= 32
+ *        (PA_E_INVALID otherwise).  The order of the additions is part of the contract.  The columns j of a row are cut
+ *        into chunks of pcoa::kChunk = 256 (pcoa_rule.h states it; the last chunk may be short).  Within chunk b,
+ *        s_b = ((A[i,j0] Q[j0,c] + A[i,j0+1] Q[j0+1,c]) + ...) in ascending j, every product rounded, one accumulator
+ *        that starts from the first product; Y[i,c] = ((s_0 + s_1) + ...) in ascending b, starting from s_0.
+ *        Device: d_A, d_Q, d_Y are device memory, none overlapping; one launch over (128-row tile x chunk) writes the
+ *        partial sums to the context's workspace (n p ceil(n / 256) doubles), a second adds them; a lane owns its
+ *        outputs, so the tiling does not show in a sum.  No host synchronisation.
+ *   pa_gower_center   B = the doubly centred matrix of the squared distances.  D as for pa_nj: n x n f64, finite,
+ *        >= 0, bitwise symmetric, zero diagonal, 1 <= n <= 65535; otherwise PA_E_INVALID and pa_last_error() names the
+ *        first offending cell in row-major order as D[i,j].  a[i,j] = D[i,j] * D[i,j];
+ *        r[i] = (a[i,0] + ... + a[i,n-1]) / n, added in ascending order into one accumulator that starts from a[i,0];
+ *        g = (r[0] + ... + r[n-1]) / n likewise; B[i,j] = -0.5 * ((a[i,j] - (r[i] + r[j])) + g), which makes B bitwise
+ *        symmetric; *h_trace = B[0,0] + B[1,1] + ...; *h_fro2 = the sum over ascending i of the rows' sums over
+ *        ascending j of B[i,j] * B[i,j].  d_B (n x n) must not overlap d_D.  Two host synchronisations (the check, the
+ *        two scalars).
+ *   pa_symm_top_eigs  the k algebraically largest eigenvalues of the symmetric n x n matrix B, 1 <= k <= min(n, 24), in
+ *        descending order (h_values[k]), their unit eigenvectors as the columns of h_vectors (n x k row-major), each
+ *        pair's residual norm ||B v - lambda v||_2 (h_residuals[k]) and h_info[3] = (iterations of phase 1, iterations
+ *        in all, the shift used).  Block subspace iteration with Rayleigh-Ritz, block width
+ *        p = min(n, max(2k, k + 8), 32): the product's limit caps it, which at k = 24 still leaves k + 8 columns.
+ *        The start block is pcoa::start_value(i * p + c) (a fixed 64-bit integer mix mapped to (-1, 1)),
+ *        orthonormalised.  An iteration: Y = B Q by pa_mul_tall_f64, Y += sigma Q; H = Q^T Y, symmetrised as
+ *        0.5 (H + H^T); its eigen-decomposition H = S diag(theta) S^T by cyclic Jacobi; theta sorted descending,
+ *        lambda = theta - sigma; X = Q S; R = Y S - X diag(theta).  A pair has converged when
+ *        ||R_c||_2 <= tol * max|lambda|, the maximum over the p Ritz values.  The next Q is Y orthonormalised by
+ *        twice-applied modified Gram-Schmidt (a column that vanishes is replaced by a fresh one).
+ *        Phase 1 runs with sigma = 0 until the first k pairs have converged, 200 iterations at most.  With
+ *        rho = sqrt(max(fro2 - sum of lambda_c^2 over the converged pairs among the first k, 0)) every other eigenvalue
+ *        of B has magnitude <= rho: when all k have converged and lambda_k > rho the result is certified and returned
+ *        (shift 0).  Otherwise phase 2 goes on with sigma = rho (B + sigma I has no negative eigenvalue outside the
+ *        converged pairs, so the largest in magnitude are the largest) until the first k pairs have converged: from
+ *        the current block when phase 1 ended at its cap; when it ended with all k converged the block spans an
+ *        invariant subspace, which no product leads out of, so its first k Ritz vectors are kept and the other
+ *        p - k columns start again from fresh start values.  fro2 is the squared Frobenius norm of B (pa_gower_center's).  After max_iter iterations in
+ *        all (>= 1) without convergence the call returns PA_E_NOCONVERGE, the message names the iteration count and the
+ *        worst residual, and the outputs are left untouched.  Sign: each vector is scaled by +-1 so that its entry of
+ *        largest magnitude, the first such in index order, is positive.  tol must be finite and > 0 (1e-10 is the
+ *        callers' default).
+ *        Everything but the product is p-wide algebra on one host thread, the same compiled code for both entry
+ *        points.  Device: d_B is device memory and is only read; Q goes up and Y comes down once per iteration.  Host
+ *        twin: the product runs on n_threads. */
+#define PA_MUL_TALL_MAX_P 32
+#define PA_EIGS_MAX_K 24
+PA_API int pa_mul_tall_f64(pa_ctx *ctx, const double *d_A, uint32_t n, const double *d_Q, uint32_t p, double *d_Y);
+PA_API int pa_mul_tall_f64_host(const double *h_A, uint32_t n, const double *h_Q, uint32_t p, double *h_Y, uint32_t n_threads);
+PA_API int pa_gower_center(pa_ctx *ctx, const double *d_D, uint32_t n, double *d_B, double *h_trace, double *h_fro2);
+PA_API int pa_gower_center_host(const double *h_D, uint32_t n, double *h_B, double *h_trace, double *h_fro2, uint32_t n_threads);
+PA_API int pa_symm_top_eigs(pa_ctx *ctx, const double *d_B, uint32_t n, uint32_t k, double tol, uint32_t max_iter, double fro2,
+                            double *h_values, double *h_vectors, double *h_residuals, double *h_info);
+PA_API int pa_symm_top_eigs_host(const double *h_B, uint32_t n, uint32_t k, double tol, uint32_t max_iter, double fro2, double *h_values,
+                                 double *h_vectors, double *h_residuals, double *h_info, uint32_t n_threads);
 
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */

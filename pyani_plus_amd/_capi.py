@@ -25,6 +25,9 @@ PA_E_INVALID = -1
 PA_E_NOMEM = -3
 PA_E_CAPACITY = -4
 PA_E_IO = -6
+PA_E_NOCONVERGE = -7  # pa_symm_top_eigs used up its max_iter
+PA_MUL_TALL_MAX_P = 32  # pa_mul_tall_f64: columns of the thin block, at most
+PA_EIGS_MAX_K = 24  # pa_symm_top_eigs: eigenpairs, at most
 PA_SIG_UNHANDLED = 1
 PA_FRAGANI_REUSE_INDEX = 1
 PA_FRAGANI_COLUMNS_ONLY = 2
@@ -204,6 +207,12 @@ SIGNATURES: dict[str, tuple] = {
     "pa_tetra_corr_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _vp, C.c_uint32]),
     "pa_nj": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
     "pa_nj_host": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32]),
+    "pa_mul_tall_f64": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    "pa_mul_tall_f64_host": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32]),
+    "pa_gower_center": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "pa_gower_center_host": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32]),
+    "pa_symm_top_eigs": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_double, _vp, _vp, _vp, _vp]),
+    "pa_symm_top_eigs_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_double, _vp, _vp, _vp, _vp, C.c_uint32]),
     "pa_append_identity_json": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, _vp, _vp]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),

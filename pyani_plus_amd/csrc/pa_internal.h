@@ -142,7 +142,8 @@ constexpr ScalarSlot kCompactTotal{8, 2};      // pa_classify_edges, pa_runcomp_
 constexpr ScalarSlot kRegionOverflow{12, 1};   // pa_sketch, pa_sketch_streamed: a region was too small; zeroed there, read by pa_sketch_from_regions
 constexpr ScalarSlot kNjPick{16, 8};           // pa_nj: the pair a join chose, written by its join kernel and read by its update kernel (NjPick, nj.hip)
 constexpr ScalarSlot kNjBad{24, 4};            // pa_nj: two 64-bit words zeroed / set as one: [0] cells that break the contract, [1] the first of them
-static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow, kNjPick, kNjBad}),
+constexpr ScalarSlot kGowerBad{28, 4};         // pa_gower_center: the same two words for its own check of D
+static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow, kNjPick, kNjBad, kGowerBad}),
               "two slots of pa_ctx::counters overlap or leave the block");
 
 // The words of pa_ctx::dict_scalars (pa_ctx::dict_slot), the hash dictionary's own block, touched by no other phase
@@ -167,10 +168,11 @@ constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of
 //   plot-run's scatter figures (scatter.hip): bin2d, the two edge arrays, then the cells' counts and last indices
 //   TETRA-hip (tetra.hip): tetra_tab, the genomes' first blocks and first chunks (u32[2 (n + 1)])
 //   tree-run (nj.hip): nj_work, the row sums, the slots' node ids, the scan's candidates and the join table
+//   ordinate-run (pcoa.hip): pcoa_work, the thin blocks Q and Y, the chunks' partial sums, the centring's row sums
 #define PA_CTX_BUFFERS(ONE, PAIR)                                                                                   \
   PAIR(cand_keys) PAIR(cand_vals) ONE(genome_blk) ONE(counters) ONE(hist) ONE(flags) ONE(scan_tmp) ONE(region_off) \
   ONE(region_cursor) ONE(dirty) PAIR(dict_keys) PAIR(dict_vals) ONE(ids) ONE(post_genome) ONE(bitrows)             \
-  ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d) ONE(tetra_tab) ONE(nj_work)
+  ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d) ONE(tetra_tab) ONE(nj_work) ONE(pcoa_work)
 
 struct pa_ctx {
   int device = 0;

@@ -874,6 +874,66 @@ class HipEngine:
         self._check(self.lib.pa_nj(self.ctx, work.data_ptr(), n, *(a.ctypes.data for a in out)), "pa_nj")
         return out[0], out[1], out[2], float(out[3][0])
 
+    # -- ordinate-run
+    def _square_f64_on_device(self, M, what: str):
+        if isinstance(M, np.ndarray) and not M.flags.writeable:
+            M = M.copy()  # torch wraps writable arrays only
+        m = self._f64_on_device(M)
+        if m.dim() != 2 or m.shape[0] != m.shape[1]:
+            raise ValueError(f"{what} of shape {tuple(m.shape)}, expected a square one")
+        if m.shape[0] > 65535:
+            raise ValueError(f"{m.shape[0]} rows; at most 65535")
+        return m
+
+    def mul_tall_device(self, A, Q):
+        """``pa_mul_tall_f64``: ``A @ Q`` for the n x n float64 ``A`` and the n x p block ``Q`` (host arrays or tensors
+        on this device; p <= 32) as a device tensor, added in the order of the contract: the same
+        bits run to run and as ``mul_tall_host``."""
+        t = self.torch
+        a = self._square_f64_on_device(A, "matrix")
+        q = self._f64_on_device(Q.copy() if isinstance(Q, np.ndarray) and not Q.flags.writeable else Q)
+        if q.dim() != 2 or q.shape[0] != a.shape[0]:
+            raise ValueError(f"block of shape {tuple(q.shape)} for a matrix of {a.shape[0]} rows")
+        y = t.empty(q.shape, dtype=t.float64, device=self.device)
+        self._check(self.lib.pa_mul_tall_f64(self.ctx, a.data_ptr(), a.shape[0], q.data_ptr(), q.shape[1], y.data_ptr()), "pa_mul_tall_f64")
+        return y
+
+    def mul_tall(self, A, Q) -> np.ndarray:
+        """``mul_tall_device`` copied back."""
+        return self.mul_tall_device(A, Q).cpu().numpy()
+
+    def gower_center_device(self, D):
+        """``pa_gower_center``: ``(B, trace, fro2)`` of the n x n float64 distance matrix ``D`` (a host array or a tensor
+        on this device; finite, >= 0, bitwise symmetric, zero diagonal), ``B`` the doubly centred matrix of the squared
+        distances as a device tensor, with its trace and its squared Frobenius norm.  ``D`` is not modified."""
+        t = self.torch
+        d = self._square_f64_on_device(D, "distance matrix")
+        b = t.empty_like(d)
+        trace, fro2 = C.c_double(0.0), C.c_double(0.0)
+        self._check(self.lib.pa_gower_center(self.ctx, d.data_ptr(), d.shape[0], b.data_ptr(), C.byref(trace), C.byref(fro2)), "pa_gower_center")
+        return b, trace.value, fro2.value
+
+    def gower_center(self, D) -> tuple[np.ndarray, float, float]:
+        """``gower_center_device`` with ``B`` copied back: the same bits as ``gower_center_host``."""
+        b, trace, fro2 = self.gower_center_device(D)
+        return b.cpu().numpy(), trace, fro2
+
+    def symm_top_eigs(self, B, k: int, fro2: float, tol: float = 1e-10, max_iter: int = 10000):
+        """``pa_symm_top_eigs``: the ``k`` algebraically largest eigenvalues of the symmetric n x n float64 ``B`` (a host
+        array or a tensor on this device, only read) with ``fro2`` its squared Frobenius norm, as ``(values, vectors,
+        residuals, info)``: descending values, the unit eigenvectors as the columns of the n x k ``vectors``, each pair's
+        residual norm and ``info = (iterations of phase 1, iterations in all, shift used)``.  The products run on the
+        GPU, the p-wide algebra on the host: the same bits as ``symm_top_eigs_host``.  A call that uses up ``max_iter``
+        raises with status ``PA_E_NOCONVERGE``."""
+        b = self._square_f64_on_device(B, "matrix")
+        n = b.shape[0]
+        out = _eigs_outputs(n, k)
+        self._check(
+            self.lib.pa_symm_top_eigs(self.ctx, b.data_ptr(), n, int(k), float(tol), int(max_iter), float(fro2), *(a.ctypes.data for a in out)),
+            "pa_symm_top_eigs",
+        )
+        return _eigs_result(out)
+
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")
 
@@ -934,6 +994,62 @@ def nj_tree_host(D, threads: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarra
     out = _nj_outputs(n)
     check(_capi.load_library().pa_nj_host(d.ctypes.data, n, *(a.ctypes.data for a in out), int(threads)), "pa_nj_host")
     return out[0], out[1], out[2], float(out[3][0])
+
+
+# ------------------------------------------------------------------ ordinate-run: the host forms (no GPU needed)
+def _square_f64(M, what: str) -> np.ndarray:
+    m = np.ascontiguousarray(M, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError(f"{what} of shape {m.shape}, expected a square one")
+    if m.shape[0] > 65535:
+        raise ValueError(f"{m.shape[0]} rows; at most 65535")
+    return m
+
+
+def _eigs_outputs(n: int, k: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    k = max(int(k), 0)
+    return np.zeros(k, dtype=np.float64), np.zeros((n, k), dtype=np.float64), np.zeros(k, dtype=np.float64), np.zeros(3, dtype=np.float64)
+
+
+def _eigs_result(out) -> tuple[np.ndarray, np.ndarray, np.ndarray, tuple[int, int, float]]:
+    return out[0], out[1], out[2], (int(out[3][0]), int(out[3][1]), float(out[3][2]))
+
+
+def mul_tall_host(A, Q, threads: int = 0) -> np.ndarray:
+    """``pa_mul_tall_f64_host``: what ``HipEngine.mul_tall`` returns, bit for bit, on ``threads`` host threads (0: as many
+    as the process may use), whose number does not show in the result."""
+    a = _square_f64(A, "matrix")
+    q = np.ascontiguousarray(Q, dtype=np.float64)
+    if q.ndim != 2 or q.shape[0] != a.shape[0]:
+        raise ValueError(f"block of shape {q.shape} for a matrix of {a.shape[0]} rows")
+    y = np.empty_like(q)
+    check(_capi.load_library().pa_mul_tall_f64_host(a.ctypes.data, a.shape[0], q.ctypes.data, q.shape[1], y.ctypes.data, int(threads)),
+          "pa_mul_tall_f64_host")
+    return y
+
+
+def gower_center_host(D, threads: int = 0) -> tuple[np.ndarray, float, float]:
+    """``pa_gower_center_host``: what ``HipEngine.gower_center`` returns, bit for bit."""
+    d = _square_f64(D, "distance matrix")
+    b = np.empty_like(d)
+    trace, fro2 = C.c_double(0.0), C.c_double(0.0)
+    check(_capi.load_library().pa_gower_center_host(d.ctypes.data, d.shape[0], b.ctypes.data, C.byref(trace), C.byref(fro2), int(threads)),
+          "pa_gower_center_host")
+    return b, trace.value, fro2.value
+
+
+def symm_top_eigs_host(B, k: int, fro2: float, tol: float = 1e-10, max_iter: int = 10000, threads: int = 0):
+    """``pa_symm_top_eigs_host``: what ``HipEngine.symm_top_eigs`` returns, bit for bit; the products run on ``threads``
+    host threads."""
+    b = _square_f64(B, "matrix")
+    n = b.shape[0]
+    out = _eigs_outputs(n, k)
+    check(
+        _capi.load_library().pa_symm_top_eigs_host(b.ctypes.data, n, int(k), float(tol), int(max_iter), float(fro2),
+                                                   *(a.ctypes.data for a in out), int(threads)),
+        "pa_symm_top_eigs_host",
+    )
+    return _eigs_result(out)
 
 
 def tetra_counts_host(arena: HostArena, threads: int = 0) -> np.ndarray:

@@ -52,7 +52,8 @@ from . import _capi, launch, wire
 from . import classify as classify_mod
 from . import cluster as cluster_mod
 from . import distribution as distribution_mod
-from . import distribution_figure, heatmap_figure, run_comp_figure, scatter_figure
+from . import distribution_figure, heatmap_figure, ordination_figure, run_comp_figure, scatter_figure
+from . import ordination as ordination_mod
 from . import run_comp as run_comp_mod
 from . import scatter as scatter_mod
 from . import tree as tree_mod
@@ -1466,23 +1467,17 @@ def classify(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     return written
 
 
-# ------------------------------------------------------------------ tree-run (this project's own: the reference writes no tree)
-def tree_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", method: str = "nj", missing: float = 1.0,  # noqa: PLR0913
-             engine=None, logger: logging.Logger | None = None) -> Path:
-    """Write ``<method>_identity_<nj|upgma>.nwk``: the tree of a complete run's genomes as one line of Newick text, from
-    the distances ``1 - identity`` (``tree.run_distances``: the two directions averaged; ``missing`` where a pair has no
-    identity either way).  ``method`` "nj" is canonical neighbour joining (DESIGN.md section 7h; unrooted, written with a
-    trifurcation at the last join), "upgma" the average-linkage tree of the same distances.  The matrices and labels are
-    the ones ``classify`` and ``plot-run`` read, with the reference's messages for a missing database, an incomplete run,
-    duplicate stems and an unknown label.
-
-    ``engine``: a ``HipEngine`` makes the joins of "nj" on the GPU; None makes them on the host, with the same bits.
-    UPGMA runs on the host either way."""
-    logger = logger or logging.getLogger("pyani_plus_amd")
+# ------------------------------------------------------------------ a run's distances (tree-run, ordinate-run)
+def _require_database(logger, database) -> None:
     if str(database) == ":memory:" or not Path(database).is_file():
         sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
-    if method not in tree_mod.METHODS:
-        sourmash_hip.log_sys_exit(logger, f"Unknown tree method {method!r}: expected one of {', '.join(tree_mod.METHODS)}")
+
+
+def _distance_run(logger, database, outdir, run_id: int | None, label: str, missing: float, what: str):  # noqa: PLR0913
+    """What tree-run and ordinate-run start from: ``(outdir, method, identity, distances)`` of a complete run -- the
+    output directory made, the run opened and checked, its identity frame relabelled and sorted by label as ``classify``
+    and ``plot-run`` read it, and ``tree.run_distances`` of it -- with the reference's messages for an incomplete run,
+    duplicate stems and an unknown label.  ``what`` is the thing an identity above 1 leaves undefined."""
     if not (math.isfinite(missing) and missing >= 0):
         sourmash_hip.log_sys_exit(logger, f"The distance of a pair without identity must be finite and not negative, not {missing!r}")
     outdir = Path(outdir)
@@ -1504,11 +1499,76 @@ def tree_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     identity = _relabelled(logger, run, frames, label)[0]
     distances = tree_mod.run_distances(identity, missing, logger)
     if (distances < 0).any():
-        sourmash_hip.log_sys_exit(logger, "An identity above 1 gives a negative distance: no tree is defined")
+        sourmash_hip.log_sys_exit(logger, f"An identity above 1 gives a negative distance: no {what} is defined")
+    return outdir, run_method, identity, distances
+
+
+# ------------------------------------------------------------------ tree-run (this project's own: the reference writes no tree)
+def tree_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", method: str = "nj", missing: float = 1.0,  # noqa: PLR0913
+             engine=None, logger: logging.Logger | None = None) -> Path:
+    """Write ``<method>_identity_<nj|upgma>.nwk``: the tree of a complete run's genomes as one line of Newick text, from
+    the distances ``1 - identity`` (``tree.run_distances``: the two directions averaged; ``missing`` where a pair has no
+    identity either way).  ``method`` "nj" is canonical neighbour joining (DESIGN.md section 7h; unrooted, written with a
+    trifurcation at the last join), "upgma" the average-linkage tree of the same distances.  The matrices and labels are
+    the ones ``classify`` and ``plot-run`` read, with the reference's messages for a missing database, an incomplete run,
+    duplicate stems and an unknown label.
+
+    ``engine``: a ``HipEngine`` makes the joins of "nj" on the GPU; None makes them on the host, with the same bits.
+    UPGMA runs on the host either way."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    _require_database(logger, database)
+    if method not in tree_mod.METHODS:
+        sourmash_hip.log_sys_exit(logger, f"Unknown tree method {method!r}: expected one of {', '.join(tree_mod.METHODS)}")
+    outdir, run_method, identity, distances = _distance_run(logger, database, outdir, run_id, label, missing, "tree")
     table = tree_mod.neighbour_joining(distances, engine=engine) if method == "nj" else tree_mod.upgma(distances)
     written = outdir / f"{run_method}_identity_{method}.nwk"
     written.write_text(tree_mod.newick(table, [str(x) for x in identity.columns]) + "\n")
     logger.info("Wrote %s tree to %s", method, written)
+    return written
+
+
+# ------------------------------------------------------------------ ordinate-run (this project's own: the reference writes no ordination)
+def ordinate_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", dimensions: int = 3,  # noqa: PLR0913
+                 missing: float = 1.0, formats: tuple[str, ...] = ("tsv",), engine=None, logger: logging.Logger | None = None) -> list[Path]:
+    """Write the principal coordinates of a complete run's genomes (``ordination.pcoa``) from the
+    distances ``1 - identity`` that ``tree-run`` uses (``tree.run_distances``; ``missing`` where a pair has no identity
+    either way), opened and checked exactly as ``tree_run`` does, with the same messages:
+
+    * ``<method>_identity_pcoa.tsv``: ``genome, PC1 .. PCk``, one row per genome in the label-sorted order of the
+      matrices, values as ``repr(float)``;
+    * ``<method>_identity_pcoa_eigenvalues.tsv``: ``component, eigenvalue, proportion_of_trace, cumulative, residual``
+      (the trace includes the negative eigenvalues: see ``ordination.Ordination``);
+    * with an image format (``png``, ``pdf``, ``svg``, ``jpg``), ``<method>_identity_pcoa.<ext>``: PC1 against PC2.
+
+    ``engine``: a ``HipEngine`` centres the matrix and does the solver's products on the GPU; None does both on the
+    host, with the same bytes.  Returns the written paths."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    _require_database(logger, database)
+    formats = tuple(formats)
+    images = [ext for ext in formats if ext != "tsv"]
+    if images:
+        try:
+            importlib.import_module("matplotlib")
+        except ImportError:
+            sourmash_hip.log_sys_exit(logger, f"Image formats ({', '.join(images)}) need matplotlib, which cannot be imported; only tsv is available")
+    if int(dimensions) < 1 or int(dimensions) > _capi.PA_EIGS_MAX_K:
+        sourmash_hip.log_sys_exit(logger, f"Expected 1 to {_capi.PA_EIGS_MAX_K} dimensions, not {dimensions!r}")
+    outdir, method, identity, distances = _distance_run(logger, database, outdir, run_id, label, missing, "ordination")
+    n = len(distances)
+    if int(dimensions) > n:
+        sourmash_hip.log_sys_exit(logger, f"{int(dimensions)} dimensions for {n} genomes: at most as many axes as genomes")
+    result = ordination_mod.pcoa(distances, int(dimensions), engine=engine)
+    labels = [str(x) for x in identity.columns]
+    stem = f"{method}_identity_pcoa"
+    written = []
+    if "tsv" in formats:
+        written += [outdir / f"{stem}.tsv", outdir / f"{stem}_eigenvalues.tsv"]
+        written[-2].write_text(ordination_mod.coordinates_tsv(result, labels))
+        written[-1].write_text(ordination_mod.eigenvalues_tsv(result))
+    for ext in images:
+        written.append(outdir / f"{stem}.{ext}")
+        ordination_figure.draw_ordination(result, labels, f"{method} identity", written[-1])
+    logger.info("Wrote %d axes of %d genomes (%d iterations, shift %r) to %s", int(dimensions), n, result.info[1], result.info[2], outdir)
     return written
 
 
@@ -1813,7 +1873,7 @@ def plot_run_comp(database: Path | str, outdir: Path, run_ids, *, columns: int =
 
 # ------------------------------------------------------------------ the driver as a process
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run,ordinate-run} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -1900,6 +1960,16 @@ def main(argv: list[str] | None = None) -> int:
     p_tr.add_argument("--missing", type=float, default=1.0, help="distance of a pair with no identity in either direction (default 1.0)")
     p_tr.add_argument("--device", type=int, default=None, help="make the joins of neighbour joining on this GPU (default: on the host)")
     p_tr.add_argument("--verbose", "-v", action="store_true")
+    p_or = sub.add_parser("ordinate-run", help="the principal coordinates of a complete run as <method>_identity_pcoa.tsv and its eigenvalue table")
+    p_or.add_argument("--database", "-d", required=True, type=Path)
+    p_or.add_argument("--outdir", "-o", required=True, type=Path)
+    p_or.add_argument("--run-id", type=int, default=None)
+    p_or.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
+    p_or.add_argument("--dimensions", type=int, default=3, help="principal axes to compute (default 3)")
+    p_or.add_argument("--missing", type=float, default=1.0, help="distance of a pair with no identity in either direction (default 1.0)")
+    p_or.add_argument("--formats", default="tsv", help="comma separated: tsv for the two tables, png, pdf, svg or jpg for the figure (matplotlib)")
+    p_or.add_argument("--device", type=int, default=None, help="centre the matrix and do the solver's products on this GPU (default: on the host)")
+    p_or.add_argument("--verbose", "-v", action="store_true")
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
     logger = logging.getLogger("pyani_plus_amd")
@@ -1929,7 +1999,7 @@ def main(argv: list[str] | None = None) -> int:
         elif args.command == "resume":
             run = resume(args.database, run_id=args.run_id, cache=args.cache, temp=args.temp, logger=logger, ingest=args.ingest,
                          gpus=args.gpus, engine_factory=args.engine_factory)
-        elif args.command in {"classify", "plot-run", "plot-run-comp", "tree-run"}:
+        elif args.command in {"classify", "plot-run", "plot-run-comp", "tree-run", "ordinate-run"}:
             engine = None
             if args.device is not None:
                 from .engine import HipEngine
@@ -1942,6 +2012,11 @@ def main(argv: list[str] | None = None) -> int:
                 elif args.command == "tree-run":
                     print(tree_run(args.database, args.outdir, run_id=args.run_id, label=args.label, method=args.method, missing=args.missing,
                                    engine=engine, logger=logger))
+                elif args.command == "ordinate-run":
+                    formats = tuple(f for f in args.formats.split(",") if f)
+                    for path in ordinate_run(args.database, args.outdir, run_id=args.run_id, label=args.label, dimensions=args.dimensions,
+                                             missing=args.missing, formats=formats, engine=engine, logger=logger):
+                        print(path)
                 elif args.command == "plot-run-comp":
                     formats = tuple(f for f in args.formats.split(",") if f)
                     for path in plot_run_comp(args.database, args.outdir, args.run_ids, columns=args.columns, formats=formats, engine=engine, logger=logger):
