@@ -1,41 +1,29 @@
-"""Run driver and persistence for the four methods ``sourmash-hip``, ``fastANI-hip``, ``external-alignment-hip`` and
-``TETRA-hip`` (stdlib ``sqlite3``).
+"""Run drivers for the four methods ``sourmash-hip``, ``fastANI-hip``, ``external-alignment-hip`` and ``TETRA-hip``,
+``resume``, and the command line of the drivers and of the run reports.
 
-The reference's Python (Typer CLI, SQLAlchemy ORM, snakemake) does not travel to the GPU
-box, so this module is the build's own counterpart of ``cli_sourmash`` / ``fastani`` / ``external_alignment`` +
-``start_and_run_method`` + ``run_method`` minus snakemake (pyani_plus/public_cli.py:115-329, 502-554,
-598-699), of ``resume``, ``export-run``, ``plot-run`` and ``plot-run-comp`` (their tables; pyani_plus/plot_run.py) and ``classify``
-(702-828, 974-1091, 1095-1208, 1211-1331) and of the parts of ``db_orm`` they use (SURVEY.md
-section 8b, last row):
-
-* FASTA enumeration by the four extensions +- ``.gz`` (pyani_plus/utils.py:226-242)
-* genome identity = md5 of the decompressed bytes (utils.py:142-196); length = sum of
-  residues, description = first title (db_orm.py:832-866); duplicate md5 aborts
-  (public_cli.py:165-171)
-* the same tables / constraints as ``Base.metadata.create_all``
-* JSON column import with INSERT OR IGNORE (private_cli.py:507-614, db_orm.py:1076)
-* ``cache_comparisons``: N x N matrices over sorted md5, pandas ``to_json(orient="split")``
-  (db_orm.py:393-466) -- built without the reference's O(N^3) ``hashes.index`` loop.
+The reference's Python (Typer CLI, SQLAlchemy ORM, snakemake) does not travel to the GPU box, so this module is the
+build's own counterpart of ``cli_sourmash`` / ``fastani`` / ``external_alignment`` + ``start_and_run_method`` +
+``run_method`` minus snakemake (pyani_plus/public_cli.py:115-329, 502-554, 598-699) and of ``resume`` (702-828); a
+second file with the md5 of an earlier one aborts the run (public_cli.py:165-171).
 
 Every run takes the same steps: register the genomes, record the run, find what the database lacks
 (``_begin_missing``), compute it (the method's ``_compute_missing_<method>``, listed in ``_METHODS``) and finish
 (``_finish_run``); ``_RunState`` carries what the steps share.
 
-Databases written here can be opened by the reference and vice versa.
+The database layer is ``run_store`` and the six reports of a recorded run (``export_run``, ``classify``, ``plot_run``,
+``plot_run_comp``, ``tree_run``, ``ordinate_run``) are ``reports``.  This module imports ``reports``, which imports
+``run_store``, never the other way round, and re-exports both: ``rundb.<name>`` is the public face of all three.
 """
 
 from __future__ import annotations
 
 import argparse
-import ctypes as C
-import datetime
+import contextlib
 import enum
 import hashlib
 import importlib
 import logging
-import math
 import os
-import platform
 import sqlite3
 import sys
 import tempfile
@@ -43,475 +31,24 @@ import time
 import zipfile
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
-from io import StringIO
 from pathlib import Path
 
 import numpy as np
 
-from . import _capi, launch, wire
+from . import launch, wire
 from . import classify as classify_mod
-from . import cluster as cluster_mod
-from . import distribution as distribution_mod
-from . import distribution_figure, heatmap_figure, ordination_figure, run_comp_figure, scatter_figure
-from . import ordination as ordination_mod
-from . import run_comp as run_comp_mod
 from . import scatter as scatter_mod
 from . import tree as tree_mod
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
-from .engine import load_fasta_files
+from .engine import HipEngine, load_fasta_files
 from .methods import external_alignment_hip, fastani_hip, sourmash_hip, tetra_hip
-from .methods.external_alignment_hip import filename_stem  # also reached as ``rundb.filename_stem``
-
-FASTA_EXTENSIONS = {".fasta", ".fas", ".fna", ".fa"}  # pyani_plus/__init__.py:48
-
-SCHEMA = """
-CREATE TABLE IF NOT EXISTS genomes (
-    genome_hash VARCHAR NOT NULL, path VARCHAR NOT NULL, length INTEGER NOT NULL, description VARCHAR NOT NULL,
-    CONSTRAINT pk_genomes PRIMARY KEY (genome_hash));
-CREATE TABLE IF NOT EXISTS configurations (
-    configuration_id INTEGER NOT NULL, method VARCHAR NOT NULL, program VARCHAR NOT NULL, version VARCHAR NOT NULL,
-    fragsize INTEGER, mode VARCHAR, kmersize INTEGER, minmatch FLOAT, extra VARCHAR,
-    CONSTRAINT pk_configurations PRIMARY KEY (configuration_id),
-    CONSTRAINT uq_configurations_method UNIQUE (method, program, version, fragsize, mode, kmersize, minmatch, extra));
-CREATE TABLE IF NOT EXISTS comparisons (
-    comparison_id INTEGER NOT NULL, query_hash VARCHAR NOT NULL, subject_hash VARCHAR NOT NULL,
-    configuration_id INTEGER NOT NULL, identity FLOAT, aln_length INTEGER, sim_errors INTEGER, cov_query FLOAT,
-    cov_subject FLOAT, uname_system VARCHAR NOT NULL, uname_release VARCHAR NOT NULL, uname_machine VARCHAR NOT NULL,
-    CONSTRAINT pk_comparisons PRIMARY KEY (comparison_id),
-    CONSTRAINT uq_comparisons_query_hash UNIQUE (query_hash, subject_hash, configuration_id),
-    CONSTRAINT fk_comparisons_query_hash_genomes FOREIGN KEY(query_hash) REFERENCES genomes (genome_hash),
-    CONSTRAINT fk_comparisons_subject_hash_genomes FOREIGN KEY(subject_hash) REFERENCES genomes (genome_hash),
-    CONSTRAINT fk_comparisons_configuration_id_configurations FOREIGN KEY(configuration_id)
-        REFERENCES configurations (configuration_id));
-CREATE TABLE IF NOT EXISTS runs (
-    run_id INTEGER NOT NULL, configuration_id INTEGER NOT NULL, cmdline VARCHAR NOT NULL,
-    fasta_directory VARCHAR NOT NULL, date DATETIME NOT NULL, status VARCHAR NOT NULL, name VARCHAR NOT NULL,
-    df_identity VARCHAR, df_cov_query VARCHAR, df_aln_length VARCHAR, df_sim_errors VARCHAR, df_hadamard VARCHAR,
-    CONSTRAINT pk_runs PRIMARY KEY (run_id),
-    CONSTRAINT fk_runs_configuration_id_configurations FOREIGN KEY(configuration_id)
-        REFERENCES configurations (configuration_id));
-CREATE TABLE IF NOT EXISTS runs_genomes (
-    genome_hash VARCHAR NOT NULL, run_id INTEGER NOT NULL, fasta_filename VARCHAR NOT NULL,
-    CONSTRAINT pk_runs_genomes PRIMARY KEY (genome_hash, run_id),
-    CONSTRAINT fk_runs_genomes_genome_hash_genomes FOREIGN KEY(genome_hash) REFERENCES genomes (genome_hash),
-    CONSTRAINT fk_runs_genomes_run_id_runs FOREIGN KEY(run_id) REFERENCES runs (run_id));
-"""
-
-
-# ------------------------------------------------------------------ plain-object mirrors of the ORM rows
-@dataclass
-class Configuration:
-    configuration_id: int
-    method: str
-    program: str
-    version: str
-    fragsize: int | None = None
-    mode: str | None = None
-    kmersize: int | None = None
-    minmatch: float | None = None
-    extra: str | None = None
-
-
-@dataclass
-class RunGenomeAssociation:
-    genome_hash: str
-    fasta_filename: str
-
-
-@dataclass
-class Run:
-    """Duck-type of ``db_orm.Run`` as far as the method module reads it."""
-
-    run_id: int
-    configuration: Configuration
-    fasta_directory: str
-    fasta_hashes: list[RunGenomeAssociation]
-    status: str
-    name: str = ""
-
-    @property
-    def configuration_id(self) -> int:
-        return self.configuration.configuration_id
-
-
-class Session:
-    """Minimal session: ``commit()`` persists ``run.status`` (what the worker's interrupt path needs)."""
-
-    def __init__(self, conn: sqlite3.Connection, run: Run | None = None):
-        self.conn = conn
-        self.run = run
-
-    def commit(self) -> None:
-        if self.run is not None:
-            self.conn.execute("UPDATE runs SET status=? WHERE run_id=?", (self.run.status, self.run.run_id))
-        self.conn.commit()
-
-
-# ------------------------------------------------------------------ FASTA bookkeeping
-def check_fasta(logger: logging.Logger, fasta: Path) -> list[Path]:
-    """FASTA files of a directory by extension (pyani_plus/utils.py:226-242)."""
-    fasta = Path(fasta)
-    if not fasta.is_dir():
-        sourmash_hip.log_sys_exit(logger, f"FASTA input {fasta} is not a directory")
-    names: list[Path] = []
-    for ext in sorted(FASTA_EXTENSIONS):
-        names.extend(fasta.glob("*" + ext))
-        names.extend(fasta.glob("*" + ext + ".gz"))
-    if not names:
-        sourmash_hip.log_sys_exit(
-            logger, f"No FASTA input genomes under {fasta} with extensions {', '.join(sorted(FASTA_EXTENSIONS))}"
-        )
-    return sorted(names)
-
-
-def fasta_length_and_description(text: bytes) -> tuple[int, str | None]:
-    """Sum of residues and first title, as fasta_bytes_iterator sees them (utils.py:67-90)."""
-    length = 0
-    description = None
-    in_record = False
-    for line in text.split(b"\n"):
-        if line[:1] == b">":
-            in_record = True
-            if description is None:
-                description = line[1:].rstrip().decode()
-            continue
-        if in_record:
-            length += len(line.translate(None, b" \t\r\n"))
-    return length, description
-
-
-# ------------------------------------------------------------------ database
-def connect_to_db(database: Path | str) -> sqlite3.Connection:
-    conn = sqlite3.connect(str(database), timeout=30.0)
-    conn.executescript(SCHEMA)
-    conn.commit()
-    return conn
-
-
-def _find_configuration(conn, values: tuple):
-    """The (configuration_id,) row with these values of ``wire.CONFIG_FIELDS``, or None."""
-    return conn.execute(
-        "SELECT configuration_id FROM configurations WHERE method=? AND program=? AND version=? AND fragsize IS ? "
-        "AND mode IS ? AND kmersize IS ? AND minmatch IS ? AND extra IS ?",
-        values,
-    ).fetchone()
-
-
-def db_configuration(conn, method, program, version, fragsize=None, mode=None, kmersize=None, minmatch=None,
-                     extra=None) -> Configuration:
-    """Return the matching configuration row, creating it if needed (db_orm.py:705-782)."""
-    row = _find_configuration(conn, (method, program, version, fragsize, mode, kmersize, minmatch, extra))
-    if row is None:
-        cur = conn.execute(
-            "INSERT INTO configurations (method, program, version, fragsize, mode, kmersize, minmatch, extra) "
-            "VALUES (?,?,?,?,?,?,?,?)",
-            (method, program, version, fragsize, mode, kmersize, minmatch, extra),
-        )
-        conn.commit()
-        cid = cur.lastrowid
-    else:
-        cid = row[0]
-    return Configuration(cid, method, program, version, fragsize, mode, kmersize, minmatch, extra)
-
-
-def db_genome(conn, path: Path, md5: str, length: int, description: str) -> None:
-    conn.execute(
-        "INSERT OR IGNORE INTO genomes (genome_hash, path, length, description) VALUES (?,?,?,?)",
-        (md5, str(path), length, description),
-    )
-
-
-def add_run(conn, config: Configuration, cmdline: str, fasta_directory: Path, status: str, name: str,
-            fasta_to_hash: dict[Path, str]) -> Run:
-    now = datetime.datetime.now(datetime.timezone.utc).replace(tzinfo=None).isoformat(sep=" ")
-    cur = conn.execute(
-        "INSERT INTO runs (configuration_id, cmdline, fasta_directory, date, status, name) VALUES (?,?,?,?,?,?)",
-        (config.configuration_id, cmdline, str(fasta_directory), now, status, name),
-    )
-    run_id = cur.lastrowid
-    assoc = []
-    for filename, md5 in fasta_to_hash.items():
-        conn.execute(
-            "INSERT INTO runs_genomes (genome_hash, run_id, fasta_filename) VALUES (?,?,?)",
-            (md5, run_id, Path(filename).name),
-        )
-        assoc.append(RunGenomeAssociation(md5, Path(filename).name))
-    conn.commit()
-    return Run(run_id, config, str(fasta_directory), assoc, status, name)
-
-
-def load_run(conn, run_id: int) -> Run:
-    row = conn.execute(
-        "SELECT configuration_id, fasta_directory, status, name FROM runs WHERE run_id=?", (run_id,)
-    ).fetchone()
-    if row is None:
-        msg = f"Database has no run {run_id}"
-        raise ValueError(msg)
-    crow = conn.execute(
-        "SELECT configuration_id, method, program, version, fragsize, mode, kmersize, minmatch, extra "
-        "FROM configurations WHERE configuration_id=?",
-        (row[0],),
-    ).fetchone()
-    assoc = [
-        RunGenomeAssociation(h, f)
-        for h, f in conn.execute("SELECT genome_hash, fasta_filename FROM runs_genomes WHERE run_id=?", (run_id,))
-    ]
-    return Run(run_id, Configuration(*crow), row[1], assoc, row[2], row[3])
-
-
-def _open_run(logger, database: Path | str, run_id: int | None, doing: str) -> tuple[sqlite3.Connection, Run]:
-    """The database and its run ``run_id`` (None: the latest one), with the reference's messages
-    (pyani_plus/public_cli.py:718-741)."""
-    conn = connect_to_db(database)
-    if run_id is None:
-        row = conn.execute("SELECT MAX(run_id) FROM runs").fetchone()
-        if row is None or row[0] is None:
-            sourmash_hip.log_sys_exit(logger, f"Database {database} contains no runs.")
-        run_id = row[0]
-        logger.info("%s run-id %d", doing, run_id)
-    try:
-        return conn, load_run(conn, run_id)
-    except ValueError:
-        sourmash_hip.log_sys_exit(logger, f"Database {database} has no run-id {run_id}.")
-
-
-def _select_run_comparisons(conn, run: Run, what: str, tail: str = "") -> sqlite3.Cursor:
-    """``what`` of the comparisons among this run's genomes under its configuration (Run.comparisons(),
-    db_orm.py:353-391)."""
-    return conn.execute(
-        f"SELECT {what} FROM comparisons c "
-        "JOIN runs_genomes q ON c.query_hash = q.genome_hash AND q.run_id = ? "
-        "JOIN runs_genomes s ON c.subject_hash = s.genome_hash AND s.run_id = ? "
-        f"WHERE c.configuration_id = ? {tail}",
-        (run.run_id, run.run_id, run.configuration_id),
-    )
-
-
-def count_run_comparisons(conn, run: Run) -> int:
-    return _select_run_comparisons(conn, run, "COUNT(*)").fetchone()[0]
-
-
-INSERT_COMPARISON = (
-    "INSERT OR IGNORE INTO comparisons (query_hash, subject_hash, configuration_id, identity, aln_length, "
-    "sim_errors, cov_query, uname_system, uname_release, uname_machine) VALUES (?,?,?,?,?,?,?,?,?,?)"
-)
-
-
-def import_json_comparisons(logger: logging.Logger, conn, json_filename: Path) -> int:
-    """Import one column file; the configuration must already exist; ``cov_subject`` is ignored
-    (pyani_plus/private_cli.py:507-614)."""
-    data = wire.load_json_comparisons(json_filename)
-    cfg = data["configuration"]
-    row = _find_configuration(conn, tuple(cfg[k] for k in wire.CONFIG_FIELDS))
-    if row is None:
-        sourmash_hip.log_sys_exit(logger, f"JSON file {json_filename} configuration not in database")
-    cid = row[0]
-    uname = data["uname"]
-    rows = [
-        (
-            e["query_hash"], e["subject_hash"], cid, e["identity"], e.get("aln_length"), e.get("sim_errors"),
-            e.get("cov_query"), uname["system"], uname["release"], uname["machine"],
-        )  # fmt: skip
-        for e in data["comparisons"]
-    ]
-    conn.executemany(INSERT_COMPARISON, rows)
-    conn.commit()
-    return len(rows)
-
-
-def _database_file(conn) -> str | None:
-    """Path of the connection's main database, or None for an in-memory / temporary one."""
-    for _seq, name, path in conn.execute("PRAGMA database_list"):
-        if name == "main":
-            return path or None
-    return None
-
-
-def ingest_matrices_native(conn, run: Run, queries: list[str], subjects: list[str], identity, cov_query, is_null, *,
-                           aln_length=None, sim_errors=None) -> int | None:
-    """``ingest_matrices`` through ``pa_sqlite_insert_comparisons`` (one prepared statement stepped from C on a
-    connection of its own).  Returns the number of comparisons handled, or None when the native route does not
-    apply (in-memory database, libsqlite3.so.0 not loadable) -- the caller then uses Python's sqlite3 module."""
-    path = _database_file(conn)
-    if path is None:
-        return None
-    nq, ns = len(queries), len(subjects)
-    if nq == 0 or ns == 0:
-        return 0
-    uname = platform.uname()
-    identity = np.ascontiguousarray(identity, dtype=np.float64)
-    cov_query = np.ascontiguousarray(cov_query, dtype=np.float64)
-    null = np.ascontiguousarray(is_null, dtype=np.uint8)
-    assert identity.shape == (nq, ns) == cov_query.shape == null.shape
-    q_arr = (C.c_char_p * nq)(*[q.encode() for q in queries])
-    s_arr = (C.c_char_p * ns)(*[s.encode() for s in subjects])
-    conn.commit()  # the call opens its own connection: nothing of ours may hold the write lock
-    inserted = C.c_uint64()
-    aln = err = None
-    if aln_length is not None:
-        aln = np.ascontiguousarray(aln_length, dtype=np.int64)
-        err = np.ascontiguousarray(sim_errors, dtype=np.int64)
-        assert aln.shape == (nq, ns) == err.shape
-    status = _capi.load_library().pa_sqlite_insert_comparisons_ex(
-        path.encode(), run.configuration_id, uname.system.encode(), uname.release.encode(), uname.machine.encode(),
-        q_arr, nq, s_arr, ns, identity.ctypes.data, cov_query.ctypes.data, null.ctypes.data,
-        None if aln is None else aln.ctypes.data, None if err is None else err.ctypes.data, C.byref(inserted),
-    )  # fmt: skip
-    if status == _capi.PA_E_IO and "libsqlite3" in _capi.last_error():
-        return None
-    _capi.check(status, "pa_sqlite_insert_comparisons")
-    return nq * ns
-
-
-def ingest_matrices(conn, run: Run, queries: list[str], subjects: list[str], identity, cov_query, is_null, *,
-                    chunk_rows: int = 1_000_000, native: bool = True, aln_length=None, sim_errors=None) -> int:
-    """Comparison rows straight from the result matrices (the reference goes through one
-    Python dict per row, a JSON file and its re-parse: pyani_plus/private_cli.py:1863-1888, 507-614).
-
-    Rows go in query-major with ascending subjects -- the order of the UNIQUE(query_hash, subject_hash,
-    configuration_id) index when both lists are sorted, so the index grows by appends.  With ``native`` the rows
-    are stepped from C (``ingest_matrices_native``); otherwise, or when that route does not apply, in chunks of
-    ``chunk_rows`` through one ``executemany`` each."""
-    if native:
-        done = ingest_matrices_native(conn, run, queries, subjects, identity, cov_query, is_null, aln_length=aln_length, sim_errors=sim_errors)
-        if done is not None:
-            return done
-    uname = platform.uname()
-    cid = run.configuration_id
-    nq, ns = len(queries), len(subjects)
-    identity = np.asarray(identity, dtype=np.float64)
-    cov_query = np.asarray(cov_query, dtype=np.float64)
-    null = np.asarray(is_null, dtype=bool)
-    rows_per_chunk = max(1, chunk_rows // max(ns, 1))
-    constants = (uname.system, uname.release, uname.machine)
-    for q0 in range(0, nq, rows_per_chunk):
-        q1 = min(nq, q0 + rows_per_chunk)
-        ident = identity[q0:q1].astype(object)
-        cov = cov_query[q0:q1].astype(object)
-        ident[null[q0:q1]] = None
-        cov[null[q0:q1]] = None
-        if aln_length is None:
-            aln = err = np.full(ident.shape, None, dtype=object)
-        else:
-            aln = np.asarray(aln_length)[q0:q1].astype(np.int64).astype(object)  # Python ints: sqlite3 stores numpy scalars as blobs
-            err = np.asarray(sim_errors)[q0:q1].astype(np.int64).astype(object)
-            aln[null[q0:q1]] = None
-            err[null[q0:q1]] = None
-        rows = (
-            (q, s, cid, i, a, e, c, *constants)
-            for q, irow, crow, arow, erow in zip(queries[q0:q1], ident, cov, aln, err)
-            for s, i, c, a, e in zip(subjects, irow, crow, arow, erow)
-        )
-        conn.executemany(INSERT_COMPARISON, rows)
-    conn.commit()
-    return nq * ns
-
-
-def _matrices_to_json(hashes: list[str], mats: dict) -> dict[str, str]:
-    """The five ``runs.df_*`` strings as pandas writes them (db_orm.py:442-465); hadamard = identity * cov_query."""
-    import pandas as pd  # loaded when the first matrix cache is formatted, not with the module
-
-    mats["hadamard"] = mats["identity"] * mats["cov_query"]
-    return {
-        f"df_{key}": pd.DataFrame(data=mat, index=hashes, columns=hashes, dtype=float).to_json(orient="split")
-        for key, mat in mats.items()
-    }
-
-
-def format_matrix_cache(hashes: list[str], identity, cov_query, is_null, *, aln_length=None, sim_errors=None) -> dict[str, str] | None:
-    """The five ``runs.df_*`` strings from matrices in memory (rows = query, columns = subject, both in ``hashes``
-    order = sorted md5); None when they would not fit a SQLite value."""
-    assert hashes == sorted(hashes)
-    n = len(hashes)
-    if _matrix_cache_too_big(n):
-        return None
-    ident = np.where(is_null, np.nan, identity)
-    cov = np.where(is_null, np.nan, cov_query)
-    nan = np.full((n, n), np.nan)
-    aln = nan if aln_length is None else np.where(is_null, np.nan, np.asarray(aln_length, dtype=np.float64))
-    err = nan if sim_errors is None else np.where(is_null, np.nan, np.asarray(sim_errors, dtype=np.float64))
-    return _matrices_to_json(hashes, {"identity": ident, "cov_query": cov, "aln_length": aln, "sim_errors": err})
-
-
-def cache_matrices(conn, run: Run, hashes: list[str], identity, cov_query, is_null, *, formatted=None) -> dict[str, str]:
-    """``cache_comparisons`` from matrices that are already in memory: same strings as the SELECT-based form, without
-    reading 10^8 rows back.  ``formatted`` = the result of an earlier ``format_matrix_cache`` of the same matrices."""
-    out = formatted if formatted is not None else format_matrix_cache(hashes, identity, cov_query, is_null)
-    _store_matrix_cache(conn, run, out)
-    return out or {}
-
-
-def _matrix_cache_too_big(n: int) -> bool:
-    """A cached matrix is about 13 characters per cell ("0.9997081124,"): beyond ~7.5e7 cells its JSON text passes
-    SQLite's 10^9-byte value limit, so formatting it would be wasted work."""
-    return n * n * 13 > 950_000_000
-
-
-def _store_matrix_cache(conn, run: Run, out: dict[str, str] | None) -> bool:
-    """``runs.df_*`` hold the matrices as JSON text (db_orm.py:442-465).  SQLite refuses a value of more than
-    10^9 bytes (SQLITE_MAX_LENGTH), which a 10 000 x 10 000 matrix exceeds (about 1.3 GB of text) -- in the
-    reference just as here.  The comparisons table is complete either way; the cache columns then stay NULL, which
-    the reference treats as "not cached yet" (db_orm.py:393-405)."""
-    try:
-        if out is None:
-            raise sqlite3.DataError("not attempted")
-        conn.execute(
-            "UPDATE runs SET df_identity=?, df_cov_query=?, df_aln_length=?, df_sim_errors=?, df_hadamard=? WHERE run_id=?",
-            (out["df_identity"], out["df_cov_query"], out["df_aln_length"], out["df_sim_errors"], out["df_hadamard"],
-             run.run_id),
-        )
-    except (sqlite3.DataError, OverflowError) as err:
-        logging.getLogger("pyani_plus_amd").warning(
-            "matrix cache of run %d not stored (%s): %d genomes give JSON strings beyond SQLite's 10^9-byte limit",
-            run.run_id, err, len(run.fasta_hashes),
-        )
-        conn.rollback()
-        return False
-    conn.commit()
-    return True
-
-
-def cache_comparisons(conn, run: Run) -> dict[str, str]:
-    """Fill runs.df_* with the N x N matrices (rows = query, columns = subject, sorted md5)."""
-    if _matrix_cache_too_big(len(run.fasta_hashes)):
-        _store_matrix_cache(conn, run, None)
-        return {}
-    hashes, mats = _comparison_matrices(conn, run)
-    out = _matrices_to_json(hashes, mats)
-    _store_matrix_cache(conn, run, out)
-    return out
-
-
-def _comparison_matrices(conn, run: Run) -> tuple[list[str], dict]:
-    """(sorted md5s, the four N x N matrices of the run's comparisons: rows = query, columns = subject, NaN where there
-    is no value)."""
-    hashes = sorted(a.genome_hash for a in run.fasta_hashes)
-    index = {h: i for i, h in enumerate(hashes)}
-    n = len(hashes)
-    mats = {k: np.full((n, n), np.nan, float) for k in ("identity", "cov_query", "aln_length", "sim_errors")}
-    rows = _select_run_comparisons(conn, run, "c.query_hash, c.subject_hash, c.identity, c.cov_query, c.aln_length, c.sim_errors").fetchall()
-    if rows:
-        # one dictionary lookup per row (the reference does a list.index per row: O(N^3) overall)
-        r_idx = np.fromiter((index[r[0]] for r in rows), dtype=np.int64, count=len(rows))
-        c_idx = np.fromiter((index[r[1]] for r in rows), dtype=np.int64, count=len(rows))
-        for col, key in enumerate(("identity", "cov_query", "aln_length", "sim_errors"), start=2):
-            mats[key][r_idx, c_idx] = np.array([r[col] for r in rows], dtype=float)  # None -> NaN
-    return hashes, mats
-
-
-def _load_tile(logger, tile_file: Path, config: Configuration) -> tuple:
-    """(queries, subjects, identity, cov_query, is_null) of a ``wire.save_tile`` file made under ``config``."""
-    tile_config, *tile = wire.load_tile(tile_file)
-    for key in wire.CONFIG_FIELDS:
-        if tile_config[key] != getattr(config, key):
-            sourmash_hip.log_sys_exit(logger, f"Tile file {tile_file} configuration does not match the run ({key})")
-    return tuple(tile)
-
-
-def import_tile(logger: logging.Logger, conn, run: Run, tile_file: Path) -> int:
-    """Import one binary column file written by ``wire.save_tile`` (resuming a direct-ingest run)."""
-    return ingest_matrices(conn, run, *_load_tile(logger, tile_file, run.configuration))
+from .methods.external_alignment_hip import filename_stem  # noqa: F401  (reached as ``rundb.filename_stem``)
+from .reports import _require_database, classify, export_run, ordinate_run, plot_run, plot_run_comp, tree_run  # noqa: F401
+from .run_store import (FASTA_EXTENSIONS, INSERT_COMPARISON, SCHEMA, Configuration, Run, RunGenomeAssociation, Session, _load_tile,  # noqa: F401
+                        _open_run, _select_run_comparisons, _store_matrix_cache, add_run, cache_comparisons, cache_matrices, check_fasta,
+                        connect_to_db, count_run_comparisons, db_configuration, db_genome, fasta_length_and_description,
+                        format_matrix_cache, import_json_comparisons, import_tile, ingest_matrices, ingest_matrices_native, load_run)  # fmt: skip
 
 
 # ------------------------------------------------------------------ what the steps of a run share
@@ -1270,8 +807,7 @@ def resume(database: Path | str, *, run_id: int | None = None, cache: Path | Non
     with the run must be the one at hand (``We have ... but run-id N used ... instead``), the FASTA directory and
     every file of the run must still be there.  A complete run is left as it is."""
     logger = logger or logging.getLogger("pyani_plus_amd")
-    if str(database) == ":memory:" or not Path(database).is_file():
-        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
+    _require_database(logger, database)
     conn, run = _open_run(logger, database, run_id, "Resuming")
     run_id, config = run.run_id, run.configuration
     n = len(run.fasta_hashes)
@@ -1302,576 +838,72 @@ def resume(database: Path | str, *, run_id: int | None = None, cache: Path | Non
     return _finish_run(state, compute_missing(state))
 
 
-# ------------------------------------------------------------------ export-run (pyani_plus/public_cli.py:974-1091)
-def export_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem",
-               logger: logging.Logger | None = None) -> list[Path]:
-    """Write ``<method>_run_<id>.tsv`` (long form) and the six matrices ``<method>_{identity,aln_lengths,sim_errors,
-    query_cov,hadamard,tANI}.tsv`` of a run, byte for byte what the reference's ``export-run`` writes from the same
-    database: long form in ``Run.comparisons()`` order with ``NA`` for NULL and Python ``str(float)``; matrices from
-    the cached ``df_*`` strings through pandas ``to_csv(sep="\t")``, labelled by ``md5``, ``filename`` or ``stem`` and
-    sorted by label (db_orm.py:590-624).  A partial run gets the long form only and then the reference's error."""
-    import pandas as pd
-
-    logger = logger or logging.getLogger("pyani_plus_amd")
-    if str(database) == ":memory:" or not Path(database).is_file():
-        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
-    outdir = Path(outdir)
-    if not outdir.is_dir():
-        logger.warning("Output directory %s does not exist, making it.", outdir)
-        outdir.mkdir()
-    conn, run = _open_run(logger, database, run_id, "Exporting")
-    run_id = run.run_id
-    if not run.fasta_hashes:
-        sourmash_hip.log_sys_exit(logger, f"Run-id {run_id} has no genomes")
-    method = run.configuration.method
-    if label == "md5":
-        mapping = {a.genome_hash: a.genome_hash for a in run.fasta_hashes}
-    elif label == "filename":
-        mapping = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
-    elif label == "stem":
-        mapping = {a.genome_hash: filename_stem(a.fasta_filename) for a in run.fasta_hashes}
-    else:
-        sourmash_hip.log_sys_exit(logger, f"Unexpected label scheme {label!r}")
-
-    def float_or_na(value) -> str:
-        return "NA" if value is None else str(value)
-
-    written = [outdir / f"{method}_run_{run_id}.tsv"]
-    rows = _select_run_comparisons(
-        conn, run, "c.query_hash, c.subject_hash, c.identity, c.cov_query, c.cov_subject, c.aln_length, c.sim_errors", "ORDER BY c.comparison_id"
-    ).fetchall()
-    with written[0].open("w") as handle:
-        handle.write("#Query\tSubject\tIdentity\tQuery-Cov\tSubject-Cov\tHadamard\ttANI\tAlign-Len\tSim-Errors\n")
-        for q, s_hash, identity, cov_query, cov_subject, aln_length, sim_errors in rows:
-            hadamard = None if identity is None or cov_query is None else identity * cov_query
-            tani = None if hadamard is None else -math.log(hadamard)
-            handle.write(
-                f"{mapping[q]}\t{mapping[s_hash]}\t{float_or_na(identity)}\t{float_or_na(cov_query)}\t{float_or_na(cov_subject)}"
-                f"\t{float_or_na(hadamard)}\t{float_or_na(tani)}\t{float_or_na(aln_length)}\t{float_or_na(sim_errors)}\n"
-            )
-    logger.info("Wrote long-form to %s", written[0])
-    n = len(run.fasta_hashes)
-    if len(rows) != n * n:  # db_orm.load_run(check_complete=True)
-        sourmash_hip.log_sys_exit(logger, f"run-id {run_id} has {len(rows)} of {n}^2={n * n} comparisons, {n * n - len(rows)} needed")
-    cached = conn.execute(
-        "SELECT df_identity, df_aln_length, df_sim_errors, df_cov_query, df_hadamard FROM runs WHERE run_id=?", (run_id,)
-    ).fetchone()
-    if any(c is None for c in cached):
-        out = cache_comparisons(conn, run)
-        cached = tuple(out.get(k) for k in ("df_identity", "df_aln_length", "df_sim_errors", "df_cov_query", "df_hadamard"))
-        if any(c is None for c in cached):
-            sourmash_hip.log_sys_exit(logger, f"Could not load run {method} matrix")
-    frames = [pd.read_json(StringIO(c), orient="split", dtype=float) for c in cached]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        frames.append(-np.log(frames[4]))  # tANI = -ln(hadamard), not cached (db_orm.py:566-588)
-    if label == "stem" and len(set(mapping.values())) < len(mapping):
-        sourmash_hip.log_sys_exit(logger, "Duplicate filename stems, consider using MD5 labelling.")
-    for frame, kind in zip(frames, ("identity", "aln_lengths", "sim_errors", "query_cov", "hadamard", "tANI")):
-        if label != "md5":
-            frame = frame.rename(index=mapping, columns=mapping).sort_index(axis=0).sort_index(axis=1)  # noqa: PLW2901
-        written.append(outdir / f"{method}_{kind}.tsv")
-        frame.to_csv(written[-1], sep="\t")
-    logger.info("Wrote matrices to %s/%s_*.tsv", outdir, method)
-    conn.close()
-    return written
-
-
-# ------------------------------------------------------------------ what classify and plot-run read of a complete run
-def _score_frames(logger, conn, run: Run) -> list:
-    """The identity, query coverage and Hadamard matrices of a complete run as frames over sorted md5: the cached
-    ``runs.df_*`` strings the reference reads (10 decimals), filled with ``cache_comparisons`` first when they are missing;
-    for a run too large for the cache, the comparisons table, unrounded."""
-    import pandas as pd
-
-    kinds = ("identity", "cov_query", "hadamard")
-    if _matrix_cache_too_big(len(run.fasta_hashes)):
-        hashes, mats = _comparison_matrices(conn, run)
-        mats["hadamard"] = mats["identity"] * mats["cov_query"]
-        return [pd.DataFrame(mats[k], index=hashes, columns=hashes) for k in kinds]
-    cached = conn.execute("SELECT df_identity, df_cov_query, df_hadamard FROM runs WHERE run_id=?", (run.run_id,)).fetchone()
-    if any(c is None for c in cached):
-        out = cache_comparisons(conn, run)
-        cached = tuple(out.get(f"df_{k}") for k in kinds)
-        if any(c is None for c in cached):
-            sourmash_hip.log_sys_exit(logger, f"Could not load run {run.configuration.method} matrix")
-    return [pd.read_json(StringIO(c), orient="split", dtype=float) for c in cached]
-
-
-def _relabelled(logger, run: Run, frames: list, label: str) -> list:
-    """``Run.relabelled_matrix`` (db_orm.py:590-624) of every frame: labelled by ``md5`` (as they are), ``filename`` or
-    ``stem`` and sorted by label on both axes, with the reference's messages for duplicate stems and an unknown label."""
-    if label == "md5":
-        return frames
-    if label == "filename":
-        mapping = {a.genome_hash: a.fasta_filename for a in run.fasta_hashes}
-    elif label == "stem":
-        mapping = {a.genome_hash: filename_stem(a.fasta_filename) for a in run.fasta_hashes}
-        if len(set(mapping.values())) < len(mapping):
-            sourmash_hip.log_sys_exit(logger, "Duplicate filename stems, consider using MD5 labelling.")
-    else:
-        sourmash_hip.log_sys_exit(logger, f"Unexpected label scheme {label!r}")
-    return [f.rename(index=mapping, columns=mapping).sort_index(axis=0).sort_index(axis=1) for f in frames]
-
-
-# ------------------------------------------------------------------ classify (pyani_plus/public_cli.py:1211-1331)
-def classify(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", coverage_edges: str = "min",  # noqa: PLR0913
-             score_edges: str = "mean", cov_min: float = classify_mod.MIN_COVERAGE, mode: str = "identity", engine=None,
-             logger: logging.Logger | None = None) -> Path:
-    """Write ``<method>_classify.tsv``, the table of genome cliques of a complete run (``n_nodes, max_cov,
-    min_<score>, max_<score>, members``; the score is ``identity`` or ``-tANI``), with the reference's header and number
-    formatting and its messages for a missing database, an incomplete run, duplicate stems and an unknown label.
-
-    The matrices are the ones the reference reads: the cached ``runs.df_*`` JSON strings (10 decimals), filled with
-    ``cache_comparisons`` first when they are missing, relabelled and sorted by label.  Which rows there are is the
-    reference's answer whenever no two edges have the same score; with ties, and for the order of rows and members,
-    ``pyani_plus_amd.classify`` says what this project defines.  A run too large for the cache (about 8 500 genomes
-    and more) cannot be classified by the reference at all; its matrices are then taken from the comparisons table,
-    unrounded, which is beyond what the reference defines.
-
-    ``engine``: a ``HipEngine`` builds and sorts the edge list on the GPU; None does it on the host.  The plot of the
-    reference (``plot_classify``) is not made."""
-    logger = logger or logging.getLogger("pyani_plus_amd")
-    if str(database) == ":memory:" or not Path(database).is_file():
-        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
-    for name, role in ((coverage_edges, "coverage"), (score_edges, "score")):
-        if name not in classify_mod.AGG_NAMES:
-            sourmash_hip.log_sys_exit(logger, f"Unknown {role} aggregator {name!r}: expected one of {', '.join(classify_mod.AGG_NAMES)}")
-    if mode not in classify_mod.MODES:
-        sourmash_hip.log_sys_exit(logger, f"Unknown classify mode {mode!r}: expected one of {', '.join(classify_mod.MODES)}")
-    outdir = Path(outdir)
-    if not outdir.is_dir():
-        logger.warning("Output directory %s does not exist, making it.", outdir)
-        outdir.mkdir()
-    conn, run = _open_run(logger, database, run_id, "Exporting")
-    run_id = run.run_id
-    n = len(run.fasta_hashes)
-    done = count_run_comparisons(conn, run)
-    if not n:
-        sourmash_hip.log_sys_exit(logger, f"Run-id {run_id} has no genomes")
-    if done != n * n:  # db_orm.load_run(check_complete=True)
-        sourmash_hip.log_sys_exit(logger, f"run-id {run_id} has {done} of {n}^2={n * n} comparisons, {n * n - done} needed")
-    method = run.configuration.method
-    frames = _score_frames(logger, conn, run)
-    conn.close()
-    if done == 1 and n == 1:
-        logger.warning("Run %d has %d comparison across %d genome. Reporting single clique.", run_id, done, n)
-    else:
-        logger.info("Run %d has %d comparisons across %d genomes.", run_id, done, n)
-    identity, cov, hadamard = _relabelled(logger, run, frames, label)
-    score = identity.to_numpy(dtype=float) if mode == "identity" else classify_mod.tani_scores(hadamard.to_numpy(dtype=float))
-    rows = classify_mod.classify_matrices([str(x) for x in cov.columns], score, cov.to_numpy(dtype=float), coverage_edges=coverage_edges,
-                                          score_edges=score_edges, cov_min=cov_min, engine=engine)
-    written = outdir / f"{method}_classify.tsv"
-    written.write_text(classify_mod.classify_tsv(rows, mode))
-    logger.info("Wrote classify output to %s", outdir)
-    return written
-
-
-# ------------------------------------------------------------------ a run's distances (tree-run, ordinate-run)
-def _require_database(logger, database) -> None:
-    if str(database) == ":memory:" or not Path(database).is_file():
-        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
-
-
-def _distance_run(logger, database, outdir, run_id: int | None, label: str, missing: float, what: str):  # noqa: PLR0913
-    """What tree-run and ordinate-run start from: ``(outdir, method, identity, distances)`` of a complete run -- the
-    output directory made, the run opened and checked, its identity frame relabelled and sorted by label as ``classify``
-    and ``plot-run`` read it, and ``tree.run_distances`` of it -- with the reference's messages for an incomplete run,
-    duplicate stems and an unknown label.  ``what`` is the thing an identity above 1 leaves undefined."""
-    if not (math.isfinite(missing) and missing >= 0):
-        sourmash_hip.log_sys_exit(logger, f"The distance of a pair without identity must be finite and not negative, not {missing!r}")
-    outdir = Path(outdir)
-    if not outdir.is_dir():
-        logger.warning("Output directory %s does not exist, making it.", outdir)
-        outdir.mkdir()
-    conn, run = _open_run(logger, database, run_id, "Exporting")
-    run_id = run.run_id
-    n = len(run.fasta_hashes)
-    done = count_run_comparisons(conn, run)
-    if not n:
-        sourmash_hip.log_sys_exit(logger, f"Run-id {run_id} has no genomes")
-    if done != n * n:  # db_orm.load_run(check_complete=True)
-        sourmash_hip.log_sys_exit(logger, f"run-id {run_id} has {done} of {n}^2={n * n} comparisons, {n * n - done} needed")
-    run_method = run.configuration.method
-    frames = _score_frames(logger, conn, run)
-    conn.close()
-    logger.info("Run %d has %d comparisons across %d genomes.", run_id, done, n)
-    identity = _relabelled(logger, run, frames, label)[0]
-    distances = tree_mod.run_distances(identity, missing, logger)
-    if (distances < 0).any():
-        sourmash_hip.log_sys_exit(logger, f"An identity above 1 gives a negative distance: no {what} is defined")
-    return outdir, run_method, identity, distances
-
-
-# ------------------------------------------------------------------ tree-run (this project's own: the reference writes no tree)
-def tree_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", method: str = "nj", missing: float = 1.0,  # noqa: PLR0913
-             engine=None, logger: logging.Logger | None = None) -> Path:
-    """Write ``<method>_identity_<nj|upgma>.nwk``: the tree of a complete run's genomes as one line of Newick text, from
-    the distances ``1 - identity`` (``tree.run_distances``: the two directions averaged; ``missing`` where a pair has no
-    identity either way).  ``method`` "nj" is canonical neighbour joining (unrooted, written with a
-    trifurcation at the last join), "upgma" the average-linkage tree of the same distances.  The matrices and labels are
-    the ones ``classify`` and ``plot-run`` read, with the reference's messages for a missing database, an incomplete run,
-    duplicate stems and an unknown label.
-
-    ``engine``: a ``HipEngine`` makes the joins of "nj" on the GPU; None makes them on the host, with the same bits.
-    UPGMA runs on the host either way."""
-    logger = logger or logging.getLogger("pyani_plus_amd")
-    _require_database(logger, database)
-    if method not in tree_mod.METHODS:
-        sourmash_hip.log_sys_exit(logger, f"Unknown tree method {method!r}: expected one of {', '.join(tree_mod.METHODS)}")
-    outdir, run_method, identity, distances = _distance_run(logger, database, outdir, run_id, label, missing, "tree")
-    table = tree_mod.neighbour_joining(distances, engine=engine) if method == "nj" else tree_mod.upgma(distances)
-    written = outdir / f"{run_method}_identity_{method}.nwk"
-    written.write_text(tree_mod.newick(table, [str(x) for x in identity.columns]) + "\n")
-    logger.info("Wrote %s tree to %s", method, written)
-    return written
-
-
-# ------------------------------------------------------------------ ordinate-run (this project's own: the reference writes no ordination)
-def ordinate_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", dimensions: int = 3,  # noqa: PLR0913
-                 missing: float = 1.0, formats: tuple[str, ...] = ("tsv",), engine=None, logger: logging.Logger | None = None) -> list[Path]:
-    """Write the principal coordinates of a complete run's genomes (``ordination.pcoa``) from the
-    distances ``1 - identity`` that ``tree-run`` uses (``tree.run_distances``; ``missing`` where a pair has no identity
-    either way), opened and checked exactly as ``tree_run`` does, with the same messages:
-
-    * ``<method>_identity_pcoa.tsv``: ``genome, PC1 .. PCk``, one row per genome in the label-sorted order of the
-      matrices, values as ``repr(float)``;
-    * ``<method>_identity_pcoa_eigenvalues.tsv``: ``component, eigenvalue, proportion_of_trace, cumulative, residual``
-      (the trace includes the negative eigenvalues: see ``ordination.Ordination``);
-    * with an image format (``png``, ``pdf``, ``svg``, ``jpg``), ``<method>_identity_pcoa.<ext>``: PC1 against PC2.
-
-    ``engine``: a ``HipEngine`` centres the matrix and does the solver's products on the GPU; None does both on the
-    host, with the same bytes.  Returns the written paths."""
-    logger = logger or logging.getLogger("pyani_plus_amd")
-    _require_database(logger, database)
-    formats = tuple(formats)
-    images = [ext for ext in formats if ext != "tsv"]
-    if images:
-        try:
-            importlib.import_module("matplotlib")
-        except ImportError:
-            sourmash_hip.log_sys_exit(logger, f"Image formats ({', '.join(images)}) need matplotlib, which cannot be imported; only tsv is available")
-    if int(dimensions) < 1 or int(dimensions) > _capi.PA_EIGS_MAX_K:
-        sourmash_hip.log_sys_exit(logger, f"Expected 1 to {_capi.PA_EIGS_MAX_K} dimensions, not {dimensions!r}")
-    outdir, method, identity, distances = _distance_run(logger, database, outdir, run_id, label, missing, "ordination")
-    n = len(distances)
-    if int(dimensions) > n:
-        sourmash_hip.log_sys_exit(logger, f"{int(dimensions)} dimensions for {n} genomes: at most as many axes as genomes")
-    result = ordination_mod.pcoa(distances, int(dimensions), engine=engine)
-    labels = [str(x) for x in identity.columns]
-    stem = f"{method}_identity_pcoa"
-    written = []
-    if "tsv" in formats:
-        written += [outdir / f"{stem}.tsv", outdir / f"{stem}_eigenvalues.tsv"]
-        written[-2].write_text(ordination_mod.coordinates_tsv(result, labels))
-        written[-1].write_text(ordination_mod.eigenvalues_tsv(result))
-    for ext in images:
-        written.append(outdir / f"{stem}.{ext}")
-        ordination_figure.draw_ordination(result, labels, f"{method} identity", written[-1])
-    logger.info("Wrote %d axes of %d genomes (%d iterations, shift %r) to %s", int(dimensions), n, result.info[1], result.info[2], outdir)
-    return written
-
-
-# ------------------------------------------------------------------ plot-run (pyani_plus/public_cli.py:1095-1136)
-# score, colour map, what a NaN cell counts as when the rows are clustered (pyani_plus/plot_run.py:320-325)
-_PLOT_SCORES = (("identity", "spbnd_BuRd", 0), ("query_cov", "BuRd", 0), ("hadamard", "viridis", 0), ("tANI", "viridis_r", -5))
-
-
-def _write_scatter_tables(logger, conn, run: Run, outdir: Path) -> list[Path]:
-    """``<method>_{query_cov,tANI}_scatter.tsv`` (pyani_plus/plot_run.py:231-293): identity, the y value and the query's
-    length of every comparison that has both, unrounded, in ``comparison_id`` order, numbers as Python's ``str``."""
-    method = run.configuration.method
-    lengths = dict(conn.execute("SELECT genome_hash, length FROM genomes"))
-    rows = [
-        (identity, cov_query, lengths[query])
-        for query, identity, cov_query in _select_run_comparisons(conn, run, "c.query_hash, c.identity, c.cov_query", "ORDER BY c.comparison_id")
-    ]
-    written = []
-    for caption, name in (("Query coverage", "query_cov"), ("tANI", "tANI")):
-        values = [(x, y, c) for x, y, c in rows if x is not None and y is not None]
-        if not values:
-            logger.warning("No valid identity, %s values from %s run", caption, method)
-            return written
-        logger.info("Plotting %d/%d %s vs identity %s comparisons", len(values), len(rows), caption, method)
-        if name == "tANI":
-            zeros = sum(1 for x, y, _c in values if x * y == 0)
-            if zeros:
-                # -log(0): the reference raises here and plots nothing more; this row is written with inf instead
-                logger.warning("%d %s comparisons have a zero Hadamard product: their tANI is written as inf", zeros, method)
-            values = [(x, -math.log(x * y) if x * y else math.inf, c) for x, y, c in values]
-        written.append(outdir / f"{method}_{name}_scatter.tsv")
-        with written[-1].open("w") as handle:
-            handle.write(f"#identity\t{name}\tquery_length\n")
-            for x, y, c in values:
-                handle.write(f"{x}\t{y}\t{c}\n")
-    return written
-
-
-def _run_label(genome, label: str) -> str:
-    """The label ``_relabelled`` gives a genome of the run."""
-    return {"md5": genome.genome_hash, "filename": genome.fasta_filename}.get(label) or filename_stem(genome.fasta_filename)
-
-
-def _write_scatter_figures(logger, method: str, frames: dict, lengths: np.ndarray, outdir: Path, formats: tuple[str, ...], bins: int,  # noqa: PLR0913
-                           engine, warned: int | None) -> list[Path]:
-    """The scatter figures of ``plot_run(scatter=True)`` and their tables (``pyani_plus_amd.scatter``), from the
-    relabelled identity, query coverage and Hadamard frames; ``lengths``: the query length of each row.  ``warned``: the
-    position of the score the scatter tables have already logged the no-valid-values warning for, or None."""
-    n = len(lengths)
-    cells = {name: np.ascontiguousarray(frames[name].to_numpy(dtype=float)) for name in ("identity", "query_cov")}
-    cells["tANI"] = -classify_mod.tani_scores(frames["hadamard"].to_numpy(dtype=float))  # -log(h) if h else nan
-    written: list[Path] = []
-    try:
-        if engine is not None:
-            cells = {name: engine.torch.from_numpy(np.ascontiguousarray(v)).to(engine.device) for name, v in cells.items()}  # uploaded once
-        for position, (caption, name) in enumerate((("Query coverage", "query_cov"), ("tANI", "tANI"))):
-            data = scatter_mod.describe(cells["identity"], cells[name], lengths, n, engine, bins, logger)
-            if data is None:
-                if warned != position:
-                    logger.warning("No valid identity, %s values from %s run", caption, method)
-                return written
-            if "tsv" in formats:
-                written.append(outdir / f"{method}_{name}_scatter_grid.tsv")
-                scatter_mod.write_grid_tsv(written[-1], data)
-                for axis, hist in (("x", data.x_hist), ("y", data.y_hist)):
-                    written.append(outdir / f"{method}_{name}_scatter_{axis}_hist.tsv")
-                    distribution_mod.write_hist_tsv(written[-1], hist)
-            for ext in formats:
-                if ext != "tsv":
-                    written.append(outdir / f"{method}_{name}_scatter.{ext}")
-                    scatter_figure.draw_scatter(data, caption, written[-1])
-    except HipBackendError as err:
-        sourmash_hip.backend_failure(logger, "plot-run scatter figures", err)
-    return written
-
-
-def plot_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", formats: tuple[str, ...] = ("tsv",),  # noqa: PLR0913
-             engine=None, logger: logging.Logger | None = None, distributions: bool = False, scatter: bool = False,
-             scatter_bins: int = scatter_mod.GRID) -> list[Path]:
-    """Write what the reference's ``plot-run`` computes for a complete run: the clustered heatmap tables
-    ``<method>_{identity,query_cov,hadamard,tANI}_heatmap.tsv`` and the scatter tables
-    ``<method>_{query_cov,tANI}_scatter.tsv``, byte for byte what the reference writes from the same database, with its
-    messages for a missing database, an incomplete run, duplicate stems, an unknown label, an all-NaN matrix and a
-    matrix with some NaNs.
-
-    Each matrix (the cached ``runs.df_*`` strings; tANI is ``-log(h) if h else nan`` of the relabelled Hadamard matrix)
-    is relabelled, sorted by label, and put into the leaf order of the average-linkage clustering of its rows with NaN
-    cells counted as 0 (tANI: -5): what seaborn's ``clustermap`` computes for the reference, restated by
-    ``pyani_plus_amd.cluster`` with the same bits.  Every matrix is clustered on its own.
-
-    ``formats``: ``tsv`` writes the tables; any other format (``png``, ``pdf``, ``svg``, ``jpg``) adds the heatmap figure
-    with its row dendrogram, drawn with matplotlib alone.  The reference's scatter figures are made with ``scatter``.
-    A comparison with a zero Hadamard product is written to the tANI scatter table as ``inf``, where the reference raises.
-
-    ``distributions``: also the score distribution of each matrix that is plotted (``pyani_plus_amd.distribution``):
-    with ``tsv`` the tables ``<method>_<score>_dist_hist.tsv`` (``#left TAB right TAB count``, the bins of
-    ``numpy.histogram(cells, "auto")``) and ``<method>_<score>_dist_kde.tsv`` (``#x TAB density``, scipy's
-    ``gaussian_kde`` on seaborn's 200-point grid; the header alone for fewer than two cells or cells that are all
-    equal), floats as ``repr``; with an image format the reference's ``<method>_<score>_dist.<ext>``, histogram, density
-    and rug.  The reference writes no table for a distribution: the two are this project's.  Off by default.
-
-    ``scatter``: also the reference's two scatter figures, identity against query coverage and against tANI
-    (``pyani_plus_amd.scatter``), after everything else and in that order.  The reference draws a marker per comparison,
-    coloured by the query's length, with automatic histograms on the margins; here the joint panel is a raster of
-    ``scatter_bins`` x ``scatter_bins`` cells (1 to 1024, 256 by default) over the ranges of the valid points, a cell in
-    the colour of the last point that falls into it, which is what overdrawn markers show.  The points are the cells of
-    the matrices above in row-major order (rows = query); a point is valid iff neither value is NaN, so a zero Hadamard
-    product (tANI NaN) drops out.  Two things are this project's choices: "last" is by that row-major order of the
-    label-sorted matrix, where the reference's is ``comparison_id`` order, and for runs that fit the cache the values are
-    the cached 10-decimal ones, as for the distributions.  With ``tsv``: ``<method>_<y>_scatter_grid.tsv``
-    (``#x_left x_right y_left y_right count query_length``, a line per non-empty cell, x-major) and the margins
-    ``<method>_<y>_scatter_x_hist.tsv`` and ``<method>_<y>_scatter_y_hist.tsv`` (as ``_dist_hist.tsv``); with an image
-    format the reference's ``<method>_<y>_scatter.<ext>``.  Without a valid point the reference's warning is logged and
-    neither this figure nor the next is made.  Off by default.
-
-    ``engine``: a ``HipEngine`` computes the row distances, the distributions and the scatter rasters on the GPU; None on
-    the host.  Returns the written paths."""
-    logger = logger or logging.getLogger("pyani_plus_amd")
-    if str(database) == ":memory:" or not Path(database).is_file():
-        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
-    formats = tuple(formats)
-    images = [ext for ext in formats if ext != "tsv"]
-    if images:
-        try:
-            importlib.import_module("matplotlib")
-        except ImportError:
-            sourmash_hip.log_sys_exit(logger, f"Image formats ({', '.join(images)}) need matplotlib, which cannot be imported; only tsv is available")
-    if scatter and not 1 <= int(scatter_bins) <= scatter_mod.MAX_BINS:
-        sourmash_hip.log_sys_exit(logger, f"--scatter-bins {scatter_bins}: expected 1 to {scatter_mod.MAX_BINS}")
-    outdir = Path(outdir)
-    if not outdir.is_dir():
-        logger.warning("Output directory %s does not exist, making it.", outdir)
-        outdir.mkdir()
-    conn, run = _open_run(logger, database, run_id, "Plotting")
-    run_id = run.run_id
-    n = len(run.fasta_hashes)
-    done = count_run_comparisons(conn, run)
-    if not n:
-        sourmash_hip.log_sys_exit(logger, f"Run-id {run_id} has no genomes")
-    if done != n * n:  # db_orm.load_run(check_complete=True)
-        sourmash_hip.log_sys_exit(logger, f"run-id {run_id} has {done} of {n}^2={n * n} comparisons, {n * n - done} needed")
-    method = run.configuration.method
-    frames = dict(zip(("identity", "query_cov", "hadamard"), _relabelled(logger, run, _score_frames(logger, conn, run), label)))
-    written = _write_scatter_tables(logger, conn, run, outdir) if "tsv" in formats else []
-    scatter_tables = len(written)
-    genome_lengths = dict(conn.execute("SELECT genome_hash, length FROM genomes")) if scatter else {}
-    conn.close()
-    for name, color_scheme, na_fill in _PLOT_SCORES:
-        if name == "tANI":
-            hadamard = frames["hadamard"]
-            matrix = hadamard.copy()
-            matrix.iloc[:, :] = -classify_mod.tani_scores(hadamard.to_numpy(dtype=float))  # -log(h) if h else nan; -log(1.0) is -0.0
-        else:
-            matrix = frames[name]
-        nulls = int(matrix.isna().to_numpy().sum())
-        if nulls == n * n:
-            logger.warning("Cannot plot %s as all NA", name)
-            continue
-        if nulls:
-            logger.warning("%s matrix contains %d nulls (out of %d\u00b2=%d %s comparisons)", name, nulls, n, n * n, method)
-        try:
-            tree, leaves = cluster_mod.cluster_tree(matrix.to_numpy(dtype=float), na_fill, engine)
-        except HipBackendError as err:
-            sourmash_hip.backend_failure(logger, f"plot-run clustering of {name}", err)
-        table = matrix.iloc[leaves, leaves]
-        for ext in formats:
-            written.append(outdir / f"{method}_{name}_heatmap.{ext}")
-            if ext == "tsv":
-                table.to_csv(written[-1], sep="\t")
-            else:
-                heatmap_figure.draw_heatmap(table, tree, leaves, name, color_scheme, written[-1])
-        if distributions:
-            try:
-                cells = np.ascontiguousarray(matrix.to_numpy(dtype=float))
-                values = engine.torch.from_numpy(cells).to(engine.device) if engine is not None else cells  # uploaded once
-                dist = distribution_mod.describe(values, engine, logger)
-                rug = distribution_mod.rug_counts(values, name, dist, engine) if images else None
-            except HipBackendError as err:
-                sourmash_hip.backend_failure(logger, f"plot-run distribution of {name}", err)
-            if "tsv" in formats:
-                written.append(outdir / f"{method}_{name}_dist_hist.tsv")
-                distribution_mod.write_hist_tsv(written[-1], dist)
-                written.append(outdir / f"{method}_{name}_dist_kde.tsv")
-                distribution_mod.write_kde_tsv(written[-1], dist)
-            for ext in images:
-                written.append(outdir / f"{method}_{name}_dist.{ext}")
-                distribution_figure.draw_distribution(dist, rug, name, written[-1])
-    if scatter:
-        by_label = {_run_label(a, label): genome_lengths[a.genome_hash] for a in run.fasta_hashes}
-        lengths = np.array([by_label[q] for q in frames["identity"].index], dtype=np.int64)
-        # the scatter tables have logged the warning for the first score they found no comparison for
-        warned = scatter_tables if "tsv" in formats else None
-        written += _write_scatter_figures(logger, method, frames, lengths, outdir, formats, int(scatter_bins), engine, warned)
-    logger.info("Wrote %d images to %s/%s_*.*", len(written), outdir, method)
-    return written
-
-
-# ------------------------------------------------------------------ plot-run-comp (pyani_plus/public_cli.py:1140-1208)
-_RUN_COMP_CHUNK = 1 << 16  # comparisons fetched from SQLite at a time
-
-
-def _run_comparison_columns(conn, run: Run) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """``(q, s, identity)`` of the run's comparisons in ``comparison_id`` order: uint32 positions of the query and the
-    subject in the TEMP table ``run_comp_ref`` (``run_comp.NONE`` for a genome that is not in it) and float64 identities
-    (NaN for NULL).  The hashes are turned into positions by SQLite and the rows become arrays a chunk at a time: no
-    Python dictionary is consulted per row and no list of all the rows is built."""
-    cursor = _select_run_comparisons(
-        conn, run,
-        "COALESCE((SELECT h.idx FROM temp.run_comp_ref h WHERE h.genome_hash = c.query_hash), -1), "
-        "COALESCE((SELECT h.idx FROM temp.run_comp_ref h WHERE h.genome_hash = c.subject_hash), -1), c.identity",
-        "ORDER BY c.comparison_id",
-    )  # fmt: skip
-    parts: list[tuple[np.ndarray, np.ndarray, np.ndarray]] = []
-    while rows := cursor.fetchmany(_RUN_COMP_CHUNK):
-        q, s, y = zip(*rows)
-        parts.append((np.array(q, dtype=np.int64).astype(np.uint32), np.array(s, dtype=np.int64).astype(np.uint32), np.array(y, dtype=np.float64)))
-    if not parts:
-        return np.empty(0, dtype=np.uint32), np.empty(0, dtype=np.uint32), np.empty(0, dtype=np.float64)
-    return tuple(np.concatenate(column) for column in zip(*parts))
-
-
-def plot_run_comp(database: Path | str, outdir: Path, run_ids, *, columns: int = 0, formats: tuple[str, ...] = ("tsv",),  # noqa: PLR0913
-                  engine=None, logger: logging.Logger | None = None) -> list[Path]:
-    """Compare the identities of runs of one database pair by pair, as the reference's ``plot-run-comp`` does: the first
-    of ``run_ids`` (a comma separated string, or integers) is the reference run, and for each further run the table
-    ``<method>_identity_<ref>_vs_<other>.tsv`` holds a line ``x TAB y`` for every ordered genome pair both runs have an
-    identity for (x the reference run's, y the other's, unrounded, under the header ``#<ref name> TAB <other name>``),
-    with the reference's messages.  The rows are in the order of the other run's ``comparison_id``, where the reference
-    leaves the order to the SQLite planner.  The runs need not be complete.
-
-    ``formats``: ``tsv`` writes the tables; any other format (``png``, ``pdf``, ``svg``, ``jpg``) adds
-    ``<method>_identity_<ref>_{scatter,diff}_vs_others.<ext>`` on the reference's grid (``columns`` panels a row, 0 for a
-    square tiling), drawn with matplotlib alone from the computed 30-bin histograms (``pyani_plus_amd.run_comp``).
-
-    ``engine``: a ``HipEngine`` joins the runs and takes the histograms on the GPU; None on the host, with the same
-    bytes.  Returns the written paths."""
-    logger = logger or logging.getLogger("pyani_plus_amd")
-    if str(database) == ":memory:" or not Path(database).is_file():
-        sourmash_hip.log_sys_exit(logger, f"Database {database} does not exist")
-    formats = tuple(formats)
-    images = [ext for ext in formats if ext != "tsv"]
-    if images:
-        try:
-            importlib.import_module("matplotlib")
-        except ImportError:
-            sourmash_hip.log_sys_exit(logger, f"Image formats ({', '.join(images)}) need matplotlib, which cannot be imported; only tsv is available")
-    outdir = Path(outdir)
-    if not outdir.is_dir():
-        logger.warning("Output directory %s does not exist, making it.", outdir)
-        outdir.mkdir()
-    try:
-        runs = [int(x) for x in (run_ids.split(",") if isinstance(run_ids, str) else run_ids)]
-    except (TypeError, ValueError):
-        sourmash_hip.log_sys_exit(logger, f"Expected comma separated list of runs, not: {run_ids}")
-    if len(runs) < 2:  # noqa: PLR2004
-        sourmash_hip.log_sys_exit(logger, "Need at least two runs for a comparison")
-    ref_id, other_ids = runs[0], runs[1:]
-    conn, ref_run = _open_run(logger, database, ref_id, "Plotting")
-    if not count_run_comparisons(conn, ref_run):
-        sourmash_hip.log_sys_exit(logger, f"Run {ref_id} has no comparisons")
-    method = ref_run.configuration.method
-    hashes = sorted(a.genome_hash for a in ref_run.fasta_hashes)
-    conn.execute("DROP TABLE IF EXISTS temp.run_comp_ref")
-    conn.execute("CREATE TEMP TABLE run_comp_ref (genome_hash VARCHAR NOT NULL PRIMARY KEY, idx INTEGER NOT NULL)")
-    conn.executemany("INSERT INTO temp.run_comp_ref VALUES (?, ?)", zip(hashes, range(len(hashes))))
-    q, s, y = _run_comparison_columns(conn, ref_run)
-    ref = np.full((len(hashes), len(hashes)), np.nan)
-    ref[q, s] = y  # (query, subject) is unique under one configuration
-    del q, s, y
-    logger.info("Plotting %d runs against %s run %d which has %d comparisons", len(other_ids), method, ref_id, int(np.count_nonzero(~np.isnan(ref))))
-    written: list[Path] = []
-    comparisons, other_names = [], []
-    try:
-        ref_values = engine.torch.from_numpy(ref).to(engine.device) if engine is not None else ref  # uploaded once
-        x_hist = run_comp_mod.range_and_counts(ref_values, engine)
-        for other_id in other_ids:
-            try:
-                other = load_run(conn, other_id)
-            except ValueError:
-                sourmash_hip.log_sys_exit(logger, f"Database {database} has no run-id {other_id}.")
-            comp = run_comp_mod.compare(ref_values, *_run_comparison_columns(conn, other), engine, x_hist=x_hist)
-            if not len(comp.x):
-                sourmash_hip.log_sys_exit(logger, f"Runs {ref_id} and {other_id} have no comparisons in common")
-            logger.info("Plotting %s run %d vs %s run %d, with %d comparisons in common", other.configuration.method, other_id, method, ref_id, len(comp.x))
-            if "tsv" in formats:
-                written.append(outdir / f"{method}_identity_{ref_id}_vs_{other_id}.tsv")
-                run_comp_mod.write_pairs_tsv(written[-1], f"#{ref_run.name}\t{other.name}", comp.x, comp.y)
-            if images:  # the figures need every run's values at once; the tables do not
-                comparisons.append(comp)
-                other_names.append(other.name)
-    except HipBackendError as err:
-        sourmash_hip.backend_failure(logger, "plot-run-comp", err)
-    finally:
-        conn.close()
-    for mode in ("scatter", "diff"):
-        for ext in images:
-            written.append(outdir / f"{method}_identity_{ref_id}_{mode}_vs_others.{ext}")
-            run_comp_figure.draw_comparison(mode, ref_run.name, other_names, comparisons, written[-1], columns)
-    logger.info("Wrote %d images to %s/%s_identity_%d_vs_*.*", 2 * len(images), outdir, method, ref_id)
-    return written
-
-
 # ------------------------------------------------------------------ the driver as a process
+_LABEL_OPTION = dict(choices=("md5", "filename", "stem"), default="stem")  # noqa: C408  every ``--label``
+_MISSING_OPTION = ("--missing", {"type": float, "default": 1.0, "help": "distance of a pair with no identity in either direction (default 1.0)"})
+
+
+def _device_option(p, what: str) -> None:
+    p.add_argument("--device", type=int, default=None, help=f"{what} on this GPU (default: on the host)")
+
+
+def _report_parser(sub, name: str, help_: str, *, run_id: bool = True, label: bool = True, own=(), formats=None, more=(), device=None) -> None:  # noqa: PLR0913
+    """The subparser of a report command, its options in the order ``--help`` lists them: database, output directory,
+    ``--run-id``, ``--label``, its ``own`` options (pairs of a flag and ``add_argument``'s keywords), ``--formats`` (given
+    as what ``tsv`` and what an image format write), ``more`` of its own, ``--device`` (given as what then runs on the GPU)."""
+    p = sub.add_parser(name, help=help_)
+    p.add_argument("--database", "-d", required=True, type=Path)
+    p.add_argument("--outdir", "-o", required=True, type=Path)
+    if run_id:
+        p.add_argument("--run-id", type=int, default=None)
+    if label:
+        p.add_argument("--label", **_LABEL_OPTION)
+    for flag, keywords in own:
+        p.add_argument(flag, **keywords)
+    if formats:
+        p.add_argument("--formats", type=lambda text: tuple(f for f in text.split(",") if f), default="tsv",
+                       help=f"comma separated: tsv for {formats[0]}, png, pdf, svg or jpg for {formats[1]} (matplotlib)")  # fmt: skip
+    for flag, keywords in more:
+        p.add_argument(flag, **keywords)
+    if device:
+        _device_option(p, device)
+    p.add_argument("--verbose", "-v", action="store_true")
+
+
+@contextlib.contextmanager
+def _device_engine(device: int | None):
+    """A ``HipEngine`` on GPU ``device`` (None: none), closed on the way out."""
+    engine = None if device is None else HipEngine(device)
+    try:
+        yield engine
+    finally:
+        if engine is not None:
+            engine.close()
+
+
+_COMMANDS = {  # subcommand -> its call from (the parsed arguments, the engine of ``--device`` or None, the logger)
+    "sourmash": lambda a, _engine, logger: run_sourmash_hip(a.fasta, a.database, cache=a.cache, name=a.name, kmersize=a.kmersize, scaled=a.scaled,
+                                                            temp=a.temp, logger=logger, ingest=a.ingest, gpus=a.gpus, engine_factory=a.engine_factory),
+    "fastani": lambda a, _engine, logger: run_fastani_hip(a.fasta, a.database, name=a.name, kmersize=a.kmersize, fragsize=a.fragsize, minmatch=a.minmatch, temp=a.temp,
+                                                          logger=logger, ingest=a.ingest, gpus=a.gpus, engine_factory=a.engine_factory, query_batch=a.query_batch),
+    "external-alignment": lambda a, _engine, logger: run_external_alignment_hip(a.fasta, a.database, alignment=a.alignment, label=a.label, name=a.name,
+                                                                                temp=a.temp, logger=logger, gpus=a.gpus),
+    "tetra": lambda a, engine, logger: run_tetra_hip(a.fasta, a.database, cache=a.cache, name=a.name, temp=a.temp, logger=logger, engine=engine, gpus=a.gpus),
+    "resume": lambda a, _engine, logger: resume(a.database, run_id=a.run_id, cache=a.cache, temp=a.temp, logger=logger, ingest=a.ingest, gpus=a.gpus,
+                                                engine_factory=a.engine_factory),
+    "export-run": lambda a, _engine, logger: export_run(a.database, a.outdir, run_id=a.run_id, label=a.label, logger=logger),
+    "classify": lambda a, engine, logger: classify(a.database, a.outdir, run_id=a.run_id, label=a.label, coverage_edges=a.coverage_edges,
+                                                   score_edges=a.score_edges, cov_min=a.cov_min, mode=a.mode, engine=engine, logger=logger),
+    "plot-run": lambda a, engine, logger: plot_run(a.database, a.outdir, run_id=a.run_id, label=a.label, formats=a.formats, engine=engine, logger=logger,
+                                                   distributions=a.distributions, scatter=a.scatter, scatter_bins=a.scatter_bins),
+    "plot-run-comp": lambda a, engine, logger: plot_run_comp(a.database, a.outdir, a.run_ids, columns=a.columns, formats=a.formats, engine=engine, logger=logger),
+    "tree-run": lambda a, engine, logger: tree_run(a.database, a.outdir, run_id=a.run_id, label=a.label, method=a.method, missing=a.missing, engine=engine,
+                                                   logger=logger),
+    "ordinate-run": lambda a, engine, logger: ordinate_run(a.database, a.outdir, run_id=a.run_id, label=a.label, dimensions=a.dimensions, missing=a.missing,
+                                                           formats=a.formats, engine=engine, logger=logger),
+}  # fmt: skip
+
+
 def main(argv: list[str] | None = None) -> int:
     """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run,ordinate-run} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
@@ -1906,135 +938,48 @@ def main(argv: list[str] | None = None) -> int:
     p_x = sub.add_parser("external-alignment", help="FASTA directory + its MSA -> all N^2 external-alignment-hip comparisons")
     common(p_x, run_options=True)
     p_x.add_argument("--alignment", required=True, type=Path, help="FASTA MSA of the genomes, one row per genome")
-    p_x.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
+    p_x.add_argument("--label", **_LABEL_OPTION)
     p_t = sub.add_parser("tetra", help="FASTA directory -> all N^2 TETRA-hip comparisons (tetranucleotide Z-score correlations)")
     common(p_t, run_options=True)
     p_t.add_argument("--cache", type=Path, default=None)
-    p_t.add_argument("--device", type=int, default=None, help="count and correlate on this GPU (default: on the host)")
+    _device_option(p_t, "count and correlate")
     p_r = sub.add_parser("resume", help="complete a partial run")
     common(p_r, run_options=False)
     p_r.add_argument("--run-id", type=int, default=None)
     p_r.add_argument("--cache", type=Path, default=None)
-    p_e = sub.add_parser("export-run", help="long form and matrices of a run as TSV files")
-    p_e.add_argument("--database", "-d", required=True, type=Path)
-    p_e.add_argument("--outdir", "-o", required=True, type=Path)
-    p_e.add_argument("--run-id", type=int, default=None)
-    p_e.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
-    p_e.add_argument("--verbose", "-v", action="store_true")
-    p_c = sub.add_parser("classify", help="the genome cliques of a complete run as <method>_classify.tsv")
-    p_c.add_argument("--database", "-d", required=True, type=Path)
-    p_c.add_argument("--outdir", "-o", required=True, type=Path)
-    p_c.add_argument("--run-id", type=int, default=None)
-    p_c.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
-    p_c.add_argument("--coverage-edges", choices=classify_mod.AGG_NAMES, default="min")
-    p_c.add_argument("--score-edges", choices=classify_mod.AGG_NAMES, default="mean")
-    p_c.add_argument("--cov-min", type=float, default=classify_mod.MIN_COVERAGE)
-    p_c.add_argument("--mode", choices=classify_mod.MODES, default="identity")
-    p_c.add_argument("--device", type=int, default=None, help="build and sort the edge list on this GPU (default: on the host)")
-    p_c.add_argument("--verbose", "-v", action="store_true")
-    p_p = sub.add_parser("plot-run", help="the clustered heatmap tables and the scatter tables of a complete run")
-    p_p.add_argument("--database", "-d", required=True, type=Path)
-    p_p.add_argument("--outdir", "-o", required=True, type=Path)
-    p_p.add_argument("--run-id", type=int, default=None)
-    p_p.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
-    p_p.add_argument("--formats", default="tsv", help="comma separated: tsv for the tables, png, pdf, svg or jpg for the heatmap figures (matplotlib)")
-    p_p.add_argument("--distributions", action="store_true", help="also each score's distribution: histogram and density tables, and the figure with an image format")
-    p_p.add_argument("--scatter", action="store_true", help="also the two scatter figures (identity against query coverage and tANI) as rasters: their grid and margin tables, and the figure with an image format")
-    p_p.add_argument("--scatter-bins", type=int, default=scatter_mod.GRID, help="cells per axis of a scatter figure's raster, 1 to 1024 (default 256)")
-    p_p.add_argument("--device", type=int, default=None, help="compute the row distances, the distributions and the scatter rasters on this GPU (default: on the host)")
-    p_p.add_argument("--verbose", "-v", action="store_true")
-    p_pc = sub.add_parser("plot-run-comp", help="the identities of further runs against a reference run's, pair by pair")
-    p_pc.add_argument("--database", "-d", required=True, type=Path)
-    p_pc.add_argument("--outdir", "-o", required=True, type=Path)
-    p_pc.add_argument("--run-ids", required=True, help="comma separated list of runs, the reference run first")
-    p_pc.add_argument("--columns", type=int, default=0, help="panels per row of the figures (default 0: a square tiling)")
-    p_pc.add_argument("--formats", default="tsv", help="comma separated: tsv for the tables, png, pdf, svg or jpg for the two figures (matplotlib)")
-    p_pc.add_argument("--device", type=int, default=None, help="join the runs and take the histograms on this GPU (default: on the host)")
-    p_pc.add_argument("--verbose", "-v", action="store_true")
-    p_tr = sub.add_parser("tree-run", help="the neighbour-joining or UPGMA tree of a complete run as <method>_identity_<nj|upgma>.nwk")
-    p_tr.add_argument("--database", "-d", required=True, type=Path)
-    p_tr.add_argument("--outdir", "-o", required=True, type=Path)
-    p_tr.add_argument("--run-id", type=int, default=None)
-    p_tr.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
-    p_tr.add_argument("--method", choices=tree_mod.METHODS, default="nj")
-    p_tr.add_argument("--missing", type=float, default=1.0, help="distance of a pair with no identity in either direction (default 1.0)")
-    p_tr.add_argument("--device", type=int, default=None, help="make the joins of neighbour joining on this GPU (default: on the host)")
-    p_tr.add_argument("--verbose", "-v", action="store_true")
-    p_or = sub.add_parser("ordinate-run", help="the principal coordinates of a complete run as <method>_identity_pcoa.tsv and its eigenvalue table")
-    p_or.add_argument("--database", "-d", required=True, type=Path)
-    p_or.add_argument("--outdir", "-o", required=True, type=Path)
-    p_or.add_argument("--run-id", type=int, default=None)
-    p_or.add_argument("--label", choices=("md5", "filename", "stem"), default="stem")
-    p_or.add_argument("--dimensions", type=int, default=3, help="principal axes to compute (default 3)")
-    p_or.add_argument("--missing", type=float, default=1.0, help="distance of a pair with no identity in either direction (default 1.0)")
-    p_or.add_argument("--formats", default="tsv", help="comma separated: tsv for the two tables, png, pdf, svg or jpg for the figure (matplotlib)")
-    p_or.add_argument("--device", type=int, default=None, help="centre the matrix and do the solver's products on this GPU (default: on the host)")
-    p_or.add_argument("--verbose", "-v", action="store_true")
+    _report_parser(sub, "export-run", "long form and matrices of a run as TSV files")
+    _report_parser(sub, "classify", "the genome cliques of a complete run as <method>_classify.tsv", device="build and sort the edge list", own=(
+        ("--coverage-edges", {"choices": classify_mod.AGG_NAMES, "default": "min"}),
+        ("--score-edges", {"choices": classify_mod.AGG_NAMES, "default": "mean"}),
+        ("--cov-min", {"type": float, "default": classify_mod.MIN_COVERAGE}),
+        ("--mode", {"choices": classify_mod.MODES, "default": "identity"}),
+    ))  # fmt: skip
+    _report_parser(sub, "plot-run", "the clustered heatmap tables and the scatter tables of a complete run", formats=("the tables", "the heatmap figures"),
+                   device="compute the row distances, the distributions and the scatter rasters", more=(
+        ("--distributions", {"action": "store_true", "help": "also each score's distribution: histogram and density tables, and the figure with an image format"}),
+        ("--scatter", {"action": "store_true", "help": "also the two scatter figures (identity against query coverage and tANI) as rasters: their grid and margin tables, and the figure with an image format"}),
+        ("--scatter-bins", {"type": int, "default": scatter_mod.GRID, "help": "cells per axis of a scatter figure's raster, 1 to 1024 (default 256)"}),
+    ))  # fmt: skip
+    _report_parser(sub, "plot-run-comp", "the identities of further runs against a reference run's, pair by pair", run_id=False, label=False,
+                   formats=("the tables", "the two figures"), device="join the runs and take the histograms", own=(
+        ("--run-ids", {"required": True, "help": "comma separated list of runs, the reference run first"}),
+        ("--columns", {"type": int, "default": 0, "help": "panels per row of the figures (default 0: a square tiling)"}),
+    ))  # fmt: skip
+    _report_parser(sub, "tree-run", "the neighbour-joining or UPGMA tree of a complete run as <method>_identity_<nj|upgma>.nwk",
+                   device="make the joins of neighbour joining", own=(("--method", {"choices": tree_mod.METHODS, "default": "nj"}), _MISSING_OPTION))
+    _report_parser(sub, "ordinate-run", "the principal coordinates of a complete run as <method>_identity_pcoa.tsv and its eigenvalue table",
+                   formats=("the two tables", "the figure"), device="centre the matrix and do the solver's products",
+                   own=(("--dimensions", {"type": int, "default": 3, "help": "principal axes to compute (default 3)"}), _MISSING_OPTION))
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
     logger = logging.getLogger("pyani_plus_amd")
-    with launch.signals_as_interrupt():
-        if args.command == "sourmash":
-            run = run_sourmash_hip(args.fasta, args.database, cache=args.cache, name=args.name, kmersize=args.kmersize, scaled=args.scaled,
-                                   temp=args.temp, logger=logger, ingest=args.ingest, gpus=args.gpus, engine_factory=args.engine_factory)
-        elif args.command == "fastani":
-            run = run_fastani_hip(args.fasta, args.database, name=args.name, kmersize=args.kmersize, fragsize=args.fragsize,
-                                  minmatch=args.minmatch, temp=args.temp, logger=logger, ingest=args.ingest, gpus=args.gpus,
-                                  engine_factory=args.engine_factory, query_batch=args.query_batch)
-        elif args.command == "external-alignment":
-            run = run_external_alignment_hip(args.fasta, args.database, alignment=args.alignment, label=args.label, name=args.name,
-                                             temp=args.temp, logger=logger, gpus=args.gpus)
-        elif args.command == "tetra":
-            engine = None
-            if args.device is not None:
-                from .engine import HipEngine
-
-                engine = HipEngine(args.device)
-            try:
-                run = run_tetra_hip(args.fasta, args.database, cache=args.cache, name=args.name, temp=args.temp, logger=logger, engine=engine,
-                                    gpus=args.gpus)
-            finally:
-                if engine is not None:
-                    engine.close()
-        elif args.command == "resume":
-            run = resume(args.database, run_id=args.run_id, cache=args.cache, temp=args.temp, logger=logger, ingest=args.ingest,
-                         gpus=args.gpus, engine_factory=args.engine_factory)
-        elif args.command in {"classify", "plot-run", "plot-run-comp", "tree-run", "ordinate-run"}:
-            engine = None
-            if args.device is not None:
-                from .engine import HipEngine
-
-                engine = HipEngine(args.device)
-            try:
-                if args.command == "classify":
-                    print(classify(args.database, args.outdir, run_id=args.run_id, label=args.label, coverage_edges=args.coverage_edges,
-                                   score_edges=args.score_edges, cov_min=args.cov_min, mode=args.mode, engine=engine, logger=logger))
-                elif args.command == "tree-run":
-                    print(tree_run(args.database, args.outdir, run_id=args.run_id, label=args.label, method=args.method, missing=args.missing,
-                                   engine=engine, logger=logger))
-                elif args.command == "ordinate-run":
-                    formats = tuple(f for f in args.formats.split(",") if f)
-                    for path in ordinate_run(args.database, args.outdir, run_id=args.run_id, label=args.label, dimensions=args.dimensions,
-                                             missing=args.missing, formats=formats, engine=engine, logger=logger):
-                        print(path)
-                elif args.command == "plot-run-comp":
-                    formats = tuple(f for f in args.formats.split(",") if f)
-                    for path in plot_run_comp(args.database, args.outdir, args.run_ids, columns=args.columns, formats=formats, engine=engine, logger=logger):
-                        print(path)
-                else:
-                    formats = tuple(f for f in args.formats.split(",") if f)
-                    for path in plot_run(args.database, args.outdir, run_id=args.run_id, label=args.label, formats=formats, engine=engine, logger=logger,
-                                         distributions=args.distributions, scatter=args.scatter, scatter_bins=args.scatter_bins):
-                        print(path)
-            finally:
-                if engine is not None:
-                    engine.close()
-            return 0
-        else:
-            for path in export_run(args.database, args.outdir, run_id=args.run_id, label=args.label, logger=logger):
+    with launch.signals_as_interrupt(), _device_engine(getattr(args, "device", None)) as engine:
+        result = _COMMANDS[args.command](args, engine, logger)
+        if isinstance(result, Run):
+            logger.info("run-id %d: %s", result.run_id, result.status)
+        else:  # a report: the path it wrote, or the paths
+            for path in [result] if isinstance(result, Path) else result:
                 print(path)
-            return 0
-    logger.info("run-id %d: %s", run.run_id, run.status)
     return 0
 
 

@@ -39,7 +39,7 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
-from pyani_plus_amd import run_comp, rundb  # noqa: E402
+from pyani_plus_amd import reports, run_comp, rundb  # noqa: E402
 
 SEED = 41
 NULLS = 0.02
@@ -175,7 +175,7 @@ def phase_times(n: int, engine, repeat: int) -> dict:
         hashes = sorted(a.genome_hash for a in runs[0].fasta_hashes)
         conn.execute("CREATE TEMP TABLE run_comp_ref (genome_hash VARCHAR NOT NULL PRIMARY KEY, idx INTEGER NOT NULL)")
         conn.executemany("INSERT INTO temp.run_comp_ref VALUES (?, ?)", zip(hashes, range(n)))
-        out["sqlite_read_both_runs_s"], columns = timed(lambda: [rundb._run_comparison_columns(conn, run) for run in runs], repeat, 1)  # noqa: SLF001
+        out["sqlite_read_both_runs_s"], columns = timed(lambda: [reports._run_comparison_columns(conn, run) for run in runs], repeat, 1)  # noqa: SLF001
         conn.close()
         (rq, rs, ry), (oq, os_, oy) = columns
         matrix = np.full((n, n), np.nan)
