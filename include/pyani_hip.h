@@ -823,6 +823,25 @@ PA_API int pa_prof_reset(pa_ctx *ctx);
 /* total milliseconds and number of timed launches of a phase (syncs the stream) */
 PA_API int pa_prof_get(pa_ctx *ctx, int phase, double *total_ms, uint64_t *launches);
 
+/* ---- probes of the internal device primitives: libpyani_hip_tools.so (-DPA_TOOLS) only ----
+ * Not part of the ABI (PA_ABI_VERSION does not count them) and absent from libpyani_hip.so: they let
+ * tests/test_gpu_sort_scan.py call the radix sort and the exclusive scan of radix_sort.hip -- the one object both
+ * libraries link -- directly, on the context's stream, without waiting for it.
+ *   pa_tool_radix_sort_pairs   stable LSD radix sort of n (u64 key, u32 value) pairs on bits [bit_lo, bit_hi) of the
+ *        key, or of the value with by_val != 0.  keys0/keys1 and vals0/vals1 are the two halves of the double
+ *        buffers, n elements each; *which (0 or 1) names the half that holds the input on entry and the result on
+ *        return.  bit_lo >= 0, bit_hi - bit_lo a multiple of 8, bit_hi <= 64 (<= 32 with by_val): anything else is
+ *        PA_E_INVALID before a launch.  n <= 1 or bit_hi <= bit_lo: nothing is touched.
+ *   pa_tool_exclusive_scan_u32 d_out[i] = (d_in[0] + ... + d_in[i - 1]) mod 2^32; d_out may be d_in.  The exact
+ *        64-bit sum of all n values goes to *d_total_u64 where that is not null (0 for n = 0). */
+#ifdef PA_TOOLS
+#define PA_TOOL_API __attribute__((visibility("default")))
+PA_TOOL_API int pa_tool_radix_sort_pairs(pa_ctx *ctx, uint64_t *d_keys0, uint64_t *d_keys1, uint32_t *d_vals0,
+                                         uint32_t *d_vals1, uint64_t n, int bit_lo, int bit_hi, int by_val, int *which);
+PA_TOOL_API int pa_tool_exclusive_scan_u32(pa_ctx *ctx, const uint32_t *d_in, uint32_t *d_out, uint64_t n,
+                                           uint64_t *d_total_u64);
+#endif
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,13 @@ SIGNATURES: dict[str, tuple] = {
     "pa_prof_get": (C.c_int, [_vp, C.c_int, _f64p, _u64p]),
 }
 
+# The probes of the internal radix sort and exclusive scan (csrc/radix_sort.hip): libpyani_hip_tools.so alone exports
+# them, for tests/test_gpu_sort_scan.py; load_library(tools=True) types them as well.  Not part of the ABI version.
+TOOL_SIGNATURES: dict[str, tuple] = {
+    "pa_tool_radix_sort_pairs": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "pa_tool_exclusive_scan_u32": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp]),
+}
+
 
 class HipBackendError(RuntimeError):
     """The HIP extension is missing, failed to load, or a call into it failed."""
@@ -240,7 +247,7 @@ def build_library(force: bool = False) -> Path:
 
 
 def load_library(tools: bool = False) -> C.CDLL:
-    """Load the shared library (``tools``: the -DPA_TOOLS build) and type every symbol of the header; raise loudly if absent."""
+    """Load the shared library (``tools``: the -DPA_TOOLS build, with its probes) and type every symbol of the header; raise loudly if absent."""
     if tools in _libs:
         return _libs[tools]
     path = TOOLS_LIB_PATH if tools else LIB_PATH
@@ -260,7 +267,7 @@ def load_library(tools: bool = False) -> C.CDLL:
         lib = C.CDLL(str(path))
     except OSError as err:  # missing ROCm runtime, wrong arch, ...
         raise HipBackendError(f"cannot load {path}: {err}") from err
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **(TOOL_SIGNATURES if tools else {})}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as err:

@@ -382,4 +382,27 @@ int pa_prof_get(pa_ctx *c, int phase, double *total_ms, uint64_t *launches) {
   return PA_OK;
 }
 
+#ifdef PA_TOOLS
+// ---- probes of the device primitives (tests/test_gpu_sort_scan.py) ---------------
+// The argument checks of an entry point, then the primitive of radix_sort.hip itself on c->stream.
+int pa_tool_radix_sort_pairs(pa_ctx *c, uint64_t *d_keys0, uint64_t *d_keys1, uint32_t *d_vals0, uint32_t *d_vals1, uint64_t n, int bit_lo,
+                             int bit_hi, int by_val, int *which) {
+  PA_REQUIRE(c != nullptr && which != nullptr, "pa_tool_radix_sort_pairs: null context or which");
+  PA_REQUIRE(*which == 0 || *which == 1, "pa_tool_radix_sort_pairs: *which is %d, not 0 or 1", *which);
+  PA_REQUIRE(n == 0 || (d_keys0 && d_keys1 && d_vals0 && d_vals1), "pa_tool_radix_sort_pairs: null buffer for %llu elements",
+             (unsigned long long)n);
+  PA_HIP(hipSetDevice(c->device));
+  uint64_t *keys[2] = {d_keys0, d_keys1};
+  uint32_t *vals[2] = {d_vals0, d_vals1};
+  return pa_radix_sort_pairs(c, keys, vals, n, bit_lo, bit_hi, by_val != 0, which);
+}
+
+int pa_tool_exclusive_scan_u32(pa_ctx *c, const uint32_t *d_in, uint32_t *d_out, uint64_t n, uint64_t *d_total_u64) {
+  PA_REQUIRE(c != nullptr, "null context");
+  PA_REQUIRE(n == 0 || (d_in && d_out), "pa_tool_exclusive_scan_u32: null buffer for %llu values", (unsigned long long)n);
+  PA_HIP(hipSetDevice(c->device));
+  return pa_exclusive_scan_u32(c, d_in, d_out, n, d_total_u64);
+}
+#endif
+
 }  // extern "C"

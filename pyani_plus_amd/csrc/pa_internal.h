@@ -310,8 +310,10 @@ int pa_launch(pa_ctx *c, const char *name, void (*kernel)(Params...), bool raise
 // ---- device primitives implemented in the .hip files -----------------------
 // radix_sort.hip
 // Stable LSD radix sort of (u64 key, u32 val) pairs on bits [bit_lo, bit_hi) of the key
-// (or of the value when by_val).  keys/vals are double buffers: *which says which one holds
-// the input on entry and the result on return.
+// (or of the value when by_val), in passes of one whole 8-bit digit: bit_lo >= 0, bit_hi - bit_lo
+// a multiple of 8, bit_hi <= 64 (<= 32 when by_val); anything else is PA_E_INVALID before a launch.
+// keys/vals are double buffers: *which says which one holds the input on entry and the result
+// on return.  n <= 1 or bit_hi <= bit_lo: nothing to do, nothing is touched.
 int pa_radix_sort_pairs(pa_ctx *c, uint64_t *keys[2], uint32_t *vals[2], uint64_t n, int bit_lo,
                         int bit_hi, bool by_val, int *which);
 // Exclusive prefix sums of n u32 values, themselves u32: they wrap past 2^32.  The total is

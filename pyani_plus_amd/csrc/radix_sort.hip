@@ -13,6 +13,7 @@
 // wavefront multi-split: 8 ballots build the mask of lanes holding the same
 // digit, popcounts below the lane give the in-wave rank, and a per-wave LDS
 // counter row carries the running count from one 64-element row to the next.
+#include "block_reduce_dev.h"
 #include "pa_internal.h"
 
 namespace {
@@ -191,20 +192,27 @@ __global__ __launch_bounds__(kScanThreads) void scan_tile_sums_kernel(const uint
   if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
 }
 
-// single workgroup: exclusive scan of m values in place (u32), total (u64) out
+// single workgroup: exclusive scan of m values in place (u32, wrapping), total (u64, exact) out.  The prefixes and the
+// carry from one round of 256 values to the next are 32-bit like the scan's outputs; the total does not come from
+// them: every thread adds the values it reads in 64 bits, and one 64-bit reduction after the last round adds those up.
 __global__ __launch_bounds__(kScanThreads) void scan_sums_kernel(uint32_t *__restrict__ sums, uint32_t m,
                                                                  unsigned long long *__restrict__ total_out) {
   __shared__ uint32_t s_w[kScanThreads / 64];
-  uint64_t carry = 0;
+  __shared__ uint64_t s_total[kScanThreads];
+  uint32_t carry = 0;
+  uint64_t mine = 0;
   for (uint32_t base = 0; base < m; base += kScanThreads) {
     const uint32_t i = base + threadIdx.x;
     const uint32_t v = i < m ? sums[i] : 0u;
     uint32_t tot;
     const uint32_t ex = block_excl_scan(v, s_w, &tot);
-    if (i < m) sums[i] = (uint32_t)(carry + ex);
+    if (i < m) sums[i] = carry + ex;
     carry += tot;
+    mine += v;
   }
-  if (threadIdx.x == 0 && total_out) *total_out = carry;
+  if (!total_out) return;  // uniform: a kernel argument
+  const uint64_t total = pa_dev::block_reduce<kScanThreads>(mine, s_total, [](uint64_t a, uint64_t b) { return a + b; });
+  if (threadIdx.x == 0) *total_out = total;
 }
 
 __global__ __launch_bounds__(kScanThreads) void scan_apply_kernel(const uint32_t *__restrict__ in,
@@ -246,6 +254,11 @@ int pa_exclusive_scan_u32(pa_ctx *c, const uint32_t *d_in, uint32_t *d_out, uint
 int pa_radix_sort_pairs(pa_ctx *c, uint64_t *keys[2], uint32_t *vals[2], uint64_t n, int bit_lo, int bit_hi,
                         bool by_val, int *which) {
   if (n <= 1 || bit_hi <= bit_lo) return PA_OK;
+  // a pass takes a whole 8-bit digit at its shift: a narrower last digit would order by bits above bit_hi as well
+  PA_REQUIRE(bit_lo >= 0, "radix sort: bit_lo %d is negative", bit_lo);
+  PA_REQUIRE((bit_hi - bit_lo) % 8 == 0, "radix sort: bits [%d, %d) are not whole 8-bit digits", bit_lo, bit_hi);
+  PA_REQUIRE(bit_hi <= (by_val ? 32 : 64), "radix sort: bit_hi %d is beyond the %d bits of a %s", bit_hi, by_val ? 32 : 64,
+             by_val ? "value" : "key");
   PA_REQUIRE(n < (1ULL << 32), "radix sort: %llu elements exceed the 32-bit index space", (unsigned long long)n);
   const uint32_t tiles = (uint32_t)ceil_div(n, kTile);  // n < 2^32
   const uint64_t hist_n = (uint64_t)kRadix * tiles;

@@ -73,6 +73,30 @@ def test_tool_switches_are_not_in_the_product_library():
                 os.environ[n] = v
 
 
+def test_primitive_probes_are_in_the_tools_library_only():
+    """``pa_tool_radix_sort_pairs`` and ``pa_tool_exclusive_scan_u32`` (tests/test_gpu_sort_scan.py calls the device
+    primitives through them) are exported by ``libpyani_hip_tools.so`` alone: the product library does not hold their names,
+    the header's ``PA_API`` surface and the ABI version do not count them."""
+    assert set(_capi.TOOL_SIGNATURES) == {"pa_tool_radix_sort_pairs", "pa_tool_exclusive_scan_u32"}
+    assert not set(_capi.TOOL_SIGNATURES) & set(_capi.SIGNATURES)
+    product, tools = _capi.LIB_PATH.read_bytes(), _capi.TOOLS_LIB_PATH.read_bytes()
+    assert b"pa_tool_" not in product
+    for name in _capi.TOOL_SIGNATURES:
+        assert name.encode() in tools, name
+    product_lib, tools_lib = _capi.load_library(), _capi.load_library(tools=True)
+    for name, (restype, argtypes) in _capi.TOOL_SIGNATURES.items():
+        fn = getattr(tools_lib, name)  # AttributeError if the symbol does not resolve
+        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
+        assert not hasattr(product_lib, name), name
+    assert product_lib.pa_abi_version() == tools_lib.pa_abi_version() == _capi.ABI_VERSION == 5
+    # the header declares them, for the tools build only and outside the PA_API lines the product is matched against
+    header = (ROOT / "include" / "pyani_hip.h").read_text()
+    for name in _capi.TOOL_SIGNATURES:
+        assert re.search(rf"^PA_TOOL_API int {name}\(", header, flags=re.M), name
+        assert not re.search(rf"^PA_API [^;]*\b{name}\(", header, flags=re.M), name
+    assert header.index("#ifdef PA_TOOLS") < header.index("PA_TOOL_API int pa_tool_")
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
 
