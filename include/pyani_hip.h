@@ -799,6 +799,50 @@ PA_API int pa_symm_top_eigs(pa_ctx *ctx, const double *d_B, uint32_t n, uint32_t
 PA_API int pa_symm_top_eigs_host(const double *h_B, uint32_t n, uint32_t k, double tol, uint32_t max_iter, double fro2, double *h_values,
                                  double *h_vectors, double *h_residuals, double *h_info, uint32_t n_threads);
 
+/* ---- mantel-run-comp: Mantel's permutation test between two distance matrices ----
+ * Replaces nothing in the reference: pyani-plus compares runs with figures only.  The definitions below are this
+ * project's own contract, pinned by an independent restatement in tests/mantel_cases.py.  DESIGN.md section 7j.  Every
+ * step is one IEEE double operation (no FMA), no floating-point atomics: pa_mantel gives the same bits run to run and the
+ * same bits as pa_mantel_host, whose result does not depend on n_threads (0: as many as the process may use); neither
+ * depends on how the permutations are batched or on how many a call brings.  mantel_rule.h states the constants and
+ * formulas once for both.
+ *
+ *   Inputs.  X and Y are n x n f64 row-major, each as for pa_nj: finite, >= 0, bitwise symmetric, zero diagonal;
+ *        3 <= n <= PA_MANTEL_MAX_N (a row of 128 KB, which the device holds in the LDS of one CU; the host twin has the
+ *        same limit).  h_perms is n_perms x n u32, every row a permutation of 0 .. n - 1: row q pairs row i of X with
+ *        row h_perms[q n + i] of Y.  n_perms = 0 is valid.  Nothing is modified.
+ *   tri(T), the sum of the terms T[i,j], j > i.  Row i has PA_MANTEL_LANES = 64 accumulators; a_l takes the terms with
+ *        j % 64 == l, j > i, in ascending j, and starts at -0.0 (so the first term enters unchanged and an accumulator
+ *        without terms is -0.0).  Then for w = 32, 16, 8, 4, 2, 1: a_l = a_l + a_{l+w} for l < w.  The row's sum is
+ *        rho_i = a_0.  tri = (((-0.0 + rho_0) + rho_1) + ...) + rho_{n-1}, one accumulator, ascending i.
+ *   Moments.  m = n (n - 1) / 2 as a double; mean_x = tri(X) / m; x[i,j] = X[i,j] - mean_x for i != j;
+ *        ss_x = tri(x x), each square rounded.  The same for y.  h_stats[4] = mean_x, mean_y, ss_x, ss_y.
+ *   Cross sums.  cross(pi) = tri(T) with T[i,j] = x[i,j] * y[pi[i],pi[j]], each product rounded.  h_cross[n_perms + 1]:
+ *        entry 0 is the identity's, entry 1 + q that of row q of h_perms.  Mantel's r of a permutation is
+ *        cross / sqrt(ss_x ss_y), which the callers compute.
+ *   Checks, in this order, the same code for both entry points: null arguments; the range of n (before anything is
+ *        read); every row of h_perms (PA_E_INVALID names the row and the position of the first value that is out of
+ *        range or repeated); X, then Y (PA_E_INVALID names the matrix and the first offending cell in row-major order,
+ *        "pa_mantel: Y[3,1] ...").  The permutations are checked on the host before the first launch: that is what keeps
+ *        the kernel's LDS index inside the row.  A refused call leaves the context usable.
+ *   Device: d_X and d_Y are device memory, h_* host memory.  A workgroup holds one centred row of Y in LDS and its waves
+ *        gather from it at pi[j] while row pi^-1[r] of X streams past; the identity and the permutations go through the
+ *        context's workspace PA_MANTEL_BATCH at a time.  Two host synchronisations (the check, the results).
+ *   pa_mantel_permutations  rows first .. first + count - 1 of the permutations of seed `seed` (h_perms: count x n u32,
+ *        1 <= n <= PA_MANTEL_MAX_N).  fin(v) is the splitmix64 finaliser: z = v + 0x9E3779B97F4A7C15,
+ *        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9, z = (z ^ (z >> 27)) * 0x94D049BB133111EB, z ^ (z >> 31), all mod 2^64.
+ *        Row q: base = fin(fin(seed) + q); start from 0 .. n - 1; for t = n - 1 down to 1, k = fin(base + t) mod (t + 1),
+ *        swap entries t and k.  The modulo prefers small remainders by less than 2^-48; nothing is rejected.  Row q
+ *        depends on (seed, n, q) alone.  seed 1, n 5: rows 0, 1, 2 are [2,1,3,4,0], [0,1,2,4,3], [0,1,4,3,2]. */
+#define PA_MANTEL_MAX_N 16384
+#define PA_MANTEL_LANES 64
+#define PA_MANTEL_BATCH 256 /* cross sums the device makes per launch; shows in no result */
+PA_API int pa_mantel_permutations(uint64_t seed, uint32_t n, uint64_t first, uint64_t count, uint32_t *h_perms);
+PA_API int pa_mantel(pa_ctx *ctx, const double *d_X, const double *d_Y, uint32_t n, const uint32_t *h_perms, uint64_t n_perms, double *h_stats,
+                     double *h_cross);
+PA_API int pa_mantel_host(const double *h_X, const double *h_Y, uint32_t n, const uint32_t *h_perms, uint64_t n_perms, double *h_stats,
+                          double *h_cross, uint32_t n_threads);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */

@@ -28,6 +28,9 @@ PA_E_IO = -6
 PA_E_NOCONVERGE = -7  # pa_symm_top_eigs used up its max_iter
 PA_MUL_TALL_MAX_P = 32  # pa_mul_tall_f64: columns of the thin block, at most
 PA_EIGS_MAX_K = 24  # pa_symm_top_eigs: eigenpairs, at most
+PA_MANTEL_MAX_N = 16384  # pa_mantel, pa_mantel_host: genomes, at most (a 128 KB row)
+PA_MANTEL_LANES = 64  # ... accumulators of a row's sum
+PA_MANTEL_BATCH = 256  # ... cross sums the device makes per launch; shows in no result
 PA_SIG_UNHANDLED = 1
 PA_FRAGANI_REUSE_INDEX = 1
 PA_FRAGANI_COLUMNS_ONLY = 2
@@ -213,6 +216,9 @@ SIGNATURES: dict[str, tuple] = {
     "pa_gower_center_host": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32]),
     "pa_symm_top_eigs": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_double, _vp, _vp, _vp, _vp]),
     "pa_symm_top_eigs_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_double, _vp, _vp, _vp, _vp, C.c_uint32]),
+    "pa_mantel_permutations": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
+    "pa_mantel": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
+    "pa_mantel_host": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, C.c_uint32]),
     "pa_append_identity_json": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, _vp, _vp]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),

@@ -169,10 +169,13 @@ constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of
 //   TETRA-hip (tetra.hip): tetra_tab, the genomes' first blocks and first chunks (u32[2 (n + 1)])
 //   tree-run (nj.hip): nj_work, the row sums, the slots' node ids, the scan's candidates and the join table
 //   ordinate-run (pcoa.hip): pcoa_work, the thin blocks Q and Y, the chunks' partial sums, the centring's row sums
+//   mantel-run-comp (mantel.hip): mantel_work, the check's words, the moments, the cross sums, a batch's permutations,
+//   inverses and row sums
 #define PA_CTX_BUFFERS(ONE, PAIR)                                                                                   \
   PAIR(cand_keys) PAIR(cand_vals) ONE(genome_blk) ONE(counters) ONE(hist) ONE(flags) ONE(scan_tmp) ONE(region_off) \
   ONE(region_cursor) ONE(dirty) PAIR(dict_keys) PAIR(dict_vals) ONE(ids) ONE(post_genome) ONE(bitrows)             \
-  ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d) ONE(tetra_tab) ONE(nj_work) ONE(pcoa_work)
+  ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d) ONE(tetra_tab) ONE(nj_work) ONE(pcoa_work) \
+  ONE(mantel_work)
 
 struct pa_ctx {
   int device = 0;

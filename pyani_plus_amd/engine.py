@@ -934,6 +934,20 @@ class HipEngine:
         )
         return _eigs_result(out)
 
+    # -- mantel-run-comp
+    def mantel(self, X, Y, perms) -> tuple[np.ndarray, np.ndarray]:
+        """``pa_mantel``: ``(stats, cross)`` of the n x n float64 distance matrices ``X`` and ``Y`` (host arrays or tensors
+        on this device, which are used as they are and left alone; each finite, >= 0, bitwise symmetric, zero diagonal)
+        under the rows of ``perms`` (uint32, P x n, each a permutation of 0 .. n - 1; row q pairs row i of ``X`` with row
+        ``perms[q, i]`` of ``Y``).  ``stats`` = (mean_x, mean_y, ss_x, ss_y); ``cross[0]`` is the identity's cross sum
+        and ``cross[1 + q]`` that of row q: the same bits as ``mantel_host``."""
+        x = self._square_f64_on_device(X, "distance matrix")
+        y = self._square_f64_on_device(Y, "distance matrix")
+        n, p = _mantel_arguments(x.shape, y.shape, perms)
+        out = _mantel_outputs(len(p))
+        self._check(self.lib.pa_mantel(self.ctx, x.data_ptr(), y.data_ptr(), n, p.ctypes.data, len(p), *(a.ctypes.data for a in out)), "pa_mantel")
+        return out
+
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")
 
@@ -994,6 +1008,49 @@ def nj_tree_host(D, threads: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarra
     out = _nj_outputs(n)
     check(_capi.load_library().pa_nj_host(d.ctypes.data, n, *(a.ctypes.data for a in out), int(threads)), "pa_nj_host")
     return out[0], out[1], out[2], float(out[3][0])
+
+
+# ------------------------------------------------------------------ mantel-run-comp: the host forms (no GPU needed)
+def _mantel_arguments(x_shape, y_shape, perms) -> tuple[int, np.ndarray]:
+    """``(n, the permutations as a contiguous uint32 P x n array)``; the library checks n and the rows themselves."""
+    n = int(x_shape[0])
+    if tuple(y_shape) != tuple(x_shape):
+        raise ValueError(f"distance matrices of shapes {tuple(x_shape)} and {tuple(y_shape)}, expected the same")
+    p = np.ascontiguousarray(perms, dtype=np.uint32)
+    if p.size == 0:
+        p = p.reshape(0, n)
+    if p.ndim != 2 or p.shape[1] != n:
+        raise ValueError(f"permutations of shape {p.shape} for {n} genomes, expected (P, {n})")
+    return n, p
+
+
+def _mantel_outputs(n_perms: int) -> tuple[np.ndarray, np.ndarray]:
+    return np.zeros(4, dtype=np.float64), np.zeros(n_perms + 1, dtype=np.float64)
+
+
+def mantel_host(X, Y, perms, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """``pa_mantel_host``: what ``HipEngine.mantel`` returns, bit for bit, on ``threads`` host threads (0: as many as the
+    process may use), whose number does not show in the result.  ``X`` and ``Y`` are not modified."""
+    x = np.ascontiguousarray(X, dtype=np.float64)
+    y = np.ascontiguousarray(Y, dtype=np.float64)
+    for m in (x, y):
+        if m.ndim != 2 or m.shape[0] != m.shape[1]:
+            raise ValueError(f"distance matrix of shape {m.shape}, expected a square one")
+    n, p = _mantel_arguments(x.shape, y.shape, perms)
+    out = _mantel_outputs(len(p))
+    check(_capi.load_library().pa_mantel_host(x.ctypes.data, y.ctypes.data, n, p.ctypes.data, len(p), *(a.ctypes.data for a in out), int(threads)),
+          "pa_mantel_host")
+    return out
+
+
+def mantel_permutations(seed: int, n: int, first: int, count: int) -> np.ndarray:
+    """``pa_mantel_permutations``: rows ``first .. first + count - 1`` of the permutations of ``seed`` over ``n`` genomes
+    (uint32, count x n).  A row depends on (seed, n, its number) alone."""
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"seed {seed!r}; 0 to 2^64 - 1")
+    out = np.empty((int(count), int(n)), dtype=np.uint32)
+    check(_capi.load_library().pa_mantel_permutations(int(seed), int(n), int(first), int(count), out.ctypes.data), "pa_mantel_permutations")
+    return out
 
 
 # ------------------------------------------------------------------ ordinate-run: the host forms (no GPU needed)

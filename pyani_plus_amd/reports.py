@@ -1,8 +1,8 @@
 """The reports of a recorded run: the build's own counterpart of ``export-run``, ``plot-run`` and ``plot-run-comp``
 (their tables; pyani_plus/plot_run.py) and ``classify`` (pyani_plus/public_cli.py:974-1091, 1095-1208, 1211-1331), and
-this project's ``tree-run`` and ``ordinate-run``.  They read the database through ``run_store`` and compute in the
-report modules (``classify``, ``cluster``, ``distribution``, ``scatter``, ``run_comp``, ``tree``, ``ordination`` and the
-figure modules); ``rundb`` re-exports them and is their command line, and nothing here imports it.
+this project's ``tree-run``, ``ordinate-run`` and ``mantel-run-comp``.  They read the database through ``run_store`` and compute in the
+report modules (``classify``, ``cluster``, ``distribution``, ``scatter``, ``run_comp``, ``tree``, ``ordination``, ``mantel``
+and the figure modules); ``rundb`` re-exports them and is their command line, and nothing here imports it.
 
 Every command opens the same way -- the database is there, the image formats can be drawn, the output directory is
 made, the run is there and complete, the labels are known and distinct -- and each check is stated once below.  The
@@ -23,6 +23,7 @@ from . import classify as classify_mod
 from . import cluster as cluster_mod
 from . import distribution as distribution_mod
 from . import distribution_figure, heatmap_figure, ordination_figure, run_comp_figure, scatter_figure
+from . import mantel as mantel_mod
 from . import ordination as ordination_mod
 from . import run_comp as run_comp_mod
 from . import scatter as scatter_mod
@@ -228,13 +229,22 @@ def classify(database: Path | str, outdir: Path, *, run_id: int | None = None, l
 
 
 # ------------------------------------------------------------------ a run's distances (tree-run, ordinate-run)
+def _require_missing_distance(logger, missing: float) -> None:
+    if not (math.isfinite(missing) and missing >= 0):
+        sourmash_hip.log_sys_exit(logger, f"The distance of a pair without identity must be finite and not negative, not {missing!r}")
+
+
+def _require_no_negative_distance(logger, distances: np.ndarray, what: str) -> None:
+    if (distances < 0).any():
+        sourmash_hip.log_sys_exit(logger, f"An identity above 1 gives a negative distance: no {what} is defined")
+
+
 def _distance_run(logger, database, outdir, run_id: int | None, label: str, missing: float, what: str):  # noqa: PLR0913
     """What tree-run and ordinate-run start from: ``(outdir, method, identity, distances)`` of a complete run -- the
     output directory made, the run opened and checked, its identity frame relabelled and sorted by label as ``classify``
     and ``plot-run`` read it, and ``tree.run_distances`` of it -- with the reference's messages for an incomplete run,
     duplicate stems and an unknown label.  ``what`` is the thing an identity above 1 leaves undefined."""
-    if not (math.isfinite(missing) and missing >= 0):
-        sourmash_hip.log_sys_exit(logger, f"The distance of a pair without identity must be finite and not negative, not {missing!r}")
+    _require_missing_distance(logger, missing)
     outdir = _make_outdir(logger, outdir)
     conn, run, n, done = _open_complete_run(logger, database, run_id, "Exporting")
     frames = _score_frames(logger, conn, run)
@@ -242,8 +252,7 @@ def _distance_run(logger, database, outdir, run_id: int | None, label: str, miss
     logger.info("Run %d has %d comparisons across %d genomes.", run.run_id, done, n)
     identity = _relabelled(logger, run, frames, label)[0]
     distances = tree_mod.run_distances(identity, missing, logger)
-    if (distances < 0).any():
-        sourmash_hip.log_sys_exit(logger, f"An identity above 1 gives a negative distance: no {what} is defined")
+    _require_no_negative_distance(logger, distances, what)
     return outdir, run.configuration.method, identity, distances
 
 
@@ -505,6 +514,17 @@ def _run_comparison_columns(conn, run: Run) -> tuple[np.ndarray, np.ndarray, np.
     return tuple(np.concatenate(column) for column in zip(*parts))
 
 
+def _parse_run_ids(logger, run_ids) -> list[int]:
+    """The runs of a comparison, the reference run first: a comma separated string, or integers."""
+    try:
+        runs = [int(x) for x in (run_ids.split(",") if isinstance(run_ids, str) else run_ids)]
+    except (TypeError, ValueError):
+        sourmash_hip.log_sys_exit(logger, f"Expected comma separated list of runs, not: {run_ids}")
+    if len(runs) < 2:  # noqa: PLR2004
+        sourmash_hip.log_sys_exit(logger, "Need at least two runs for a comparison")
+    return runs
+
+
 def plot_run_comp(database: Path | str, outdir: Path, run_ids, *, columns: int = 0, formats: tuple[str, ...] = ("tsv",),  # noqa: PLR0913
                   engine=None, logger: logging.Logger | None = None) -> list[Path]:
     """Compare the identities of runs of one database pair by pair, as the reference's ``plot-run-comp`` does: the first
@@ -524,12 +544,7 @@ def plot_run_comp(database: Path | str, outdir: Path, run_ids, *, columns: int =
     _require_database(logger, database)
     formats, images = _image_formats(logger, formats)
     outdir = _make_outdir(logger, outdir)
-    try:
-        runs = [int(x) for x in (run_ids.split(",") if isinstance(run_ids, str) else run_ids)]
-    except (TypeError, ValueError):
-        sourmash_hip.log_sys_exit(logger, f"Expected comma separated list of runs, not: {run_ids}")
-    if len(runs) < 2:  # noqa: PLR2004
-        sourmash_hip.log_sys_exit(logger, "Need at least two runs for a comparison")
+    runs = _parse_run_ids(logger, run_ids)
     ref_id, other_ids = runs[0], runs[1:]
     conn, ref_run = _open_run(logger, database, ref_id, "Plotting")
     if not count_run_comparisons(conn, ref_run):
@@ -573,4 +588,66 @@ def plot_run_comp(database: Path | str, outdir: Path, run_ids, *, columns: int =
             written.append(outdir / f"{method}_identity_{ref_id}_{mode}_vs_others.{ext}")
             run_comp_figure.draw_comparison(mode, ref_run.name, other_names, comparisons, written[-1], columns)
     logger.info("Wrote %d images to %s/%s_identity_%d_vs_*.*", 2 * len(images), outdir, method, ref_id)
+    return written
+
+
+# ------------------------------------------------------------------ mantel-run-comp (this project's own: the reference gives no number)
+def mantel_run_comp(database: Path | str, outdir: Path, run_ids, *, permutations: int = 9999, seed: int = 0, missing: float = 1.0,  # noqa: PLR0913
+                    engine=None, logger: logging.Logger | None = None) -> list[Path]:
+    """Mantel's permutation test (``mantel.mantel_test``) between complete runs of one database:
+    the first of ``run_ids`` (a comma separated string, or integers) is the reference run, and each further run is
+    compared with it over the genomes both runs hold (their hashes, sorted; at least 3).  A run's distances are the ones
+    ``tree-run`` uses (``tree.run_distances`` of its identity matrix; ``missing`` where a pair has no identity either
+    way), restricted to those genomes.  ``permutations`` (0 to 1 000 000) permutations of the other run's genomes come
+    from ``seed`` (0 to 2^64 - 1).
+
+    * ``<method>_identity_<ref>_mantel.tsv``: ``#run_id method name genomes pairs mantel_r permutations seed
+      at_least_observed p_value``, one line per other run, floats as ``repr``, ``NA`` where a run's distances are all
+      equal;
+    * ``<method>_identity_<ref>_vs_<other>_mantel_null.tsv`` for every other run: ``#permutation mantel_r``, one line per
+      permutation (with ``NA`` above, the header alone).
+
+    ``engine``: a ``HipEngine`` makes the cross sums on the GPU; None makes them on the host, with the same bytes.
+    Returns the written paths, the summary first."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    _require_database(logger, database)
+    if isinstance(permutations, bool) or not isinstance(permutations, int) or not 0 <= permutations <= mantel_mod.MAX_PERMUTATIONS:
+        sourmash_hip.log_sys_exit(logger, f"Expected 0 to {mantel_mod.MAX_PERMUTATIONS} permutations, not {permutations!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        sourmash_hip.log_sys_exit(logger, f"Expected a seed from 0 to 2^64 - 1, not {seed!r}")
+    _require_missing_distance(logger, missing)
+    outdir = _make_outdir(logger, outdir)
+    runs = _parse_run_ids(logger, run_ids)
+    opened = []
+    for run_id in runs:
+        conn, run, n, done = _open_complete_run(logger, database, run_id, "Comparing")
+        identity = _score_frames(logger, conn, run)[0]
+        conn.close()
+        logger.info("Run %d has %d comparisons across %d genomes.", run.run_id, done, n)
+        opened.append((run, identity))
+    ref_run, ref_identity = opened[0]
+    method = ref_run.configuration.method
+
+    def distances(identity, hashes: list[str]) -> np.ndarray:
+        d = tree_mod.run_distances(identity.loc[hashes, hashes], missing, logger)
+        _require_no_negative_distance(logger, d, "Mantel test")
+        return d
+
+    lines, written = [], [outdir / f"{method}_identity_{ref_run.run_id}_mantel.tsv"]
+    try:
+        for run, identity in opened[1:]:
+            common = sorted({a.genome_hash for a in ref_run.fasta_hashes} & {a.genome_hash for a in run.fasta_hashes})
+            if len(common) < 3:  # noqa: PLR2004
+                sourmash_hip.log_sys_exit(
+                    logger, f"Runs {ref_run.run_id} and {run.run_id} have {len(common)} genomes in common: a Mantel test needs at least 3")
+            test = mantel_mod.mantel_test(distances(ref_identity, common), distances(identity, common), permutations, seed, engine=engine, logger=logger)
+            logger.info("%s run %d vs %s run %d over %d genomes: Mantel r %s, p %s", run.configuration.method, run.run_id, method, ref_run.run_id,
+                        len(common), test.r, test.p)
+            lines.append(mantel_mod.summary_line(run.run_id, run.configuration.method, run.name, test))
+            written.append(outdir / f"{method}_identity_{ref_run.run_id}_vs_{run.run_id}_mantel_null.tsv")
+            mantel_mod.write_null_tsv(written[-1], test)
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, "mantel-run-comp", err)
+    mantel_mod.write_summary_tsv(written[0], lines)
+    logger.info("Wrote %d tables to %s/%s_identity_%d_*mantel*.tsv", len(written), outdir, method, ref_run.run_id)
     return written
