@@ -843,6 +843,55 @@ PA_API int pa_mantel(pa_ctx *ctx, const double *d_X, const double *d_Y, uint32_t
 PA_API int pa_mantel_host(const double *h_X, const double *h_Y, uint32_t n, const uint32_t *h_perms, uint64_t n_perms, double *h_stats,
                           double *h_cross, uint32_t n_threads);
 
+/* ---- dereplicate-run: one representative genome per group of a run's threshold graph ----
+ * Replaces nothing in the reference, which has no such command.  The definitions below are this project's own contract,
+ * pinned by an independent restatement in tests/derep_cases.py.  DESIGN.md section 7k.  Everything but the scores is
+ * integer work and every score is classify's aggregate of two cells, so each device entry point gives the same bits run
+ * to run and the same bits as its _host twin, whose result does not depend on n_threads (0: as many as the process may
+ * use).  derep_rule.h states the rules once for both.
+ *
+ *   Nodes.  Node p is row and column p of S (score) and C (query coverage), n x n f64 row-major, rows the query;
+ *        1 <= n <= 65535.  A lower index is a preferred genome: the callers order the genomes, this layer knows no other
+ *        priority.  Nothing is modified.
+ *   Edge.  For lo < hi: score = agg_score(S[hi,lo], S[lo,hi]), cov = agg_cov(C[hi,lo], C[lo,hi]) with the argument order
+ *        and NaN behaviour of pa_classify_edges (PA_AGG_MIN, PA_AGG_MAX keep the first argument unless the comparison
+ *        with the second holds; PA_AGG_MEAN is (a + b) / 2).  lo and hi are adjacent iff neither value is NaN,
+ *        cov > cov_min and score >= min_score: the graph classify has at the moment its min_score column reads that
+ *        value.  Every node is adjacent to itself, whatever the diagonal holds.
+ *   Bits.  W = ceil(n / 64) uint64_t words per row, row-major: bit b of word w of row a is adjacency(a, 64 w + b).
+ *        Symmetric, the diagonal set, the padding bits zero.
+ *   pa_derep_select, PA_DEREP_GREEDY: for p = 0 .. n - 1 in order, p is a representative iff no earlier representative
+ *        is adjacent to it (the lexicographically first maximal independent set).  PA_DEREP_COVER: start with every node
+ *        uncovered; while one is, gain(p) = uncovered nodes in p's closed neighbourhood; choose the largest gain, among
+ *        equal gains a p that is itself uncovered, then the smaller p; its closed neighbourhood is covered.  (Once the
+ *        largest gain is 1, exactly the nodes still uncovered become representatives.)  is_rep[n] is 1 or 0,
+ *        *n_reps their number.  The device runs rounds of small launches, PA_DEREP_BATCH of them between two looks at a
+ *        device scalar that makes the rest return at once when nothing is left; *n_rounds (nullable, device entry only)
+ *        is the number of rounds that had work: a diagnostic, not part of the contract.
+ *   pa_derep_assign.  rep[p] = p for a representative; otherwise the adjacent representative with the largest
+ *        score(p, r), equal scores (== on doubles) to the smaller r; rep_score[p] is that score, for a representative the
+ *        score of the pair (p, p) by the same formula.  Both modes guarantee an adjacent representative; with an is_rep
+ *        that offers none (or only NaN scores) rep[p] = PA_DEREP_NONE and rep_score[p] = NaN.  Bits of is_rep at or past
+ *        n are never read.
+ *   Checks, the same code and messages for both forms: n = 0 or n > 65535; null arguments; an unknown aggregator or
+ *        mode; a NaN min_score or cov_min: PA_E_INVALID.
+ *   Device: every pointer but n_reps and n_rounds is device memory.  No grid-wide barrier, no floating-point atomics;
+ *        one read-back per batch of rounds. */
+#define PA_DEREP_GREEDY 0
+#define PA_DEREP_COVER 1
+#define PA_DEREP_BATCH 64 /* rounds the device enqueues between two read-backs; shows in no result */
+#define PA_DEREP_NONE 0xFFFFFFFFu
+PA_API int pa_derep_adjacency(pa_ctx *ctx, const double *d_S, const double *d_C, uint32_t n, int agg_score, int agg_cov, double min_score,
+                              double cov_min, uint64_t *d_bits);
+PA_API int pa_derep_adjacency_host(const double *h_S, const double *h_C, uint32_t n, int agg_score, int agg_cov, double min_score, double cov_min,
+                                   uint64_t *h_bits, uint32_t n_threads);
+PA_API int pa_derep_select(pa_ctx *ctx, const uint64_t *d_bits, uint32_t n, int mode, uint8_t *d_is_rep, uint32_t *n_reps, uint32_t *n_rounds);
+PA_API int pa_derep_select_host(const uint64_t *h_bits, uint32_t n, int mode, uint8_t *h_is_rep, uint32_t *n_reps);
+PA_API int pa_derep_assign(pa_ctx *ctx, const double *d_S, uint32_t n, int agg_score, const uint64_t *d_bits, const uint8_t *d_is_rep,
+                           uint32_t *d_rep, double *d_rep_score);
+PA_API int pa_derep_assign_host(const double *h_S, uint32_t n, int agg_score, const uint64_t *h_bits, const uint8_t *h_is_rep, uint32_t *h_rep,
+                                double *h_rep_score, uint32_t n_threads);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */

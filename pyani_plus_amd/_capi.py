@@ -31,6 +31,10 @@ PA_EIGS_MAX_K = 24  # pa_symm_top_eigs: eigenpairs, at most
 PA_MANTEL_MAX_N = 16384  # pa_mantel, pa_mantel_host: genomes, at most (a 128 KB row)
 PA_MANTEL_LANES = 64  # ... accumulators of a row's sum
 PA_MANTEL_BATCH = 256  # ... cross sums the device makes per launch; shows in no result
+PA_DEREP_GREEDY, PA_DEREP_COVER = 0, 1  # pa_derep_select: the modes
+PA_DEREP_MODE = {"greedy": PA_DEREP_GREEDY, "cover": PA_DEREP_COVER}
+PA_DEREP_BATCH = 64  # ... rounds the device enqueues between two read-backs; shows in no result
+PA_DEREP_NONE = 0xFFFFFFFF  # pa_derep_assign: the representative of a node that is adjacent to none
 PA_SIG_UNHANDLED = 1
 PA_FRAGANI_REUSE_INDEX = 1
 PA_FRAGANI_COLUMNS_ONLY = 2
@@ -219,6 +223,12 @@ SIGNATURES: dict[str, tuple] = {
     "pa_mantel_permutations": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
     "pa_mantel": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
     "pa_mantel_host": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, C.c_uint32]),
+    "pa_derep_adjacency": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),
+    "pa_derep_adjacency_host": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int, C.c_int, C.c_double, C.c_double, _vp, C.c_uint32]),
+    "pa_derep_select": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int, _vp, _u32p, _u32p]),
+    "pa_derep_select_host": (C.c_int, [_vp, C.c_uint32, C.c_int, _vp, _u32p]),
+    "pa_derep_assign": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp]),
+    "pa_derep_assign_host": (C.c_int, [_vp, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, C.c_uint32]),
     "pa_append_identity_json": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, _vp, _vp]),
     "pa_prof_enable": (C.c_int, [_vp, C.c_int]),
     "pa_prof_reset": (C.c_int, [_vp]),

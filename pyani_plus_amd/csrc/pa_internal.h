@@ -143,7 +143,8 @@ constexpr ScalarSlot kRegionOverflow{12, 1};   // pa_sketch, pa_sketch_streamed:
 constexpr ScalarSlot kNjPick{16, 8};           // pa_nj: the pair a join chose, written by its join kernel and read by its update kernel (NjPick, nj.hip)
 constexpr ScalarSlot kNjBad{24, 4};            // pa_nj: two 64-bit words zeroed / set as one: [0] cells that break the contract, [1] the first of them
 constexpr ScalarSlot kGowerBad{28, 4};         // pa_gower_center: the same two words for its own check of D
-static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow, kNjPick, kNjBad, kGowerBad}),
+constexpr ScalarSlot kDerepProgress{14, 2};    // pa_derep_select: [0] nodes settled, [1] rounds that had work; zeroed as one, read once per batch of rounds
+static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow, kNjPick, kNjBad, kGowerBad, kDerepProgress}),
               "two slots of pa_ctx::counters overlap or leave the block");
 
 // The words of pa_ctx::dict_scalars (pa_ctx::dict_slot), the hash dictionary's own block, touched by no other phase
@@ -171,11 +172,12 @@ constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of
 //   ordinate-run (pcoa.hip): pcoa_work, the thin blocks Q and Y, the chunks' partial sums, the centring's row sums
 //   mantel-run-comp (mantel.hip): mantel_work, the check's words, the moments, the cross sums, a batch's permutations,
 //   inverses and row sums
+//   dereplicate-run (derep.hip): derep_work, the nodes still open as bits, then a round's new representatives or candidates
 #define PA_CTX_BUFFERS(ONE, PAIR)                                                                                   \
   PAIR(cand_keys) PAIR(cand_vals) ONE(genome_blk) ONE(counters) ONE(hist) ONE(flags) ONE(scan_tmp) ONE(region_off) \
   ONE(region_cursor) ONE(dirty) PAIR(dict_keys) PAIR(dict_vals) ONE(ids) ONE(post_genome) ONE(bitrows)             \
   ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d) ONE(tetra_tab) ONE(nj_work) ONE(pcoa_work) \
-  ONE(mantel_work)
+  ONE(mantel_work) ONE(derep_work)
 
 struct pa_ctx {
   int device = 0;

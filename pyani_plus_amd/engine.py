@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 
@@ -948,6 +949,76 @@ class HipEngine:
         self._check(self.lib.pa_mantel(self.ctx, x.data_ptr(), y.data_ptr(), n, p.ctypes.data, len(p), *(a.ctypes.data for a in out)), "pa_mantel")
         return out
 
+    # -- dereplicate-run
+    def derep_adjacency_device(self, score, cov, *, score_edges: str = "mean", coverage_edges: str = "min", min_score: float = 0.95,
+                               cov_min: float = 0.5):
+        """``pa_derep_adjacency``: the threshold graph of the n x n float64 ``score`` and ``cov`` (host arrays or tensors on
+        this device, left alone) as a device tensor of n x ceil(n / 64) int64 words (views of uint64): bit b of word w of
+        row a says whether a and 64 w + b are adjacent."""
+        t = self.torch
+        s = self._square_f64_on_device(score, "score matrix")
+        c = self._square_f64_on_device(cov, "coverage matrix")
+        _derep_same_shape(s.shape, c.shape)
+        n = s.shape[0]
+        bits = t.empty((n, (n + 63) // 64), dtype=t.int64, device=self.device)
+        self._check(
+            self.lib.pa_derep_adjacency(self.ctx, s.data_ptr(), c.data_ptr(), n, _derep_agg(score_edges, "score"), _derep_agg(coverage_edges, "coverage"),
+                                        float(min_score), float(cov_min), bits.data_ptr()),
+            "pa_derep_adjacency",
+        )  # fmt: skip
+        return bits
+
+    def _derep_bits_on_device(self, bits, n: int):
+        """A bit matrix of n nodes (a host array of uint64, or an int64 tensor with the same bits) on this device."""
+        t = self.torch
+        b = bits if isinstance(bits, t.Tensor) else t.from_numpy(np.ascontiguousarray(bits, dtype=np.uint64).view(np.int64).copy())
+        b = b.to(self.device).contiguous()
+        if b.dtype != t.int64 or b.numel() != n * ((n + 63) // 64):
+            raise ValueError(f"bit matrix of {b.numel()} {b.dtype} words for {n} nodes, expected {n} x {(n + 63) // 64} of 64 bits")
+        return b
+
+    def derep_select_device(self, bits, n: int, mode: str = "greedy"):
+        """``pa_derep_select``: ``(is_rep, n_reps, n_rounds)`` of the bit matrix ``bits`` (n x ceil(n / 64) words, a host
+        array or a tensor on this device): ``is_rep`` a device tensor of n uint8, the number of representatives, and the
+        number of rounds the device took (a diagnostic)."""
+        t = self.torch
+        n = int(n)
+        b = self._derep_bits_on_device(bits, n)
+        is_rep = t.empty(max(n, 1), dtype=t.uint8, device=self.device)
+        n_reps, n_rounds = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.lib.pa_derep_select(self.ctx, b.data_ptr(), n, _derep_mode(mode), is_rep.data_ptr(), C.byref(n_reps), C.byref(n_rounds)),
+                    "pa_derep_select")
+        return is_rep[:n], n_reps.value, n_rounds.value
+
+    def derep_assign_device(self, score, bits, is_rep, *, score_edges: str = "mean"):
+        """``pa_derep_assign``: ``(rep, rep_score)`` as device tensors (int32 views of uint32, float64): every node's
+        representative among the set bits of its row that ``is_rep`` marks, and the pair's score."""
+        t = self.torch
+        s = self._square_f64_on_device(score, "score matrix")
+        n = s.shape[0]
+        b = self._derep_bits_on_device(bits, n)
+        r = (is_rep if isinstance(is_rep, t.Tensor) else t.from_numpy(np.ascontiguousarray(is_rep, dtype=np.uint8).copy())).to(self.device).contiguous()
+        if r.dtype != t.uint8 or r.numel() != n:
+            raise ValueError(f"{r.numel()} marks of {r.dtype} for {n} nodes, expected {n} of uint8")
+        rep = t.empty(max(n, 1), dtype=t.int32, device=self.device)
+        rep_score = t.empty(max(n, 1), dtype=t.float64, device=self.device)
+        self._check(self.lib.pa_derep_assign(self.ctx, s.data_ptr(), n, _derep_agg(score_edges, "score"), b.data_ptr(), r.data_ptr(), rep.data_ptr(),
+                                             rep_score.data_ptr()), "pa_derep_assign")  # fmt: skip
+        return rep[:n], rep_score[:n]
+
+    def dereplicate(self, score, cov, *, score_edges: str = "mean", coverage_edges: str = "min", min_score: float = 0.95, cov_min: float = 0.5,  # noqa: PLR0913
+                    mode: str = "greedy") -> Dereplication:
+        """One representative per group of the threshold graph of ``score`` and ``cov`` (n x n float64, host arrays or
+        tensors on this device, left alone; node p is row and column p, a lower index is the preferred genome): the
+        three calls above, the matrices uploaded once and the bit matrix never leaving the device.  The same bits as
+        ``dereplicate_host``."""
+        s = self._square_f64_on_device(score, "score matrix")
+        c = self._square_f64_on_device(cov, "coverage matrix")
+        bits = self.derep_adjacency_device(s, c, score_edges=score_edges, coverage_edges=coverage_edges, min_score=min_score, cov_min=cov_min)
+        is_rep, n_reps, n_rounds = self.derep_select_device(bits, s.shape[0], mode)
+        rep, rep_score = self.derep_assign_device(s, bits, is_rep, score_edges=score_edges)
+        return Dereplication(is_rep.cpu().numpy().astype(bool), rep.cpu().numpy().view(np.uint32), rep_score.cpu().numpy(), n_reps, n_rounds)
+
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")
 
@@ -1051,6 +1122,89 @@ def mantel_permutations(seed: int, n: int, first: int, count: int) -> np.ndarray
     out = np.empty((int(count), int(n)), dtype=np.uint32)
     check(_capi.load_library().pa_mantel_permutations(int(seed), int(n), int(first), int(count), out.ctypes.data), "pa_mantel_permutations")
     return out
+
+
+# ------------------------------------------------------------------ dereplicate-run: the host forms (no GPU needed)
+class Dereplication(NamedTuple):
+    """``is_rep[p]``: node p is a representative; ``rep[p]`` the representative of p (itself for a representative;
+    uint32); ``rep_score[p]`` the score of the pair (p, rep[p]); ``n_reps`` their number; ``rounds`` the rounds the device
+    took (None on the host: a diagnostic, not a result)."""
+
+    is_rep: np.ndarray
+    rep: np.ndarray
+    rep_score: np.ndarray
+    n_reps: int
+    rounds: int | None
+
+
+def _derep_agg(name: str, role: str) -> int:
+    if name not in _capi.PA_AGG:
+        raise ValueError(f"Unknown {role} aggregator {name!r}: expected one of min, max, mean")
+    return _capi.PA_AGG[name]
+
+
+def _derep_mode(name: str) -> int:
+    if name not in _capi.PA_DEREP_MODE:
+        raise ValueError(f"Unknown dereplication mode {name!r}: expected one of greedy, cover")
+    return _capi.PA_DEREP_MODE[name]
+
+
+def _derep_same_shape(score_shape, cov_shape) -> None:
+    if tuple(score_shape) != tuple(cov_shape):
+        raise ValueError(f"score and coverage matrices of shapes {tuple(score_shape)} and {tuple(cov_shape)}, expected the same")
+
+
+def derep_adjacency_host(score, cov, *, score_edges: str = "mean", coverage_edges: str = "min", min_score: float = 0.95, cov_min: float = 0.5,  # noqa: PLR0913
+                         threads: int = 0) -> np.ndarray:
+    """``pa_derep_adjacency_host``: what ``HipEngine.derep_adjacency_device`` computes, bit for bit, as an n x ceil(n / 64)
+    uint64 array."""
+    s, c = _square_f64(score, "score matrix"), _square_f64(cov, "coverage matrix")
+    _derep_same_shape(s.shape, c.shape)
+    n = s.shape[0]
+    bits = np.zeros((n, (n + 63) // 64), dtype=np.uint64)
+    check(
+        _capi.load_library().pa_derep_adjacency_host(s.ctypes.data, c.ctypes.data, n, _derep_agg(score_edges, "score"), _derep_agg(coverage_edges, "coverage"),
+                                                     float(min_score), float(cov_min), bits.ctypes.data, int(threads)),
+        "pa_derep_adjacency_host",
+    )  # fmt: skip
+    return bits
+
+
+def derep_select_host(bits, n: int, mode: str = "greedy") -> tuple[np.ndarray, int]:
+    """``pa_derep_select_host``: ``(is_rep as n uint8, n_reps)`` of the bit matrix, by the sequential rules."""
+    n = int(n)
+    b = np.ascontiguousarray(bits, dtype=np.uint64)
+    if b.size != n * ((n + 63) // 64):
+        raise ValueError(f"bit matrix of {b.size} words for {n} nodes, expected {n} x {(n + 63) // 64}")
+    is_rep = np.zeros(max(n, 1), dtype=np.uint8)
+    n_reps = C.c_uint32(0)
+    check(_capi.load_library().pa_derep_select_host(b.ctypes.data, n, _derep_mode(mode), is_rep.ctypes.data, C.byref(n_reps)), "pa_derep_select_host")
+    return is_rep[:n], n_reps.value
+
+
+def derep_assign_host(score, bits, is_rep, *, score_edges: str = "mean", threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """``pa_derep_assign_host``: ``(rep as uint32, rep_score)``, what ``HipEngine.derep_assign_device`` computes, bit for bit."""
+    s = _square_f64(score, "score matrix")
+    n = s.shape[0]
+    b = np.ascontiguousarray(bits, dtype=np.uint64)
+    r = np.ascontiguousarray(is_rep, dtype=np.uint8)
+    if b.size != n * ((n + 63) // 64) or r.size != n:
+        raise ValueError(f"bit matrix of {b.size} words and {r.size} marks for {n} nodes")
+    rep, rep_score = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.float64)
+    check(_capi.load_library().pa_derep_assign_host(s.ctypes.data, n, _derep_agg(score_edges, "score"), b.ctypes.data, r.ctypes.data, rep.ctypes.data,
+                                                    rep_score.ctypes.data, int(threads)), "pa_derep_assign_host")  # fmt: skip
+    return rep[:n], rep_score[:n]
+
+
+def dereplicate_host(score, cov, *, score_edges: str = "mean", coverage_edges: str = "min", min_score: float = 0.95, cov_min: float = 0.5,  # noqa: PLR0913
+                     mode: str = "greedy", threads: int = 0) -> Dereplication:
+    """What ``HipEngine.dereplicate`` returns, bit for bit, from the three host twins on ``threads`` host threads (0: as
+    many as the process may use), whose number does not show in the result.  The inputs are not modified."""
+    _derep_mode(mode)
+    bits = derep_adjacency_host(score, cov, score_edges=score_edges, coverage_edges=coverage_edges, min_score=min_score, cov_min=cov_min, threads=threads)
+    is_rep, n_reps = derep_select_host(bits, len(bits), mode)
+    rep, rep_score = derep_assign_host(score, bits, is_rep, score_edges=score_edges, threads=threads)
+    return Dereplication(is_rep.astype(bool), rep, rep_score, n_reps, None)
 
 
 # ------------------------------------------------------------------ ordinate-run: the host forms (no GPU needed)

@@ -1,8 +1,8 @@
 """The reports of a recorded run: the build's own counterpart of ``export-run``, ``plot-run`` and ``plot-run-comp``
 (their tables; pyani_plus/plot_run.py) and ``classify`` (pyani_plus/public_cli.py:974-1091, 1095-1208, 1211-1331), and
-this project's ``tree-run``, ``ordinate-run`` and ``mantel-run-comp``.  They read the database through ``run_store`` and compute in the
-report modules (``classify``, ``cluster``, ``distribution``, ``scatter``, ``run_comp``, ``tree``, ``ordination``, ``mantel``
-and the figure modules); ``rundb`` re-exports them and is their command line, and nothing here imports it.
+this project's ``tree-run``, ``ordinate-run``, ``mantel-run-comp`` and ``dereplicate-run``.  They read the database through ``run_store`` and compute in the
+report modules (``classify``, ``cluster``, ``distribution``, ``scatter``, ``run_comp``, ``tree``, ``ordination``, ``mantel``,
+``dereplicate`` and the figure modules); ``rundb`` re-exports them and is their command line, and nothing here imports it.
 
 Every command opens the same way -- the database is there, the image formats can be drawn, the output directory is
 made, the run is there and complete, the labels are known and distinct -- and each check is stated once below.  The
@@ -21,6 +21,7 @@ import numpy as np
 from . import _capi
 from . import classify as classify_mod
 from . import cluster as cluster_mod
+from . import dereplicate as dereplicate_mod
 from . import distribution as distribution_mod
 from . import distribution_figure, heatmap_figure, ordination_figure, run_comp_figure, scatter_figure
 from . import mantel as mantel_mod
@@ -32,7 +33,7 @@ from ._capi import HipBackendError
 from .methods import sourmash_hip
 from .methods.external_alignment_hip import filename_stem
 from .run_store import (Run, _comparison_matrices, _matrix_cache_too_big, _open_run, _select_run_comparisons, cache_comparisons,
-                        count_run_comparisons, load_run)  # fmt: skip
+                        count_run_comparisons, genome_lengths, load_run)  # fmt: skip
 
 
 # ------------------------------------------------------------------ how every report opens
@@ -650,4 +651,58 @@ def mantel_run_comp(database: Path | str, outdir: Path, run_ids, *, permutations
         sourmash_hip.backend_failure(logger, "mantel-run-comp", err)
     mantel_mod.write_summary_tsv(written[0], lines)
     logger.info("Wrote %d tables to %s/%s_identity_%d_*mantel*.tsv", len(written), outdir, method, ref_run.run_id)
+    return written
+
+
+# ------------------------------------------------------------------ dereplicate-run (this project's own: the reference picks no representatives)
+def dereplicate_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem",  # noqa: PLR0913
+                    min_identity: float = dereplicate_mod.MIN_IDENTITY, cov_min: float = classify_mod.MIN_COVERAGE, score_edges: str = "mean",
+                    coverage_edges: str = "min", mode: str = "greedy", prefer: str = "length", engine=None,
+                    logger: logging.Logger | None = None) -> list[Path]:
+    """One representative genome per group of a complete run (``dereplicate.dereplicate_matrices``; DESIGN.md section
+    7k): two genomes are adjacent when their aggregated identity is at least ``min_identity`` and their aggregated query
+    coverage above ``cov_min`` -- the graph ``classify`` has at the moment its ``min_identity`` column reads that value.
+    ``mode`` "greedy" walks the genomes in order of preference and keeps one that no kept genome is adjacent to (the
+    galah / skDER rule); "cover" chooses again and again the genome whose neighbourhood holds the most genomes not yet
+    represented.  Every other genome goes to the adjacent representative of the highest identity.  ``prefer`` "length"
+    puts the longer genome first (ties by label), "label" is label order.  The matrices and labels are the ones
+    ``classify`` reads, with the reference's messages for a missing database, an incomplete run, duplicate stems and an
+    unknown label.
+
+    * ``<method>_dereplicate.tsv``: ``genome, representative, identity, length``, a row per genome, grouped by
+      representative in order of preference, the representative's own row first;
+    * ``<method>_representatives.tsv``: ``representative, n_members, length, min_identity``, a row per representative.
+
+    ``engine``: a ``HipEngine`` builds the graph, selects and assigns on the GPU; None does so on the host, with the
+    same bytes.  Returns the written paths."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    _require_database(logger, database)
+    for value, what in ((min_identity, "identity"), (cov_min, "coverage")):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or math.isnan(value):
+            sourmash_hip.log_sys_exit(logger, f"The minimum {what} must be a number, not {value!r}")
+    for name, role in ((coverage_edges, "coverage"), (score_edges, "score")):
+        if name not in classify_mod.AGG_NAMES:
+            sourmash_hip.log_sys_exit(logger, f"Unknown {role} aggregator {name!r}: expected one of {', '.join(classify_mod.AGG_NAMES)}")
+    if mode not in dereplicate_mod.MODES:
+        sourmash_hip.log_sys_exit(logger, f"Unknown dereplication mode {mode!r}: expected one of {', '.join(dereplicate_mod.MODES)}")
+    if prefer not in dereplicate_mod.PREFERENCES:
+        sourmash_hip.log_sys_exit(logger, f"Unknown preference {prefer!r}: expected one of {', '.join(dereplicate_mod.PREFERENCES)}")
+    outdir = _make_outdir(logger, outdir)
+    conn, run, n, done = _open_complete_run(logger, database, run_id, "Exporting")
+    frames = _score_frames(logger, conn, run)
+    lengths = genome_lengths(conn, run)
+    conn.close()
+    logger.info("Run %d has %d comparisons across %d genomes.", run.run_id, done, n)
+    mapping = _label_mapping(logger, run, label)
+    identity, cov, _hadamard = _relabelled(logger, run, frames, label)
+    labels = [str(x) for x in cov.columns]
+    length_of = {str(mapping[h]): lengths[h] for h in mapping}
+    try:
+        result = dereplicate_mod.dereplicate_matrices(labels, [length_of[x] for x in labels], identity.to_numpy(dtype=float), cov.to_numpy(dtype=float),
+                                                      prefer=prefer, min_identity=min_identity, cov_min=cov_min, score_edges=score_edges,
+                                                      coverage_edges=coverage_edges, mode=mode, engine=engine)  # fmt: skip
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, "dereplicate-run", err)
+    written = dereplicate_mod.write_tables(outdir, run.configuration.method, result)
+    logger.info("Wrote %d representatives of %d genomes to %s", int((result.representative == np.arange(n)).sum()), n, outdir)
     return written

@@ -477,3 +477,11 @@ def _comparison_matrices(conn, run: Run) -> tuple[list[str], dict]:
         for col, key in enumerate(("identity", "cov_query", "aln_length", "sim_errors"), start=2):
             mats[key][r_idx, c_idx] = np.array([r[col] for r in rows], dtype=float)  # None -> NaN
     return hashes, mats
+
+
+def genome_lengths(conn, run: Run) -> dict[str, int]:
+    """genome_hash -> ``genomes.length`` (bases) of the run's genomes."""
+    wanted = {a.genome_hash for a in run.fasta_hashes}
+    rows = conn.execute("SELECT g.genome_hash, g.length FROM genomes g JOIN runs_genomes rg ON rg.genome_hash = g.genome_hash WHERE rg.run_id=?",
+                        (run.run_id,)).fetchall()  # fmt: skip
+    return {h: int(length) for h, length in rows if h in wanted}

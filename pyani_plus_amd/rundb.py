@@ -10,8 +10,8 @@ Every run takes the same steps: register the genomes, record the run, find what 
 (``_begin_missing``), compute it (the method's ``_compute_missing_<method>``, listed in ``_METHODS``) and finish
 (``_finish_run``); ``_RunState`` carries what the steps share.
 
-The database layer is ``run_store`` and the seven reports of a recorded run (``export_run``, ``classify``, ``plot_run``,
-``plot_run_comp``, ``tree_run``, ``ordinate_run``, ``mantel_run_comp``) are ``reports``.  This module imports ``reports``, which
+The database layer is ``run_store`` and the eight reports of a recorded run (``export_run``, ``classify``, ``plot_run``,
+``plot_run_comp``, ``tree_run``, ``ordinate_run``, ``mantel_run_comp``, ``dereplicate_run``) are ``reports``.  This module imports ``reports``, which
 imports ``run_store``, never the other way round, and re-exports both: ``rundb.<name>`` is the public face of all three.
 """
 
@@ -37,6 +37,7 @@ import numpy as np
 
 from . import launch, wire
 from . import classify as classify_mod
+from . import dereplicate as dereplicate_mod
 from . import scatter as scatter_mod
 from . import tree as tree_mod
 from ._capi import HipBackendError
@@ -44,7 +45,7 @@ from .distributed import shard_bounds_by_cost
 from .engine import HipEngine, load_fasta_files
 from .methods import external_alignment_hip, fastani_hip, sourmash_hip, tetra_hip
 from .methods.external_alignment_hip import filename_stem  # noqa: F401  (reached as ``rundb.filename_stem``)
-from .reports import _require_database, classify, export_run, mantel_run_comp, ordinate_run, plot_run, plot_run_comp, tree_run  # noqa: F401
+from .reports import _require_database, classify, dereplicate_run, export_run, mantel_run_comp, ordinate_run, plot_run, plot_run_comp, tree_run  # noqa: F401
 from .run_store import (FASTA_EXTENSIONS, INSERT_COMPARISON, SCHEMA, Configuration, Run, RunGenomeAssociation, Session, _load_tile,  # noqa: F401
                         _open_run, _select_run_comparisons, _store_matrix_cache, add_run, cache_comparisons, cache_matrices, check_fasta,
                         connect_to_db, count_run_comparisons, db_configuration, db_genome, fasta_length_and_description,
@@ -903,11 +904,14 @@ _COMMANDS = {  # subcommand -> its call from (the parsed arguments, the engine o
                                                            formats=a.formats, engine=engine, logger=logger),
     "mantel-run-comp": lambda a, engine, logger: mantel_run_comp(a.database, a.outdir, a.run_ids, permutations=a.permutations, seed=a.seed, missing=a.missing,
                                                                  engine=engine, logger=logger),
+    "dereplicate-run": lambda a, engine, logger: dereplicate_run(a.database, a.outdir, run_id=a.run_id, label=a.label, min_identity=a.min_identity,
+                                                                 cov_min=a.cov_min, score_edges=a.score_edges, coverage_edges=a.coverage_edges, mode=a.mode,
+                                                                 prefer=a.prefer, engine=engine, logger=logger),
 }  # fmt: skip
 
 
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run,ordinate-run,mantel-run-comp} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run,ordinate-run,mantel-run-comp,dereplicate-run} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -978,6 +982,15 @@ def main(argv: list[str] | None = None) -> int:
         ("--permutations", {"type": int, "default": 9999, "help": "permutations of the other run's genomes, 0 to 1000000 (default 9999)"}),
         ("--seed", {"type": int, "default": 0, "help": "seed of the permutations, 0 to 2^64 - 1 (default 0)"}),
         _MISSING_OPTION,
+    ))  # fmt: skip
+    _report_parser(sub, "dereplicate-run", "one representative genome per group of a complete run as <method>_dereplicate.tsv and <method>_representatives.tsv",
+                   device="build the graph, select and assign", own=(
+        ("--min-identity", {"type": float, "default": dereplicate_mod.MIN_IDENTITY, "help": "two genomes are adjacent from this aggregated identity on (default 0.95)"}),
+        ("--cov-min", {"type": float, "default": classify_mod.MIN_COVERAGE, "help": "... and above this aggregated query coverage (default 0.5)"}),
+        ("--score-edges", {"choices": classify_mod.AGG_NAMES, "default": "mean"}),
+        ("--coverage-edges", {"choices": classify_mod.AGG_NAMES, "default": "min"}),
+        ("--mode", {"choices": dereplicate_mod.MODES, "default": "greedy", "help": "greedy: keep a genome that no kept genome is adjacent to; cover: greedy dominating set"}),
+        ("--prefer", {"choices": dereplicate_mod.PREFERENCES, "default": "length", "help": "the order of preference: the longer genome first (ties by label), or label order"}),
     ))  # fmt: skip
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
