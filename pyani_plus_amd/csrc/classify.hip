@@ -10,12 +10,9 @@
 //
 // Steps, all on the context's stream:
 //   1. cls_edges_kernel<false>: one workgroup per 64 x 64 tile (ti <= tj) of the upper triangle, a wave per row of
-//      the tile, a lane per column.  M[i,j] is read from global memory as it lies (a row of the tile is 512
-//      contiguous bytes).  M[j,i] lies in the mirrored tile, whose rows are read the same coalesced way into LDS and
-//      read back transposed.  The tile is held as [64][65] doubles: the transposed read has a lane stride of 65
-//      doubles = 130 words, so the 32 lanes of a ds_read_b64 group touch the 64 banks once each (bank = 2 * lane and
-//      2 * lane + 1, mod 64); with a stride of 64 doubles all of them would meet on two banks.  Coverage and score go
-//      through the same 33 KB buffer one after the other.  Each wave counts the surviving pairs of its (row, tile)
+//      the tile, a lane per column.  pair_tile_dev.h has the loader of a tile's values, shared with derep.hip: for
+//      the pairs kept here (i < j) a value is agg(M[j,i], M[i,j]) (pair_rule.h's agg2).  Coverage and score go
+//      through the same 33 KB LDS buffer one after the other.  Each wave counts the surviving pairs of its (row, tile)
 //      with one ballot and writes the count to counts[i][tj].
 //   2. pa_exclusive_scan_u32 over counts[n][nt], row-major: the offset of (row i, tile tj) is then the number of
 //      edges before it in (i, j) order, because inside one (row, tile) the lanes are consecutive j.  The total E is
@@ -32,49 +29,19 @@
 //   5. cls_gather_kernel: the four output arrays in sorted order.
 #include "pa_internal.h"
 
+// pair_rule.h asks for this and for -ffp-contract=off (the Makefile); the kernels here hold no multiply-add to contract
+#pragma clang fp contract(off)
+
+#include "pair_tile_dev.h"
+
 namespace {
 
-constexpr int kTile = 64;
-constexpr int kThreads = 256;
-constexpr int kRows = kTile / (kThreads / 64);  // rows of the tile per wave
-constexpr int kPad = kTile + 1;
-
-// Python's min([a, b]), max([a, b]) and numpy.mean([a, b]) with a = M[j,i], b = M[i,j]: the built-ins keep the first
-// argument unless the comparison with the second holds, so a NaN in a stays and a NaN in b is passed over.
-__device__ __forceinline__ double agg2(int how, double a, double b) {
-  if (how == PA_AGG_MIN) return b < a ? b : a;
-  if (how == PA_AGG_MAX) return b > a ? b : a;
-  return (a + b) / 2.0;
-}
+using pair_rule::agg_ok;
+using namespace pair_tile;  // kTile, kThreads, kRows, kPad, tile_values
 
 __device__ __forceinline__ uint64_t score_key(double s) {
   uint64_t bits = (uint64_t)__double_as_longlong(s == 0.0 ? 0.0 : s);
   return (bits >> 63) ? ~bits : (bits | (1ULL << 63));
-}
-
-// out[k] = agg(M[j,i], M[i,j]) for the rows i = i0 + wave * kRows + k of the tile and j = j0 + lane; NaN outside
-// the matrix.
-__device__ __forceinline__ void tile_values(const double *__restrict__ m, uint32_t n, uint32_t i0, uint32_t j0, int how,
-                                            double (*tile)[kPad], double out[kRows]) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const double nan = __builtin_nan("");
-  __syncthreads();  // the previous matrix has been read
-#pragma unroll
-  for (int k = 0; k < kRows; ++k) {
-    const uint32_t r = wave * kRows + k;
-    const uint32_t jj = j0 + r, ii = i0 + lane;
-    tile[r][lane] = (jj < n && ii < n) ? m[(uint64_t)jj * n + ii] : nan;
-  }
-  __syncthreads();
-  const uint32_t j = j0 + lane;
-#pragma unroll
-  for (int k = 0; k < kRows; ++k) {
-    const uint32_t r = wave * kRows + k;
-    const uint32_t i = i0 + r;
-    const double a = tile[lane][r];
-    const double b = (i < n && j < n) ? m[(uint64_t)i * n + j] : nan;
-    out[k] = agg2(how, a, b);
-  }
 }
 
 template <bool SCATTER>
@@ -90,8 +57,8 @@ __global__ __launch_bounds__(kThreads) void cls_edges_kernel(const double *__res
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t i0 = ti * kTile, j0 = tj * kTile;
   double c[kRows], s[kRows];
-  tile_values(cov, n, i0, j0, agg_cov, tile, c);
-  tile_values(score, n, i0, j0, agg_score, tile, s);
+  tile_values<false>(cov, n, i0, j0, agg_cov, tile, c);
+  tile_values<false>(score, n, i0, j0, agg_score, tile, s);
   const uint32_t j = j0 + lane;
   const uint64_t below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));
 #pragma unroll
@@ -130,8 +97,6 @@ __global__ __launch_bounds__(kThreads) void cls_gather_kernel(const uint32_t *__
   o_score[p] = e_score[e];
   o_cov[p] = e_cov[e];
 }
-
-inline bool agg_ok(int how) { return how == PA_AGG_MIN || how == PA_AGG_MAX || how == PA_AGG_MEAN; }
 
 }  // namespace
 

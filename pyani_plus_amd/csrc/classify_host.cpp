@@ -18,6 +18,14 @@
 
 #include "../../include/pyani_hip.h"
 
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#elif defined(__GNUC__)
+#pragma GCC optimize("fp-contract=off")
+#endif
+
+#include "pair_rule.h"  // after the pragma
+
 void pa_set_error(const char *fmt, ...);
 
 struct pa_cliques {
@@ -30,13 +38,8 @@ struct pa_cliques {
 
 namespace {
 
-// Python's min([a, b]) / max([a, b]) / numpy.mean([a, b]) with a = M[j,i], b = M[i,j]
-inline double agg2(int how, double a, double b) {
-  if (how == PA_AGG_MIN) return b < a ? b : a;
-  if (how == PA_AGG_MAX) return b > a ? b : a;
-  return (a + b) / 2.0;
-}
-inline bool agg_ok(int how) { return how == PA_AGG_MIN || how == PA_AGG_MAX || how == PA_AGG_MEAN; }
+using pair_rule::agg2;  // with a = M[j,i], b = M[i,j], i < j
+using pair_rule::agg_ok;
 
 // a node of the component tree: the leaves are the genomes, an inner node is the union of its two children
 struct Node {

@@ -4,11 +4,9 @@
 // The reference has no such command: DESIGN.md section 7k has the contract, tests/derep_cases.py restates it
 // independently, derep_host.cpp is the twin with the same bits and derep_rule.h states the rules once for both.
 //
-//   pa_derep_adjacency  derep_adjacency_kernel: one workgroup per 64 x 64 tile (ti <= tj) of the pairs, as classify.hip
-//                       tiles them: a wave per row of the tile, a lane per column, so that one ballot of the edge
-//                       predicate is one word of the row.  M[a,b] is read as it lies; M[b,a] lies in the mirrored tile,
-//                       whose rows are read the same coalesced way into LDS ([64][65] doubles: a lane stride of 130
-//                       words meets every bank once) and read back transposed.  The tile's 64 words go to LDS as well and
+//   pa_derep_adjacency  derep_adjacency_kernel: one workgroup per 64 x 64 tile (ti <= tj) of the pairs, classify.hip's
+//                       tiling and loader (pair_tile_dev.h): a wave per row of the tile, a lane per column, so that one
+//                       ballot of the edge predicate is one word of the row.  The tile's 64 words go to LDS as well and
 //                       lane t of the first wave gathers bit t of each: the word of row tj * 64 + t in the other
 //                       triangle.  Every word of the matrix is written by exactly one plain vector store.
 //   pa_derep_select     rounds of two small launches that the host enqueues PA_DEREP_BATCH at a time, in the manner of
@@ -35,44 +33,16 @@
 
 #include "block_reduce_dev.h"
 #include "derep_rule.h"
+#include "pair_tile_dev.h"
 #include "wave_dev.h"
 
 namespace {
 
-constexpr int kTile = 64;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kRows = kTile / kWaves;  // rows of a tile, or nodes of a word, per wave
-constexpr int kPad = kTile + 1;
+using namespace pair_tile;  // kTile, kThreads, kPad, tile_values, and kRows: rows of a tile, or nodes of a word, per wave
 static_assert(kTile == 64, "a tile's row is one word");
 
 // kDerepProgress: [0] nodes settled (decided in greedy mode, covered in cover mode), [1] rounds that had work
 constexpr uint32_t kSettled = 0, kRounds = 1;
-
-// out[k] = the aggregate of the pair (a, b), a = a0 + wave * kRows + k, b = b0 + lane; NaN outside the matrix.  On the
-// diagonal tile a > b happens: the two cells change places there (pair_value).
-__device__ __forceinline__ void tile_values(const double *__restrict__ m, uint32_t n, uint32_t a0, uint32_t b0, int how, double (*tile)[kPad],
-                                            double out[kRows]) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const double nan = __builtin_nan("");
-  __syncthreads();  // the previous matrix has been read
-#pragma unroll
-  for (int k = 0; k < kRows; ++k) {
-    const uint32_t r = wave * kRows + k;
-    const uint32_t bb = b0 + r, aa = a0 + lane;
-    tile[r][lane] = (bb < n && aa < n) ? m[(uint64_t)bb * n + aa] : nan;  // M[b0 + r, a0 + lane]
-  }
-  __syncthreads();
-  const uint32_t b = b0 + lane;
-#pragma unroll
-  for (int k = 0; k < kRows; ++k) {
-    const uint32_t r = wave * kRows + k;
-    const uint32_t a = a0 + r;
-    const double m_ba = tile[lane][r];
-    const double m_ab = (a < n && b < n) ? m[(uint64_t)a * n + b] : nan;
-    out[k] = derep::pair_value(how, a, b, m_ab, m_ba);
-  }
-}
 
 __global__ __launch_bounds__(kThreads) void derep_adjacency_kernel(const double *__restrict__ score, const double *__restrict__ cov, uint32_t n,
                                                                    uint32_t W, int agg_score, int agg_cov, double min_score, double cov_min,
@@ -84,8 +54,8 @@ __global__ __launch_bounds__(kThreads) void derep_adjacency_kernel(const double 
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t a0 = ti * kTile, b0 = tj * kTile;
   double c[kRows], s[kRows];
-  tile_values(cov, n, a0, b0, agg_cov, tile, c);
-  tile_values(score, n, a0, b0, agg_score, tile, s);
+  tile_values<true>(cov, n, a0, b0, agg_cov, tile, c);
+  tile_values<true>(score, n, a0, b0, agg_score, tile, s);
   const uint32_t b = b0 + lane;
 #pragma unroll
   for (int k = 0; k < kRows; ++k) {

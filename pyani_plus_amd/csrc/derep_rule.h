@@ -1,12 +1,13 @@
 // derep_rule.h -- the rules of dereplicate-run, stated once for derep.hip and derep_host.cpp (DESIGN.md section 7k has
 // the contract): the edge of two genomes, the total order in which the cover mode chooses, and the total order in which a
 // genome is given its representative.  Include this after `#pragma clang fp contract(off)` in a file that is also
-// compiled with -ffp-contract=off: the mean is one rounded addition and one division on both sides.
+// compiled with -ffp-contract=off, as pair_rule.h asks.
 #pragma once
 
 #include <cstdint>
 
 #include "../../include/pyani_hip.h"
+#include "pair_rule.h"
 
 #if defined(__HIPCC__)
 #define PA_DEREP_FN __host__ __device__ __forceinline__
@@ -19,25 +20,11 @@ namespace derep {
 constexpr uint32_t kMaxN = 65535;
 constexpr uint32_t kNone = PA_DEREP_NONE;  // the representative of a node that is adjacent to none
 
-PA_DEREP_FN bool agg_ok(int how) { return how == PA_AGG_MIN || how == PA_AGG_MAX || how == PA_AGG_MEAN; }
+// classify's aggregators and the value of a pair from its two cells (pair_rule.h)
+using pair_rule::agg_ok;
+using pair_rule::pair_value;
 PA_DEREP_FN bool mode_ok(int mode) { return mode == PA_DEREP_GREEDY || mode == PA_DEREP_COVER; }
 PA_DEREP_FN uint32_t words(uint32_t n) { return (n + 63u) / 64u; }
-
-// classify's aggregators: Python's min([a, b]), max([a, b]) and numpy.mean([a, b]) with a = M[hi,lo], b = M[lo,hi].  The
-// built-ins keep the first argument unless the comparison with the second holds, so a NaN in a stays and a NaN in b is
-// passed over.
-PA_DEREP_FN double agg2(int how, double a, double b) {
-  if (how == PA_AGG_MIN) return b < a ? b : a;
-  if (how == PA_AGG_MAX) return b > a ? b : a;
-  const double s = a + b;
-  return s / 2.0;
-}
-
-// The aggregated value of the pair (p, q) from its two cells: the cell of the larger index as the row comes first.
-// p == q is the pair (p, p) by the same formula.
-PA_DEREP_FN double pair_value(int how, uint32_t p, uint32_t q, double m_pq, double m_qp) {
-  return p < q ? agg2(how, m_qp, m_pq) : agg2(how, m_pq, m_qp);
-}
 
 // lo != hi are adjacent iff neither value is NaN, cov > cov_min (strict) and score >= min_score (inclusive)
 PA_DEREP_FN bool edge(double score, double cov, double min_score, double cov_min) {

@@ -23,7 +23,6 @@
 #pragma clang fp contract(off)
 
 #include "mantel_rule.h"
-#include "nj_rule.h"
 
 namespace {
 
@@ -47,23 +46,6 @@ __device__ __forceinline__ double lanes_tree(double a, uint32_t lane) {
     if (lane < w) a = a + other;
   }
   return a;
-}
-
-// pa_nj's rule over one matrix: bad[0] counts the cells that break it, bad[1] is the first of them
-__global__ __launch_bounds__(kThreads) void mantel_validate_kernel(const double *__restrict__ M, uint32_t n, unsigned long long *__restrict__ bad) {
-  const uint64_t cells = (uint64_t)n * n;
-  uint64_t count = 0, first = ~0ull;
-  for (uint64_t at = (uint64_t)blockIdx.x * kThreads + threadIdx.x; at < cells; at += (uint64_t)gridDim.x * kThreads) {
-    const uint32_t i = (uint32_t)(at / n), j = (uint32_t)(at % n);
-    if (nj::bad_cell(M[at], M[(uint64_t)j * n + i], i == j)) {
-      ++count;
-      if (at < first) first = at;
-    }
-  }
-  if (count) {  // integer atomics: the count and the minimum do not depend on the order
-    atomicAdd(&bad[0], (unsigned long long)count);
-    atomicMin(&bad[1], (unsigned long long)first);
-  }
 }
 
 // out[i] = the sum of row i's terms, j > i: M[i, j] itself (mean == nullptr) or the square of M[i, j] - *mean.
@@ -146,16 +128,16 @@ __global__ __launch_bounds__(kThreadsLong) void mantel_cross_kernel(const double
 
 // the workspace of a call over `total` cross sums (the identity's and the permutations')
 struct Work {
-  unsigned long long *bad;  // two words per matrix
   double *stats;            // mean_x, mean_y, ss_x, ss_y
   double *cross;            // `total` sums
   double *rows;             // n x kBatch row sums; the moments use its first n
   uint32_t *perms, *inverse;  // kBatch x n each
-  static uint64_t bytes(uint32_t n, uint64_t total) { return 32 + 32 + total * 8 + (uint64_t)n * kBatch * (8 + 4 + 4); }
+  // stats is given 64 bytes for its 32: 32 bytes earlier, every 256-byte wave read of pi in the cross kernel at N = 10 000,
+  // 1 000 sums (rows of 40 000 bytes) spans three 128-byte lines where every other permutation's spans two: 0.7 % of the call
+  static uint64_t bytes(uint32_t n, uint64_t total) { return 64 + total * 8 + (uint64_t)n * kBatch * (8 + 4 + 4); }
   Work(void *base, uint32_t n, uint64_t total) {
     char *at = static_cast<char *>(base);
-    bad = reinterpret_cast<unsigned long long *>(at), at += 32;
-    stats = reinterpret_cast<double *>(at), at += 32;
+    stats = reinterpret_cast<double *>(at), at += 64;
     cross = reinterpret_cast<double *>(at), at += total * 8;
     rows = reinterpret_cast<double *>(at), at += (uint64_t)n * kBatch * 8;
     perms = reinterpret_cast<uint32_t *>(at), at += (uint64_t)n * kBatch * 4;
@@ -166,21 +148,12 @@ struct Work {
 // pa_mantel behind the checks of its arguments; the host arrays it copies from outlive the stream's work (the caller waits)
 int mantel_device(pa_ctx *c, const double *d_X, const double *d_Y, uint32_t n, const uint32_t *h_perms, uint64_t n_perms,
                   const std::vector<uint32_t> &h_inverse, double *h_stats, double *h_cross) {
-  const uint64_t total = n_perms + 1, cells = (uint64_t)n * n;
+  const uint64_t total = n_perms + 1;
   PA_TRY(c->mantel_work.reserve(Work::bytes(n, total)));
   const Work w(c->mantel_work.p, n, total);
-  // the check of the two matrices: one read-back
   const double *matrices[2] = {d_X, d_Y};
-  for (int m = 0; m < 2; ++m) {
-    PA_HIP(hipMemsetAsync(w.bad + 2 * m, 0, 8, c->stream));
-    PA_HIP(hipMemsetAsync(w.bad + 2 * m + 1, 0xFF, 8, c->stream));
-    PA_TRY(PA_LAUNCH(c, mantel_validate_kernel, std::min<uint64_t>((cells + kThreads - 1) / kThreads, 1u << 16), kThreads, 0, matrices[m], n,
-                     w.bad + 2 * m));
-  }
-  unsigned long long bad[4] = {0, 0, 0, 0};
-  PA_TRY(pa_read_back(c, (const unsigned long long *)w.bad, bad, 4));
-  for (int m = 0; m < 2; ++m)
-    if (bad[2 * m]) return mantel::refuse_matrix(m ? "Y" : "X", n, bad[2 * m], bad[2 * m + 1]);
+  const char *const names[2] = {"X", "Y"};
+  PA_TRY(pa_check_distance_matrices(c, "pa_mantel", names, matrices, 2, n));  // one read-back for both
   // the moments: stats[m] = tri(M) / pairs, stats[2 + m] = tri of the centred squares
   const uint32_t row_blocks = (n + kThreads / kLanes - 1) / (kThreads / kLanes);
   const double pairs = (double)((uint64_t)n * (n - 1) / 2);

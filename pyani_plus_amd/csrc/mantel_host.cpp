@@ -22,8 +22,8 @@
 #pragma GCC optimize("fp-contract=off")
 #endif
 
+#include "distmat_rule.h"
 #include "mantel_rule.h"  // after the pragma
-#include "nj_rule.h"      // the check of a distance matrix is pa_nj's
 
 void pa_set_error(const char *fmt, ...);
 
@@ -53,15 +53,6 @@ double chain(const double *v, uint32_t n) {
   double s = kSumStart;
   for (uint32_t i = 0; i < n; ++i) s = s + v[i];
   return s;
-}
-
-// pa_nj's rule on a host matrix: the number of cells that break it and the first of them
-uint64_t bad_cells(const double *M, uint64_t N, uint64_t *first) {
-  uint64_t bad = 0;
-  for (uint64_t i = 0; i < N; ++i)
-    for (uint64_t j = 0; j < N; ++j)
-      if (nj::bad_cell(M[i * N + j], M[j * N + i], i == j) && bad++ == 0) *first = i * N + j;
-  return bad;
 }
 
 }  // namespace
@@ -114,12 +105,6 @@ int mantel::check_arguments(const void *X, const void *Y, uint32_t n, const uint
   });
 }
 
-int mantel::refuse_matrix(const char *name, uint32_t n, uint64_t bad, uint64_t first) {
-  pa_set_error("pa_mantel: %s[%llu,%llu] is not finite, is negative, differs from its transpose's bits or is a non-zero diagonal cell (%llu such cells)",
-               name, (unsigned long long)(first / n), (unsigned long long)(first % n), (unsigned long long)bad);
-  return PA_E_INVALID;
-}
-
 extern "C" int pa_mantel_permutations(uint64_t seed, uint32_t n, uint64_t first, uint64_t count, uint32_t *h_perms) {
   if (n < 1 || n > PA_MANTEL_MAX_N) { pa_set_error("pa_mantel_permutations: %u genomes; 1 to %d", n, PA_MANTEL_MAX_N); return PA_E_INVALID; }
   if (count && !h_perms) { pa_set_error("pa_mantel_permutations: null argument"); return PA_E_INVALID; }
@@ -142,10 +127,8 @@ extern "C" int pa_mantel_host(const double *h_X, const double *h_Y, uint32_t n, 
     const uint64_t N = n;
     const uint32_t *identity = inverse.data();
     const std::pair<const char *, const double *> matrices[2] = {{"X", h_X}, {"Y", h_Y}};
-    for (const auto &[name, M] : matrices) {
-      uint64_t first = 0;
-      if (const uint64_t bad = bad_cells(M, N, &first)) return mantel::refuse_matrix(name, n, bad, first);
-    }
+    for (const auto &[name, M] : matrices)
+      if (const int s = pa_check_distance_matrix_host("pa_mantel", name, M, n)) return s;
     // the moments
     std::vector<double> rows(N * std::min<uint64_t>(kHostBatch, n_perms + 1));
     const double pairs = (double)(N * (N - 1) / 2);

@@ -68,7 +68,5 @@ inline double row_sum(uint32_t i, uint32_t n, Term &&term) {
 // identity's inverse and then each row's: inverse[(1 + q) * n + h_perms[q * n + t]] = t.  mantel_host.cpp has the body.
 int check_arguments(const void *X, const void *Y, uint32_t n, const uint32_t *h_perms, uint64_t n_perms, const void *h_stats, const void *h_cross,
                     std::vector<uint32_t> *inverse);
-// The refusal of a matrix: `bad` cells break pa_nj's rule, the first of them in row-major order at cell `first`
-int refuse_matrix(const char *name, uint32_t n, uint64_t bad, uint64_t first);
 
 }  // namespace mantel

@@ -8,7 +8,7 @@
 //
 // The contract, in short (nj_rule.h has each formula as one function, shared with the twin):
 //   input   D, n x n f64 row-major, finite, >= 0, bitwise symmetric, zero diagonal, 1 <= n <= 65535; anything else is
-//           PA_E_INVALID and the message names the first offending cell in row-major order;
+//           PA_E_INVALID and the message names the first offending cell in row-major order (the check is distmat.hip's);
 //   ids     leaves 0 .. n - 1, the node made by join t is n + t;
 //   set-up  r[i] = D[i, 0] + ... + D[i, n - 1], added in this order into one accumulator; m = n live nodes;
 //   while m > 2
@@ -98,22 +98,6 @@ struct NjWork {
 };
 uint64_t table_f64(uint32_t n) { return n > 2 ? 2ull * (n - 2) + 1 : 1; }
 uint64_t table_u32(uint32_t n) { return n > 2 ? 2ull * (n - 2) + 2 : 2; }
-
-__global__ __launch_bounds__(kThreads) void nj_validate_kernel(const double *__restrict__ D, uint32_t n, unsigned long long *__restrict__ bad) {
-  const uint64_t cells = (uint64_t)n * n;
-  uint64_t count = 0, first = ~0ull;
-  for (uint64_t at = (uint64_t)blockIdx.x * kThreads + threadIdx.x; at < cells; at += (uint64_t)gridDim.x * kThreads) {
-    const uint32_t i = (uint32_t)(at / n), j = (uint32_t)(at % n);
-    if (nj::bad_cell(D[at], D[(uint64_t)j * n + i], i == j)) {
-      ++count;
-      if (at < first) first = at;
-    }
-  }
-  if (count) {  // integer atomics: the count and the minimum do not depend on the order
-    atomicAdd(&bad[0], (unsigned long long)count);
-    atomicMin(&bad[1], (unsigned long long)first);
-  }
-}
 
 // r[i] by walking k upwards: D[k, i] is D[i, k] bit for bit and is read coalesced across i.  Also id and slot_of.
 __global__ __launch_bounds__(kSumThreads) void nj_rowsum_kernel(const double *__restrict__ D, uint32_t n, double *__restrict__ r,
@@ -295,17 +279,7 @@ extern "C" int pa_nj(pa_ctx *c, double *d_D, uint32_t n, uint32_t *h_child, doub
   PA_HIP(hipSetDevice(c->device));
   NjWork w;
   PA_TRY(nj_workspace(c, n, &w));
-  // the check: one read-back
-  unsigned long long *d_bad = c->slot<unsigned long long>(kNjBad);
-  PA_HIP(hipMemsetAsync(d_bad, 0, 8, c->stream));
-  PA_HIP(hipMemsetAsync(d_bad + 1, 0xFF, 8, c->stream));
-  const uint64_t cells = (uint64_t)n * n;
-  PA_TRY(PA_LAUNCH(c, nj_validate_kernel, std::min<uint64_t>((cells + kThreads - 1) / kThreads, 1u << 16), kThreads, 0, (const double *)d_D, n, d_bad));
-  unsigned long long bad[2] = {0, 0};
-  PA_TRY(pa_read_back(c, d_bad, bad, 2));
-  PA_REQUIRE(bad[0] == 0,
-             "pa_nj: D[%llu,%llu] is not finite, is negative, differs from its transpose's bits or is a non-zero diagonal cell (%llu such cells)",
-             bad[1] / n, bad[1] % n, bad[0]);
+  PA_TRY(pa_check_distance_matrix(c, "pa_nj", d_D, n));  // one read-back
   if (n == 1) return PA_OK;
   PA_TRY(PA_LAUNCH(c, nj_rowsum_kernel, (n + kSumThreads - 1) / kSumThreads, kSumThreads, 0, (const double *)d_D, n, w.r, w.id, w.slot_of));
   NjPick *d_pick = c->slot<NjPick>(kNjPick);

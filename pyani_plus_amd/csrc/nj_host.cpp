@@ -21,6 +21,7 @@
 #pragma GCC optimize("fp-contract=off")
 #endif
 
+#include "distmat_rule.h"
 #include "nj_rule.h"  // after the pragma
 
 void pa_set_error(const char *fmt, ...);
@@ -41,17 +42,7 @@ extern "C" int pa_nj_host(const double *h_D, uint32_t n, uint32_t *h_child, doub
   if (n >= 2 && (!h_last || !h_last_len)) { pa_set_error("pa_nj_host: null argument for the last edge"); return PA_E_INVALID; }
   if (n >= 3 && (!h_child || !h_len)) { pa_set_error("pa_nj_host: null argument for the join table"); return PA_E_INVALID; }
   const uint64_t N = n;
-  {
-    uint64_t bad = 0, first = 0;
-    for (uint64_t i = 0; i < N; ++i)
-      for (uint64_t j = 0; j < N; ++j)
-        if (nj::bad_cell(h_D[i * N + j], h_D[j * N + i], i == j) && bad++ == 0) first = i * N + j;
-    if (bad) {
-      pa_set_error("pa_nj_host: D[%llu,%llu] is not finite, is negative, differs from its transpose's bits or is a non-zero diagonal cell (%llu such cells)",
-                   (unsigned long long)(first / N), (unsigned long long)(first % N), (unsigned long long)bad);
-      return PA_E_INVALID;
-    }
-  }
+  if (const int s = pa_check_distance_matrix_host("pa_nj_host", "D", h_D, n)) return s;
   if (n == 1) return PA_OK;
   return pa_host_guard("pa_nj_host", pa_set_error, [&]() -> int {
     std::vector<double> D(h_D, h_D + N * N);  // the joins overwrite it: work on a copy

@@ -1,6 +1,7 @@
 // nj_rule.h -- the arithmetic and the order of neighbour joining, stated once for nj.hip and nj_host.cpp (DESIGN.md
-// section 7h has the contract).  Every function is one line of the contract, each operation rounded on its own: include
-// this after `#pragma clang fp contract(off)` in a file that is also compiled with -ffp-contract=off.
+// section 7h has the contract; the check of D is distmat_rule.h's).  Every function is one line of the contract, each
+// operation rounded on its own: include this after `#pragma clang fp contract(off)` in a file that is also compiled with
+// -ffp-contract=off.
 #pragma once
 
 #include <cstdint>
@@ -64,15 +65,6 @@ PA_NJ_FN double row_sum_joined(double m, double d, double r_lo, double r_hi) {
   const double s = r_lo + r_hi;
   const double p = m * d;
   return 0.5 * (s - p);
-}
-
-// A cell the contract refuses: not finite, below zero, not the bits of its transpose, or a diagonal cell that is not zero
-PA_NJ_FN bool bad_cell(double v, double transposed, bool diagonal) {
-  uint64_t a, b;
-  __builtin_memcpy(&a, &v, 8);
-  __builtin_memcpy(&b, &transposed, 8);
-  const bool finite = (a & 0x7FF0000000000000ULL) != 0x7FF0000000000000ULL;
-  return !finite || v < 0.0 || a != b || (diagonal && v != 0.0);
 }
 
 }  // namespace nj

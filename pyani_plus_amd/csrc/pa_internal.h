@@ -141,10 +141,9 @@ constexpr uint32_t kDenseOr = 0, kDenseDistinct = 1;  // 64-bit words within kDe
 constexpr ScalarSlot kCompactTotal{8, 2};      // pa_classify_edges, pa_runcomp_join: the 64-bit total of their scan (written, never zeroed)
 constexpr ScalarSlot kRegionOverflow{12, 1};   // pa_sketch, pa_sketch_streamed: a region was too small; zeroed there, read by pa_sketch_from_regions
 constexpr ScalarSlot kNjPick{16, 8};           // pa_nj: the pair a join chose, written by its join kernel and read by its update kernel (NjPick, nj.hip)
-constexpr ScalarSlot kNjBad{24, 4};            // pa_nj: two 64-bit words zeroed / set as one: [0] cells that break the contract, [1] the first of them
-constexpr ScalarSlot kGowerBad{28, 4};         // pa_gower_center: the same two words for its own check of D
+constexpr ScalarSlot kDistBad{24, 8};          // pa_check_distance_matrices (pa_nj, pa_gower_center, pa_mantel): per matrix, of up to two, two 64-bit words: [0] cells that break the rule, [1] the first of them
 constexpr ScalarSlot kDerepProgress{14, 2};    // pa_derep_select: [0] nodes settled, [1] rounds that had work; zeroed as one, read once per batch of rounds
-static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow, kNjPick, kNjBad, kGowerBad, kDerepProgress}),
+static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow, kNjPick, kDistBad, kDerepProgress}),
               "two slots of pa_ctx::counters overlap or leave the block");
 
 // The words of pa_ctx::dict_scalars (pa_ctx::dict_slot), the hash dictionary's own block, touched by no other phase
@@ -170,7 +169,7 @@ constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of
 //   TETRA-hip (tetra.hip): tetra_tab, the genomes' first blocks and first chunks (u32[2 (n + 1)])
 //   tree-run (nj.hip): nj_work, the row sums, the slots' node ids, the scan's candidates and the join table
 //   ordinate-run (pcoa.hip): pcoa_work, the thin blocks Q and Y, the chunks' partial sums, the centring's row sums
-//   mantel-run-comp (mantel.hip): mantel_work, the check's words, the moments, the cross sums, a batch's permutations,
+//   mantel-run-comp (mantel.hip): mantel_work, the moments, the cross sums, a batch's permutations,
 //   inverses and row sums
 //   dereplicate-run (derep.hip): derep_work, the nodes still open as bits, then a round's new representatives or candidates
 #define PA_CTX_BUFFERS(ONE, PAIR)                                                                                   \
@@ -329,6 +328,17 @@ int pa_exclusive_scan_u32(pa_ctx *c, const uint32_t *d_in, uint32_t *d_out, uint
 inline int pa_scan_total_u32(pa_ctx *c, const uint32_t *d_in, uint32_t *d_out, uint64_t n, uint64_t *d_total_u64, uint64_t *h_total) {
   PA_TRY(pa_exclusive_scan_u32(c, d_in, d_out, n, d_total_u64));
   return pa_read_back(c, d_total_u64, h_total);
+}
+
+// distmat.hip
+// The check of `count` (1 or 2) n x n distance matrices on the device against distmat_rule.h's rule: one launch each, one
+// read-back for all through kDistBad.  PA_OK, or PA_E_INVALID with the message "<who>: <names[m]>[i,j] is ..." for the
+// first matrix, in argument order, that breaks it.
+int pa_check_distance_matrices(pa_ctx *c, const char *who, const char *const *names, const double *const *d_M, int count, uint32_t n);
+// One matrix, named D
+inline int pa_check_distance_matrix(pa_ctx *c, const char *who, const double *d_D, uint32_t n) {
+  const char *const name = "D";
+  return pa_check_distance_matrices(c, who, &name, &d_D, 1, n);
 }
 
 // fragani.hip

@@ -23,7 +23,7 @@
 //   LDS 128 * 33 * 8 + 32 * 32 * 8 = 42 KB at most; 124 VGPRs at p = 11 (four waves a SIMD), 222 at p = 32 (two).
 // The memory system bounds it: 8 bytes per cell of A against PC multiplications and additions.  No floating-point atomics.
 //
-// The centring.  Six launches: the check (pa_nj's rule, nj_rule.h), the rows' means of the squares (a lane per row,
+// The centring.  Six launches: the check (distmat.hip, pa_nj's too), the rows' means of the squares (a lane per row,
 // walking its column instead: D is bitwise symmetric and a column is read coalesced), the mean of the means (one lane:
 // the order is the contract's), B and its diagonal, the rows' sums of B^2 (B is bitwise symmetric too), and one lane
 // for the trace and the squared Frobenius norm.
@@ -31,7 +31,6 @@
 
 #pragma clang fp contract(off)
 
-#include "nj_rule.h"
 #include "pcoa_rule.h"
 #include "pcoa_solver.h"
 
@@ -168,22 +167,6 @@ int mul_tall(pa_ctx *c, const double *d_A, uint32_t n, const double *d_Q, uint32
 uint64_t partial_doubles(uint32_t n, uint32_t p) { return chunks_of(n) > 1 ? (uint64_t)chunks_of(n) * n * p : 0; }
 
 // ---- the centring
-__global__ __launch_bounds__(kThreads) void gower_validate_kernel(const double *__restrict__ D, uint32_t n, unsigned long long *__restrict__ bad) {
-  const uint64_t cells = (uint64_t)n * n;
-  uint64_t count = 0, first = ~0ull;
-  for (uint64_t at = (uint64_t)blockIdx.x * kThreads + threadIdx.x; at < cells; at += (uint64_t)gridDim.x * kThreads) {
-    const uint32_t i = (uint32_t)(at / n), j = (uint32_t)(at % n);
-    if (nj::bad_cell(D[at], D[(uint64_t)j * n + i], i == j)) {
-      ++count;
-      if (at < first) first = at;
-    }
-  }
-  if (count) {  // integer atomics: the count and the minimum do not depend on the order
-    atomicAdd(&bad[0], (unsigned long long)count);
-    atomicMin(&bad[1], (unsigned long long)first);
-  }
-}
-
 // out[i] = (M[i, 0]^2 + ... + M[i, n - 1]^2) / divisor for a bitwise symmetric M, by walking k upwards: M[k, i] is
 // M[i, k] bit for bit and is read coalesced across i
 __global__ __launch_bounds__(kSumThreads) void gower_row_squares_kernel(const double *__restrict__ M, uint32_t n, double divisor,
@@ -243,17 +226,7 @@ extern "C" int pa_gower_center(pa_ctx *c, const double *d_D, uint32_t n, double 
   PA_REQUIRE(n >= 1 && n <= 65535, "pa_gower_center: %u rows; 1 to 65535", n);
   PA_REQUIRE(d_D != nullptr && d_B != nullptr && h_trace != nullptr && h_fro2 != nullptr, "pa_gower_center: null argument");
   PA_HIP(hipSetDevice(c->device));
-  // the check: one read-back
-  unsigned long long *d_bad = c->slot<unsigned long long>(kGowerBad);
-  PA_HIP(hipMemsetAsync(d_bad, 0, 8, c->stream));
-  PA_HIP(hipMemsetAsync(d_bad + 1, 0xFF, 8, c->stream));
-  const uint64_t cells = (uint64_t)n * n;
-  PA_TRY(PA_LAUNCH(c, gower_validate_kernel, std::min<uint64_t>((cells + kThreads - 1) / kThreads, 1u << 16), kThreads, 0, d_D, n, d_bad));
-  unsigned long long bad[2] = {0, 0};
-  PA_TRY(pa_read_back(c, d_bad, bad, 2));
-  PA_REQUIRE(bad[0] == 0,
-             "pa_gower_center: D[%llu,%llu] is not finite, is negative, differs from its transpose's bits or is a non-zero diagonal cell (%llu such cells)",
-             bad[1] / n, bad[1] % n, bad[0]);
+  PA_TRY(pa_check_distance_matrix(c, "pa_gower_center", d_D, n));  // one read-back
   // workspace: r, the rows' sums of B^2, B's diagonal, then g, the trace and the squared norm
   PA_TRY(c->pcoa_work.reserve((3ull * n + 3) * 8));
   double *r = c->pcoa_work.as<double>(), *row_sq = r + n, *diag = row_sq + n, *g = diag + n, *totals = g + 1;

@@ -22,8 +22,8 @@
 #pragma GCC optimize("fp-contract=off")
 #endif
 
-#include "nj_rule.h"    // after the pragma; the check of a distance matrix is pa_nj's
-#include "pcoa_rule.h"
+#include "distmat_rule.h"
+#include "pcoa_rule.h"  // after the pragma
 #include "pcoa_solver.h"
 
 void pa_set_error(const char *fmt, ...);
@@ -324,17 +324,7 @@ extern "C" int pa_gower_center_host(const double *h_D, uint32_t n, double *h_B, 
   if (n < 1 || n > 65535) { pa_set_error("pa_gower_center_host: %u rows; 1 to 65535", n); return PA_E_INVALID; }
   if (!h_D || !h_B || !h_trace || !h_fro2) { pa_set_error("pa_gower_center_host: null argument"); return PA_E_INVALID; }
   const uint64_t N = n;
-  {
-    uint64_t bad = 0, first = 0;
-    for (uint64_t i = 0; i < N; ++i)
-      for (uint64_t j = 0; j < N; ++j)
-        if (nj::bad_cell(h_D[i * N + j], h_D[j * N + i], i == j) && bad++ == 0) first = i * N + j;
-    if (bad) {
-      pa_set_error("pa_gower_center_host: D[%llu,%llu] is not finite, is negative, differs from its transpose's bits or is a non-zero diagonal cell (%llu such cells)",
-                   (unsigned long long)(first / N), (unsigned long long)(first % N), (unsigned long long)bad);
-      return PA_E_INVALID;
-    }
-  }
+  if (const int s = pa_check_distance_matrix_host("pa_gower_center_host", "D", h_D, n)) return s;
   return pa_host_guard("pa_gower_center_host", pa_set_error, [&]() -> int {
     std::vector<double> r(n), row_sq(n);
     const double count = (double)n;

@@ -646,9 +646,7 @@ class HipEngine:
         n = d_score.shape[0]
         if d_score.shape != (n, n) or d_cov.shape != (n, n):
             raise ValueError(f"score {tuple(d_score.shape)} and coverage {tuple(d_cov.shape)} must be square and equal")
-        for name, role in ((score_edges, "score"), (coverage_edges, "coverage")):
-            if name not in _capi.PA_AGG:
-                raise ValueError(f"Unknown {role} aggregator {name!r}: expected one of min, max, mean")
+        agg_score, agg_cov = _pair_agg(score_edges, "score"), _pair_agg(coverage_edges, "coverage")
         cap = n * (n - 1) // 2
         e_i = t.empty(cap, dtype=t.int32, device=self.device)
         e_j = t.empty(cap, dtype=t.int32, device=self.device)
@@ -657,7 +655,7 @@ class HipEngine:
         count = C.c_uint64(0)
         self._check(
             self.lib.pa_classify_edges(
-                self.ctx, d_score.data_ptr(), d_cov.data_ptr(), n, _capi.PA_AGG[score_edges], _capi.PA_AGG[coverage_edges], float(cov_min), cap,
+                self.ctx, d_score.data_ptr(), d_cov.data_ptr(), n, agg_score, agg_cov, float(cov_min), cap,
                 e_i.data_ptr(), e_j.data_ptr(), e_s.data_ptr(), e_c.data_ptr(), C.byref(count),
             ),  # fmt: skip
             "pa_classify_edges",
@@ -962,7 +960,7 @@ class HipEngine:
         n = s.shape[0]
         bits = t.empty((n, (n + 63) // 64), dtype=t.int64, device=self.device)
         self._check(
-            self.lib.pa_derep_adjacency(self.ctx, s.data_ptr(), c.data_ptr(), n, _derep_agg(score_edges, "score"), _derep_agg(coverage_edges, "coverage"),
+            self.lib.pa_derep_adjacency(self.ctx, s.data_ptr(), c.data_ptr(), n, _pair_agg(score_edges, "score"), _pair_agg(coverage_edges, "coverage"),
                                         float(min_score), float(cov_min), bits.data_ptr()),
             "pa_derep_adjacency",
         )  # fmt: skip
@@ -1002,7 +1000,7 @@ class HipEngine:
             raise ValueError(f"{r.numel()} marks of {r.dtype} for {n} nodes, expected {n} of uint8")
         rep = t.empty(max(n, 1), dtype=t.int32, device=self.device)
         rep_score = t.empty(max(n, 1), dtype=t.float64, device=self.device)
-        self._check(self.lib.pa_derep_assign(self.ctx, s.data_ptr(), n, _derep_agg(score_edges, "score"), b.data_ptr(), r.data_ptr(), rep.data_ptr(),
+        self._check(self.lib.pa_derep_assign(self.ctx, s.data_ptr(), n, _pair_agg(score_edges, "score"), b.data_ptr(), r.data_ptr(), rep.data_ptr(),
                                              rep_score.data_ptr()), "pa_derep_assign")  # fmt: skip
         return rep[:n], rep_score[:n]
 
@@ -1137,7 +1135,7 @@ class Dereplication(NamedTuple):
     rounds: int | None
 
 
-def _derep_agg(name: str, role: str) -> int:
+def _pair_agg(name: str, role: str) -> int:
     if name not in _capi.PA_AGG:
         raise ValueError(f"Unknown {role} aggregator {name!r}: expected one of min, max, mean")
     return _capi.PA_AGG[name]
@@ -1163,7 +1161,7 @@ def derep_adjacency_host(score, cov, *, score_edges: str = "mean", coverage_edge
     n = s.shape[0]
     bits = np.zeros((n, (n + 63) // 64), dtype=np.uint64)
     check(
-        _capi.load_library().pa_derep_adjacency_host(s.ctypes.data, c.ctypes.data, n, _derep_agg(score_edges, "score"), _derep_agg(coverage_edges, "coverage"),
+        _capi.load_library().pa_derep_adjacency_host(s.ctypes.data, c.ctypes.data, n, _pair_agg(score_edges, "score"), _pair_agg(coverage_edges, "coverage"),
                                                      float(min_score), float(cov_min), bits.ctypes.data, int(threads)),
         "pa_derep_adjacency_host",
     )  # fmt: skip
@@ -1191,7 +1189,7 @@ def derep_assign_host(score, bits, is_rep, *, score_edges: str = "mean", threads
     if b.size != n * ((n + 63) // 64) or r.size != n:
         raise ValueError(f"bit matrix of {b.size} words and {r.size} marks for {n} nodes")
     rep, rep_score = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.float64)
-    check(_capi.load_library().pa_derep_assign_host(s.ctypes.data, n, _derep_agg(score_edges, "score"), b.ctypes.data, r.ctypes.data, rep.ctypes.data,
+    check(_capi.load_library().pa_derep_assign_host(s.ctypes.data, n, _pair_agg(score_edges, "score"), b.ctypes.data, r.ctypes.data, rep.ctypes.data,
                                                     rep_score.ctypes.data, int(threads)), "pa_derep_assign_host")  # fmt: skip
     return rep[:n], rep_score[:n]
 

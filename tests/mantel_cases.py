@@ -9,6 +9,8 @@ from functools import lru_cache
 
 import numpy as np
 
+from tests.helpers import invalid_distance_matrices
+
 LANES = 64
 SIZES = (3, 4, 63, 64, 65, 127, 128, 129, 130, 513)  # the minimum, the edges of one and two strides, rows 62 to 64 either side of a stride
 GENERATED = 20  # generated permutations a size, before the reversal and the one with pi[0] = n - 1
@@ -130,18 +132,7 @@ def case(n: int):
 
 def invalid_matrices(n: int = 9):
     """``(what, a matrix that breaks the rule, the first offending cell in row-major order)``."""
-    out = []
-    for what, cell, value in (("nan", (2, 5), np.nan), ("negative", (3, 1), -0.25)):
-        d = random_distances(n, 5)
-        d[cell] = d[cell[::-1]] = value
-        out.append((what, d, min(cell, cell[::-1])))
-    d = random_distances(n, 5)
-    d[4, 6] = np.nextafter(d[4, 6], 2.0)
-    out.append(("asymmetric", d, (4, 6)))
-    d = random_distances(n, 5)
-    d[7, 7] = 0.5
-    out.append(("diagonal", d, (7, 7)))
-    return out
+    return invalid_distance_matrices(n, 5)
 
 
 def bits(x) -> np.ndarray:

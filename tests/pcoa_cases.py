@@ -26,6 +26,8 @@ from typing import NamedTuple
 
 import numpy as np
 
+from tests.helpers import invalid_distance_matrices
+
 ROOT = Path(__file__).resolve().parent.parent
 TOL = 1e-10  # the solver's default stop rule
 PHASE1_CAP = 200  # iterations of the unshifted phase, at most
@@ -128,16 +130,7 @@ CENTRING_SIZES = (1, 2, 3, 65, 257)
 
 def invalid_matrices() -> list[tuple[str, np.ndarray, tuple[int, int]]]:
     """(what, matrix, the first offending cell in row-major order)."""
-    base = random_distances(6, 1)
-    out = []
-    for what, (i, j), value, mirror in (("nan", (1, 4), np.nan, True), ("negative", (2, 3), -0.25, True),
-                                        ("asymmetric", (3, 5), 0.75, False), ("diagonal", (4, 4), 0.5, False)):
-        D = base.copy()
-        D[i, j] = value
-        if mirror:
-            D[j, i] = value
-        out.append((what, D, (i, j)))
-    return out
+    return invalid_distance_matrices(6, 1)
 
 
 # ---------------------------------------------------------------- the start block

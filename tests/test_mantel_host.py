@@ -17,6 +17,7 @@ from pyani_plus_amd import mantel as mantel_mod
 from pyani_plus_amd._capi import PA_E_INVALID, HipBackendError
 from pyani_plus_amd.engine import mantel_host, mantel_permutations
 from tests import mantel_cases as mc
+from tests.helpers import distance_check_cases, distance_refusal
 from tests.mantel_cases import bits
 
 HEADER = Path(__file__).resolve().parent.parent / "include" / "pyani_hip.h"
@@ -202,6 +203,16 @@ def test_refuses_matrices_that_break_the_rule(what, D, cell):
     perms = mc.permutations(1, len(D), 0, 2)
     refused(rf"pa_mantel: X\[{cell[0]},{cell[1]}\] is not finite, is negative", D, good, perms)
     refused(rf"pa_mantel: Y\[{cell[0]},{cell[1]}\] is not finite, is negative", good, D, perms)
+
+
+@pytest.mark.parametrize("name,D,cell,count", distance_check_cases(), ids=[c[0] for c in distance_check_cases()])
+def test_a_refusal_names_the_first_cell_and_counts_them_all(name, D, cell, count):
+    good = mc.random_distances(len(D), 8)
+    perms = mc.permutations(1, len(D), 0, 2)
+    for matrix, arguments in (("X", (D, good, perms)), ("Y", (good, D, perms))):
+        with pytest.raises(HipBackendError) as err:
+            mantel_host(*arguments)
+        assert err.value.status == PA_E_INVALID and str(err.value).endswith(distance_refusal("pa_mantel", matrix, cell, count))
 
 
 def test_two_bad_matrices_name_x_and_bad_rows_come_first():

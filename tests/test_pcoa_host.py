@@ -17,7 +17,7 @@ from pyani_plus_amd._capi import PA_E_INVALID, PA_E_NOCONVERGE, HipBackendError
 from pyani_plus_amd.engine import gower_center_host, mul_tall_host, symm_top_eigs_host
 from tests import pcoa_cases as pc
 from tests.fake_engine import OracleEngine
-from tests.helpers import FIXTURE_SETS, GOLDEN
+from tests.helpers import FIXTURE_SETS, GOLDEN, distance_check_cases, distance_refusal
 
 
 def bits(x) -> np.ndarray:
@@ -84,6 +84,13 @@ def test_centring_refuses_and_names_the_cell(what, D, cell):
     assert err.value.status == PA_E_INVALID
     good = pc.random_distances(3, 1)
     assert np.array_equal(bits(gower_center_host(good)[0]), bits(pc.gower_center(good).B))  # a good call works afterwards
+
+
+@pytest.mark.parametrize("name,D,cell,count", distance_check_cases(), ids=[c[0] for c in distance_check_cases()])
+def test_centring_names_the_first_cell_and_counts_them_all(name, D, cell, count):
+    with pytest.raises(HipBackendError) as err:
+        gower_center_host(D)
+    assert err.value.status == PA_E_INVALID and str(err.value).endswith(distance_refusal("pa_gower_center_host", "D", cell, count))
 
 
 # ------------------------------------------------------------------ the solver

@@ -15,7 +15,7 @@ from pyani_plus_amd._capi import PA_E_INVALID, HipBackendError
 from pyani_plus_amd.engine import nj_tree_host
 from tests import tree_cases as tc
 from tests.fake_engine import OracleEngine
-from tests.helpers import FIXTURE_SETS, GOLDEN
+from tests.helpers import FIXTURE_SETS, GOLDEN, distance_check_cases, distance_refusal
 
 RESTATED = [c.name for c in tc.cases() if len(c.D) <= tc.RESTATED_UP_TO]
 ADDITIVE = [c.name for c in tc.cases() if c.edges is not None]
@@ -100,6 +100,13 @@ def test_invalid_matrices_are_refused(what, D, cell):
     with pytest.raises(HipBackendError, match=rf"pa_nj_host: D\[{cell[0]},{cell[1]}\]") as err:
         nj_tree_host(D)
     assert err.value.status == PA_E_INVALID
+
+
+@pytest.mark.parametrize("name,D,cell,count", distance_check_cases(), ids=[c[0] for c in distance_check_cases()])
+def test_a_refusal_names_the_first_cell_and_counts_them_all(name, D, cell, count):
+    with pytest.raises(HipBackendError) as err:
+        nj_tree_host(D)
+    assert err.value.status == PA_E_INVALID and str(err.value).endswith(distance_refusal("pa_nj_host", "D", cell, count))
 
 
 def test_no_nodes_is_refused():

@@ -28,6 +28,8 @@ from typing import NamedTuple
 
 import numpy as np
 
+from tests.helpers import invalid_distance_matrices
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -237,13 +239,4 @@ def restated(name: str) -> Joins:
 
 def invalid_matrices() -> list[tuple[str, np.ndarray, tuple[int, int]]]:
     """(what, matrix, the first offending cell in row-major order)."""
-    base = random_symmetric(6, 1)
-    out = []
-    for what, (i, j), value, mirror in (("nan", (1, 4), np.nan, True), ("negative", (2, 3), -0.25, True), ("infinite", (0, 5), np.inf, True),
-                                        ("asymmetric", (3, 5), 0.75, False), ("diagonal", (4, 4), 0.5, False)):
-        D = base.copy()
-        D[i, j] = value
-        if mirror:
-            D[j, i] = value
-        out.append((what, D, (i, j)))
-    return out
+    return invalid_distance_matrices(6, 1)
