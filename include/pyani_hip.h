@@ -739,6 +739,52 @@ PA_API int pa_nj(pa_ctx *ctx, double *d_D, uint32_t n, uint32_t *h_child, double
 PA_API int pa_nj_host(const double *h_D, uint32_t n, uint32_t *h_child, double *h_len, uint32_t *h_last, double *h_last_len,
                       uint32_t n_threads);
 
+/* ---- bootstrap-run: column-bootstrap support of a run's neighbour-joining tree ----
+ * Replaces nothing in the reference: pyani-plus writes no tree and no support.  The definitions below are this project's
+ * own contract (Felsenstein's bootstrap over the columns of the alignment of an external-alignment-hip run), pinned by an
+ * independent restatement in tests/bootstrap_cases.py.  DESIGN.md section 7l.
+ *
+ * Weights.  fin is the splitmix64 finaliser of mantel-run-comp.  Replicate r of `seed` over L = n_cols columns has
+ * base = fin(fin(seed) + r); its draw t = 0 .. L - 1 hits column mulhi64(fin(base + t), L), the high 64 bits of the
+ * 128-bit product; w_r[c] is the number of hits on column c, a uint8.
+ * Counts.  Per replicate and ordered pair of rows, over the columns c: M = sum of w[c] where q_c == s_c and q_c != '-',
+ * B = sum of w[c] where q_c != '-' and s_c != '-'; the diagonal included, so B[i, i] is row i's weighted residue count
+ * n_i.  Integers, at most L < 2^32.
+ * Distances.  aln = n_i + n_j - B[i, j]; D[i, j] = 1.0 - (double)M[i, j] / (double)aln, `missing` when aln is 0, 0.0 for
+ * i == j: one division and one subtraction, no FMA.
+ * Support.  A join table (pa_nj) is an unrooted tree.  The clade of an edge is the set of leaves on its side away from
+ * leaf 0; it is trivial with fewer than 2 or more than n - 2 leaves.  Node n + t stands for the edge above it: the edge
+ * to the node whose join takes it, and the last edge for the last node made.  Its support is the number of replicate
+ * trees that have an edge with the same clade (equal as sets); a trivial clade is in every tree, so its support is n_reps.
+ *
+ *   pa_msa_boot_weights        (host) rows first .. first + count - 1 of the weights of `seed`: count x n_cols uint8.  A
+ *        row depends on (seed, n_cols, its number) alone.  PA_E_INVALID, naming the replicate and the column, for a
+ *        weight that would pass 255.
+ *   pa_msa_boot_counts         (device) d_planes as pa_msa_pack made them for n_rows rows; h_weights: n_reps x n_cols
+ *        uint8 on the host, every row adding up to n_cols (else PA_E_INVALID naming the row).  d_match, d_both:
+ *        n_reps x n_rows x n_rows uint32, replicate after replicate.  Only the 64 x 64 tiles on and above the diagonal are
+ *        evaluated and the rest mirrored.  Up to PA_MSA_BOOT_BATCH replicates go into one launch; a call may hold more.
+ *        The call returns when the stream has finished.
+ *   pa_msa_boot_counts_host    the same from the rows as bytes (n_rows rows of row_stride >= n_cols bytes, as
+ *        pa_msa_copy_rows lays them out) on n_threads host threads (0: as many as the process may use).
+ *   pa_msa_boot_distances      (device) counts -> D, n_reps x n x n f64 on the device, replicate after replicate, each
+ *        ready for pa_nj as it is.  `missing` finite and >= 0.
+ *   pa_msa_boot_distances_host the same on the host, with the same bits.
+ *   pa_tree_support            (host) h_ref_child: the child table of the reference tree, 2 (n - 2) uint32;
+ *        h_rep_child: those of n_reps replicate trees, one after the other; h_support: n - 2 uint32, entry t for node
+ *        n + t.  4 <= n <= 65535.  Day's algorithm: O(n) per tree, exact.  PA_E_INVALID for a table that is no tree. */
+#define PA_MSA_BOOT_BATCH 32 /* replicates the device takes per launch; shows in no result */
+PA_API int pa_msa_boot_weights(uint64_t seed, uint64_t n_cols, uint64_t first, uint64_t count, uint8_t *h_weights);
+PA_API int pa_msa_boot_counts(pa_ctx *ctx, const uint32_t *d_planes, uint32_t n_rows, uint64_t n_cols, uint32_t bits, const uint8_t *h_weights,
+                              uint32_t n_reps, uint32_t *d_match, uint32_t *d_both);
+PA_API int pa_msa_boot_counts_host(const uint8_t *h_rows, uint64_t row_stride, uint32_t n_rows, uint64_t n_cols, const uint8_t *h_weights,
+                                   uint32_t n_reps, uint32_t *h_match, uint32_t *h_both, uint32_t n_threads);
+PA_API int pa_msa_boot_distances(pa_ctx *ctx, const uint32_t *d_match, const uint32_t *d_both, uint32_t n, uint32_t n_reps, double missing,
+                                 double *d_D);
+PA_API int pa_msa_boot_distances_host(const uint32_t *h_match, const uint32_t *h_both, uint32_t n, uint32_t n_reps, double missing, double *h_D,
+                                      uint32_t n_threads);
+PA_API int pa_tree_support(uint32_t n, const uint32_t *h_ref_child, uint32_t n_reps, const uint32_t *h_rep_child, uint32_t *h_support);
+
 /* ---- ordinate-run: principal coordinates (classical scaling) of a distance matrix ----
  * Replaces nothing in the reference: pyani-plus writes no ordination.  The definitions below are this project's own
  * contract, pinned by an independent restatement in tests/pcoa_cases.py; no parity with any other program is claimed.
@@ -910,7 +956,9 @@ PA_API int pa_derep_assign_host(const double *h_S, uint32_t n, int agg_score, co
 #define PA_PROF_NJ_SCAN 13   /* tree-run: the scan of the live pairs before each join (nj_scan_kernel) */
 #define PA_PROF_NJ_JOIN 14   /* tree-run: the choice among the tiles' candidates and the record (nj_join_kernel) */
 #define PA_PROF_NJ_UPDATE 15 /* tree-run: the new node's row and column, the row sums, the swap-remove (nj_update_kernel) */
-#define PA_PROF_NPHASES 16
+#define PA_PROF_MSA_BOOT 16      /* bootstrap-run: weight planes, weighted pair counts, mirror (msa_boot_pairs_kernel) */
+#define PA_PROF_MSA_BOOT_DIST 17 /* bootstrap-run: counts -> distances (msa_boot_distances_kernel) */
+#define PA_PROF_NPHASES 18
 PA_API int pa_prof_enable(pa_ctx *ctx, int on);
 PA_API int pa_prof_reset(pa_ctx *ctx);
 /* total milliseconds and number of timed launches of a phase (syncs the stream) */

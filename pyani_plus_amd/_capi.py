@@ -31,6 +31,7 @@ PA_EIGS_MAX_K = 24  # pa_symm_top_eigs: eigenpairs, at most
 PA_MANTEL_MAX_N = 16384  # pa_mantel, pa_mantel_host: genomes, at most (a 128 KB row)
 PA_MANTEL_LANES = 64  # ... accumulators of a row's sum
 PA_MANTEL_BATCH = 256  # ... cross sums the device makes per launch; shows in no result
+PA_MSA_BOOT_BATCH = 32  # pa_msa_boot_counts: replicates the device takes per launch; shows in no result
 PA_DEREP_GREEDY, PA_DEREP_COVER = 0, 1  # pa_derep_select: the modes
 PA_DEREP_MODE = {"greedy": PA_DEREP_GREEDY, "cover": PA_DEREP_COVER}
 PA_DEREP_BATCH = 64  # ... rounds the device enqueues between two read-backs; shows in no result
@@ -50,7 +51,8 @@ PA_BIN2D_NONE = 0xFFFFFFFFFFFFFFFF  # the `last` of an empty cell
 PA_TETRA_BINS = 336  # pa_tetra_counts: u64 per genome, 256 tetra-, 64 tri- and 16 dinucleotides
 PA_TETRA_WORDS = 256  # columns of a Z-score row and of a unit row
 PROF_PHASES = {"kmer_hash": 0, "sketch_sort": 1, "pair_dict": 2, "pair_count": 3, "ani": 4, "frag_index": 5, "frag_seed": 6, "frag_map": 7,
-               "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11, "rowdist": 12, "nj_scan": 13, "nj_join": 14, "nj_update": 15}
+               "msa_pack": 8, "msa_pairs": 9, "cls_edges": 10, "cls_sort": 11, "rowdist": 12, "nj_scan": 13, "nj_join": 14, "nj_update": 15,
+               "msa_boot": 16, "msa_boot_dist": 17}
 PA_AGG = {"min": 0, "max": 1, "mean": 2}
 
 _u8p = C.POINTER(C.c_uint8)
@@ -223,6 +225,12 @@ SIGNATURES: dict[str, tuple] = {
     "pa_mantel_permutations": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
     "pa_mantel": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
     "pa_mantel_host": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, C.c_uint32]),
+    "pa_msa_boot_weights": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _vp]),
+    "pa_msa_boot_counts": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    "pa_msa_boot_counts_host": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, C.c_uint32, _vp, _vp, C.c_uint32]),
+    "pa_msa_boot_distances": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_double, _vp]),
+    "pa_msa_boot_distances_host": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_double, _vp, C.c_uint32]),
+    "pa_tree_support": (C.c_int, [C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "pa_derep_adjacency": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),
     "pa_derep_adjacency_host": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int, C.c_int, C.c_double, C.c_double, _vp, C.c_uint32]),
     "pa_derep_select": (C.c_int, [_vp, _vp, C.c_uint32, C.c_int, _vp, _u32p, _u32p]),

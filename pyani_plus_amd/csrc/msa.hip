@@ -12,24 +12,13 @@
 //   B += popcount(ng_q & ng_s)    v_and + v_bcnt
 // b + 4 VALU instructions for 32 columns of one pair.
 //
-// Plane layout (word-major, so that the 64 rows of a tile are one 256-byte load per plane and word):
-//   planes[(w * P + p) * n_pad + row],  P = b + 1 (plane b = non-gap),  n_pad = n_rows rounded up to 64.
+// msa_tile_dev.h has the plane layout and the tile that this kernel shares with the weighted counts of msa_boot.hip.
 #include <algorithm>
 
-#include "pa_internal.h"
+#include "msa_tile_dev.h"
 
 namespace {
-constexpr int kTile = 64;     // rows of a pair tile, queries and subjects alike
-constexpr int kThreads = 256; // 16 x 16 lanes of 4 x 4 pairs each
-constexpr int kChunk = 8;     // words of a stage through LDS
-constexpr uint32_t kMaxBits = 8;
-
-// v_bitop3_b32 (gfx950): bit i of the result is bit (a_i << 2 | b_i << 1 | c_i) of the table; the table of f(a, b, c) is
-// f(0xf0, 0xcc, 0xaa).  The compiler does not always fuse these itself (it kept v_xor + v_or + v_not + v_and here).
-constexpr uint32_t kXorOr = (0xf0u ^ 0xccu) | 0xaau;  // (a ^ b) | c
-constexpr uint32_t kAndNot = ~0xf0u & 0xccu & 0xffu;   // ~a & b
-template <uint32_t T>
-__device__ inline uint32_t bitop3_t(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, T); }
+using namespace msa_tile;
 
 struct CodeTable {
   uint32_t w[64];  // byte c -> code (w[c / 4] >> (8 * (c % 4))) & 0xff
@@ -75,104 +64,38 @@ __global__ __launch_bounds__(kThreads) void msa_pack_kernel(const uint8_t *__res
   if (count) atomicAdd(nongap + row, count);
 }
 
-// Upper-triangle tile t (row-major over the pairs ti <= tj of nt x nt tiles) -> (ti, tj)
-__device__ inline void tri_tile(uint32_t t, uint32_t nt, uint32_t &ti, uint32_t &tj) {
-  // tiles before row i: i * nt - i * (i - 1) / 2
-  const double b = 2.0 * nt + 1.0;
-  uint32_t i = (uint32_t)((b - sqrt(b * b - 8.0 * (double)t)) * 0.5);
-  if (i >= nt) i = nt - 1;
-  auto start = [nt](uint32_t r) { return (uint64_t)r * nt - (uint64_t)r * (r - 1u) / 2u; };
-  while (i > 0 && start(i) > t) --i;
-  while (i + 1 < nt && start(i + 1) <= t) ++i;
-  ti = i;
-  tj = i + (uint32_t)(t - start(i));
-}
-
-// One block: a 64 x 64 tile of pairs over the words [blockIdx.y * words_per_split, ...) -- the whole row when
-// words_per_split covers it, a slice of it otherwise (split-K: the partial counts are added with atomics).
-// Thread (tx, ty) owns queries ty*4 .. ty*4+3 and subjects tx*4 .. tx*4+3 of the tile.  Rows outside [q0, q1) or
-// [s0, s1), and words past the last, are staged as zero: no gap bit, so they count nothing.
+// One block: a 64 x 64 tile of pairs over the words of blockIdx.y's slice (msa_tile::tile_geom; split-K: the partial
+// counts are added with atomics).  b + 4 VALU instructions for 32 columns of one pair.
 template <int P>
 __global__ __launch_bounds__(kThreads) void msa_pairs_kernel(const uint32_t *__restrict__ planes, uint32_t n_pad, uint32_t n_words,
                                                              uint32_t words_per_split, uint32_t q0, uint32_t nq, uint32_t s0, uint32_t ns,
                                                              uint32_t n_tiles_s, int symmetric, int accumulate,
                                                              uint32_t *__restrict__ match, uint32_t *__restrict__ both) {
-  __shared__ uint32_t stage[2][kChunk][P][kTile];  // [0] queries, [1] subjects
-  uint32_t ti, tj;
-  if (symmetric) tri_tile(blockIdx.x, n_tiles_s, ti, tj);
-  else { ti = blockIdx.x / n_tiles_s; tj = blockIdx.x % n_tiles_s; }
+  __shared__ Stage<P> stage;
+  const TileGeom g = tile_geom(n_tiles_s, symmetric, n_words, words_per_split);
+  const Ranges r{q0, nq, s0, ns};
   const uint32_t tid = threadIdx.x, tx = tid & 15u, ty = tid >> 4;
-  const uint32_t w_lo = blockIdx.y * words_per_split;
-  const uint32_t w_hi = min(n_words, w_lo + words_per_split);
-  const uint32_t q_tile = ti * kTile, s_tile = tj * kTile;
   uint32_t m[4][4] = {{0}}, bo[4][4] = {{0}};
-  constexpr uint32_t kHalf = kChunk * P * kTile;
-  for (uint32_t wc = w_lo; wc < w_hi; wc += kChunk) {
+  for (uint32_t wc = g.w_lo; wc < g.w_hi; wc += kChunk) {
     __syncthreads();
-    for (uint32_t i = tid; i < 2u * kHalf; i += kThreads) {
-      const uint32_t half = i / kHalf, rem = i % kHalf, r = rem % kTile, wp = rem / kTile;
-      const uint32_t w = wc + wp / P, p = wp % P;
-      const uint32_t local = (half ? s_tile : q_tile) + r;
-      const bool ok = w < w_hi && local < (half ? ns : nq);
-      const uint32_t row = (half ? s0 : q0) + local;
-      (&stage[0][0][0][0])[i] = ok ? planes[((uint64_t)w * P + p) * n_pad + row] : 0u;
-    }
+    stage_words<P>(stage, planes, n_pad, wc, g, r, tid);
     __syncthreads();
 #pragma unroll 1
     for (int k = 0; k < kChunk; ++k) {
       uint32_t qv[P][4], sv[P][4];
-#pragma unroll
-      for (int p = 0; p < P; ++p) {
-        const uint4 x = *reinterpret_cast<const uint4 *>(&stage[0][k][p][ty * 4u]);
-        const uint4 y = *reinterpret_cast<const uint4 *>(&stage[1][k][p][tx * 4u]);
-        qv[p][0] = x.x; qv[p][1] = x.y; qv[p][2] = x.z; qv[p][3] = x.w;
-        sv[p][0] = y.x; sv[p][1] = y.y; sv[p][2] = y.z; sv[p][3] = y.w;
-      }
+      load_rows<P>(stage, k, tx, ty, qv, sv);
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-          uint32_t d = qv[0][a] ^ sv[0][b];
-#pragma unroll
-          for (int p = 1; p < P - 1; ++p) d = bitop3_t<kXorOr>(qv[p][a], sv[p][b], d);
-          m[a][b] += __builtin_popcount(bitop3_t<kAndNot>(d, qv[P - 1][a], 0u));
-          bo[a][b] += __builtin_popcount(qv[P - 1][a] & sv[P - 1][b]);
+          m[a][b] += __builtin_popcount(eq_word<P>(qv, sv, a, b));
+          bo[a][b] += __builtin_popcount(both_word<P>(qv, sv, a, b));
         }
       }
     }
   }
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const uint32_t qi = q_tile + ty * 4u + a;
-    if (qi >= nq) continue;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const uint32_t sj = s_tile + tx * 4u + b;
-      if (sj >= ns) continue;
-      const uint64_t idx = (uint64_t)qi * ns + sj;
-      if (accumulate) {
-        atomicAdd(match + idx, m[a][b]);
-        atomicAdd(both + idx, bo[a][b]);
-      } else {
-        match[idx] = m[a][b];
-        both[idx] = bo[a][b];
-      }
-    }
-  }
+  write_counts(m, bo, g, r, tx, ty, accumulate, match, both);
 }
-
-// Symmetric form: the tiles below the diagonal were not evaluated; (r, c) with tile(c) < tile(r) takes (c, r).
-__global__ __launch_bounds__(kThreads) void msa_mirror_kernel(uint32_t n, uint32_t *__restrict__ match, uint32_t *__restrict__ both) {
-  for (uint32_t r = blockIdx.y; r < n; r += gridDim.y) {
-    const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-    if (c >= (r / kTile) * kTile) continue;
-    match[(uint64_t)r * n + c] = match[(uint64_t)c * n + r];
-    both[(uint64_t)r * n + c] = both[(uint64_t)c * n + r];
-  }
-}
-
-inline uint32_t n_pad_of(uint32_t n_rows) { return (n_rows + kTile - 1u) / kTile * kTile; }
-inline uint64_t n_words_of(uint64_t n_cols) { return (n_cols + 31u) / 32u; }
 
 }  // namespace
 
@@ -230,15 +153,8 @@ int pa_msa_pair_counts(pa_ctx *c, const uint32_t *d_planes, uint32_t n_rows, uin
   const uint32_t tq = (nq + kTile - 1) / kTile, ts = (ns + kTile - 1) / kTile;
   const uint64_t tiles = symmetric ? (uint64_t)tq * (tq + 1) / 2 : (uint64_t)tq * ts;
   PA_REQUIRE(tiles < (1ull << 31), "pa_msa_pair_counts: %llu tiles", (unsigned long long)tiles);
-  // split the columns when the tiles alone leave CUs idle: about 8 blocks per CU, each slice at least 64 words
-  const uint64_t want = 8ull * (uint64_t)c->prop.multiProcessorCount;
-  uint64_t splits = tiles >= want ? 1 : (want + tiles - 1) / tiles;
-  splits = std::max<uint64_t>(1, std::min<uint64_t>({splits, (n_words + 63) / 64, 65535}));
-  uint32_t wps = (uint32_t)((n_words + splits - 1) / splits);
-  wps = (wps + kChunk - 1) / kChunk * kChunk;
-  if (wps == 0) wps = kChunk;
-  splits = (n_words + wps - 1) / wps;
-  if (splits == 0) splits = 1;
+  const ColumnSplit split = split_columns(c, tiles, n_words);
+  const uint32_t splits = split.splits, wps = split.words_per_split;
   const int accumulate = splits > 1;
   if (accumulate || n_words == 0) {
     PA_HIP(hipMemsetAsync(d_match, 0, (uint64_t)nq * ns * 4u, c->stream));
@@ -255,8 +171,7 @@ int pa_msa_pair_counts(pa_ctx *c, const uint32_t *d_planes, uint32_t n_rows, uin
     if (!dispatch_value(bits + 1, value_list<2, 7>{}, launch_pairs)) launch_pairs(std::integral_constant<int, 9>{});
     PA_TRY(status);
   }
-  if (symmetric && tq > 1)
-    PA_TRY(PA_LAUNCH(c, msa_mirror_kernel, LaunchDim((nq + kThreads - 1) / kThreads, nq < 65535u ? nq : 65535u), kThreads, 0, nq, d_match, d_both));
+  if (symmetric && tq > 1) PA_TRY(launch_mirror(c, nq, 1, d_match, d_both));
   return PA_OK;
 }
 

@@ -172,11 +172,12 @@ constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of
 //   mantel-run-comp (mantel.hip): mantel_work, the moments, the cross sums, a batch's permutations,
 //   inverses and row sums
 //   dereplicate-run (derep.hip): derep_work, the nodes still open as bits, then a round's new representatives or candidates
+//   bootstrap-run (msa_boot.hip): boot_work, a launch's weights as bytes and as bit planes
 #define PA_CTX_BUFFERS(ONE, PAIR)                                                                                   \
   PAIR(cand_keys) PAIR(cand_vals) ONE(genome_blk) ONE(counters) ONE(hist) ONE(flags) ONE(scan_tmp) ONE(region_off) \
   ONE(region_cursor) ONE(dirty) PAIR(dict_keys) PAIR(dict_vals) ONE(ids) ONE(post_genome) ONE(bitrows)             \
   ONE(dict_scalars) ONE(cls_i) ONE(cls_j) ONE(cls_score) ONE(cls_cov) ONE(bin2d) ONE(tetra_tab) ONE(nj_work) ONE(pcoa_work) \
-  ONE(mantel_work) ONE(derep_work)
+  ONE(mantel_work) ONE(derep_work) ONE(boot_work)
 
 struct pa_ctx {
   int device = 0;

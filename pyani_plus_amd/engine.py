@@ -636,6 +636,42 @@ class HipEngine:
         )
         return match, both
 
+    # -- bootstrap-run
+    def msa_boot_counts(self, dm: "DeviceMSA", weights):
+        """``pa_msa_boot_counts``: ``(M, B)`` of every pair of rows of ``dm`` under each row of ``weights`` (uint8,
+        R x ``dm.n_cols`` on the host, each row adding up to the columns) as torch.int32 ``[R, n, n]`` on the device (uint32
+        values), the diagonal included: the same integers as ``msa_boot_counts_host``."""
+        t = self.torch
+        w = _boot_weights(weights, dm.n_cols)
+        n = dm.n_rows
+        match = t.empty((len(w), n, n), dtype=t.int32, device=self.device)
+        both = t.empty((len(w), n, n), dtype=t.int32, device=self.device)
+        if match.numel():
+            self._check(
+                self.lib.pa_msa_boot_counts(self.ctx, dm.planes.data_ptr(), n, dm.n_cols, dm.bits, w.ctypes.data, len(w), match.data_ptr(), both.data_ptr()),
+                "pa_msa_boot_counts",
+            )
+        return match, both
+
+    def msa_boot_distances(self, match, both, missing: float = 1.0):
+        """``pa_msa_boot_distances``: the replicates' distance matrices, float64 ``[R, n, n]`` on the device, from the
+        counts of ``msa_boot_counts``; each ``D[r]`` is ready for ``nj_tree_inplace``.  The same bits as
+        ``msa_boot_distances_host``."""
+        t = self.torch
+        reps, n = int(match.shape[0]), int(match.shape[1])
+        d = t.empty((reps, n, n), dtype=t.float64, device=self.device)
+        if d.numel():
+            self._check(self.lib.pa_msa_boot_distances(self.ctx, match.data_ptr(), both.data_ptr(), n, reps, float(missing), d.data_ptr()),
+                        "pa_msa_boot_distances")
+        return d
+
+    def nj_tree_inplace(self, d) -> tuple[np.ndarray, np.ndarray, np.ndarray, float]:
+        """``nj_tree`` of a contiguous n x n float64 tensor on this device, which the call overwrites: no copy is made."""
+        n = int(d.shape[0])
+        out = _nj_outputs(n)
+        self._check(self.lib.pa_nj(self.ctx, d.data_ptr(), n, *(a.ctypes.data for a in out)), "pa_nj")
+        return out[0], out[1], out[2], float(out[3][0])
+
     # -- classify
     def classify_edges_device(self, score, cov, *, score_edges: str = "mean", coverage_edges: str = "min", cov_min: float = 0.5):
         """``pa_classify_edges``: the edges of the genome graph in removal order as device tensors ``(i, j, score, cov)``
@@ -1119,6 +1155,69 @@ def mantel_permutations(seed: int, n: int, first: int, count: int) -> np.ndarray
         raise ValueError(f"seed {seed!r}; 0 to 2^64 - 1")
     out = np.empty((int(count), int(n)), dtype=np.uint32)
     check(_capi.load_library().pa_mantel_permutations(int(seed), int(n), int(first), int(count), out.ctypes.data), "pa_mantel_permutations")
+    return out
+
+
+# ------------------------------------------------------------------ bootstrap-run: the host forms (no GPU needed)
+def _boot_weights(weights, n_cols: int) -> np.ndarray:
+    """The weights as a contiguous uint8 R x ``n_cols`` array; the library checks the rows' sums."""
+    w = np.ascontiguousarray(weights, dtype=np.uint8)
+    if w.ndim != 2 or w.shape[1] != int(n_cols):
+        raise ValueError(f"weights of shape {w.shape} for {n_cols} columns, expected (R, {n_cols})")
+    return w
+
+
+def msa_boot_weights(seed: int, n_cols: int, first: int, count: int, *, lib=None) -> np.ndarray:
+    """``pa_msa_boot_weights``: rows ``first .. first + count - 1`` of the bootstrap weights of ``seed`` over ``n_cols``
+    columns (uint8, count x n_cols): how often each column is drawn among ``n_cols`` draws.  A row depends on (seed,
+    n_cols, its number) alone."""
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"seed {seed!r}; 0 to 2^64 - 1")
+    out = np.empty((int(count), int(n_cols)), dtype=np.uint8)
+    lib = lib or _capi.load_library()
+    check(lib.pa_msa_boot_weights(int(seed), int(n_cols), int(first), int(count), out.ctypes.data), "pa_msa_boot_weights", lib)
+    return out
+
+
+def msa_boot_counts_host(rows, n_cols: int, weights, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """``pa_msa_boot_counts_host``: what ``HipEngine.msa_boot_counts`` returns (uint32 ``[R, n, n]``) from the rows as
+    bytes (``LoadedMSA.rows``: uint8, n x stride with stride >= ``n_cols``)."""
+    r = np.ascontiguousarray(rows, dtype=np.uint8)
+    if r.ndim != 2 or r.shape[1] < int(n_cols):
+        raise ValueError(f"rows of shape {r.shape} for {n_cols} columns")
+    w = _boot_weights(weights, n_cols)
+    n = r.shape[0]
+    match, both = np.zeros((len(w), n, n), dtype=np.uint32), np.zeros((len(w), n, n), dtype=np.uint32)
+    check(
+        _capi.load_library().pa_msa_boot_counts_host(r.ctypes.data, r.shape[1], n, int(n_cols), w.ctypes.data, len(w), match.ctypes.data, both.ctypes.data,
+                                                     int(threads)),
+        "pa_msa_boot_counts_host",
+    )  # fmt: skip
+    return match, both
+
+
+def msa_boot_distances_host(match, both, missing: float = 1.0, threads: int = 0) -> np.ndarray:
+    """``pa_msa_boot_distances_host``: what ``HipEngine.msa_boot_distances`` returns, bit for bit (float64 ``[R, n, n]``)."""
+    m = np.ascontiguousarray(match, dtype=np.uint32)
+    b = np.ascontiguousarray(both, dtype=np.uint32)
+    if m.ndim != 3 or m.shape[1] != m.shape[2] or b.shape != m.shape:
+        raise ValueError(f"counts of shapes {m.shape} and {b.shape}, expected the same (R, n, n)")
+    d = np.zeros(m.shape, dtype=np.float64)
+    check(_capi.load_library().pa_msa_boot_distances_host(m.ctypes.data, b.ctypes.data, m.shape[1], m.shape[0], float(missing), d.ctypes.data, int(threads)),
+          "pa_msa_boot_distances_host")
+    return d
+
+
+def tree_support(n: int, ref_child, rep_child) -> np.ndarray:
+    """``pa_tree_support``: per node ``n + t`` of the reference join table ``ref_child`` ((n - 2) x 2 uint32) the number of
+    the replicate tables ``rep_child`` (R x (n - 2) x 2) that have the edge above it."""
+    ref = np.ascontiguousarray(ref_child, dtype=np.uint32)
+    rep = np.ascontiguousarray(rep_child, dtype=np.uint32)
+    joins = max(int(n) - 2, 0)
+    if ref.shape != (joins, 2) or rep.ndim != 3 or rep.shape[1:] != (joins, 2):
+        raise ValueError(f"join tables of shapes {ref.shape} and {rep.shape} for {n} leaves")
+    out = np.zeros(joins, dtype=np.uint32)
+    check(_capi.load_library().pa_tree_support(int(n), ref.ctypes.data, len(rep), rep.ctypes.data, out.ctypes.data), "pa_tree_support")
     return out
 
 

@@ -1,6 +1,6 @@
 """The reports of a recorded run: the build's own counterpart of ``export-run``, ``plot-run`` and ``plot-run-comp``
 (their tables; pyani_plus/plot_run.py) and ``classify`` (pyani_plus/public_cli.py:974-1091, 1095-1208, 1211-1331), and
-this project's ``tree-run``, ``ordinate-run``, ``mantel-run-comp`` and ``dereplicate-run``.  They read the database through ``run_store`` and compute in the
+this project's ``tree-run``, ``bootstrap-run``, ``ordinate-run``, ``mantel-run-comp`` and ``dereplicate-run``.  They read the database through ``run_store`` and compute in the
 report modules (``classify``, ``cluster``, ``distribution``, ``scatter``, ``run_comp``, ``tree``, ``ordination``, ``mantel``,
 ``dereplicate`` and the figure modules); ``rundb`` re-exports them and is their command line, and nothing here imports it.
 
@@ -19,6 +19,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _capi
+from . import bootstrap as bootstrap_mod
 from . import classify as classify_mod
 from . import cluster as cluster_mod
 from . import dereplicate as dereplicate_mod
@@ -30,7 +31,7 @@ from . import run_comp as run_comp_mod
 from . import scatter as scatter_mod
 from . import tree as tree_mod
 from ._capi import HipBackendError
-from .methods import sourmash_hip
+from .methods import external_alignment_hip, sourmash_hip
 from .methods.external_alignment_hip import filename_stem
 from .run_store import (Run, _comparison_matrices, _matrix_cache_too_big, _open_run, _select_run_comparisons, cache_comparisons,
                         count_run_comparisons, genome_lengths, load_run)  # fmt: skip
@@ -278,6 +279,103 @@ def tree_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
     written = outdir / f"{run_method}_identity_{method}.nwk"
     written.write_text(tree_mod.newick(table, [str(x) for x in identity.columns]) + "\n")
     logger.info("Wrote %s tree to %s", method, written)
+    return written
+
+
+# ------------------------------------------------------------------ bootstrap-run (this project's own: the reference writes no support)
+def _bootstrap_alignment(logger, run: Run, conn, alignment: Path | None, hashes: list[str]):
+    """The run's alignment as ``engine.LoadedMSA`` with one row per genome, in the order of ``hashes``: found and checked
+    as the column worker does (``external_alignment_hip.check_configuration``: next to the database unless ``alignment``
+    says where; the md5 is the configuration's either way), a genome's row being its first record."""
+    from types import SimpleNamespace
+
+    from . import engine as engine_mod
+
+    found, md5, msa_label = external_alignment_hip.check_configuration(logger, run, SimpleNamespace(conn=conn))
+    path = Path(alignment) if alignment is not None else found
+    logger.info("Parsing %s (MD5=%s, label=%s)", path, md5, msa_label)
+    if not path.is_file():
+        sourmash_hip.log_sys_exit(logger, f"Missing alignment file {path}")
+    try:
+        msa = engine_mod.load_msa(path)
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, "bootstrap-run alignment loading", err)
+    if md5 != msa.md5:
+        sourmash_hip.log_sys_exit(logger, f"MD5 checksum of {path} didn't match.")
+    cols = external_alignment_hip.MsaColumns(logger, msa, external_alignment_hip.label_mapping(run, msa_label), msa_label, path)
+    records = []
+    for genome_hash in hashes:
+        if genome_hash not in cols.first_record:
+            sourmash_hip.log_sys_exit(logger, f"Did not find genome {genome_hash} in {path.name}")
+        records.append(cols.first_record[genome_hash])
+    lengths = cols.rec_len[records]
+    if (lengths != msa.n_cols).any():
+        short = records[int(np.flatnonzero(lengths != msa.n_cols)[0])]
+        sourmash_hip.log_sys_exit(logger, f"Bad external-alignment, different lengths {cols.rec_len[short]} and {msa.n_cols} from {cols.names[short]} in {path.name}")
+    rows = np.ascontiguousarray(msa.rows[records])
+    return engine_mod.LoadedMSA(msa.md5, [msa.titles[r] for r in records], msa.lengths[records], msa.histogram, rows, msa.n_cols)
+
+
+def bootstrap_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", replicates: int = 100, seed: int = 0,  # noqa: PLR0913
+                  missing: float = 1.0, alignment: Path | None = None, keep_trees: bool = False, engine=None,
+                  logger: logging.Logger | None = None) -> list[Path]:
+    """Column-bootstrap support of ``tree-run``'s neighbour-joining tree of a complete ``external-alignment-hip`` run
+    (``bootstrap.bootstrap``): ``replicates`` (1 to 100 000) times the columns of the run's
+    alignment are drawn anew with replacement from ``seed`` (0 to 2^64 - 1), the tree is rebuilt from the distances
+    ``1 - identity`` of the drawn columns (``missing`` where a pair has no aligned column left), and every edge of
+    ``tree-run``'s tree is given the number of rebuilt trees that have it.  The genomes are in the order of
+    ``tree-run``'s matrix under the same ``label``; the alignment is looked for next to the database, as the worker
+    does, or at ``alignment``, and its md5 is checked against the run's configuration.  A run of another method has no
+    columns to resample, and fewer than 4 genomes have no internal edge: each ends with its message.
+
+    * ``<method>_identity_nj_bootstrap.nwk``: ``tree-run``'s tree, every internal node but the root of the text labelled
+      with the support of the edge above it, a count and not a percentage;
+    * ``<method>_identity_nj_bootstrap.tsv``: ``#node n_leaves length support replicates``, a line per labelled node;
+    * with ``keep_trees``, ``<method>_identity_nj_replicates.nwk``: a replicate tree per line, in replicate order.
+
+    ``engine``: a ``HipEngine`` makes the weighted counts, the distances and the joins on the GPU; None makes them on
+    the host, with the same bytes.  Returns the written paths."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    _require_database(logger, database)
+    if isinstance(replicates, bool) or not isinstance(replicates, int) or not 1 <= replicates <= bootstrap_mod.MAX_REPLICATES:
+        sourmash_hip.log_sys_exit(logger, f"Expected 1 to {bootstrap_mod.MAX_REPLICATES} replicates, not {replicates!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        sourmash_hip.log_sys_exit(logger, f"Expected a seed from 0 to 2^64 - 1, not {seed!r}")
+    _require_missing_distance(logger, missing)
+    outdir = _make_outdir(logger, outdir)
+    conn, run, n, done = _open_complete_run(logger, database, run_id, "Exporting")
+    method = run.configuration.method
+    if method != external_alignment_hip.METHOD:
+        sourmash_hip.log_sys_exit(
+            logger, f"Run-id {run.run_id} is a {method} run: it has no columns to resample (bootstrap-run needs an {external_alignment_hip.METHOD} run)")
+    if n < 4:  # noqa: PLR2004
+        sourmash_hip.log_sys_exit(logger, f"Run-id {run.run_id} has {n} genomes: a tree of fewer than 4 has no internal edge to support")
+    frames = _score_frames(logger, conn, run)
+    logger.info("Run %d has %d comparisons across %d genomes.", run.run_id, done, n)
+    mapping = _label_mapping(logger, run, label)
+    identity = _relabelled(logger, run, frames, label)[0]
+    labels = [str(x) for x in identity.columns]
+    hash_of = {str(shown): genome_hash for genome_hash, shown in mapping.items()}
+    try:
+        msa = _bootstrap_alignment(logger, run, conn, alignment, [hash_of[x] for x in labels])
+    finally:
+        conn.close()
+    distances = tree_mod.run_distances(identity, missing, logger)
+    _require_no_negative_distance(logger, distances, "tree")
+    try:
+        table = tree_mod.neighbour_joining(distances, engine=engine)
+        device_msa = engine.msa_upload(msa) if engine is not None else None
+        result = bootstrap_mod.bootstrap(table, msa.rows, msa.n_cols, replicates, seed, missing, engine=engine, device_msa=device_msa)
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, "bootstrap-run", err)
+    stem = f"{method}_identity_nj"
+    written = [outdir / f"{stem}_bootstrap.nwk", outdir / f"{stem}_bootstrap.tsv"]
+    written[0].write_text(bootstrap_mod.support_newick(result, labels) + "\n")
+    written[1].write_text(bootstrap_mod.support_tsv(result))
+    if keep_trees:
+        written.append(outdir / f"{stem}_replicates.nwk")
+        written[-1].write_text("".join(tree_mod.newick(t, labels) + "\n" for t in result.trees))
+    logger.info("Wrote the support of %d edges among %d replicates to %s", max(n - 3, 0), replicates, written[0])
     return written
 
 

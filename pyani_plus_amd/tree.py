@@ -88,13 +88,20 @@ def quote_label(label: str) -> str:
     return label if _PLAIN_LABEL.fullmatch(label) else "'" + label.replace("'", "''") + "'"
 
 
-def newick(table: JoinTable, labels) -> str:
+def newick(table: JoinTable, labels, support=None) -> str:
     """The tree as one line of Newick text.  Lengths are ``repr(float)``, which round-trips the bits.  A neighbour-joining
     tree is unrooted, so its root is a trifurcation: the two children of the last node made, then the other remaining
     node, which carries ``last_len``; two leaves give ``(A:h,B:h);`` with ``h = 0.5 * d`` and one gives ``(A);``.  A
-    UPGMA tree starts from its last node.  The writer keeps its own stack: a caterpillar tree is as deep as it is long."""
+    UPGMA tree starts from its last node.  The writer keeps its own stack: a caterpillar tree is as deep as it is long.
+
+    ``support``: one integer per join; every internal node but the root of the text then carries, as its label, the
+    entry of its join, which is the support of the edge above it (``bootstrap-run``).  Without it the text has no
+    internal labels."""
     names = [quote_label(x) for x in labels]
     n = table.n
+    if support is not None and len(support) != len(table.child):
+        msg = f"{len(support)} support values for {len(table.child)} joins"
+        raise ValueError(msg)
     if len(names) != n:
         msg = f"{len(names)} labels for {n} leaves"
         raise ValueError(msg)
@@ -129,7 +136,7 @@ def newick(table: JoinTable, labels) -> str:
         if state == 2:
             out.append(",")
         elif state == 1:
-            out.append(f"):{ln!r}")
+            out.append(f"):{ln!r}" if support is None else f"){int(support[node - n])}:{ln!r}")
         elif node < n:
             out.append(f"{names[node]}:{ln!r}")
         else:
