@@ -438,7 +438,9 @@ PA_API int pa_sqlite_insert_comparisons_ex(const char *database, int64_t configu
  *        bytes each, a row's tail after its residues filled with '-'.
  *   pa_msa_pack          rows -> bit planes + non-gap counts n_x (device)
  *        d_rows: n_chunk_rows rows of row_stride bytes (a multiple of 32 covering ceil(n_cols / 32) words; 16-byte
- *        aligned), rows row0 .. of an MSA of n_rows rows.  h_code256: byte -> code, '-' -> 0, codes below 2^bits
+ *        aligned), rows row0 .. of an MSA of n_rows rows.  The bytes of a row at or past n_cols, up to the end of its
+ *        last 32-byte word, are read and ignored: those columns are gap in every plane whatever the bytes say, so the
+ *        padding need not be '-'.  h_code256: byte -> code, '-' -> 0, codes below 2^bits
  *        (1 <= bits <= 8).  d_planes: pa_msa_plane_words(n_rows, n_cols, bits) uint32, word-major
  *        [(w * (bits + 1) + p) * n_pad + row], n_pad = n_rows rounded up to 64, plane `bits` = non-gap.  d_nongap:
  *        n_rows uint32, zero before the first chunk; each chunk adds its rows' non-gap columns.

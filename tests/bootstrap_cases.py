@@ -178,7 +178,7 @@ def count_cases() -> tuple[CountCase, ...]:
     for n_cols in (1, 31, 32, 33, 8 * 32, 8 * 32 + 1):  # the seam of a stage through LDS
         out.append(CountCase(f"cols{n_cols}", alignment(5, n_cols, 400 + n_cols), _drawn(n_cols, 3, n_cols)))
     out.append(CountCase("split", alignment(3, SPLIT_COLUMNS, 5), _drawn(SPLIT_COLUMNS, 1, 5)))
-    for symbols, bits in ((1, 1), (3, 2), (15, 4), (255 - 1, 8)):
+    for symbols, bits in ((1, 1), (3, 2), (15, 4), (31, 5), (63, 6), (127, 7), (255 - 1, 8)):  # ACGT, everywhere else, is bits 3
         assert symbols.bit_length() == bits
         out.append(CountCase(f"bits{bits}", alignment(6, 100, 500 + bits, alphabet=_alphabet(symbols), mutate=0.3), _drawn(100, 2, bits)))
     rows = alignment(6, 75, 600)

@@ -40,6 +40,14 @@ def test_small_alignments_reach_three_weight_planes():
 
 
 # ------------------------------------------------------------------ counts and distances
+def test_the_count_cases_have_every_plane_count():
+    """One case per ``bits`` (ACGT, the alphabet of every other case, is 3): the twin below and the device run them all."""
+    for bits in (1, 2, 4, 5, 6, 7, 8):
+        hist = np.bincount(cases.count_case(f"bits{bits}").rows.ravel(), minlength=256)
+        assert engine_mod.msa_code_table(hist)[1] == bits
+    assert engine_mod.msa_code_table(np.bincount(cases.count_case("rows65").rows.ravel(), minlength=256))[1] == 3
+
+
 @pytest.mark.parametrize("name", [c.name for c in cases.count_cases()])
 def test_host_counts_equal_the_restatement(name):
     case = cases.count_case(name)

@@ -43,8 +43,9 @@ def u32(tensor) -> np.ndarray:
 def test_the_cases_cover_what_they_name():
     assert _capi.PA_MSA_BOOT_BATCH == cases.BATCH
     assert len(cases.count_case("batch_plus_one").weights) == cases.BATCH + 1
-    for bits in (1, 2, 4, 8):
+    for bits in (1, 2, 4, 5, 6, 7, 8):
         assert msa_code_table(loaded(cases.count_case(f"bits{bits}").rows).histogram)[1] == bits
+    assert msa_code_table(loaded(cases.count_case("rows65").rows).histogram)[1] == 3  # ACGT: every other case
     assert cases.count_case("weights_max1").weights.max() == 1 and cases.count_case("weights_max255").weights.max() == 255
     assert 3 <= max(int(cases.count_case(f"rows{n}").weights.max()) for n in (1, 4, 63, 64, 65, 130)) <= 7
 
