@@ -29,9 +29,6 @@
 //   5. cls_gather_kernel: the four output arrays in sorted order.
 #include "pa_internal.h"
 
-// pair_rule.h asks for this and for -ffp-contract=off (the Makefile); the kernels here hold no multiply-add to contract
-#pragma clang fp contract(off)
-
 #include "pair_tile_dev.h"
 
 namespace {

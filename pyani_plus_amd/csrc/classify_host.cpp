@@ -16,17 +16,9 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
+#include "pa_host.h"
 
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#elif defined(__GNUC__)
-#pragma GCC optimize("fp-contract=off")
-#endif
-
-#include "pair_rule.h"  // after the pragma
-
-void pa_set_error(const char *fmt, ...);
+#include "pair_rule.h"
 
 struct pa_cliques {
   std::vector<uint32_t> n_nodes;

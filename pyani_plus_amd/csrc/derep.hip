@@ -29,8 +29,6 @@
 // order-free.  The results are the same bits run to run.
 #include "pa_internal.h"
 
-#pragma clang fp contract(off)
-
 #include "block_reduce_dev.h"
 #include "derep_rule.h"
 #include "pair_tile_dev.h"

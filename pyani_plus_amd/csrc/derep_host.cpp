@@ -2,47 +2,23 @@
 // and the twins pa_derep_adjacency_host, pa_derep_select_host and pa_derep_assign_host: what derep.hip is compared with,
 // bit for bit, and what dereplicate-run uses on a machine without a GPU.  include/pyani_hip.h and DESIGN.md section 7k
 // have the contract; derep_rule.h has its rules, the same functions the kernels call, compiled here too with contraction
-// off (the pragma below and the Makefile).
+// off (strict_fp.h and the Makefile).
 //
 // The twins are the plain sequential algorithms.  Adjacency and assignment hand out rows to host-pool threads, each row
 // made by one thread, so the number of threads does not show in a result; the selection is one thread's loop.
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <limits>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
+#include "pa_host.h"
 
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#elif defined(__GNUC__)
-#pragma GCC optimize("fp-contract=off")
-#endif
-
-#include "derep_rule.h"  // after the pragma
-
-void pa_set_error(const char *fmt, ...);
+#include "derep_rule.h"
 
 namespace {
 
 constexpr uint32_t kStrip = 64;  // rows a thread takes at a time: one word of the columns they are transposed from
-
-// strips of kStrip rows to host-pool threads
-template <typename Strip>
-void for_strips(uint32_t n, uint64_t work_per_row, uint32_t n_threads, Strip &&strip) {
-  const uint32_t nt = pa_host_threads((uint64_t)n * work_per_row, 1u << 16, n_threads);
-  std::atomic<uint32_t> next{0};
-  HostPool::get().run(nt, [&](uint32_t, uint32_t) {
-    for (;;) {
-      const uint32_t i0 = next.fetch_add(kStrip, std::memory_order_relaxed);
-      if (i0 >= n) break;
-      strip(i0, std::min(kStrip, n - i0));
-    }
-  });
-}
 
 int refuse_n(const char *who, uint32_t n) {
   pa_set_error("%s: %u genomes; 1 to %u", who, n, derep::kMaxN);
@@ -82,11 +58,12 @@ int derep::check_assign(const void *S, uint32_t n, int agg_score, const void *bi
 extern "C" int pa_derep_adjacency_host(const double *h_S, const double *h_C, uint32_t n, int agg_score, int agg_cov, double min_score, double cov_min,
                                        uint64_t *h_bits, uint32_t n_threads) {
   if (const int s = derep::check_adjacency(h_S, h_C, n, agg_score, agg_cov, min_score, cov_min, h_bits)) return s;
-  return pa_host_guard("pa_derep_adjacency_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_derep_adjacency_host", [&]() -> int {
     const uint64_t N = n, W = derep::words(n);
     // A strip of rows a0 .. a0 + rows - 1: the columns of the same numbers are transposed first (kStrip contiguous doubles
     // of every row b), so that the pair loop reads both directions along b.
-    for_strips(n, N, n_threads, [&](uint32_t a0, uint32_t rows) {
+    pa_for_chunks(0, n, kStrip, pa_host_threads(N * N, 1u << 16, n_threads), [&](uint32_t, uint64_t a0, uint64_t a1) {
+      const uint32_t rows = (uint32_t)(a1 - a0);
       std::vector<double> t_s((size_t)kStrip * N), t_c((size_t)kStrip * N);
       for (uint64_t b = 0; b < N; ++b)
         for (uint32_t r = 0; r < rows; ++r) {
@@ -94,7 +71,7 @@ extern "C" int pa_derep_adjacency_host(const double *h_S, const double *h_C, uin
           t_c[r * N + b] = h_C[b * N + a0 + r];
         }
       for (uint32_t r = 0; r < rows; ++r) {
-        const uint32_t a = a0 + r;
+        const uint32_t a = (uint32_t)a0 + r;
         uint64_t *out = h_bits + a * W;
         for (uint64_t w = 0; w < W; ++w) {
           uint64_t word = 0;
@@ -118,7 +95,7 @@ extern "C" int pa_derep_adjacency_host(const double *h_S, const double *h_C, uin
 
 extern "C" int pa_derep_select_host(const uint64_t *h_bits, uint32_t n, int mode, uint8_t *h_is_rep, uint32_t *n_reps) {
   if (const int s = derep::check_select(h_bits, n, mode, h_is_rep, n_reps)) return s;
-  return pa_host_guard("pa_derep_select_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_derep_select_host", [&]() -> int {
     const uint64_t W = derep::words(n);
     uint32_t reps = 0;
     memset(h_is_rep, 0, n);
@@ -171,10 +148,10 @@ extern "C" int pa_derep_select_host(const uint64_t *h_bits, uint32_t n, int mode
 extern "C" int pa_derep_assign_host(const double *h_S, uint32_t n, int agg_score, const uint64_t *h_bits, const uint8_t *h_is_rep, uint32_t *h_rep,
                                     double *h_rep_score, uint32_t n_threads) {
   if (const int s = derep::check_assign(h_S, n, agg_score, h_bits, h_is_rep, h_rep, h_rep_score)) return s;
-  return pa_host_guard("pa_derep_assign_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_derep_assign_host", [&]() -> int {
     const uint64_t N = n, W = derep::words(n);
-    for_strips(n, W, n_threads, [&](uint32_t p0, uint32_t rows) {
-      for (uint32_t p = p0; p < p0 + rows; ++p) {
+    pa_for_chunks(0, n, kStrip, pa_host_threads(N * W, 1u << 16, n_threads), [&](uint32_t, uint64_t p0, uint64_t p1) {
+      for (uint32_t p = (uint32_t)p0; p < p1; ++p) {
         derep::Pick best{std::numeric_limits<double>::quiet_NaN(), derep::kNone};
         if (h_is_rep[p]) {
           best = derep::Pick{derep::pair_value(agg_score, p, p, h_S[p * N + p], h_S[p * N + p]), p};

@@ -1,19 +1,12 @@
 // derep_rule.h -- the rules of dereplicate-run, stated once for derep.hip and derep_host.cpp (DESIGN.md section 7k has
 // the contract): the edge of two genomes, the total order in which the cover mode chooses, and the total order in which a
-// genome is given its representative.  Include this after `#pragma clang fp contract(off)` in a file that is also
-// compiled with -ffp-contract=off, as pair_rule.h asks.
+// genome is given its representative.  The aggregate of a pair is pair_rule.h's.
 #pragma once
 
 #include <cstdint>
 
 #include "../../include/pyani_hip.h"
 #include "pair_rule.h"
-
-#if defined(__HIPCC__)
-#define PA_DEREP_FN __host__ __device__ __forceinline__
-#else
-#define PA_DEREP_FN inline
-#endif
 
 namespace derep {
 
@@ -23,22 +16,22 @@ constexpr uint32_t kNone = PA_DEREP_NONE;  // the representative of a node that 
 // classify's aggregators and the value of a pair from its two cells (pair_rule.h)
 using pair_rule::agg_ok;
 using pair_rule::pair_value;
-PA_DEREP_FN bool mode_ok(int mode) { return mode == PA_DEREP_GREEDY || mode == PA_DEREP_COVER; }
-PA_DEREP_FN uint32_t words(uint32_t n) { return (n + 63u) / 64u; }
+PA_HD bool mode_ok(int mode) { return mode == PA_DEREP_GREEDY || mode == PA_DEREP_COVER; }
+PA_HD uint32_t words(uint32_t n) { return (n + 63u) / 64u; }
 
 // lo != hi are adjacent iff neither value is NaN, cov > cov_min (strict) and score >= min_score (inclusive)
-PA_DEREP_FN bool edge(double score, double cov, double min_score, double cov_min) {
+PA_HD bool edge(double score, double cov, double min_score, double cov_min) {
   return score == score && cov == cov && cov > cov_min && score >= min_score;
 }
 
 // The cover mode's choice as one unsigned key, the largest of which wins: the gain (at most 65535), then a node that is
 // itself uncovered before one that is covered, then the smaller index.  0 stands for no candidate: a gain of 0 never
 // enters.
-PA_DEREP_FN uint64_t cover_key(uint32_t gain, bool uncovered, uint32_t p) {
+PA_HD uint64_t cover_key(uint32_t gain, bool uncovered, uint32_t p) {
   return gain == 0 ? 0ull : ((uint64_t)gain << 33) | ((uint64_t)(uncovered ? 1u : 0u) << 32) | (uint64_t)(0xFFFFFFFFu - p);
 }
-PA_DEREP_FN uint32_t cover_key_gain(uint64_t key) { return (uint32_t)(key >> 33); }
-PA_DEREP_FN uint32_t cover_key_node(uint64_t key) { return 0xFFFFFFFFu - (uint32_t)key; }
+PA_HD uint32_t cover_key_gain(uint64_t key) { return (uint32_t)(key >> 33); }
+PA_HD uint32_t cover_key_node(uint64_t key) { return 0xFFFFFFFFu - (uint32_t)key; }
 
 // The assignment's total order: the larger score, equal scores (== on doubles, so -0.0 equals 0.0) to the smaller
 // representative.  Any representative beats none; a NaN score never enters (the callers pass it over).
@@ -46,7 +39,7 @@ struct Pick {
   double score;
   uint32_t rep;
 };
-PA_DEREP_FN bool better(const Pick &x, const Pick &than) {
+PA_HD bool better(const Pick &x, const Pick &than) {
   if (x.rep == kNone) return false;
   if (than.rep == kNone) return true;
   if (x.score > than.score) return true;

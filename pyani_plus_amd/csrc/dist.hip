@@ -29,8 +29,7 @@
 
 #include "block_reduce_dev.h"
 #include "pa_internal.h"
-
-#pragma clang fp contract(off)
+#include "strict_fp.h"
 
 namespace {
 

@@ -9,11 +9,8 @@
 #include <new>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-
-void pa_set_error(const char *fmt, ...);
-
-#pragma STDC FP_CONTRACT OFF
+#include "pa_host.h"
+#include "strict_fp.h"
 
 extern "C" {
 

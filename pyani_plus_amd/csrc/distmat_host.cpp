@@ -2,10 +2,8 @@
 // check (distmat.hip) ends in too.  distmat_rule.h has the rule of a cell.
 #include <cstdint>
 
-#include "../../include/pyani_hip.h"
+#include "pa_host.h"
 #include "distmat_rule.h"
-
-void pa_set_error(const char *fmt, ...);
 
 int distmat::refuse(const char *who, const char *name, uint32_t n, uint64_t bad, uint64_t first) {
   pa_set_error("%s: %s[%llu,%llu] is not finite, is negative, differs from its transpose's bits or is a non-zero diagonal cell (%llu such cells)", who,

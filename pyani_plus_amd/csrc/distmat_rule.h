@@ -5,16 +5,12 @@
 
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define PA_DISTMAT_FN __host__ __device__ __forceinline__
-#else
-#define PA_DISTMAT_FN inline
-#endif
+#include "pa_hd.h"
 
 namespace distmat {
 
 // A cell the contract refuses: not finite, below zero, not the bits of its transpose, or a diagonal cell that is not zero
-PA_DISTMAT_FN bool bad_cell(double v, double transposed, bool diagonal) {
+PA_HD bool bad_cell(double v, double transposed, bool diagonal) {
   uint64_t a, b;
   __builtin_memcpy(&a, &v, 8);
   __builtin_memcpy(&b, &transposed, 8);

@@ -14,7 +14,6 @@
 #include <zlib.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -25,13 +24,11 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
+#include "pa_host.h"
 #include "inflate_fast.h"
 #include "md5.h"
 #include "md5_mb.h"
 
-void pa_set_error(const char *fmt, ...);
 int pa_pack_fasta_records(const uint8_t *h_text, uint64_t n_text, uint32_t *h_packed, uint32_t *h_mask, uint64_t cap_bases,
                           uint64_t *n_bases, uint64_t *n_residues, uint64_t *n_records, uint64_t *n_invalid,
                           std::vector<uint64_t> *rec_start, std::vector<uint64_t> *rec_len, std::vector<uint64_t> *amb_pos,
@@ -341,7 +338,7 @@ static int fasta_batch_load(const char *const *paths, uint32_t n, int threads, p
                  (unsigned long long)(slot_off[n] / 4 + slot_off[n] / 8 + read_room * lanes * nt));
     return PA_E_NOMEM;
   }
-  std::atomic<uint32_t> next{0};
+  ChunkQueue groups(0, n, lanes);
   HostPool::get().run(nt, [&](uint32_t worker, uint32_t) {
     std::vector<uint8_t> raw;
     std::vector<std::vector<uint8_t>> text(lanes);
@@ -349,12 +346,9 @@ static int fasta_batch_load(const char *const *paths, uint32_t n, int threads, p
     std::vector<size_t> n_data(lanes);
     std::vector<uint32_t> file(lanes);
     const std::unique_ptr<char[][33]> hex(new char[lanes][33]);
-    for (;;) {
-      const uint32_t g0 = next.fetch_add(lanes);
-      if (g0 >= n) break;
-      const uint32_t g1 = std::min(n, g0 + lanes);
+    for (uint64_t g0, g1; groups.take(g0, g1);) {
       uint32_t have = 0;
-      for (uint32_t q = g0; q < g1; ++q) {
+      for (uint64_t q = g0; q < g1; ++q) {
         const uint32_t i = order[q];
         uint8_t *buf = read_room ? reads.p + ((size_t)worker * lanes + have) * read_room : nullptr;
         try {
@@ -390,7 +384,7 @@ int pa_fasta_batch_load(const char *const *paths, uint32_t n, int threads, pa_fa
   pa_fasta_batch *b = new (std::nothrow) pa_fasta_batch();
   if (!b) { pa_set_error("out of host memory"); return PA_E_NOMEM; }
   // an allocation that fails on the calling thread or on a pool thread comes back as PA_E_NOMEM, never as std::terminate
-  const int st = pa_host_guard("pa_fasta_batch_load", pa_set_error, [&] { return fasta_batch_load(paths, n, threads, b, out); });
+  const int st = pa_host_guard("pa_fasta_batch_load", [&] { return fasta_batch_load(paths, n, threads, b, out); });
   if (st != PA_OK) { *out = nullptr; delete b; }
   return st;
 }
@@ -444,18 +438,12 @@ int pa_fasta_batch_copy_arena(const pa_fasta_batch *b, uint32_t *h_packed, uint3
   }
   h_genome_start[b->files.size()] = pos;
   // the genomes land in disjoint ranges: copy them on the host pool (2 GB at N = 1000 is 0.25 s on one core)
-  const size_t n = b->files.size();
-  std::atomic<size_t> next{0};
-  return pa_host_guard("pa_fasta_batch_copy_arena", pa_set_error, [&] {
-    HostPool::get().run(pa_host_threads(pos, 32u << 20, 0), [&](uint32_t, uint32_t) {
-      for (;;) {
-        const size_t i = next.fetch_add(1);
-        if (i >= n) break;
-        const FileResult &r = b->files[i];
-        if (r.status != PA_OK || !r.n_bases) continue;
-        memcpy(h_packed + h_genome_start[i] / 16, r.packed, r.n_bases / 4);
-        memcpy(h_mask + h_genome_start[i] / 32, r.mask, r.n_bases / 8);
-      }
+  return pa_host_guard("pa_fasta_batch_copy_arena", [&] {
+    pa_for_each(0, b->files.size(), 1, pa_host_threads(pos, 32u << 20, 0), [&](uint64_t i) {
+      const FileResult &r = b->files[i];
+      if (r.status != PA_OK || !r.n_bases) return;
+      memcpy(h_packed + h_genome_start[i] / 16, r.packed, r.n_bases / 4);
+      memcpy(h_mask + h_genome_start[i] / 32, r.mask, r.n_bases / 8);
     });
     return (int)PA_OK;
   });

@@ -6,12 +6,8 @@
 #include <cmath>
 #include <cstdint>
 
-#include "../../include/pyani_hip.h"
+#include "pa_host.h"
 #include "uniform_bins.h"
-
-void pa_set_error(const char *fmt, ...);
-
-#pragma STDC FP_CONTRACT OFF
 
 int pa_check_uniform_edges(const char *who, const char *axis, const double *e, uint32_t bins) {
   for (uint32_t b = 0; b <= bins; ++b) {

@@ -1,5 +1,7 @@
-// host_pool.h -- a small persistent pool of host threads shared by the host-side bulk routines
-// (pa_ani_host, the JSON and .sig writers, the FASTA loader).
+// host_pool.h -- what the host-side bulk routines share their work with: a small persistent pool of host threads
+// (HostPool), the one work-sharing loop that runs on it (ChunkQueue, pa_for_chunks, pa_for_each) and the number of
+// threads worth using (pa_host_threads).  Its users are pa_ani_host, the writers, the FASTA, .sig and MSA loaders, and
+// the host twins of the run reports.
 #pragma once
 
 #include <sched.h>
@@ -152,21 +154,41 @@ inline uint32_t pa_host_threads(uint64_t items, uint64_t grain, uint32_t request
 }
 
 
-// Body of an extern "C" entry point that runs host-pool jobs or allocates: C++ exceptions never cross the C ABI.
-// `set_error` is pa_set_error (declared by the including file); returns the body's status, -3 (PA_E_NOMEM) for
-// std::bad_alloc, -1 (PA_E_INVALID) for anything else.
-template <typename Body, typename SetError>
-inline int pa_host_guard(const char *what, SetError &&set_error, Body &&body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc &) {
-    set_error("%s: out of host memory", what);
-    return -3;
-  } catch (const std::exception &e) {
-    set_error("%s: %s", what, e.what());
-    return -1;
-  } catch (...) {
-    set_error("%s: unknown C++ exception", what);
-    return -1;
+// ---- the one work-sharing loop ----------------------------------------------------------------------------
+// The indices [first, last) handed out `chunk` at a time from a shared 64-bit counter: the workers of one job call
+// take() until it says no.  A worker that finishes early takes more, so uneven items balance themselves.  The counter
+// publishes nothing but itself (relaxed): what the workers write is seen by the caller through the end of
+// HostPool::run.  An empty or reversed range hands out nothing; a chunk of 0 counts as 1.
+class ChunkQueue {
+ public:
+  ChunkQueue(uint64_t first, uint64_t last, uint64_t chunk) : next_(first), last_(last), chunk_(chunk ? chunk : 1) {}
+  bool take(uint64_t &i0, uint64_t &i1) {
+    i0 = next_.fetch_add(chunk_, std::memory_order_relaxed);  // past `last` by one chunk per worker at the most
+    if (i0 >= last_) return false;
+    i1 = last_ - i0 > chunk_ ? i0 + chunk_ : last_;
+    return true;
   }
+
+ private:
+  std::atomic<uint64_t> next_;
+  const uint64_t last_, chunk_;
+};
+
+// fn(worker, i0, i1) for every chunk [i0, i1) of [first, last), on n_workers threads (1: on the caller alone).  For the
+// loops that keep no state across chunks (`worker` may index what the caller keeps per thread); one that does makes a
+// ChunkQueue and calls take() inside its own run().
+template <typename F>
+inline void pa_for_chunks(uint64_t first, uint64_t last, uint64_t chunk, uint32_t n_workers, F &&fn) {
+  ChunkQueue queue(first, last, chunk);
+  HostPool::get().run(n_workers, [&](uint32_t worker, uint32_t) {
+    for (uint64_t i0, i1; queue.take(i0, i1);) fn(worker, i0, i1);
+  });
+}
+
+// fn(i) for every i of [first, last), handed out `chunk` at a time
+template <typename F>
+inline void pa_for_each(uint64_t first, uint64_t last, uint64_t chunk, uint32_t n_workers, F &&fn) {
+  pa_for_chunks(first, last, chunk, n_workers, [&](uint32_t, uint64_t i0, uint64_t i1) {
+    for (uint64_t i = i0; i < i1; ++i) fn(i);
+  });
 }

@@ -19,10 +19,7 @@
 
 #include <algorithm>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
-
-void pa_set_error(const char *fmt, ...);
+#include "pa_host.h"
 
 namespace {
 
@@ -189,7 +186,7 @@ extern "C" int pa_write_comparisons_json(const char *path, const char *prefix, c
                                          const char *const *q_hashes, uint32_t nq, const char *const *s_hashes,
                                          uint32_t ns, const double *identity, const double *cov_query,
                                          const uint8_t *is_null) {
-  return pa_host_guard("pa_write_comparisons_json", pa_set_error, [&] {
+  return pa_host_guard("pa_write_comparisons_json", [&] {
     return write_comparisons_json(path, prefix, suffix, q_hashes, nq, s_hashes, ns, identity, cov_query, is_null);
   });
 }
@@ -198,7 +195,7 @@ extern "C" int pa_append_comparisons_json(const char *path, const char *suffix, 
                                           const char *const *q_hashes, uint32_t nq, const char *const *s_hashes,
                                           uint32_t ns, const double *identity, const double *cov_query,
                                           const uint8_t *is_null) {
-  return pa_host_guard("pa_append_comparisons_json", pa_set_error, [&] {
+  return pa_host_guard("pa_append_comparisons_json", [&] {
     return append_comparisons_json(path, suffix, file_has_rows, q_hashes, nq, s_hashes, ns, identity, cov_query, is_null);
   });
 }
@@ -211,7 +208,7 @@ extern "C" int pa_append_comparisons_json_ex(const char *path, const char *suffi
     pa_set_error("pa_append_comparisons_json_ex: aln_length and sim_errors go together");
     return PA_E_INVALID;
   }
-  return pa_host_guard("pa_append_comparisons_json_ex", pa_set_error, [&] {
+  return pa_host_guard("pa_append_comparisons_json_ex", [&] {
     return append_comparisons_json(path, suffix, file_has_rows, q_hashes, nq, s_hashes, ns, identity, cov_query, is_null, aln_length,
                                    sim_errors);
   });
@@ -221,7 +218,7 @@ extern "C" int pa_append_comparisons_json_ex(const char *path, const char *suffi
 // their is_null stands for both columns.  Same keys, "cov_query": null in every row.
 extern "C" int pa_append_identity_json(const char *path, const char *suffix, int file_has_rows, const char *const *q_hashes, uint32_t nq,
                                        const char *const *s_hashes, uint32_t ns, const double *identity, const uint8_t *is_null) {
-  return pa_host_guard("pa_append_identity_json", pa_set_error, [&] {
+  return pa_host_guard("pa_append_identity_json", [&] {
     return append_comparisons_json(path, suffix, file_has_rows, q_hashes, nq, s_hashes, ns, identity, nullptr, is_null, nullptr, nullptr, true);
   });
 }
@@ -310,7 +307,7 @@ static int append_msa_json(const char *path, const char *suffix, int file_has_ro
 extern "C" int pa_append_msa_json(const char *path, const char *suffix, int file_has_rows, const char *const *hashes, uint32_t n_hashes,
                                   const uint32_t *q_idx, const uint32_t *s_idx, uint64_t n_rows, const double *identity,
                                   const int64_t *aln_length, const int64_t *sim_errors, const double *cov_query, const double *cov_subject) {
-  return pa_host_guard("pa_append_msa_json", pa_set_error, [&] {
+  return pa_host_guard("pa_append_msa_json", [&] {
     return append_msa_json(path, suffix, file_has_rows, hashes, n_hashes, q_idx, s_idx, n_rows, identity, aln_length, sim_errors, cov_query,
                            cov_subject);
   });
@@ -385,5 +382,5 @@ static int write_pairs_tsv(const char *path, const char *header, const double *h
 }
 
 extern "C" int pa_write_pairs_tsv(const char *path, const char *header, const double *h_x, const double *h_y, uint64_t n) {
-  return pa_host_guard("pa_write_pairs_tsv", pa_set_error, [&] { return write_pairs_tsv(path, header, h_x, h_y, n); });
+  return pa_host_guard("pa_write_pairs_tsv", [&] { return write_pairs_tsv(path, header, h_x, h_y, n); });
 }

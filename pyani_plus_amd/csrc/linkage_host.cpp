@@ -8,28 +8,18 @@
 //
 // The distances: one accumulator per pair, columns in ascending order, s = s + (a - b) * (a - b) with the square
 // rounded before the addition, then the correctly rounded sqrt.  A compiler that is allowed to use FMA instructions
-// (-march=native, or a target that always has them) contracts s + d * d by default and changes the last bit: the pragma
-// below and -ffp-contract=off on this file's Makefile rule forbid it.
+// (-march=native, or a target that always has them) contracts s + d * d by default and changes the last bit:
+// strict_fp.h and -ffp-contract=off from the Makefile forbid it.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <limits>
 #include <numeric>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
+#include "pa_host.h"
 
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#elif defined(__GNUC__)
-#pragma GCC optimize("fp-contract=off")
-#endif
-
-#include "pairs_f64_host.h"  // after the pragma: its loop is compiled with contraction off
-
-void pa_set_error(const char *fmt, ...);
+#include "pairs_f64_host.h"
 
 namespace {
 
@@ -46,18 +36,14 @@ int pa_rowdist_euclid_host(const double *h_x, uint32_t n, uint32_t m, double *h_
   if (n > (1u << 16)) { pa_set_error("pa_rowdist_euclid_host: %u rows; at most 65536", n); return PA_E_INVALID; }
   if (n < 2) return PA_OK;
   if (!h_out || (m && !h_x)) { pa_set_error("pa_rowdist_euclid_host: null argument"); return PA_E_INVALID; }
-  return pa_host_guard("pa_rowdist_euclid_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_rowdist_euclid_host", [&]() -> int {
     const uint64_t steps = (uint64_t)n * (n - 1) / 2 * std::max<uint32_t>(m, 1);
     const uint32_t nt = pa_host_threads(steps, 1u << 20, n_threads);
-    std::atomic<uint32_t> next{0};
-    HostPool::get().run(nt, [&](uint32_t, uint32_t) {
-      for (;;) {  // rows are handed out one at a time (row i has n - 1 - i pairs)
-        const uint32_t i = next.fetch_add(1, std::memory_order_relaxed);
-        if (i + 1 >= n) break;
-        double *out = h_out + condensed_index(n, i, i + 1);
-        pairs_f64::pair_row_accumulate<pairs_f64::EuclidTerm>(h_x + (uint64_t)i * m, h_x + (uint64_t)(i + 1) * m, n - 1 - i, m,
-                                                              [out](uint32_t u, double s) { out[u] = std::sqrt(s); });
-      }
+    // rows are handed out one at a time (row i has n - 1 - i pairs, the last row none; n >= 2 here)
+    pa_for_each(0, n - 1, 1, nt, [&](uint32_t i) {
+      double *out = h_out + condensed_index(n, i, i + 1);
+      pairs_f64::pair_row_accumulate<pairs_f64::EuclidTerm>(h_x + (uint64_t)i * m, h_x + (uint64_t)(i + 1) * m, n - 1 - i, m,
+                                                            [out](uint32_t u, double s) { out[u] = std::sqrt(s); });
     });
     return PA_OK;
   });
@@ -75,7 +61,7 @@ int pa_linkage_average(uint32_t n, const double *h_condensed, double *h_Z, uint3
       pa_set_error("pa_linkage_average: distance %llu of %llu is not finite", (unsigned long long)k, (unsigned long long)count);
       return PA_E_INVALID;
     }
-  return pa_host_guard("pa_linkage_average", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_linkage_average", [&]() -> int {
     const uint64_t N = n;
     std::vector<double> D(h_condensed, h_condensed + N * (N - 1) / 2);  // the merges overwrite it: work on a copy
     std::vector<uint32_t> size(n, 1u), chain(n);

@@ -20,8 +20,6 @@
 // come back once.
 #include "pa_internal.h"
 
-#pragma clang fp contract(off)
-
 #include "mantel_rule.h"
 
 namespace {

@@ -2,7 +2,7 @@
 // use), the argument checks of both entry points, and pa_mantel_host, the twin of pa_mantel (what mantel.hip is compared
 // with, bit for bit, and what mantel-run-comp uses on a machine without a GPU).  include/pyani_hip.h and DESIGN.md
 // section 7j have the contract; mantel_rule.h has its constants and formulas, the same functions the kernels call,
-// compiled here too with contraction off (the pragma below and the Makefile).
+// compiled here too with contraction off (strict_fp.h and the Makefile).
 //
 // The twin hands out rows of X to host-pool threads, a batch of permutations at a time, so that a row of X stays in
 // cache across the batch.  A row's sum is made by one thread in the contract's order and the chains over the rows by the
@@ -13,19 +13,10 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
-
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#elif defined(__GNUC__)
-#pragma GCC optimize("fp-contract=off")
-#endif
+#include "pa_host.h"
 
 #include "distmat_rule.h"
-#include "mantel_rule.h"  // after the pragma
-
-void pa_set_error(const char *fmt, ...);
+#include "mantel_rule.h"
 
 namespace {
 
@@ -34,19 +25,6 @@ using mantel::kSumStart;
 constexpr uint32_t kRowsPerTurn = 8;   // rows a thread takes at a time
 constexpr uint64_t kHostBatch = 64;    // permutations a row of X is kept for
 constexpr uint32_t kNoPlace = 0xFFFFFFFFu;
-
-template <typename Row>
-void for_rows(uint32_t n, uint64_t work_per_row, uint32_t n_threads, Row &&row) {
-  const uint32_t nt = pa_host_threads((uint64_t)n * work_per_row, 1u << 16, n_threads);
-  std::atomic<uint32_t> next{0};
-  HostPool::get().run(nt, [&](uint32_t, uint32_t) {
-    for (;;) {
-      const uint32_t i0 = next.fetch_add(kRowsPerTurn, std::memory_order_relaxed);
-      if (i0 >= n) break;
-      for (uint32_t i = i0; i < std::min(i0 + kRowsPerTurn, n); ++i) row(i);
-    }
-  });
-}
 
 // (((-0.0 + v[0]) + v[1]) + ...) + v[n - 1]
 double chain(const double *v, uint32_t n) {
@@ -72,23 +50,17 @@ int mantel::check_arguments(const void *X, const void *Y, uint32_t n, const uint
                             const void *h_cross, std::vector<uint32_t> *inverse) {
   if (!X || !Y || !h_stats || !h_cross || (n_perms && !h_perms)) { pa_set_error("pa_mantel: null argument"); return PA_E_INVALID; }
   if (n < 3 || n > PA_MANTEL_MAX_N) { pa_set_error("pa_mantel: %u genomes; 3 to %d", n, PA_MANTEL_MAX_N); return PA_E_INVALID; }
-  return pa_host_guard("pa_mantel", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_mantel", [&]() -> int {
     inverse->assign((size_t)(n_perms + 1) * n, kNoPlace);
     for (uint32_t t = 0; t < n; ++t) (*inverse)[t] = t;
     // the rows are independent: host-pool threads invert them and keep the number of the first that is no permutation
     constexpr uint64_t kRowsATurn = 16;
-    std::atomic<uint64_t> next{0}, first_bad{UINT64_MAX};
-    HostPool::get().run(pa_host_threads(n_perms * n, 1u << 18, 0), [&](uint32_t, uint32_t) {
-      for (;;) {
-        const uint64_t q0 = next.fetch_add(kRowsATurn, std::memory_order_relaxed);
-        if (q0 >= n_perms) break;
-        for (uint64_t q = q0; q < std::min(q0 + kRowsATurn, n_perms); ++q) {
-          uint32_t at = 0;
-          if (invert_row(h_perms + q * n, n, inverse->data() + (q + 1) * n, &at)) continue;
-          uint64_t seen = first_bad.load(std::memory_order_relaxed);
-          while (q < seen && !first_bad.compare_exchange_weak(seen, q, std::memory_order_relaxed)) {}
-        }
-      }
+    std::atomic<uint64_t> first_bad{UINT64_MAX};
+    pa_for_each(0, n_perms, kRowsATurn, pa_host_threads(n_perms * n, 1u << 18, 0), [&](uint64_t q) {
+      uint32_t at = 0;
+      if (invert_row(h_perms + q * n, n, inverse->data() + (q + 1) * n, &at)) return;
+      uint64_t seen = first_bad.load(std::memory_order_relaxed);
+      while (q < seen && !first_bad.compare_exchange_weak(seen, q, std::memory_order_relaxed)) {}
     });
     const uint64_t q = first_bad.load();
     if (q == UINT64_MAX) return PA_OK;
@@ -121,7 +93,7 @@ extern "C" int pa_mantel_permutations(uint64_t seed, uint32_t n, uint64_t first,
 
 extern "C" int pa_mantel_host(const double *h_X, const double *h_Y, uint32_t n, const uint32_t *h_perms, uint64_t n_perms, double *h_stats,
                               double *h_cross, uint32_t n_threads) {
-  return pa_host_guard("pa_mantel_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_mantel_host", [&]() -> int {
     std::vector<uint32_t> inverse;
     if (const int s = mantel::check_arguments(h_X, h_Y, n, h_perms, n_perms, h_stats, h_cross, &inverse)) return s;
     const uint64_t N = n;
@@ -135,12 +107,12 @@ extern "C" int pa_mantel_host(const double *h_X, const double *h_Y, uint32_t n, 
     double mean[2], ss[2];
     for (int m = 0; m < 2; ++m) {
       const double *M = matrices[m].second;
-      for_rows(n, N / 2, n_threads, [&](uint32_t i) {
+      pa_for_each(0, n, kRowsPerTurn, pa_host_threads(N * (N / 2), 1u << 16, n_threads), [&](uint32_t i) {
         const double *row = M + i * N;
         rows[i] = mantel::row_sum(i, n, [row](double acc, uint32_t j) { return acc + row[j]; });
       });
       const double mu = mean[m] = chain(rows.data(), n) / pairs;
-      for_rows(n, N / 2, n_threads, [&](uint32_t i) {
+      pa_for_each(0, n, kRowsPerTurn, pa_host_threads(N * (N / 2), 1u << 16, n_threads), [&](uint32_t i) {
         const double *row = M + i * N;
         rows[i] = mantel::row_sum(i, n, [row, mu](double acc, uint32_t j) { return mantel::add_square(acc, mantel::centred(row[j], mu)); });
       });
@@ -151,7 +123,7 @@ extern "C" int pa_mantel_host(const double *h_X, const double *h_Y, uint32_t n, 
     const double mean_x = mean[0], mean_y = mean[1];
     for (uint64_t g0 = 0; g0 <= n_perms; g0 += kHostBatch) {
       const uint64_t g1 = std::min(g0 + kHostBatch, n_perms + 1);
-      for_rows(n, N / 2 * (g1 - g0), n_threads, [&](uint32_t i) {
+      pa_for_each(0, n, kRowsPerTurn, pa_host_threads(N * (N / 2 * (g1 - g0)), 1u << 16, n_threads), [&](uint32_t i) {
         const double *x_row = h_X + i * N;
         for (uint64_t g = g0; g < g1; ++g) {
           const uint32_t *pi = g ? h_perms + (g - 1) * N : identity;

@@ -1,19 +1,14 @@
 // mantel_rule.h -- the constants, the arithmetic and the argument checks of mantel-run-comp, stated once for mantel.hip
 // and mantel_host.cpp (DESIGN.md section 7j has the contract).  Every function is one line of the contract, each
-// operation rounded on its own: include this after `#pragma clang fp contract(off)` in a file that is also compiled with
-// -ffp-contract=off.
+// operation rounded on its own (strict_fp.h).
 #pragma once
 
 #include <cstdint>
 #include <vector>
 
 #include "../../include/pyani_hip.h"
-
-#if defined(__HIPCC__)
-#define PA_MANTEL_FN __host__ __device__ __forceinline__
-#else
-#define PA_MANTEL_FN inline
-#endif
+#include "pa_hd.h"
+#include "strict_fp.h"
 
 namespace mantel {
 
@@ -27,7 +22,7 @@ static_assert(kLanes == 64, "the tree starts at w = 32; on the device an accumul
 constexpr double kSumStart = -0.0;
 
 // The splitmix64 finaliser (the one pcoa_rule.h's start_value uses), mod 2^64
-PA_MANTEL_FN uint64_t fin(uint64_t v) {
+PA_HD uint64_t fin(uint64_t v) {
   uint64_t z = v + 0x9E3779B97F4A7C15ULL;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
@@ -35,14 +30,14 @@ PA_MANTEL_FN uint64_t fin(uint64_t v) {
 }
 
 // x[i, j] = X[i, j] - mean_x for i != j
-PA_MANTEL_FN double centred(double v, double mean) { return v - mean; }
+PA_HD double centred(double v, double mean) { return v - mean; }
 
 // One more term of an accumulator: the term rounded, then the addition
-PA_MANTEL_FN double add_square(double acc, double x) {
+PA_HD double add_square(double acc, double x) {
   const double t = x * x;
   return acc + t;
 }
-PA_MANTEL_FN double add_product(double acc, double x, double y) {
+PA_HD double add_product(double acc, double x, double y) {
   const double t = x * y;
   return acc + t;
 }

@@ -21,10 +21,8 @@
 
 #include "msa_tile_dev.h"
 
-#pragma clang fp contract(off)
-
-#include "host_pool.h"
 #include "msa_boot_rule.h"
+#include "pa_host.h"
 
 namespace {
 using namespace msa_tile;
@@ -189,7 +187,7 @@ int pa_msa_boot_weights(uint64_t seed, uint64_t n_cols, uint64_t first, uint64_t
   // the tools build can lower the limit, so that the refusal can be met: 256 hits on one column do not happen by chance
   const char *lowered = PA_TOOL_ENV("PA_BOOT_WEIGHT_LIMIT");
   const uint32_t limit = lowered ? std::min<uint32_t>(boot::kMaxWeight, (uint32_t)atoi(lowered)) : boot::kMaxWeight;
-  return pa_host_guard("pa_msa_boot_weights", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_msa_boot_weights", [&]() -> int {
     constexpr uint64_t kNone = ~0ull;
     std::vector<uint64_t> over(count, kNone);  // per replicate, the column of the first draw that went past the limit
     HostPool::get().run(pa_host_threads(count * n_cols, 1u << 18, 0), [&](uint32_t id, uint32_t n_workers) {

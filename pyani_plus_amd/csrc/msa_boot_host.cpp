@@ -2,29 +2,19 @@
 // twins pa_msa_boot_counts_host and pa_msa_boot_distances_host of msa_boot.hip (what the kernels are compared with, bit
 // for bit, and what bootstrap-run uses on a machine without a GPU).  include/pyani_hip.h and DESIGN.md section 7l have
 // the contract; msa_boot_rule.h has the distance's formula, the same function the kernel calls, compiled here too with
-// contraction off (the pragma below and the Makefile).
+// contraction off (strict_fp.h and the Makefile).
 //
 // The counts work from the rows as bytes.  A thread takes a pair (i <= j), writes the pair's two masks once -- 0xff
 // where the column counts for M, and for B -- and then adds, per replicate, the weights under each mask: two loops of
 // byte ANDs that the compiler vectorises.  The sums are integers, so no order shows.
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
+#include "pa_host.h"
 
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#elif defined(__GNUC__)
-#pragma GCC optimize("fp-contract=off")
-#endif
-
-#include "msa_boot_rule.h"  // after the pragma
-
-void pa_set_error(const char *fmt, ...);
+#include "msa_boot_rule.h"
 
 int boot::check_weights(const char *who, const uint8_t *h_weights, uint64_t n_cols, uint32_t n_reps, uint32_t *max_weight) {
   uint32_t largest = 0;
@@ -79,16 +69,14 @@ extern "C" int pa_msa_boot_counts_host(const uint8_t *h_rows, uint64_t row_strid
   if (n_rows == 0 || n_reps == 0) return PA_OK;
   uint32_t max_weight = 0;
   if (const int s = boot::check_weights("pa_msa_boot_counts_host", h_weights, n_cols, n_reps, &max_weight)) return s;
-  return pa_host_guard("pa_msa_boot_counts_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_msa_boot_counts_host", [&]() -> int {
     const uint64_t n = n_rows, nn = n * n, pairs = n * (n + 1) / 2;
     const uint32_t nt = pa_host_threads(pairs * std::max<uint64_t>(n_cols, 1) * n_reps, 1u << 20, n_threads);
-    std::atomic<uint64_t> next{0};
+    ChunkQueue queue(0, pairs, 1);  // one pair at a time
     HostPool::get().run(nt, [&](uint32_t, uint32_t) {
       std::vector<uint8_t> eq(n_cols), bt(n_cols);
       uint64_t i = 0, row_start = 0;  // pairs before row i: the pairs (i', j >= i') of the rows above
-      for (;;) {
-        const uint64_t p = next.fetch_add(1, std::memory_order_relaxed);
-        if (p >= pairs) break;
+      for (uint64_t p, p_end; queue.take(p, p_end);) {
         while (p >= row_start + (n - i)) { row_start += n - i; ++i; }  // p only grows for a thread
         const uint64_t j = i + (p - row_start);
         const uint8_t *q = h_rows + i * row_stride, *s = h_rows + j * row_stride;
@@ -117,7 +105,7 @@ extern "C" int pa_msa_boot_distances_host(const uint32_t *h_match, const uint32_
     return PA_E_INVALID;
   }
   if (cells == 0) return PA_OK;
-  return pa_host_guard("pa_msa_boot_distances_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_msa_boot_distances_host", [&]() -> int {
     const uint64_t rows = (uint64_t)n * n_reps;
     HostPool::get().run(pa_host_threads(cells, 1u << 16, n_threads), [&](uint32_t id, uint32_t n_workers) {
       for (uint64_t row = rows * id / n_workers; row < rows * (id + 1) / n_workers; ++row) {

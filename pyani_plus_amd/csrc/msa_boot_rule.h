@@ -1,19 +1,13 @@
 // msa_boot_rule.h -- the arithmetic of bootstrap-run, stated once for msa_boot.hip and msa_boot_host.cpp (DESIGN.md
 // section 7l has the contract): the column a draw hits, the distance of a pair's weighted counts, and what both sides
 // check of a batch of weights.  The distance is one conversion each, one division and one subtraction, each rounded on
-// its own: include this after `#pragma clang fp contract(off)` in a file that is also compiled with -ffp-contract=off.
+// its own (strict_fp.h).
 #pragma once
 
 #include <cstdint>
 
 #include "../../include/pyani_hip.h"
 #include "mantel_rule.h"  // fin, the splitmix64 finaliser
-
-#if defined(__HIPCC__)
-#define PA_BOOT_FN __host__ __device__ __forceinline__
-#else
-#define PA_BOOT_FN inline
-#endif
 
 namespace boot {
 
@@ -29,7 +23,7 @@ inline uint64_t drawn_column(uint64_t base, uint64_t t, uint64_t n_cols) { retur
 // D[i, j] of a replicate from M[i, j], B[i, j] and the rows' weighted residue counts n_i = B[i, i], n_j = B[j, j]:
 // the reference's identity M / aln_length with pa_msa_metrics' division, taken from 1.0; `missing` where the pair has
 // no aligned column left; 0.0 on the diagonal
-PA_BOOT_FN double distance(uint32_t i, uint32_t j, uint32_t m, uint32_t b, uint32_t n_i, uint32_t n_j, double missing) {
+PA_HD double distance(uint32_t i, uint32_t j, uint32_t m, uint32_t b, uint32_t n_i, uint32_t n_j, double missing) {
   if (i == j) return 0.0;
   const uint64_t aln = (uint64_t)n_i + n_j - b;
   if (aln == 0) return missing;

@@ -12,7 +12,6 @@
 // the lines of a record are joined and every byte of " \t\r\n" is deleted.  Every other byte is a residue.
 #include <algorithm>
 #include <array>
-#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -21,11 +20,8 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
+#include "pa_host.h"
 #include "md5.h"
-
-void pa_set_error(const char *fmt, ...);
 
 struct pa_msa {
   std::vector<uint8_t> seq;      // record i's residues at seq[seq0[i], seq0[i] + seq_len[i]) (seq0[i]: where its text starts)
@@ -119,11 +115,8 @@ int msa_load(const char *path, int threads, pa_msa **out) {
   std::vector<std::array<uint64_t, 256>> hists(nt);
   for (auto &h : hists) h.fill(0);
   // records are handed out in order of a shared counter: one huge record and many small ones balance themselves
-  std::atomic<uint32_t> next{0};
-  HostPool::get().run(nt, [&](uint32_t w, uint32_t) {
-    for (uint32_t r; (r = next.fetch_add(1)) < n_rec;) {
-      m->seq_len[r] = parse_body(d, m->seq.data(), m->seq0[r], body1[r], hists[w].data());
-    }
+  pa_for_chunks(0, n_rec, 1, nt, [&](uint32_t w, uint64_t r, uint64_t) {
+    m->seq_len[r] = parse_body(d, m->seq.data(), m->seq0[r], body1[r], hists[w].data());
   });
   md5_thread.join();
   md5.hex(m->md5);
@@ -136,7 +129,7 @@ int msa_load(const char *path, int threads, pa_msa **out) {
 }  // namespace
 
 extern "C" int pa_msa_load(const char *path, int threads, pa_msa **out) {
-  return pa_host_guard("pa_msa_load", pa_set_error, [&] { return msa_load(path, threads, out); });
+  return pa_host_guard("pa_msa_load", [&] { return msa_load(path, threads, out); });
 }
 
 extern "C" int pa_msa_info(const pa_msa *m, uint32_t *n_records, uint64_t *max_len, char md5hex33[33], uint64_t *h_hist256) {
@@ -166,7 +159,7 @@ extern "C" int pa_msa_copy_rows(const pa_msa *m, uint32_t r0, uint32_t r1, uint6
                    (unsigned long long)row_stride);
       return PA_E_INVALID;
     }
-  return pa_host_guard("pa_msa_copy_rows", pa_set_error, [&] {
+  return pa_host_guard("pa_msa_copy_rows", [&] {
     const uint32_t nt = pa_host_threads((uint64_t)(r1 - r0) * row_stride, 1u << 22, 0);
     HostPool::get().run(nt, [&](uint32_t w, uint32_t n_w) {
       for (uint32_t r = r0 + w; r < r1; r += n_w) {
@@ -199,7 +192,7 @@ extern "C" int pa_msa_metrics(const uint32_t *h_match, const uint32_t *h_both, c
                    h_both[i], (unsigned long long)h_nq[i], (unsigned long long)h_ns[i]);
       return PA_E_INVALID;
     }
-  return pa_host_guard("pa_msa_metrics", pa_set_error, [&] {
+  return pa_host_guard("pa_msa_metrics", [&] {
     const uint32_t nt = pa_host_threads(n_pairs, 1u << 16, n_threads);
     HostPool::get().run(nt, [&](uint32_t w, uint32_t n_w) {
       const uint64_t lo = n_pairs * w / n_w, hi = n_pairs * (w + 1) / n_w;

@@ -21,17 +21,16 @@
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-#define PA_WORDS_FN __host__ __device__ __forceinline__
-#else
-#define PA_WORDS_FN inline
 #endif
+
+#include "pa_hd.h"
 
 namespace pa_dev {
 
 constexpr uint64_t kC1 = 0x87c37b91114253d5ULL, kC2 = 0x4cf5ad432745937fULL;
 
 // 4 bases (8 bits, base j at bits 2j) -> 4 ASCII bytes (base j in byte j)
-PA_WORDS_FN uint32_t ascii4(uint32_t b8) {
+PA_HD uint32_t ascii4(uint32_t b8) {
 #if defined(__HIP_DEVICE_COMPILE__)
   // spread the 2-bit codes to one per byte, then use v_perm_b32 as a 4-entry LUT.
   uint32_t u = (b8 | (b8 << 12)) & 0x000F000Fu;
@@ -46,13 +45,13 @@ PA_WORDS_FN uint32_t ascii4(uint32_t b8) {
 }
 
 // the 4-base group `b8` (base j at bits 2j) as ASCII, keeping only its first `nv` bytes
-PA_WORDS_FN uint32_t ascii_group(uint32_t b8, int nv) {
+PA_HD uint32_t ascii_group(uint32_t b8, int nv) {
   const uint32_t a = ascii4(b8);
   return nv >= 4 ? a : (nv <= 0 ? 0u : (a & ((1u << (8 * nv)) - 1u)));
 }
 
-PA_WORDS_FN constexpr uint64_t word_c_first(int j) { return (j & 1) ? kC2 : kC1; }
-PA_WORDS_FN constexpr uint64_t word_c_second(int j) { return (j & 1) ? kC1 : kC2; }
+PA_HD constexpr uint64_t word_c_first(int j) { return (j & 1) ? kC2 : kC1; }
+PA_HD constexpr uint64_t word_c_second(int j) { return (j & 1) ? kC1 : kC2; }
 
 // the entry of lo group `g` of word j of a k-mer of k bases: T and A.hi.  16 bytes, T first: one ds_read_b128 brings
 // it, and T lands in an aligned register pair, the 64-bit addend of the v_mad_u64_u32.
@@ -60,7 +59,7 @@ struct WordLoEntry {
   uint32_t t_lo, t_hi, a_hi, pad;
 };
 
-PA_WORDS_FN WordLoEntry word_lo_entry(int j, int k, uint32_t g) {
+PA_HD WordLoEntry word_lo_entry(int j, int k, uint32_t g) {
   const uint64_t a = (uint64_t)ascii_group(g, k - 8 * j) * word_c_first(j);
   const uint32_t a_lo = (uint32_t)a;
   const uint64_t cb = word_c_second(j);
@@ -69,14 +68,14 @@ PA_WORDS_FN WordLoEntry word_lo_entry(int j, int k, uint32_t g) {
 }
 
 // the entry of hi group `g`: B
-PA_WORDS_FN uint32_t word_hi_entry(int j, int k, uint32_t g) {
+PA_HD uint32_t word_hi_entry(int j, int k, uint32_t g) {
   return (uint32_t)((uint64_t)ascii_group(g, k - 8 * j - 4) * word_c_first(j));
 }
 
 // k_j from the two entries of word j.  The 32 x 64 bit product is one 32 x 32 -> 64 bit multiply-add onto T and one
 // 32 x 32 -> 32 bit multiply into the high word; the halves are kept apart so that what goes into the high word is
 // added as 32-bit values.
-PA_WORDS_FN uint64_t second_product_of(int j, uint32_t t_lo, uint32_t t_hi, uint32_t a_hi, uint32_t b) {
+PA_HD uint64_t second_product_of(int j, uint32_t t_lo, uint32_t t_hi, uint32_t a_hi, uint32_t b) {
   const uint32_t s = a_hi + b;
   const uint64_t t = ((uint64_t)t_hi << 32) | t_lo;
   if (j & 1) {

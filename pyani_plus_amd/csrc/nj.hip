@@ -13,7 +13,7 @@
 //   set-up  r[i] = D[i, 0] + ... + D[i, n - 1], added in this order into one accumulator; m = n live nodes;
 //   while m > 2
 //     score   of a live pair with ids lo < hi: q = ((double)(m - 2) * d(lo, hi) - r[lo]) - r[hi], the product rounded
-//             before the subtractions (no FMA: contraction is off for this file, by the pragma below and in the Makefile);
+//             before the subtractions (no FMA: contraction is off for this file, by strict_fp.h below and in the Makefile);
 //     choice  the smallest q; among equal q (== on doubles) the smallest lo, then the smallest hi -- by node id, never
 //             by where a node is stored, so the storage layout below does not show in the result;
 //     join    d = d(lo, hi); len_lo = 0.5 * d + (r[lo] - r[hi]) / (2.0 * (double)(m - 2)); len_hi = d - len_lo; negative
@@ -46,8 +46,6 @@
 
 #include <memory>
 #include <new>
-
-#pragma clang fp contract(off)
 
 #include "block_reduce_dev.h"
 #include "nj_rule.h"

@@ -1,30 +1,20 @@
 // nj_host.cpp -- neighbour joining on the host: what tree-run uses on a machine without a GPU and what nj.hip is compared
 // with, bit for bit.  include/pyani_hip.h and DESIGN.md section 7h have the contract; nj_rule.h has its arithmetic, the
-// same functions the kernels call, compiled here too with contraction off (the pragma below and the Makefile).
+// same functions the kernels call, compiled here too with contraction off (strict_fp.h and the Makefile).
 //
 // The layout is the kernels': the live nodes in slots 0 .. m - 1 of a copy of D, a join puts u into the smaller of its
 // two slots and moves the last slot into the larger.  The scan of the live pairs runs on host-pool threads, rows handed
 // out a few at a time; each thread keeps its best pair under the total order of the contract and the threads' bests are
 // compared under the same order, so the number of threads does not show in the result.
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
-
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#elif defined(__GNUC__)
-#pragma GCC optimize("fp-contract=off")
-#endif
+#include "pa_host.h"
 
 #include "distmat_rule.h"
-#include "nj_rule.h"  // after the pragma
-
-void pa_set_error(const char *fmt, ...);
+#include "nj_rule.h"
 
 namespace {
 
@@ -44,7 +34,7 @@ extern "C" int pa_nj_host(const double *h_D, uint32_t n, uint32_t *h_child, doub
   const uint64_t N = n;
   if (const int s = pa_check_distance_matrix_host("pa_nj_host", "D", h_D, n)) return s;
   if (n == 1) return PA_OK;
-  return pa_host_guard("pa_nj_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_nj_host", [&]() -> int {
     std::vector<double> D(h_D, h_D + N * N);  // the joins overwrite it: work on a copy
     std::vector<double> r(n);
     std::vector<uint32_t> id(n), slot_of(2 * (size_t)n);
@@ -61,13 +51,11 @@ extern "C" int pa_nj_host(const double *h_D, uint32_t n, uint32_t *h_child, doub
       const double m_minus_2 = (double)(m - 2);
       const uint32_t nt = pa_host_threads((uint64_t)m * (m - 1) / 2, 1u << 16, n_threads);
       bests.assign(nt, Cand{0.0, kNone, kNone});
-      std::atomic<uint32_t> next{0};
+      ChunkQueue rows(0, m - 1, kRowsPerTurn);  // m >= 3 here; the last row has no pair of its own
       HostPool::get().run(nt, [&](uint32_t worker, uint32_t) {
         Cand best{0.0, kNone, kNone};
-        for (;;) {
-          const uint32_t a0 = next.fetch_add(kRowsPerTurn, std::memory_order_relaxed);
-          if (a0 + 1 >= m) break;
-          for (uint32_t a = a0; a < std::min(a0 + kRowsPerTurn, m - 1); ++a) {
+        for (uint64_t a0, a1; rows.take(a0, a1);) {
+          for (uint32_t a = (uint32_t)a0; a < a1; ++a) {
             const double *row = D.data() + a * N;
             const double r_a = r[a];
             const uint32_t id_a = id[a];

@@ -14,7 +14,6 @@
 #include <cstdint>
 #include <cstring>
 #include <algorithm>
-#include <atomic>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -22,10 +21,7 @@
 #include <vector>
 #include <unistd.h>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
-
-void pa_set_error(const char *fmt, ...);
+#include "pa_host.h"
 
 namespace {
 
@@ -141,7 +137,7 @@ static int64_t mask_runs_impl(const uint32_t *h_mask, uint64_t arena_bases, uint
 extern "C" int64_t pa_mask_runs(const uint32_t *h_mask, uint64_t arena_bases, uint64_t *h_run_start,
                                 uint64_t *h_run_len, uint64_t cap) {
   int64_t n = -1;
-  const int st = pa_host_guard("pa_mask_runs", pa_set_error, [&] {
+  const int st = pa_host_guard("pa_mask_runs", [&] {
     n = mask_runs_impl(h_mask, arena_bases, h_run_start, h_run_len, cap);
     return 0;
   });
@@ -324,7 +320,7 @@ extern "C" int64_t pa_text_ambiguous(const uint8_t *h_text, uint64_t n_text, int
                                      uint64_t cap) {
   if ((!h_text && n_text) || (cap && (!h_pos || !h_byte))) { pa_set_error("pa_text_ambiguous: null argument"); return -1; }
   int64_t found = -1;
-  const int st = pa_host_guard("pa_text_ambiguous", pa_set_error, [&] {
+  const int st = pa_host_guard("pa_text_ambiguous", [&] {
     std::vector<uint64_t> pos;
     std::vector<uint8_t> bytes;
     if (fasta) {
@@ -444,7 +440,6 @@ extern "C" int pa_ani_host(const uint32_t *h_counts, const uint64_t *h_q_sizes, 
   nt = std::min(nt, std::max(1u, nq));
   // rows are dealt in small blocks through a shared counter: NULL-heavy rows cost nothing, dense ones a pow each
   constexpr uint32_t kRowBlock = 4;
-  std::atomic<uint32_t> next1{0}, next2{0};
   // symmetric saves one pow per ordered pair and pays for it with a second pass over the matrix.  An all-against-all matrix of
   // many species is NULL almost everywhere (25 000 non-NULL pairs in 10^6 at 40 species): there the second scan costs more
   // than the pows it saves, and the two forms give the same doubles (same integers, same division, same pow) -- so a matrix
@@ -456,56 +451,47 @@ extern "C" int pa_ani_host(const uint32_t *h_counts, const uint64_t *h_q_sizes, 
       for (uint32_t s = 0; s < ns; ++s) { ++seen; non_null += h_counts[(uint64_t)q * ns + s] != 0u; }
     if (non_null * 8u < seen) symmetric = 0;
   }
-  auto pass1 = [&](uint32_t, uint32_t) {
-    for (;;) {
-      const uint32_t r0 = next1.fetch_add(kRowBlock), r1 = std::min(nq, r0 + kRowBlock);
-      if (r0 >= nq) break;
-      for (uint32_t q = r0; q < r1; ++q) {
-        const double qs = (double)h_q_sizes[q];
-        for (uint32_t s = 0; s < ns; ++s) {
-          const uint64_t idx = (uint64_t)q * ns + s;
-          // runs of empty intersections (nearly every pair of an all-against-all matrix of many species): eight NULL pairs at a time
-          if (avx2 && s + 8 <= ns && null_run8(h_counts + idx, h_identity + idx, h_cov_query + idx, h_is_null ? h_is_null + idx : nullptr)) {
-            s += 7;
-            continue;
-          }
-          const uint32_t c = h_counts[idx];
-          if (c == 0) {
-            h_identity[idx] = NAN;
-            h_cov_query[idx] = NAN;
-            if (h_is_null) h_is_null[idx] = 1;
-            continue;
-          }
-          const double qa = std::pow((double)c / qs, inv_k);
-          h_cov_query[idx] = qa;
-          if (!symmetric) {
-            const double ma = std::pow((double)c / (double)h_s_sizes[s], inv_k);
-            h_identity[idx] = qa > ma ? qa : ma;
-          }
-          if (h_is_null) h_is_null[idx] = 0;
+  auto pass1 = [&](uint32_t, uint64_t r0, uint64_t r1) {
+    for (uint32_t q = (uint32_t)r0; q < r1; ++q) {
+      const double qs = (double)h_q_sizes[q];
+      for (uint32_t s = 0; s < ns; ++s) {
+        const uint64_t idx = (uint64_t)q * ns + s;
+        // runs of empty intersections (nearly every pair of an all-against-all matrix of many species): eight NULL pairs at a time
+        if (avx2 && s + 8 <= ns && null_run8(h_counts + idx, h_identity + idx, h_cov_query + idx, h_is_null ? h_is_null + idx : nullptr)) {
+          s += 7;
+          continue;
         }
+        const uint32_t c = h_counts[idx];
+        if (c == 0) {
+          h_identity[idx] = NAN;
+          h_cov_query[idx] = NAN;
+          if (h_is_null) h_is_null[idx] = 1;
+          continue;
+        }
+        const double qa = std::pow((double)c / qs, inv_k);
+        h_cov_query[idx] = qa;
+        if (!symmetric) {
+          const double ma = std::pow((double)c / (double)h_s_sizes[s], inv_k);
+          h_identity[idx] = qa > ma ? qa : ma;
+        }
+        if (h_is_null) h_is_null[idx] = 0;
       }
     }
   };
-  auto pass2 = [&](uint32_t, uint32_t) {  // symmetric only: identity = max(cov[q][s], cov[s][q]), blocked for the transposed reads
-    constexpr uint32_t kB = 64;
-    for (;;) {
-      const uint32_t qb = next2.fetch_add(kB), qe = std::min(nq, qb + kB);
-      if (qb >= nq) break;
-      for (uint32_t sb = 0; sb < ns; sb += kB)
-        for (uint32_t q = qb; q < qe; ++q)
-          for (uint32_t s = sb; s < std::min(sb + kB, ns); ++s) {
-            const uint64_t idx = (uint64_t)q * ns + s;
-            if (h_counts[idx] == 0) continue;
-            const double qa = h_cov_query[idx], ma = h_cov_query[(uint64_t)s * ns + q];
-            h_identity[idx] = qa > ma ? qa : ma;
-          }
-    }
+  constexpr uint32_t kB = 64;
+  auto pass2 = [&](uint32_t, uint64_t qb, uint64_t qe) {  // symmetric only: identity = max(cov[q][s], cov[s][q]), blocked for the transposed reads
+    for (uint32_t sb = 0; sb < ns; sb += kB)
+      for (uint32_t q = (uint32_t)qb; q < qe; ++q)
+        for (uint32_t s = sb; s < std::min(sb + kB, ns); ++s) {
+          const uint64_t idx = (uint64_t)q * ns + s;
+          if (h_counts[idx] == 0) continue;
+          const double qa = h_cov_query[idx], ma = h_cov_query[(uint64_t)s * ns + q];
+          h_identity[idx] = qa > ma ? qa : ma;
+        }
   };
-  return pa_host_guard("pa_ani_host", pa_set_error, [&] {
-    HostPool &pool = HostPool::get();
-    pool.run(nt, pass1);
-    if (symmetric) pool.run(std::min<uint32_t>(nt, (nq + 63u) / 64u), pass2);
+  return pa_host_guard("pa_ani_host", [&] {
+    pa_for_chunks(0, nq, kRowBlock, nt, pass1);
+    if (symmetric) pa_for_chunks(0, nq, kB, std::min<uint32_t>(nt, (nq + 63u) / 64u), pass2);
     return (int)PA_OK;
   });
 }

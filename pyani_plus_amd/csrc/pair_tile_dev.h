@@ -1,6 +1,5 @@
 // pair_tile_dev.h -- the 64 x 64 tile of a run's pairs as classify.hip and derep.hip walk it (gfx950, wave64): one
-// workgroup per tile, a wave per row of the tile, a lane per column.  It includes pair_rule.h: what that asks of a file
-// about contraction holds for this one too.
+// workgroup per tile, a wave per row of the tile, a lane per column.
 //
 // M[a,b] is read from global memory as it lies (a row of the tile is 512 contiguous bytes).  M[b,a] lies in the mirrored
 // tile, whose rows are read the same coalesced way into LDS and read back transposed.  The tile is held as [64][65]

@@ -2,12 +2,13 @@
 // consecutive rows, one accumulator per pair, acc = Term::add(acc, a[c], b[c]) over the columns c in ascending order.
 // What pairs_f64_tile.h is on the device; pa_rowdist_euclid_host (linkage_host.cpp) and pa_tetra_corr_host
 // (tetra_host.cpp) are its two users.  The terms are the kernels' (rowdist.hip's EuclidTerm, tetra.hip's DotTerm), each a
-// rounded product and a rounded addition: include this only with contraction off (the including file's pragma and
-// -ffp-contract=off on its Makefile rule).
+// rounded product and a rounded addition (strict_fp.h).
 #ifndef PA_PAIRS_F64_HOST_H
 #define PA_PAIRS_F64_HOST_H
 #include <algorithm>
 #include <cstdint>
+
+#include "strict_fp.h"
 
 namespace pairs_f64 {
 

@@ -3,9 +3,8 @@
 // rowdist.hip (the squared difference, a run-time column count) and tetra.hip's correlation kernel (the product, 256
 // columns) are its two users; each keeps its own bit contract, its own early return and its own epilogue.
 //
-// Include it only with contraction off (#pragma clang fp contract(off) ahead of the include, -ffp-contract=off on the
-// Makefile rule): the functions below are inlined into the including kernel, and a Term's rounded product must not fuse
-// with its addition into a v_fma_f64.
+// The functions below are inlined into the including kernel, and a Term's rounded product must not fuse with its
+// addition into a v_fma_f64 (strict_fp.h).
 //
 // Layout: one 256-thread workgroup per tile.  Lane (ty, tx) = (tid / 16, tid % 16) holds the 4 x 4 pairs of rows
 // i0 + 4 ty .. + 3 with rows j0 + 4 tx .. + 3: 16 accumulators, one per pair, so the order of a pair's additions is the
@@ -25,6 +24,8 @@
 #ifndef PA_PAIRS_F64_TILE_H
 #define PA_PAIRS_F64_TILE_H
 #include <cstdint>
+
+#include "strict_fp.h"
 
 namespace pairs_f64 {
 

@@ -29,8 +29,6 @@
 // for the trace and the squared Frobenius norm.
 #include "pa_internal.h"
 
-#pragma clang fp contract(off)
-
 #include "pcoa_rule.h"
 #include "pcoa_solver.h"
 

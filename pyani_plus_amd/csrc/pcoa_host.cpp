@@ -2,31 +2,21 @@
 // with, bit for bit, and what ordinate-run uses on a machine without a GPU), and the eigen-solver, which lives here
 // alone: pa_symm_top_eigs (pcoa.hip) and pa_symm_top_eigs_host both call pcoa::top_eigs and hand it their product.
 // include/pyani_hip.h and DESIGN.md section 7i have the contract; pcoa_rule.h has its constants and formulas, the same
-// functions the kernels call, compiled here too with contraction off (the pragma below and the Makefile).
+// functions the kernels call, compiled here too with contraction off (strict_fp.h and the Makefile).
 //
 // The twins hand out rows to host-pool threads; a row's sums are made by one thread in the contract's order, so the
 // number of threads does not show in the result.  The solver's p-wide algebra runs on the calling thread.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
-
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#elif defined(__GNUC__)
-#pragma GCC optimize("fp-contract=off")
-#endif
+#include "pa_host.h"
 
 #include "distmat_rule.h"
-#include "pcoa_rule.h"  // after the pragma
+#include "pcoa_rule.h"
 #include "pcoa_solver.h"
-
-void pa_set_error(const char *fmt, ...);
 
 namespace {
 
@@ -38,19 +28,6 @@ constexpr uint32_t kPhase1Cap = 200;    // iterations of the unshifted phase, at
 constexpr int kJacobiSweeps = 100;      // cyclic Jacobi converges quadratically: a dozen sweeps in practice
 constexpr double kDependent = 1e-8;     // a column that keeps less than this share of its norm is replaced, not normalised
 constexpr int kDotLanes = 8;            // partial sums of the solver's dot products
-
-template <typename Row>
-void for_rows(uint32_t n, uint64_t work_per_row, uint32_t n_threads, Row &&row) {
-  const uint32_t nt = pa_host_threads((uint64_t)n * work_per_row, 1u << 16, n_threads);
-  std::atomic<uint32_t> next{0};
-  HostPool::get().run(nt, [&](uint32_t, uint32_t) {
-    for (;;) {
-      const uint32_t i0 = next.fetch_add(kRowsPerTurn, std::memory_order_relaxed);
-      if (i0 >= n) break;
-      for (uint32_t i = i0; i < std::min(i0 + kRowsPerTurn, n); ++i) row(i);
-    }
-  });
-}
 
 // ---- the solver's vector operations: each a fixed order of single operations, whatever the caller
 // x . y with kDotLanes accumulators: element i goes to accumulator i % kDotLanes, the accumulators are added pairwise
@@ -189,7 +166,7 @@ int pcoa::top_eigs(const char *what, uint32_t n, uint32_t k, double tol, uint32_
   if (max_iter < 1) { pa_set_error("%s: max_iter 0; at least 1", what); return PA_E_INVALID; }
   if (!std::isfinite(fro2) || fro2 < 0.0) { pa_set_error("%s: a squared Frobenius norm of %g; it must be finite and not negative", what, fro2); return PA_E_INVALID; }
   if (!h_values || !h_vectors || !h_residuals || !h_info) { pa_set_error("%s: null output", what); return PA_E_INVALID; }
-  return pa_host_guard(what, pa_set_error, [&]() -> int {
+  return pa_host_guard(what, [&]() -> int {
     // the block: twice the pairs asked for, eight more at least, as wide as the product allows at most
     const uint32_t p = std::min({n, std::max(2 * k, k + 8), (uint32_t)PA_MUL_TALL_MAX_P});
     static_assert(PA_EIGS_MAX_K + 8 <= PA_MUL_TALL_MAX_P, "the widest block still has eight columns beyond the pairs asked for");
@@ -299,8 +276,8 @@ extern "C" int pa_mul_tall_f64_host(const double *h_A, uint32_t n, const double 
   if (n < 1 || n > 65535) { pa_set_error("pa_mul_tall_f64_host: %u rows; 1 to 65535", n); return PA_E_INVALID; }
   if (p < 1 || p > PA_MUL_TALL_MAX_P) { pa_set_error("pa_mul_tall_f64_host: %u columns; 1 to %d", p, PA_MUL_TALL_MAX_P); return PA_E_INVALID; }
   if (!h_A || !h_Q || !h_Y) { pa_set_error("pa_mul_tall_f64_host: null argument"); return PA_E_INVALID; }
-  return pa_host_guard("pa_mul_tall_f64_host", pa_set_error, [&]() -> int {
-    for_rows(n, (uint64_t)n * p, n_threads, [&](uint32_t i) {
+  return pa_host_guard("pa_mul_tall_f64_host", [&]() -> int {
+    pa_for_each(0, n, kRowsPerTurn, pa_host_threads((uint64_t)n * n * p, 1u << 16, n_threads), [&](uint32_t i) {
       const double *row = h_A + (size_t)i * n;
       double y[PA_MUL_TALL_MAX_P], s[PA_MUL_TALL_MAX_P];
       for (uint32_t c = 0; c < p; ++c) y[c] = kSumStart;
@@ -325,10 +302,10 @@ extern "C" int pa_gower_center_host(const double *h_D, uint32_t n, double *h_B, 
   if (!h_D || !h_B || !h_trace || !h_fro2) { pa_set_error("pa_gower_center_host: null argument"); return PA_E_INVALID; }
   const uint64_t N = n;
   if (const int s = pa_check_distance_matrix_host("pa_gower_center_host", "D", h_D, n)) return s;
-  return pa_host_guard("pa_gower_center_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_gower_center_host", [&]() -> int {
     std::vector<double> r(n), row_sq(n);
     const double count = (double)n;
-    for_rows(n, N, n_threads, [&](uint32_t i) {
+    pa_for_each(0, n, kRowsPerTurn, pa_host_threads(N * N, 1u << 16, n_threads), [&](uint32_t i) {
       double s = kSumStart;
       for (uint64_t j = 0; j < N; ++j) s = s + pcoa::squared(h_D[i * N + j]);
       r[i] = s / count;
@@ -336,7 +313,7 @@ extern "C" int pa_gower_center_host(const double *h_D, uint32_t n, double *h_B, 
     double g = kSumStart;
     for (uint32_t i = 0; i < n; ++i) g = g + r[i];
     g = g / count;
-    for_rows(n, N, n_threads, [&](uint32_t i) {
+    pa_for_each(0, n, kRowsPerTurn, pa_host_threads(N * N, 1u << 16, n_threads), [&](uint32_t i) {
       double s = kSumStart;
       for (uint64_t j = 0; j < N; ++j) {
         const double b = pcoa::centred(pcoa::squared(h_D[i * N + j]), r[i], r[j], g);

@@ -1,15 +1,12 @@
 // pcoa_rule.h -- the constants and the arithmetic of ordinate-run, stated once for pcoa.hip and pcoa_host.cpp (DESIGN.md
-// section 7i has the contract).  Every function is one line of the contract, each operation rounded on its own: include
-// this after `#pragma clang fp contract(off)` in a file that is also compiled with -ffp-contract=off.
+// section 7i has the contract).  Every function is one line of the contract, each operation rounded on its own
+// (strict_fp.h).
 #pragma once
 
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define PA_PCOA_FN __host__ __device__ __forceinline__
-#else
-#define PA_PCOA_FN inline
-#endif
+#include "pa_hd.h"
+#include "strict_fp.h"
 
 namespace pcoa {
 
@@ -22,14 +19,14 @@ constexpr int kChunk = 256;
 constexpr double kSumStart = -0.0;
 
 // One more product of a chunk: the product rounded, then the addition
-PA_PCOA_FN double mul_add(double acc, double a, double q) {
+PA_HD double mul_add(double acc, double a, double q) {
   const double prod = a * q;
   return acc + prod;
 }
 
 // The start block of the eigen-solver: Q0[i, c] = start_value(i * p + c), the splitmix64 finaliser of the index mapped
 // to (-1, 1): the top 52 bits u give ((u + 0.5) * 2^-51) - 1, every step exact.
-PA_PCOA_FN double start_value(uint64_t index) {
+PA_HD double start_value(uint64_t index) {
   uint64_t z = index + 0x9E3779B97F4A7C15ULL;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
@@ -41,10 +38,10 @@ PA_PCOA_FN double start_value(uint64_t index) {
 }
 
 // a[i, j] = D[i, j] * D[i, j]
-PA_PCOA_FN double squared(double d) { return d * d; }
+PA_HD double squared(double d) { return d * d; }
 
 // B[i, j] = -0.5 * ((a[i, j] - (r[i] + r[j])) + g): r[i] + r[j] is commutative, so B is bitwise symmetric
-PA_PCOA_FN double centred(double a, double r_i, double r_j, double g) {
+PA_HD double centred(double a, double r_i, double r_j, double g) {
   const double rows = r_i + r_j;
   const double diff = a - rows;
   const double with_g = diff + g;

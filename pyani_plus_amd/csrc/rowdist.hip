@@ -9,7 +9,7 @@
 //   * one accumulator per pair, the columns added in ascending order: s = s + (a - b) * (a - b).  No split over the
 //     columns, no atomics: either would change the order of the additions;
 //   * the square is rounded before it is added.  hipcc's default is -ffp-contract=fast, which would turn s + d * d into one
-//     v_fma_f64 with an unrounded product: the pragma below switches contraction off for this whole file (the Makefile
+//     v_fma_f64 with an unrounded product: strict_fp.h below switches contraction off for this whole file (the Makefile
 //     passes -ffp-contract=off for it as well), and the loop below compiles to v_add_f64, v_mul_f64, v_add_f64;
 //   * the square root is the correctly rounded one: __dsqrt_rn, which the compiler expands into v_rsq_f64 plus a
 //     Newton-Raphson refinement with v_fma_f64 and a scaling of very small and very large arguments.  The bare v_sqrt_f64
@@ -21,8 +21,6 @@
 // bank argument, the double buffer, the register count), here with the run-time column count m and its column guard;
 // grid nt x nt, the tiles below the diagonal return at once, as in classify.hip.
 #include "pa_internal.h"
-
-#pragma clang fp contract(off)
 
 #include "pairs_f64_tile.h"
 

@@ -6,7 +6,7 @@
 // (pyani_plus/plot_run.py:404-575).  Here the reference run R is its n_ref x n_ref identity matrix (NaN: no value) and
 // the other run O is three arrays in database order: the row and the column of each of its comparisons in R's matrix,
 // and its own identity.  The join is then a gather and a stream compaction, and the histograms are reductions.
-// DESIGN.md section 7d has the definition and the measurements.  Contraction is off for this file, by the pragma below
+// DESIGN.md section 7d has the definition and the measurements.  Contraction is off for this file, by strict_fp.h below
 // and by the Makefile, as it is for the host twin.
 //
 // pa_runcomp_join, the shape of classify.hip:
@@ -41,8 +41,7 @@
 
 #include "block_reduce_dev.h"
 #include "pa_internal.h"
-
-#pragma clang fp contract(off)
+#include "strict_fp.h"
 
 namespace {
 

@@ -5,11 +5,8 @@
 #include <cmath>
 #include <cstdint>
 
-#include "../../include/pyani_hip.h"
-
-void pa_set_error(const char *fmt, ...);
-
-#pragma STDC FP_CONTRACT OFF
+#include "pa_host.h"
+#include "strict_fp.h"
 
 extern "C" {
 

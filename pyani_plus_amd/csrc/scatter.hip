@@ -27,8 +27,6 @@
 #include "pa_internal.h"
 #include "uniform_bins.h"
 
-#pragma clang fp contract(off)
-
 namespace {
 
 constexpr int kThreads = kStrideThreads;

@@ -5,12 +5,8 @@
 #include <cmath>
 #include <cstdint>
 
-#include "../../include/pyani_hip.h"
+#include "pa_host.h"
 #include "uniform_bins.h"
-
-void pa_set_error(const char *fmt, ...);
-
-#pragma STDC FP_CONTRACT OFF
 
 int pa_bin2d_validate(const char *who, const void *x, const void *y, uint64_t n, const double *h_xedges, uint32_t bins_x,
                       const double *h_yedges, uint32_t bins_y, const uint64_t *h_counts, const uint64_t *h_last) {

@@ -10,7 +10,6 @@
 // else (several sketches, other molecules) is reported as "not handled" and the caller parses that file with the
 // general JSON reader.
 #include <algorithm>
-#include <atomic>
 #include <charconv>
 #include <cstdio>
 #include <cstring>
@@ -18,11 +17,8 @@
 #include <sys/stat.h>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
+#include "pa_host.h"
 #include "md5.h"
-
-void pa_set_error(const char *fmt, ...);
 
 struct pa_sig_batch {
   struct File {
@@ -150,14 +146,9 @@ int read_sigs(const char *const *paths, uint32_t n, uint32_t ksize, uint64_t max
   b->files.resize(n);
   uint32_t nt = n_threads ? n_threads : pa_cpu_budget();
   nt = std::max<uint32_t>(1u, std::min<uint32_t>(nt, n));
-  std::atomic<uint32_t> next{0};
-  HostPool::get().run(nt, [&](uint32_t, uint32_t) {
-    for (;;) {
-      const uint32_t i = next.fetch_add(1);
-      if (i >= n) break;
-      if (!paths[i]) { b->files[i].status = PA_E_INVALID; b->files[i].message = "null path"; continue; }
-      read_one(paths[i], ksize, max_hash, b->files[i]);
-    }
+  pa_for_each(0, n, 1, nt, [&](uint64_t i) {
+    if (!paths[i]) { b->files[i].status = PA_E_INVALID; b->files[i].message = "null path"; return; }
+    read_one(paths[i], ksize, max_hash, b->files[i]);
   });
   return PA_OK;
 }
@@ -172,7 +163,7 @@ int pa_read_sigs(const char *const *paths, uint32_t n, uint32_t ksize, uint64_t 
   *out = nullptr;
   pa_sig_batch *b = new (std::nothrow) pa_sig_batch();
   if (!b) { pa_set_error("pa_read_sigs: out of host memory"); return PA_E_NOMEM; }
-  const int st = pa_host_guard("pa_read_sigs", pa_set_error, [&] { return read_sigs(paths, n, ksize, max_hash, n_threads, b); });
+  const int st = pa_host_guard("pa_read_sigs", [&] { return read_sigs(paths, n, ksize, max_hash, n_threads, b); });
   if (st != PA_OK) { delete b; return st; }
   *out = b;
   return PA_OK;

@@ -13,11 +13,8 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
+#include "pa_host.h"
 #include "md5.h"
-
-void pa_set_error(const char *fmt, ...);
 
 namespace {
 
@@ -64,7 +61,7 @@ extern "C" int pa_write_sigs(uint32_t n_files, const char *const *paths, const c
   if (n_threads == 0) n_threads = pa_cpu_budget();
   if (n_threads == 0) n_threads = 1;
   if (n_threads > n_files) n_threads = n_files;
-  return pa_host_guard("pa_write_sigs", pa_set_error, [&] {
+  return pa_host_guard("pa_write_sigs", [&] {
     std::vector<int> status(n_threads, PA_OK);
     std::vector<uint32_t> failed(n_threads, 0);
     HostPool::get().run(n_threads, [&](uint32_t t, uint32_t) {  // a throwing worker (out of memory) surfaces in run()

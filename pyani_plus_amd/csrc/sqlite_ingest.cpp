@@ -20,9 +20,7 @@
 #include <string>
 #include <type_traits>
 
-#include "../../include/pyani_hip.h"
-
-void pa_set_error(const char *fmt, ...);
+#include "pa_host.h"
 
 namespace {
 

@@ -12,10 +12,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
-
-void pa_set_error(const char *fmt, ...);
+#include "pa_host.h"
 
 namespace {
 
@@ -167,5 +164,5 @@ int tree_support(uint32_t n, const uint32_t *ref_child, uint32_t n_reps, const u
 extern "C" int pa_tree_support(uint32_t n, const uint32_t *h_ref_child, uint32_t n_reps, const uint32_t *h_rep_child, uint32_t *h_support) {
   if (!h_ref_child || !h_support || (n_reps && !h_rep_child)) { pa_set_error("pa_tree_support: null argument"); return PA_E_INVALID; }
   if (n < 4 || n > 65535) { pa_set_error("pa_tree_support: %u leaves; 4 to 65535 (fewer have no internal edge)", n); return PA_E_INVALID; }
-  return pa_host_guard("pa_tree_support", pa_set_error, [&] { return tree_support(n, h_ref_child, n_reps, h_rep_child, h_support); });
+  return pa_host_guard("pa_tree_support", [&] { return tree_support(n, h_ref_child, n_reps, h_rep_child, h_support); });
 }

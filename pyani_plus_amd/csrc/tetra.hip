@@ -40,8 +40,6 @@
 // additions stays defined.
 #include "pa_internal.h"
 
-#pragma clang fp contract(off)
-
 #include "pairs_f64_tile.h"
 
 namespace {

@@ -6,28 +6,18 @@
 // is this project's own contract (after Teeling et al. 2004); DESIGN.md section 7g has the layout and the measurements.
 //
 // Every floating-point step below is one IEEE double operation in the order the header gives; a compiler that may use
-// FMA instructions would contract a * b + c and change the last bit, so contraction is off for this file (the pragma
-// and -ffp-contract=off on its Makefile rule).
+// FMA instructions would contract a * b + c and change the last bit, so contraction is off for this file (strict_fp.h
+// and -ffp-contract=off from the Makefile).
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <limits>
 #include <vector>
 
-#include "../../include/pyani_hip.h"
-#include "host_pool.h"
+#include "pa_host.h"
 
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#elif defined(__GNUC__)
-#pragma GCC optimize("fp-contract=off")
-#endif
-
-#include "pairs_f64_host.h"  // after the pragma: its loop is compiled with contraction off
-
-void pa_set_error(const char *fmt, ...);
+#include "pairs_f64_host.h"
 
 namespace {
 
@@ -85,16 +75,11 @@ int pa_tetra_counts_host(const uint32_t *h_packed, const uint32_t *h_mask, uint6
       return PA_E_INVALID;
     }
   }
-  return pa_host_guard("pa_tetra_counts_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_tetra_counts_host", [&]() -> int {
     if (n_genomes) memset(h_counts, 0, (size_t)n_genomes * kBins * sizeof(uint64_t));
     const uint32_t nt = std::min<uint32_t>(pa_host_threads(arena_bases, 1u << 20, n_threads), std::max<uint32_t>(n_genomes, 1u));
-    std::atomic<uint32_t> next{0};
-    HostPool::get().run(nt, [&](uint32_t, uint32_t) {
-      for (;;) {  // genomes are handed out one at a time
-        const uint32_t g = next.fetch_add(1, std::memory_order_relaxed);
-        if (g >= n_genomes) break;
-        count_genome(h_packed, h_mask, h_genome_start[g], h_genome_start[g + 1], h_counts + (uint64_t)g * kBins);
-      }
+    pa_for_each(0, n_genomes, 1, nt, [&](uint64_t g) {  // genomes are handed out one at a time
+      count_genome(h_packed, h_mask, h_genome_start[g], h_genome_start[g + 1], h_counts + g * kBins);
     });
     return PA_OK;
   });
@@ -166,24 +151,19 @@ int pa_tetra_corr_host(const double *h_U, uint32_t n, uint32_t q0, uint32_t q1, 
     pa_set_error("pa_tetra_corr_host: null argument");
     return PA_E_INVALID;
   }
-  return pa_host_guard("pa_tetra_corr_host", pa_set_error, [&]() -> int {
+  return pa_host_guard("pa_tetra_corr_host", [&]() -> int {
     const uint64_t ns = s1 - s0;
     const uint32_t nt = pa_host_threads((uint64_t)(q1 - q0) * ns * kWords, 1u << 20, n_threads);
-    std::atomic<uint32_t> next{q0};
-    HostPool::get().run(nt, [&](uint32_t, uint32_t) {
-      for (;;) {
-        const uint32_t i = next.fetch_add(1, std::memory_order_relaxed);
-        if (i >= q1) break;
-        double *out = h_out + (uint64_t)(i - q0) * ns;
-        const uint32_t j_first = symmetric ? i : s0;  // symmetric: row i from the diagonal on, mirrored
-        auto finish = [&](uint32_t u, double acc) {
-          const uint32_t j = j_first + u;
-          const double r = finish_r(acc, i == j);
-          out[j - s0] = r;
-          if (symmetric) h_out[(uint64_t)(j - q0) * ns + (i - s0)] = r;
-        };
-        pairs_f64::pair_row_accumulate<pairs_f64::DotTerm>(h_U + (uint64_t)i * kWords, h_U + (uint64_t)j_first * kWords, s1 - j_first, kWords, finish);
-      }
+    pa_for_each(q0, q1, 1, nt, [&](uint32_t i) {
+      double *out = h_out + (uint64_t)(i - q0) * ns;
+      const uint32_t j_first = symmetric ? i : s0;  // symmetric: row i from the diagonal on, mirrored
+      auto finish = [&](uint32_t u, double acc) {
+        const uint32_t j = j_first + u;
+        const double r = finish_r(acc, i == j);
+        out[j - s0] = r;
+        if (symmetric) h_out[(uint64_t)(j - q0) * ns + (i - s0)] = r;
+      };
+      pairs_f64::pair_row_accumulate<pairs_f64::DotTerm>(h_U + (uint64_t)i * kWords, h_U + (uint64_t)j_first * kWords, s1 - j_first, kWords, finish);
     });
     return PA_OK;
   });

@@ -1,19 +1,13 @@
 // uniform_bins.h -- numpy's uniform-bin rule, stated once for every histogram of the library: the bin of a value among
 // uniform edges (device and host: hist.hip, scatter.hip, hist_host.cpp, scatter_host.cpp), the check of an edge array
 // that the 1-D and the 2-D entry points share, and the argument check of pa_bin2d_f64 and pa_bin2d_f64_host.
-// Every translation unit that includes this is built with -ffp-contract=off: the bin index is a rounded division, then
-// a rounded multiplication, and must not become a fused one.
+// The bin index is a rounded division, then a rounded multiplication, and must not become a fused one (strict_fp.h).
 #ifndef PA_UNIFORM_BINS_H
 #define PA_UNIFORM_BINS_H
 #include <cstdint>
 
-#ifdef __HIPCC__
-#define PA_HD __host__ __device__ __forceinline__
-#else
-#define PA_HD inline
-#endif
-
-#pragma clang fp contract(off)
+#include "pa_hd.h"
+#include "strict_fp.h"
 
 // The bin of x among `bins` uniform bins with these bins + 1 edges; the caller has checked first <= x <= last, where
 // first = edges[0], last = edges[bins], span = last - first and nb = (double)bins.  numpy/lib/_histograms_impl.py, the
