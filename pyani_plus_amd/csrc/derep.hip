@@ -285,8 +285,8 @@ extern "C" int pa_derep_select(pa_ctx *c, const uint64_t *d_bits, uint32_t n, in
   PA_HIP(hipSetDevice(c->device));
   const uint32_t W = derep::words(n);
   // the workspace: the undecided / uncovered nodes, then the new representatives / the workgroups' candidates
-  PA_TRY(c->derep_work.reserve(2ull * W * sizeof(uint64_t)));
-  uint64_t *d_open = c->derep_work.as<uint64_t>(), *d_aux = d_open + W;
+  uint64_t *d_open, *d_aux;
+  PA_TRY(pa_carve(c->derep_work, "derep_work", [&](Carve &k) { d_open = k.take<uint64_t>(W); d_aux = k.take<uint64_t>(W); }));
   uint32_t *d_progress = c->slot<uint32_t>(kDerepProgress);
   PA_HIP(hipMemsetAsync(d_progress, 0, kDerepProgress.bytes(), c->stream));
   PA_HIP(hipMemsetAsync(d_is_rep, 0, n, c->stream));

@@ -247,9 +247,8 @@ extern "C" int pa_moments_f64(pa_ctx *c, const double *d_v, uint64_t n, double *
   PA_REQUIRE(d_v != nullptr, "pa_moments_f64: null array");
   PA_HIP(hipSetDevice(c->device));
   const uint32_t blocks = stride_blocks(n);
-  PA_TRY(c->hist.reserve((2 * (uint64_t)blocks + 3) * sizeof(double)));
-  double *d_partial = c->hist.as<double>();
-  double *d_result = d_partial + 2 * (uint64_t)blocks;  // mean, sum of squared deviations, the count's bits
+  double *d_partial, *d_result;  // d_result: mean, sum of squared deviations, the count's bits
+  PA_TRY(pa_carve(c->hist, "hist", [&](Carve &k) { d_partial = k.take<double>(2 * (uint64_t)blocks); d_result = k.take<double>(3); }));
   PA_TRY(PA_LAUNCH(c, dist_moments_kernel<false>, blocks, kThreads, 0, d_v, n, (const double *)nullptr, d_partial));
   PA_TRY(PA_LAUNCH(c, dist_moments_final_kernel<false>, 1, kThreads, 0, (const double *)d_partial, blocks, d_result));
   PA_TRY(PA_LAUNCH(c, dist_moments_kernel<true>, blocks, kThreads, 0, d_v, n, (const double *)d_result, d_partial));
@@ -281,9 +280,8 @@ extern "C" int pa_kde_gauss_f64(pa_ctx *c, const double *d_v, uint64_t n, const 
   const uint64_t rows64 = (n + per_wg - 1) / per_wg;
   PA_REQUIRE(rows64 < (1ULL << 31), "pa_kde_gauss_f64: %llu values", (unsigned long long)n);
   const uint32_t rows = (uint32_t)rows64;
-  PA_TRY(c->hist.reserve(((uint64_t)rows * n_grid + n_grid) * sizeof(double)));
-  double *d_grid = c->hist.as<double>();
-  double *d_partial = d_grid + n_grid;
+  double *d_grid, *d_partial;
+  PA_TRY(pa_carve(c->hist, "hist", [&](Carve &k) { d_grid = k.take<double>(n_grid); d_partial = k.take<double>((uint64_t)rows * n_grid); }));
   PA_HIP(hipMemcpyAsync(d_grid, h_grid, (uint64_t)n_grid * 8, hipMemcpyHostToDevice, c->stream));
   PA_TRY(PA_LAUNCH(c, dist_kde_kernel, rows, kThreads, 0, d_v, n, (const double *)d_grid, n_grid, slices, bw, d_partial));
   uint32_t top = 1;

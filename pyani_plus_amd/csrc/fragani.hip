@@ -630,7 +630,8 @@ int build_dictionary(pa_ctx *c, FragWork &W, const FragCall &a, uint32_t m, int 
   const uint64_t md_room = std::max<uint32_t>(md, 1u);
   // (the two key buffers of the sort are the halves of ONE allocation: once the index stands they are free, and the seed
   // hits of the batches, 8 bytes each, go there -- memory this process has touched already instead of fresh pages)
-  PA_TRY(W.keys[0].reserve(2 * md_room * 8));
+  uint64_t *keys[2];
+  PA_TRY(pa_carve(W.keys[0], "fragani keys", [&](Carve &k) { keys[0] = k.take<uint64_t>(md_room); keys[1] = k.take<uint64_t>(md_room); }));
   for (int b = 0; b < 2; ++b) PA_TRY(W.vals[b].reserve(md_room * 4));
   PA_TRY(W.flags.reserve(md_room * 8 + 64));
   W.index_key_room = md_room;
@@ -638,7 +639,6 @@ int build_dictionary(pa_ctx *c, FragWork &W, const FragCall &a, uint32_t m, int 
   PA_TRY(W.prev_same.reserve((uint64_t)m * 4));
   PA_TRY(W.post_cw.reserve(md_room * 8));
   PA_TRY(W.post_g.reserve(md_room * 2 + 16));
-  uint64_t *keys[2] = {W.keys[0].as<uint64_t>(), W.keys[0].as<uint64_t>() + W.index_key_room};
   uint32_t *vals[2] = {W.vals[0].as<uint32_t>(), W.vals[1].as<uint32_t>()};
   int which = 0;
   PA_HIP(hipMemsetAsync(W.prev_same.p, 0xff, (uint64_t)m * 4, c->stream));  // -1: no earlier occurrence

@@ -69,9 +69,9 @@ int hist_uniform(pa_ctx *c, const char *who, uint32_t max_bins, const double *d_
   if (n == 0) return PA_OK;
   PA_REQUIRE(d_v != nullptr, "%s: null array", who);
   PA_HIP(hipSetDevice(c->device));
-  PA_TRY(c->hist.reserve((2 * (uint64_t)bins + 1) * 8));
-  unsigned long long *d_counts = c->hist.as<unsigned long long>();
-  double *d_edges = reinterpret_cast<double *>(d_counts + bins);
+  unsigned long long *d_counts;
+  double *d_edges;
+  PA_TRY(pa_carve(c->hist, "hist", [&](Carve &k) { d_counts = k.take<unsigned long long>(bins); d_edges = k.take<double>((uint64_t)bins + 1); }));
   PA_HIP(hipMemsetAsync(d_counts, 0, (uint64_t)bins * 8, c->stream));
   PA_HIP(hipMemcpyAsync(d_edges, h_edges, ((uint64_t)bins + 1) * 8, hipMemcpyHostToDevice, c->stream));
   const uint32_t blocks = stride_blocks(n);

@@ -130,16 +130,15 @@ struct Work {
   double *cross;            // `total` sums
   double *rows;             // n x kBatch row sums; the moments use its first n
   uint32_t *perms, *inverse;  // kBatch x n each
-  // stats is given 64 bytes for its 32: 32 bytes earlier, every 256-byte wave read of pi in the cross kernel at N = 10 000,
-  // 1 000 sums (rows of 40 000 bytes) spans three 128-byte lines where every other permutation's spans two: 0.7 % of the call
-  static uint64_t bytes(uint32_t n, uint64_t total) { return 64 + total * 8 + (uint64_t)n * kBatch * (8 + 4 + 4); }
-  Work(void *base, uint32_t n, uint64_t total) {
-    char *at = static_cast<char *>(base);
-    stats = reinterpret_cast<double *>(at), at += 64;
-    cross = reinterpret_cast<double *>(at), at += total * 8;
-    rows = reinterpret_cast<double *>(at), at += (uint64_t)n * kBatch * 8;
-    perms = reinterpret_cast<uint32_t *>(at), at += (uint64_t)n * kBatch * 4;
-    inverse = reinterpret_cast<uint32_t *>(at);
+  void layout(Carve &k, uint32_t n, uint64_t total) {
+    stats = k.take<double>(4);
+    // stats is given 64 bytes for its 32: 32 bytes earlier, every 256-byte wave read of pi in the cross kernel at N = 10 000,
+    // 1 000 sums (rows of 40 000 bytes) spans three 128-byte lines where every other permutation's spans two: 0.7 % of the call
+    k.slack(64 - 4 * sizeof(double));
+    cross = k.take<double>(total);
+    rows = k.take<double>((uint64_t)n * kBatch);
+    perms = k.take<uint32_t>((uint64_t)n * kBatch);
+    inverse = k.take<uint32_t>((uint64_t)n * kBatch);
   }
 };
 
@@ -147,8 +146,8 @@ struct Work {
 int mantel_device(pa_ctx *c, const double *d_X, const double *d_Y, uint32_t n, const uint32_t *h_perms, uint64_t n_perms,
                   const std::vector<uint32_t> &h_inverse, double *h_stats, double *h_cross) {
   const uint64_t total = n_perms + 1;
-  PA_TRY(c->mantel_work.reserve(Work::bytes(n, total)));
-  const Work w(c->mantel_work.p, n, total);
+  Work w;
+  PA_TRY(pa_carve(c->mantel_work, "mantel_work", [&](Carve &k) { w.layout(k, n, total); }));
   const double *matrices[2] = {d_X, d_Y};
   const char *const names[2] = {"X", "Y"};
   PA_TRY(pa_check_distance_matrices(c, "pa_mantel", names, matrices, 2, n));  // one read-back for both

@@ -125,10 +125,9 @@ struct Work {
   uint8_t *weights;   // kBatch rows of `stride` bytes
   uint32_t *wplanes;  // kBatch x n_words x 8
   static uint64_t stride(uint64_t n_words) { return n_words * 32u; }
-  static uint64_t bytes(uint64_t n_words) { return (uint64_t)kBatch * (stride(n_words) + n_words * kMaxBits * 4u); }
-  Work(void *base, uint64_t n_words) {
-    weights = static_cast<uint8_t *>(base);  // hipMalloc's alignment; each row a multiple of 32 further on
-    wplanes = reinterpret_cast<uint32_t *>(weights + (uint64_t)kBatch * stride(n_words));
+  void layout(Carve &k, uint64_t n_words) {
+    weights = k.take<uint8_t>((uint64_t)kBatch * stride(n_words), 32);  // each row a multiple of 32 further on
+    wplanes = k.take<uint32_t>((uint64_t)kBatch * n_words * kMaxBits);
   }
 };
 
@@ -143,8 +142,8 @@ int boot_counts_device(pa_ctx *c, const uint32_t *d_planes, uint32_t n, uint64_t
     PA_HIP(hipMemsetAsync(d_both, 0, nn * n_reps * 4u, c->stream));
     return PA_OK;
   }
-  PA_TRY(c->boot_work.reserve(Work::bytes(n_words)));
-  const Work w(c->boot_work.p, n_words);
+  Work w;
+  PA_TRY(pa_carve(c->boot_work, "boot_work", [&](Carve &k) { w.layout(k, n_words); }));
   const uint64_t stride = Work::stride(n_words);
   const uint32_t nt = (n + kTile - 1) / kTile;
   const uint64_t tiles = (uint64_t)nt * (nt + 1) / 2;

@@ -250,20 +250,21 @@ __global__ void nj_last_kernel(const double *__restrict__ D, uint32_t n, const u
   *last_len = D[1];
 }
 
+static_assert(alignof(uint32_t) <= alignof(double), "the join table -- len, last_len, child, last -- is read back as one block: no gap before child");
+static_assert(alignof(Cand) <= 16 && sizeof(Cand) % 16 == 0, "cand on 16 bytes puts every candidate on 16 bytes");
 int nj_workspace(pa_ctx *c, uint32_t n, NjWork *w) {
   const uint64_t nt = (n + kTile - 1) / kTile;
-  const uint64_t f64s = n + table_f64(n), u32s = table_u32(n) + 3ull * n;
-  w->table_bytes = table_f64(n) * 8 + table_u32(n) * 4;
-  PA_TRY(c->nj_work.reserve(f64s * 8 + u32s * 4 + 16 + nt * nt * sizeof(Cand)));
-  w->r = c->nj_work.as<double>();
-  w->len = w->r + n;
-  w->child = reinterpret_cast<uint32_t *>(w->len + table_f64(n));  // the table: len, last_len, child, last, contiguous
-  w->id = w->child + table_u32(n);
-  w->slot_of = w->id + n;
-  uint64_t off = (uint64_t)(reinterpret_cast<char *>(w->slot_of + 2ull * n) - c->nj_work.as<char>());
-  off = (off + 15) & ~15ull;
-  w->cand = reinterpret_cast<Cand *>(c->nj_work.as<char>() + off);
-  return PA_OK;
+  return pa_carve(c->nj_work, "nj_work", [&](Carve &k) {
+    w->r = k.take<double>(n);
+    w->len = k.take<double>(table_f64(n));
+    w->child = k.take<uint32_t>(table_u32(n));
+    w->table_bytes = k.end() - n * sizeof(double);  // from len to here
+    w->id = k.take<uint32_t>(n);
+    w->slot_of = k.take<uint32_t>(2ull * n);
+    const uint64_t skipped = k.align_to(16);  // out of the 16 bytes set aside for it: what it leaves is the tail
+    w->cand = k.take<Cand>(nt * nt, 16);
+    k.slack(16 - skipped);
+  });
 }
 
 }  // namespace

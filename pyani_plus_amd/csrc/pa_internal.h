@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/pyani_hip.h"
+#include "pa_carve.h"
 #include "pa_launch_geom.h"
 
 // ---- error plumbing -------------------------------------------------------
@@ -107,6 +108,18 @@ struct DevBuf {
   T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// A workspace of several arrays (pa_carve.h): `layout` states the parts once, as take()s on a Carve that assign the caller's pointers.  It runs
+// twice: to measure, then on buf.p after reserve(the measured bytes).  A size past 64 bits, a part off its alignment or passes that differ: PA_E_INVALID.
+template <class Layout>
+int pa_carve(DevBuf &buf, const char *name, Layout &&layout) {
+  uint64_t bytes = 0;
+  CarveVerdict v = carve_measure(layout, &bytes);
+  if (v == CarveVerdict::kOk) PA_TRY(buf.reserve(bytes));
+  if (v == CarveVerdict::kOk) v = carve_place(buf.p, bytes, layout);
+  PA_REQUIRE(v == CarveVerdict::kOk, "workspace %s, %llu bytes: %s", name, (unsigned long long)bytes, carve_verdict_text(v));
+  return PA_OK;
+}
+
 struct ProfPhase {
   double total_ms = 0.0;
   uint64_t launches = 0;
@@ -160,9 +173,12 @@ constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of
 // The device buffers of the context, each named here and nowhere else: the members of pa_ctx and their release in
 // pa_ctx_destroy follow from this list.  ONE(name): a buffer `name`; PAIR(name): two, `name[0]` and `name[1]`.
 //   sketch phase: cand_keys / cand_vals, the double-buffered radix sort storage; genome_blk, genome start block index
-//   (u32[n+1]); counters, the small device scalars above; hist, radix histograms / scan scratch; flags and scan_tmp,
-//   compaction; region_off and region_cursor, per-genome candidate regions (LDS-sort path); dirty, the dirty-block
-//   bitmap for callers that pass none
+//   (u32[n+1]); counters, the small device scalars above; hist, the radix sort's histograms and the scratch of pa_minmax_f64,
+//   pa_moments_f64, pa_select_f64, pa_kde_gauss_f64 and the uniform histograms (hist.hip); flags, compaction; scan_tmp, the scan's
+//   tile sums and the runs of pa_mask_from_runs; region_off and region_cursor, per-genome candidate regions (LDS-sort path);
+//   dirty, the dirty-block bitmap for callers that pass none.  A sort reserves hist and, through its scans, scan_tmp, and a
+//   reserve may move the buffer: those users of hist hold no pointer into it across a sort (none sorts or scans; pa_kde_gauss_f64
+//   cuts hist after its own pa_minmax_f64 is done), nor pa_mask_from_runs one into scan_tmp across a sort or a scan
 //   pair phase: dict_keys / dict_vals, ids, post_genome, bitrows; dict_scalars, the hash dictionary's scalars above
 //   classify (classify.hip): cls_i, cls_j, cls_score, cls_cov, the edges in (i, j) order, before the sort
 //   plot-run's scatter figures (scatter.hip): bin2d, the two edge arrays, then the cells' counts and last indices

@@ -377,14 +377,12 @@ int pa_dense_ids_sorted(pa_ctx *c, const uint64_t *d_hashes, const uint64_t *d_o
     PA_TRY(c->dict_vals[b].reserve(P * sizeof(uint32_t)));
   }
   PA_TRY(c->ids.reserve(P * sizeof(uint32_t)));
-  PA_TRY(c->post_genome.reserve(2 * P * sizeof(uint32_t)));
-  PA_TRY(c->flags.reserve(2 * P * sizeof(uint32_t)));
+  uint32_t *d_id_sorted, *d_genome_sorted, *d_flags, *d_pos;
+  PA_TRY(pa_carve(c->post_genome, "post_genome", [&](Carve &k) { d_id_sorted = k.take<uint32_t>(P); d_genome_sorted = k.take<uint32_t>(P); }));
+  PA_TRY(pa_carve(c->flags, "flags", [&](Carve &k) { d_flags = k.take<uint32_t>(P); d_pos = k.take<uint32_t>(P); }));
   uint64_t *keys[2] = {c->dict_keys[0].as<uint64_t>(), c->dict_keys[1].as<uint64_t>()};
   uint32_t *vals[2] = {c->dict_vals[0].as<uint32_t>(), c->dict_vals[1].as<uint32_t>()};
   uint32_t *d_ids = c->ids.as<uint32_t>();
-  uint32_t *d_id_sorted = c->post_genome.as<uint32_t>();
-  uint32_t *d_genome_sorted = d_id_sorted + P;
-  uint32_t *d_flags = c->flags.as<uint32_t>(), *d_pos = d_flags + P;
   uint64_t *d_or = c->slot<uint64_t>(kDenseIds) + kDenseOr, *d_distinct = c->slot<uint64_t>(kDenseIds) + kDenseDistinct;
 
   const uint64_t grid = ceil_div(P, kThreads);

@@ -215,8 +215,9 @@ extern "C" int pa_mul_tall_f64(pa_ctx *c, const double *d_A, uint32_t n, const d
   PA_REQUIRE(p >= 1 && p <= PA_MUL_TALL_MAX_P, "pa_mul_tall_f64: %u columns; 1 to %d", p, PA_MUL_TALL_MAX_P);
   PA_REQUIRE(d_A != nullptr && d_Q != nullptr && d_Y != nullptr, "pa_mul_tall_f64: null argument");
   PA_HIP(hipSetDevice(c->device));
-  PA_TRY(c->pcoa_work.reserve(partial_doubles(n, p) * 8));
-  return mul_tall(c, d_A, n, d_Q, p, d_Y, c->pcoa_work.as<double>());
+  double *d_partial;
+  PA_TRY(pa_carve(c->pcoa_work, "pcoa_work", [&](Carve &k) { d_partial = k.take<double>(partial_doubles(n, p)); }));
+  return mul_tall(c, d_A, n, d_Q, p, d_Y, d_partial);
 }
 
 extern "C" int pa_gower_center(pa_ctx *c, const double *d_D, uint32_t n, double *d_B, double *h_trace, double *h_fro2) {
@@ -226,8 +227,10 @@ extern "C" int pa_gower_center(pa_ctx *c, const double *d_D, uint32_t n, double 
   PA_HIP(hipSetDevice(c->device));
   PA_TRY(pa_check_distance_matrix(c, "pa_gower_center", d_D, n));  // one read-back
   // workspace: r, the rows' sums of B^2, B's diagonal, then g, the trace and the squared norm
-  PA_TRY(c->pcoa_work.reserve((3ull * n + 3) * 8));
-  double *r = c->pcoa_work.as<double>(), *row_sq = r + n, *diag = row_sq + n, *g = diag + n, *totals = g + 1;
+  double *r, *row_sq, *diag, *g, *totals;
+  PA_TRY(pa_carve(c->pcoa_work, "pcoa_work", [&](Carve &k) {
+    r = k.take<double>(n); row_sq = k.take<double>(n); diag = k.take<double>(n); g = k.take<double>(1); totals = k.take<double>(2);
+  }));
   const uint32_t sum_blocks = (n + kSumThreads - 1) / kSumThreads;
   PA_TRY(PA_LAUNCH(c, gower_row_squares_kernel, sum_blocks, kSumThreads, 0, d_D, n, (double)n, r));
   PA_TRY(PA_LAUNCH(c, gower_sums_kernel, 1, kWave, 0, (const double *)r, (const double *)nullptr, n, (double)n, g));
@@ -249,8 +252,10 @@ extern "C" int pa_symm_top_eigs(pa_ctx *c, const double *d_B, uint32_t n, uint32
   // the product of one iteration: the block goes up, the two launches, the block comes down
   auto product = [c, d_B, n](const double *h_Q, uint32_t p, double *h_Y) -> int {
     const uint64_t block = (uint64_t)n * p;
-    PA_TRY(c->pcoa_work.reserve((2 * block + partial_doubles(n, p)) * 8));
-    double *d_Q = c->pcoa_work.as<double>(), *d_Y = d_Q + block, *d_partial = d_Y + block;
+    double *d_Q, *d_Y, *d_partial;
+    PA_TRY(pa_carve(c->pcoa_work, "pcoa_work", [&](Carve &k) {
+      d_Q = k.take<double>(block); d_Y = k.take<double>(block); d_partial = k.take<double>(partial_doubles(n, p));
+    }));
     PA_HIP(hipMemcpyAsync(d_Q, h_Q, block * 8, hipMemcpyHostToDevice, c->stream));
     PA_TRY(mul_tall(c, d_B, n, d_Q, p, d_Y, d_partial));
     return pa_copy_to_host(c, h_Y, d_Y, block * 8);

@@ -180,9 +180,8 @@ extern "C" int pa_minmax_f64(pa_ctx *c, const double *d_v, uint64_t n, double *o
   PA_REQUIRE(d_v != nullptr, "pa_minmax_f64: null array");
   PA_HIP(hipSetDevice(c->device));
   const uint32_t blocks = stride_blocks(n);
-  PA_TRY(c->hist.reserve(((uint64_t)blocks + 1) * 3 * sizeof(double)));
-  double *d_partial = c->hist.as<double>();
-  double *d_result = d_partial + 3 * (uint64_t)blocks;
+  double *d_partial, *d_result;
+  PA_TRY(pa_carve(c->hist, "hist", [&](Carve &k) { d_partial = k.take<double>(3 * (uint64_t)blocks); d_result = k.take<double>(3); }));
   PA_TRY(PA_LAUNCH(c, rc_minmax_kernel, blocks, kThreads, 0, d_v, n, d_partial));
   PA_TRY(PA_LAUNCH(c, rc_minmax_final_kernel, 1, kThreads, 0, d_partial, blocks, d_result));
   double result[3];  // min, max, the count's bits

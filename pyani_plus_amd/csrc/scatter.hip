@@ -129,9 +129,9 @@ extern "C" int pa_bin2d_f64(pa_ctx *c, const double *d_x, const double *d_y, uin
   if (n == 0) return PA_OK;
   PA_HIP(hipSetDevice(c->device));
   const uint32_t n_edges = bins_x + bins_y + 2;
-  PA_TRY(c->bin2d.reserve((uint64_t)n_edges * 8 + 2 * (uint64_t)cells * 4));
-  double *d_edges = c->bin2d.as<double>();
-  uint32_t *d_count = reinterpret_cast<uint32_t *>(d_edges + n_edges), *d_last = d_count + cells;
+  double *d_edges;
+  uint32_t *d_count, *d_last;  // one memset and one copy span both
+  PA_TRY(pa_carve(c->bin2d, "bin2d", [&](Carve &k) { d_edges = k.take<double>(n_edges); d_count = k.take<uint32_t>(cells); d_last = k.take<uint32_t>(cells); }));
   PA_HIP(hipMemsetAsync(d_count, 0, 2 * (uint64_t)cells * 4, c->stream));
   PA_HIP(hipMemcpyAsync(d_edges, h_xedges, ((uint64_t)bins_x + 1) * 8, hipMemcpyHostToDevice, c->stream));
   PA_HIP(hipMemcpyAsync(d_edges + bins_x + 1, h_yedges, ((uint64_t)bins_y + 1) * 8, hipMemcpyHostToDevice, c->stream));

@@ -50,9 +50,8 @@ int pa_build_sketch_csr(pa_ctx *c, const uint64_t *d_sorted_hash, const uint32_t
     *h_total = 0;
     return PA_OK;
   }
-  PA_TRY(c->flags.reserve(2 * n_cand * sizeof(uint32_t)));
-  uint32_t *d_flags = c->flags.as<uint32_t>();
-  uint32_t *d_pos = d_flags + n_cand;
+  uint32_t *d_flags, *d_pos;
+  PA_TRY(pa_carve(c->flags, "flags", [&](Carve &k) { d_flags = k.take<uint32_t>(n_cand); d_pos = k.take<uint32_t>(n_cand); }));
   const uint64_t grid = ceil_div(n_cand, kThreads);
   PA_TRY(PA_LAUNCH(c, head_flags_kernel, grid, kThreads, 0, d_sorted_hash, d_sorted_genome, n_cand, d_flags));
   PA_TRY(pa_scan_total_u32(c, d_flags, d_pos, n_cand, c->slot<uint64_t>(kSketchTotal), h_total));

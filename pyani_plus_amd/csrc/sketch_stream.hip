@@ -97,8 +97,8 @@ int pa_mask_from_runs(pa_ctx *c, const uint64_t *h_run_start, const uint64_t *h_
     PA_REQUIRE(h_run_len[r] > 0 && h_run_start[r] + h_run_len[r] <= arena_bases &&
                    (r == 0 || h_run_start[r] >= h_run_start[r - 1] + h_run_len[r - 1]),
                "pa_mask_from_runs: run %u is empty, overlaps its predecessor or leaves the arena", r);
-  PA_TRY(c->scan_tmp.reserve((uint64_t)n_runs * 16 + 16));
-  uint64_t *d_start = c->scan_tmp.as<uint64_t>(), *d_len = d_start + n_runs;
+  uint64_t *d_start, *d_len;
+  PA_TRY(pa_carve(c->scan_tmp, "scan_tmp", [&](Carve &k) { d_start = k.take<uint64_t>(n_runs); d_len = k.take<uint64_t>(n_runs); k.slack(16); }));
   if (n_runs) {
     PA_HIP(hipMemcpyAsync(d_start, h_run_start, (uint64_t)n_runs * 8, hipMemcpyHostToDevice, c->stream));
     PA_HIP(hipMemcpyAsync(d_len, h_run_len, (uint64_t)n_runs * 8, hipMemcpyHostToDevice, c->stream));
