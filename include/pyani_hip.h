@@ -602,7 +602,7 @@ PA_API int pa_write_pairs_tsv(const char *path, const char *header, const double
  *   pa_kde_gauss_f64         (device) h_density[j] = 1 / (m bw sqrt(2 pi)) * sum over the m non-NaN elements of
  *        exp(-0.5 ((h_grid[j] - v_i) / bw)^2) for n_grid <= 1024 grid points: scipy's gaussian_kde(v)(grid) when bw is
  *        Scott's factor times the standard deviation.  The quotient is the correctly rounded one, the exponent the
- *        library's exp of a double.  A run of at most PA_KDE_CHAIN additions one after the other, then a fixed binary
+ *        library's exp of a double.  A run of at most PA_KDE_CHAIN additions (the c of DESIGN.md section 7e) one after the other, then a fixed binary
  *        tree over the partial sums, no floating-point atomics: the same bits run to run; the terms are non-negative, so
  *        the sum's relative error is at most (PA_KDE_CHAIN + the tree's depth) * 2^-53.  PA_E_INVALID for n_grid outside
  *        1 .. 1024, a grid point that is not finite, bw that is not positive and finite, an infinite element and no
@@ -694,7 +694,7 @@ PA_API int pa_bin2d_f64_host(const double *h_x, const double *h_y, uint64_t n, c
  *   pa_append_identity_json  pa_append_comparisons_json for a method without coverage: the same rows with
  *        "cov_query": null in every one, "identity": null where is_null. */
 #define PA_TETRA_BINS 336
-#define PA_TETRA_WORDS 256
+#define PA_TETRA_WORDS 256 /* columns of a Z-score row and of a unit row */
 PA_API int pa_tetra_counts(pa_ctx *ctx, const uint32_t *d_packed, const uint32_t *d_mask, const uint64_t *d_dirty, uint64_t arena_bases,
                            const uint64_t *h_genome_start, uint32_t n_genomes, uint64_t *d_counts);
 PA_API int pa_tetra_counts_host(const uint32_t *h_packed, const uint32_t *h_mask, uint64_t arena_bases, const uint64_t *h_genome_start,
@@ -836,8 +836,8 @@ PA_API int pa_tree_support(uint32_t n, const uint32_t *h_ref_child, uint32_t n_r
  *        Everything but the product is p-wide algebra on one host thread, the same compiled code for both entry
  *        points.  Device: d_B is device memory and is only read; Q goes up and Y comes down once per iteration.  Host
  *        twin: the product runs on n_threads. */
-#define PA_MUL_TALL_MAX_P 32
-#define PA_EIGS_MAX_K 24
+#define PA_MUL_TALL_MAX_P 32 /* pa_mul_tall_f64: columns of the thin block, at most */
+#define PA_EIGS_MAX_K 24     /* pa_symm_top_eigs: eigenpairs, at most */
 PA_API int pa_mul_tall_f64(pa_ctx *ctx, const double *d_A, uint32_t n, const double *d_Q, uint32_t p, double *d_Y);
 PA_API int pa_mul_tall_f64_host(const double *h_A, uint32_t n, const double *h_Q, uint32_t p, double *h_Y, uint32_t n_threads);
 PA_API int pa_gower_center(pa_ctx *ctx, const double *d_D, uint32_t n, double *d_B, double *h_trace, double *h_fro2);

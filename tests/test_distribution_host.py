@@ -184,8 +184,9 @@ def test_describe_on_the_host():
 
 def test_the_binding_states_the_library_constants():
     header = (GOLDEN.parent.parent / "include" / "pyani_hip.h").read_text()
-    for name in ("PA_SELECT_MAX_RANKS", "PA_KDE_CHAIN", "PA_HIST_WIDE_LDS_BINS"):
-        assert f"#define {name} {getattr(_capi, name)}\n" in header
+    # the binding reads the header, so each value is pinned here, against both
+    for name, value in (("PA_SELECT_MAX_RANKS", 8), ("PA_KDE_CHAIN", 2048), ("PA_HIST_WIDE_LDS_BINS", 8192)):
+        assert getattr(_capi, name) == value and f"#define {name} {value}\n" in header, name
     assert distribution.kde_tree_depth(1, 1) == 10 and distribution.kde_tree_depth(100_003, 200) == 2 + 4 and distribution.kde_tree_depth(CHAIN + 1, 1024) == 1  # noqa: PLR2004
 
 

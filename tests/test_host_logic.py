@@ -7,6 +7,7 @@ import logging
 import os
 import re
 import sqlite3
+import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -37,6 +38,20 @@ def test_library_exports_every_header_symbol():
     assert lib.pa_abi_version() == 5
     assert lib.pa_max_hash(300) == 61489146912365176 and lib.pa_max_hash(1000) == 18446744073709552
     assert max_hash_for_scaled(1) == 2**64 - 1
+    # the converse: neither library defines a pa_ symbol the header does not declare.  The dynamic symbol tables are read
+    # with the toolchain that built the libraries (the Makefile's HOSTCXX names its directory): that ROCm ships no llvm-nm,
+    # so its llvm-readelf lists them (Num Value Size Type Bind Vis Ndx Name; Ndx is UND for a symbol the library only
+    # uses).  Without the tool the test fails
+    makefile = (ROOT / "pyani_plus_amd" / "csrc" / "Makefile").read_text()
+    readelf = Path(re.search(r"^HOSTCXX \?= (\S+)$", makefile, flags=re.M).group(1)).with_name("llvm-readelf")
+    tool_names = set(re.findall(r"^PA_TOOL_API [^;(]*?\b(pa_[a-z0-9_]+)\(", header, flags=re.M))
+    assert len(tool_names) == 2 and not tool_names & declared  # noqa: PLR2004
+    for path, want in ((_capi.LIB_PATH, declared), (_capi.TOOLS_LIB_PATH, declared | tool_names)):
+        out = subprocess.run([str(readelf), "--dyn-syms", "--wide", str(path)], capture_output=True, text=True, check=True).stdout
+        rows = [line.split() for line in out.splitlines()]
+        defined = {row[7].split("@")[0] for row in rows if len(row) == 8 and row[0].rstrip(":").isdigit() and row[6] != "UND"}  # noqa: PLR2004
+        assert len(defined) > len(want)  # the table was read: the libraries also define symbols of their C++ runtime
+        assert {name for name in defined if name.startswith("pa_")} == want, (path.name, {name for name in defined if name.startswith("pa_")} ^ want)
 
 
 def test_tool_switches_are_not_in_the_product_library():

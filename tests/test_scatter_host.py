@@ -98,8 +98,9 @@ def test_host_bin2d_summed_over_y_is_the_histogram_of_x():
 
 def test_the_binding_states_the_library_constants():
     header = (GOLDEN.parent.parent / "include" / "pyani_hip.h").read_text()
-    for name in ("PA_BIN2D_MAX_BINS", "PA_BIN2D_LDS_CELLS", "PA_BIN2D_SLOTS"):
-        assert f"#define {name} {getattr(_capi, name)}\n" in header
+    # the binding reads the header, so each value is pinned here, against both
+    for name, value in (("PA_BIN2D_MAX_BINS", 1024), ("PA_BIN2D_LDS_CELLS", 4096), ("PA_BIN2D_SLOTS", 2048)):
+        assert getattr(_capi, name) == value and f"#define {name} {value}\n" in header, name
     assert "#define PA_BIN2D_NONE 0xFFFFFFFFFFFFFFFFULL\n" in header and _capi.PA_BIN2D_NONE == 2**64 - 1
     assert "#define PA_ABI_VERSION 5\n" in header
     assert SLOTS & (SLOTS - 1) == 0 and LDS_CELLS < scatter.GRID**2 <= scatter.MAX_BINS**2
