@@ -787,6 +787,53 @@ PA_API int pa_msa_boot_distances_host(const uint32_t *h_match, const uint32_t *h
                                       uint32_t n_threads);
 PA_API int pa_tree_support(uint32_t n, const uint32_t *h_ref_child, uint32_t n_reps, const uint32_t *h_rep_child, uint32_t *h_support);
 
+/* ---- phylo-run: substitution distances (p, JC69, K80) of an alignment's rows, their tree and its bootstrap ----
+ * Replaces nothing in the reference: pyani-plus has no substitution distance.  The definitions below are this project's
+ * own contract, pinned by an independent restatement in tests/subst_cases.py.  DESIGN.md section 7m.
+ *
+ * Code.  A a -> 4, G g -> 5, C c -> 6, T t U u -> 7, every other byte ('-' and the IUPAC letters included) -> 0: bit 2
+ * "is a nucleotide", bit 1 the class (0 purine, 1 pyrimidine), bit 0 the base within the class.  pa_subst_code writes
+ * the 256 codes; pa_msa_pack takes them with bits = PA_SUBST_BITS.
+ * Counts.  For rows i, j and column weights w_c (all 1 without weights): V = sum of w_c over the columns where both
+ * rows are nucleotides, S = the sum over those of them where the classes are equal and the bases differ (transitions),
+ * T = the sum over those where the classes differ (transversions).  Symmetric; V[i, i] is row i's weighted nucleotide
+ * count and S = T = 0 there.  uint32: n_cols < 2^32 and a replicate's weights add up to n_cols.
+ * Distance (csrc/subst_rule.h, every operation rounded on its own, no FMA).  i == j: 0.0.  V == 0: `missing`.
+ * S + T == 0: +0.0.  p: (double)(S + T) / (double)V.  jc69: a = 1.0 - (4.0 * (double)(S + T)) / (3.0 * (double)V);
+ * d = -0.75 * L(a).  k80: P = (double)S / (double)V; Q = (double)T / (double)V; a = (1.0 - 2.0 * P) - Q;
+ * b = 1.0 - 2.0 * Q; d = -0.5 * L(a) - 0.25 * L(b).  a <= 0 or b <= 0: `missing` (the pair is saturated).  L is the
+ * natural logarithm written out from + - * / and integer operations on the exponent: the same bits on host and device,
+ * within 1 ulp of the correctly rounded logarithm on the samples of tests/test_subst_host.py.
+ *
+ *   pa_subst_code            (host) h_code256[b] = the code of byte b.
+ *   pa_msa_subst_counts      (device) d_planes as pa_msa_pack made them from pa_subst_code's table at PA_SUBST_BITS for
+ *        n_rows <= 65535 rows.  h_weights NULL: every column once, n_reps must be 1; otherwise n_reps x n_cols uint8 on
+ *        the host, every row adding up to n_cols (else PA_E_INVALID naming the row), up to PA_MSA_BOOT_BATCH replicates
+ *        a launch.  d_valid, d_ts, d_tv: n_reps x n_rows x n_rows uint32, replicate after replicate.  Only the 64 x 64
+ *        tiles on and above the diagonal are evaluated and the rest mirrored.  n_cols == 0: all counts zero.  The call
+ *        returns when the stream has finished.
+ *   pa_msa_subst_counts_host the same from the rows as bytes (n_rows rows of row_stride >= n_cols bytes) on n_threads
+ *        host threads (0: as many as the process may use).
+ *   pa_subst_distances       (device) counts -> D, n_reps x n x n f64 on the device, each ready for pa_nj as it is;
+ *        h_undefined: per matrix two uint64 on the host, the unordered pairs that are `missing` for V == 0 and those
+ *        that are for saturation.  model: PA_SUBST_MODEL_*; `missing` finite and >= 0.
+ *   pa_subst_distances_host  the same on the host, with the same bits.
+ *   pa_subst_log_host        h_out[i] = L(h_x[i]), for the accuracy test. */
+#define PA_SUBST_BITS 3
+#define PA_SUBST_MODEL_P 0
+#define PA_SUBST_MODEL_JC69 1
+#define PA_SUBST_MODEL_K80 2
+PA_API int pa_subst_code(uint8_t *h_code256);
+PA_API int pa_msa_subst_counts(pa_ctx *ctx, const uint32_t *d_planes, uint32_t n_rows, uint64_t n_cols, const uint8_t *h_weights, uint32_t n_reps,
+                               uint32_t *d_valid, uint32_t *d_ts, uint32_t *d_tv);
+PA_API int pa_msa_subst_counts_host(const uint8_t *h_rows, uint64_t row_stride, uint32_t n_rows, uint64_t n_cols, const uint8_t *h_weights,
+                                    uint32_t n_reps, uint32_t *h_valid, uint32_t *h_ts, uint32_t *h_tv, uint32_t n_threads);
+PA_API int pa_subst_distances(pa_ctx *ctx, const uint32_t *d_valid, const uint32_t *d_ts, const uint32_t *d_tv, uint32_t n, uint32_t n_reps,
+                              int model, double missing, double *d_D, uint64_t *h_undefined);
+PA_API int pa_subst_distances_host(const uint32_t *h_valid, const uint32_t *h_ts, const uint32_t *h_tv, uint32_t n, uint32_t n_reps, int model,
+                                   double missing, double *h_D, uint64_t *h_undefined, uint32_t n_threads);
+PA_API int pa_subst_log_host(const double *h_x, uint64_t n, double *h_out);
+
 /* ---- ordinate-run: principal coordinates (classical scaling) of a distance matrix ----
  * Replaces nothing in the reference: pyani-plus writes no ordination.  The definitions below are this project's own
  * contract, pinned by an independent restatement in tests/pcoa_cases.py; no parity with any other program is claimed.
@@ -951,7 +998,7 @@ PA_API int pa_derep_assign_host(const double *h_S, uint32_t n, int agg_score, co
 #define PA_PROF_FRAG_SEED 6  /* fragment ANI: fragment sketches, seed hits bucketed by reference genome */
 #define PA_PROF_FRAG_MAP 7   /* fragment ANI: prefilter + map_segments_kernel + per-pair reduction */
 #define PA_PROF_MSA_PACK 8    /* external alignment: rows -> bit planes (msa_pack_kernel) */
-#define PA_PROF_MSA_PAIRS 9   /* external alignment: pair counts M, B (msa_pairs_kernel, mirror) */
+#define PA_PROF_MSA_PAIRS 9   /* external alignment: pair counts M, B (msa_pairs_kernel, mirror); phylo-run: the counts V, S, T, weighted or not (subst_pairs_kernel, subst_boot_pairs_kernel, mirror) */
 #define PA_PROF_CLS_EDGES 10  /* classify: pair evaluation, counts, scan, compaction (cls_edges_kernel) */
 #define PA_PROF_CLS_SORT 11   /* classify: radix sort of the edges by score + gather */
 #define PA_PROF_ROWDIST 12   /* plot-run: all-pairs row distances (rowdist_euclid_kernel) */
@@ -959,7 +1006,7 @@ PA_API int pa_derep_assign_host(const double *h_S, uint32_t n, int agg_score, co
 #define PA_PROF_NJ_JOIN 14   /* tree-run: the choice among the tiles' candidates and the record (nj_join_kernel) */
 #define PA_PROF_NJ_UPDATE 15 /* tree-run: the new node's row and column, the row sums, the swap-remove (nj_update_kernel) */
 #define PA_PROF_MSA_BOOT 16      /* bootstrap-run: weight planes, weighted pair counts, mirror (msa_boot_pairs_kernel) */
-#define PA_PROF_MSA_BOOT_DIST 17 /* bootstrap-run: counts -> distances (msa_boot_distances_kernel) */
+#define PA_PROF_MSA_BOOT_DIST 17 /* bootstrap-run: counts -> distances (msa_boot_distances_kernel); phylo-run: the same (subst_distances_kernel) */
 #define PA_PROF_NPHASES 18
 PA_API int pa_prof_enable(pa_ctx *ctx, int on);
 PA_API int pa_prof_reset(pa_ctx *ctx);

@@ -15,7 +15,7 @@ there: per replicate only the weights go up and the join table comes back.
 
 from __future__ import annotations
 
-from typing import NamedTuple
+from typing import Callable, NamedTuple
 
 import numpy as np
 
@@ -24,7 +24,7 @@ from . import engine as engine_mod
 from .tree import JoinTable, newick
 
 MAX_REPLICATES = 100_000
-# counts (two uint32) and distances (one float64) of a replicate are 16 bytes a cell: what a batch may hold of them
+# what a batch may hold of its replicates' counts and distances
 DEVICE_BATCH_BYTES = 4 << 30
 HOST_BATCH_BYTES = 1 << 30
 
@@ -39,31 +39,49 @@ class Bootstrap(NamedTuple):
     trees: list  # JoinTable per replicate
 
 
-def batch_size(n: int, replicates: int, on_device: bool) -> int:
+class DistanceStep(NamedTuple):
+    """What a batch of replicates' distances are made with: ``distances(rows, n_cols, weights, missing, engine=,
+    device_msa=, threads=)`` gives the batch's matrices (``[R, n, n]`` float64, on the device with an engine, on the host
+    without), and ``cell_bytes`` is what a replicate's counts and distances take a cell."""
+
+    distances: Callable
+    cell_bytes: int
+
+
+def _identity_distances(rows, n_cols: int, weights, missing: float, *, engine=None, device_msa=None, threads: int = 0):
+    """``1 - identity`` of the weighted pair counts (sections 3 and 4 of the contract)."""
+    if engine is not None:
+        return engine.msa_boot_distances(*engine.msa_boot_counts(device_msa, weights), missing)
+    return engine_mod.msa_boot_distances_host(*engine_mod.msa_boot_counts_host(rows, n_cols, weights, threads), missing, threads)
+
+
+# counts (two uint32) and distances (one float64) of a replicate are 16 bytes a cell
+IDENTITY_STEP = DistanceStep(_identity_distances, 16)
+
+
+def batch_size(n: int, replicates: int, on_device: bool, cell_bytes: int = IDENTITY_STEP.cell_bytes) -> int:
     """Replicates per batch: at most a launch's ``PA_MSA_BOOT_BATCH``, and what the batch's matrices may take."""
-    fit = (DEVICE_BATCH_BYTES if on_device else HOST_BATCH_BYTES) // max(16 * n * n, 1)
+    fit = (DEVICE_BATCH_BYTES if on_device else HOST_BATCH_BYTES) // max(cell_bytes * n * n, 1)
     return int(max(1, min(_capi.PA_MSA_BOOT_BATCH, replicates, fit)))
 
 
 def replicate_trees(rows: np.ndarray, n_cols: int, replicates: int, seed: int, missing: float = 1.0, *, engine=None, device_msa=None,
-                    threads: int = 0) -> list[JoinTable]:  # fmt: skip
+                    threads: int = 0, step: DistanceStep = IDENTITY_STEP) -> list[JoinTable]:  # fmt: skip
     """The neighbour-joining trees of replicates ``0 .. replicates - 1`` of ``seed`` over the alignment ``rows`` (uint8,
-    n x stride, the first ``n_cols`` bytes of a row its columns).  ``engine`` with ``device_msa`` (the rows as
-    ``HipEngine.msa_upload`` packs them): counts, distances and joins on the GPU; None: on the host, the same tables."""
+    n x stride, the first ``n_cols`` bytes of a row its columns).  ``engine`` with ``device_msa`` (the rows as the step's
+    upload packs them; ``HipEngine.msa_upload`` for the default): counts, distances and joins on the GPU; None: on the
+    host, the same tables.  ``step``: how a batch's distances are made (default: ``1 - identity``, bootstrap-run's;
+    ``substitution.replicate_step`` for phylo-run's models)."""
     n = int(rows.shape[0])
     trees: list[JoinTable] = []
-    batch = batch_size(n, replicates, engine is not None)
+    batch = batch_size(n, replicates, engine is not None, step.cell_bytes)
     for first in range(0, replicates, batch):
         count = min(batch, replicates - first)
         weights = engine_mod.msa_boot_weights(seed, n_cols, first, count)
+        distances = step.distances(rows, n_cols, weights, missing, engine=engine, device_msa=device_msa, threads=threads)
         if engine is not None:
-            match, both = engine.msa_boot_counts(device_msa, weights)
-            distances = engine.msa_boot_distances(match, both, missing)
-            del match, both
             joined = [engine.nj_tree_inplace(distances[r]) for r in range(count)]
         else:
-            match, both = engine_mod.msa_boot_counts_host(rows, n_cols, weights, threads)
-            distances = engine_mod.msa_boot_distances_host(match, both, missing, threads)
             joined = [engine_mod.nj_tree_host(distances[r], threads) for r in range(count)]
         for child, length, last, last_len in joined:
             trees.append(JoinTable(n, child, length, (int(last[0]), int(last[1])), float(last_len), False))
@@ -71,10 +89,10 @@ def replicate_trees(rows: np.ndarray, n_cols: int, replicates: int, seed: int, m
 
 
 def bootstrap(table: JoinTable, rows: np.ndarray, n_cols: int, replicates: int, seed: int, missing: float = 1.0, *, engine=None, device_msa=None,
-              threads: int = 0) -> Bootstrap:  # fmt: skip
+              threads: int = 0, step: DistanceStep = IDENTITY_STEP) -> Bootstrap:  # fmt: skip
     """The support of every edge of the reference tree ``table`` (over the rows of ``rows``, in their order) among the
     replicate trees of ``replicate_trees``."""
-    trees = replicate_trees(rows, n_cols, replicates, seed, missing, engine=engine, device_msa=device_msa, threads=threads)
+    trees = replicate_trees(rows, n_cols, replicates, seed, missing, engine=engine, device_msa=device_msa, threads=threads, step=step)
     joins = max(table.n - 2, 0)
     rep_child = np.stack([t.child for t in trees]) if trees else np.empty((0, joins, 2), dtype=np.uint32)
     return Bootstrap(table, engine_mod.tree_support(table.n, table.child, rep_child), replicates, trees)

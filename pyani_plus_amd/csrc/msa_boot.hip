@@ -19,40 +19,13 @@
 // blocks before the columns have to be split and added with atomics.
 #include <cstdlib>
 
-#include "msa_tile_dev.h"
+#include "msa_boot_dev.h"
 
 #include "msa_boot_rule.h"
 #include "pa_host.h"
 
 namespace {
 using namespace msa_tile;
-
-constexpr uint32_t kBatch = PA_MSA_BOOT_BATCH;
-static_assert(kBatch <= 65535, "the batch is the grid's z axis");
-static_assert(kChunk * kMaxBits <= kThreads, "one lane stages one weight word");
-
-// wplanes[(rep * n_words + w) * 8 + beta]: the 8 planes of a word side by side, zero from the batch's nb on.
-// weights: n_reps rows of `stride` bytes (a multiple of 32, 16-byte aligned, zero at and past n_cols).
-__global__ __launch_bounds__(kThreads) void boot_weight_planes_kernel(const uint8_t *__restrict__ weights, uint64_t stride, uint32_t n_words,
-                                                                      uint32_t n_reps, uint32_t *__restrict__ wplanes) {
-  const uint64_t total = (uint64_t)n_reps * n_words;
-  for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kThreads) {
-    const uint32_t rep = (uint32_t)(i / n_words), w = (uint32_t)(i % n_words);
-    const uint4 *p16 = reinterpret_cast<const uint4 *>(weights + (uint64_t)rep * stride + (uint64_t)w * 32u);
-    const uint4 v0 = p16[0], v1 = p16[1];
-    const uint32_t words[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    uint32_t out[kMaxBits] = {0};
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const uint32_t v = (words[j >> 2] >> (8 * (j & 3))) & 0xffu;
-#pragma unroll
-      for (uint32_t beta = 0; beta < kMaxBits; ++beta) out[beta] |= ((v >> beta) & 1u) << j;
-    }
-    uint4 *dst = reinterpret_cast<uint4 *>(wplanes + i * kMaxBits);
-    dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
-    dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
-  }
-}
 
 // One block: replicate blockIdx.z, a 64 x 64 tile of the pairs of rows [0, n) over the words of blockIdx.y's slice, as
 // msa_pairs_kernel in its symmetric form.  match and both: the replicates' n x n matrices one after the other.
@@ -71,10 +44,7 @@ __global__ __launch_bounds__(kThreads) void msa_boot_pairs_kernel(const uint32_t
   for (uint32_t wc = g.w_lo; wc < g.w_hi; wc += kChunk) {
     __syncthreads();
     stage_words<P>(stage, planes, n_pad, wc, g, r, tid);
-    if (tid < kChunk * kMaxBits) {
-      const uint32_t w = wc + tid / kMaxBits;
-      (&sw[0][0])[tid] = w < g.w_hi ? wp[(uint64_t)w * kMaxBits + tid % kMaxBits] : 0u;
-    }
+    stage_weight_words(sw, wp, wc, g.w_hi, tid);
     __syncthreads();
 #pragma unroll 1
     for (int k = 0; k < kChunk; ++k) {
@@ -120,17 +90,6 @@ __global__ __launch_bounds__(kThreads) void msa_boot_distances_kernel(const uint
   }
 }
 
-// the workspace of a launch over up to kBatch replicates
-struct Work {
-  uint8_t *weights;   // kBatch rows of `stride` bytes
-  uint32_t *wplanes;  // kBatch x n_words x 8
-  static uint64_t stride(uint64_t n_words) { return n_words * 32u; }
-  void layout(Carve &k, uint64_t n_words) {
-    weights = k.take<uint8_t>((uint64_t)kBatch * stride(n_words), 32);  // each row a multiple of 32 further on
-    wplanes = k.take<uint32_t>((uint64_t)kBatch * n_words * kMaxBits);
-  }
-};
-
 // pa_msa_boot_counts behind its checks; the caller waits for the stream, which still reads h_weights
 int boot_counts_device(pa_ctx *c, const uint32_t *d_planes, uint32_t n, uint64_t n_cols, uint32_t bits, const uint8_t *h_weights, uint32_t n_reps,
                        uint32_t nb, uint32_t *d_match, uint32_t *d_both) {
@@ -144,17 +103,13 @@ int boot_counts_device(pa_ctx *c, const uint32_t *d_planes, uint32_t n, uint64_t
   }
   Work w;
   PA_TRY(pa_carve(c->boot_work, "boot_work", [&](Carve &k) { w.layout(k, n_words); }));
-  const uint64_t stride = Work::stride(n_words);
   const uint32_t nt = (n + kTile - 1) / kTile;
   const uint64_t tiles = (uint64_t)nt * (nt + 1) / 2;
   PA_REQUIRE(tiles < (1ull << 31), "pa_msa_boot_counts: %llu tiles", (unsigned long long)tiles);
   const uint32_t np = n_pad_of(n);
   for (uint32_t r0 = 0; r0 < n_reps; r0 += kBatch) {
     const uint32_t count = std::min(kBatch, n_reps - r0);
-    PA_HIP(hipMemsetAsync(w.weights, 0, (uint64_t)count * stride, c->stream));
-    PA_HIP(hipMemcpy2DAsync(w.weights, stride, h_weights + (uint64_t)r0 * n_cols, n_cols, n_cols, count, hipMemcpyHostToDevice, c->stream));
-    PA_TRY(PA_LAUNCH(c, boot_weight_planes_kernel, stride_blocks((uint64_t)count * n_words), kThreads, 0, (const uint8_t *)w.weights, stride, n_words, count,
-                     w.wplanes));
+    PA_TRY(upload_weight_planes(c, w, h_weights, r0, count, n_cols, n_words));
     const ColumnSplit split = split_columns(c, tiles * count, n_words);
     const int accumulate = split.splits > 1;
     uint32_t *match = d_match + (uint64_t)r0 * nn, *both = d_both + (uint64_t)r0 * nn;

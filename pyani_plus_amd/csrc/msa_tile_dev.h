@@ -1,5 +1,6 @@
 // msa_tile_dev.h -- the 64 x 64 pair tile over an alignment's bit planes, stated once for msa.hip (the pair counts of
-// external-alignment-hip) and msa_boot.hip (the counts of bootstrap-run under column weights): the tile's geometry, its
+// external-alignment-hip), msa_boot.hip (the counts of bootstrap-run under column weights) and subst.hip (the three
+// substitution counts of phylo-run, which stage three planes of four): the tile's geometry, its
 // staging through LDS, the two words a pair and 32 columns come down to, the write of a tile's counts, the mirror of
 // the symmetric form and the split of the columns over the grid.
 //
@@ -78,6 +79,23 @@ __device__ inline void stage_words(Stage<P> &stage, const uint32_t *__restrict__
   }
 }
 
+// Three of the P planes, A, B and C, as the planes 0, 1 and 2 of a three-plane stage (subst.hip reads the two code bits
+// it compares and the non-gap plane of a four-plane layout): stage_words with a stride; load_rows<3> reads it back.
+template <int P, int A, int B, int C>
+__device__ inline void stage_three_planes(Stage<3> &stage, const uint32_t *__restrict__ planes, uint32_t n_pad, uint32_t wc, const TileGeom &g,
+                                          const Ranges &r, uint32_t tid) {
+  static_assert(A < P && B < P && C < P, "a plane of the layout");
+  constexpr uint32_t kHalf = kChunk * 3 * kTile;
+  for (uint32_t i = tid; i < 2u * kHalf; i += kThreads) {
+    const uint32_t half = i / kHalf, rem = i % kHalf, row_in_tile = rem % kTile, wp = rem / kTile;
+    const uint32_t w = wc + wp / 3u, slot = wp % 3u, p = slot == 0 ? A : slot == 1 ? B : C;
+    const uint32_t local = (half ? g.s_tile : g.q_tile) + row_in_tile;
+    const bool ok = w < g.w_hi && local < (half ? r.ns : r.nq);
+    const uint32_t row = (half ? r.s0 : r.q0) + local;
+    (&stage.w[0][0][0][0])[i] = ok ? planes[((uint64_t)w * P + p) * n_pad + row] : 0u;
+  }
+}
+
 // Thread (tx, ty) owns queries ty*4 .. ty*4+3 and subjects tx*4 .. tx*4+3 of the tile: their planes of staged word k
 template <int P>
 __device__ inline void load_rows(const Stage<P> &stage, int k, uint32_t tx, uint32_t ty, uint32_t (&qv)[P][4], uint32_t (&sv)[P][4]) {
@@ -124,6 +142,32 @@ __device__ inline void write_counts(const uint32_t (&m)[4][4], const uint32_t (&
       } else {
         match[idx] = m[a][b];
         both[idx] = bo[a][b];
+      }
+    }
+  }
+}
+
+// The same for three counts a pair
+__device__ inline void write_counts3(const uint32_t (&x)[4][4], const uint32_t (&y)[4][4], const uint32_t (&z)[4][4], const TileGeom &g,
+                                     const Ranges &r, uint32_t tx, uint32_t ty, int accumulate, uint32_t *__restrict__ out_x,
+                                     uint32_t *__restrict__ out_y, uint32_t *__restrict__ out_z) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const uint32_t qi = g.q_tile + ty * 4u + a;
+    if (qi >= r.nq) continue;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const uint32_t sj = g.s_tile + tx * 4u + b;
+      if (sj >= r.ns) continue;
+      const uint64_t idx = (uint64_t)qi * r.ns + sj;
+      if (accumulate) {
+        atomicAdd(out_x + idx, x[a][b]);
+        atomicAdd(out_y + idx, y[a][b]);
+        atomicAdd(out_z + idx, z[a][b]);
+      } else {
+        out_x[idx] = x[a][b];
+        out_y[idx] = y[a][b];
+        out_z[idx] = z[a][b];
       }
     }
   }

@@ -146,7 +146,7 @@ constexpr bool slots_apart(uint32_t region_bytes, std::initializer_list<ScalarSl
 }
 
 // The words of pa_ctx::counters (pa_ctx::slot).  A new feature that needs a device scalar adds its slot here.
-constexpr uint32_t kCtxScalarBytes = 128;      // what pa_ctx_create reserves
+constexpr uint32_t kCtxScalarBytes = 192;      // what pa_ctx_create reserves
 constexpr ScalarSlot kCandCount{0, 2};         // pa_sketch, general path: candidates of the k-mer hash kernel, 64-bit; zeroed and read per attempt
 constexpr ScalarSlot kSketchTotal{2, 2};       // pa_build_sketch_csr, pa_sketch_from_regions, pa_sketch_bottom: the 64-bit total of their scan (written, never zeroed)
 constexpr ScalarSlot kDenseIds{4, 4};          // pa_dense_ids_sorted, two 64-bit words zeroed as one: [0] OR of the keys, [1] distinct keys (its scan's total)
@@ -156,7 +156,8 @@ constexpr ScalarSlot kRegionOverflow{12, 1};   // pa_sketch, pa_sketch_streamed:
 constexpr ScalarSlot kNjPick{16, 8};           // pa_nj: the pair a join chose, written by its join kernel and read by its update kernel (NjPick, nj.hip)
 constexpr ScalarSlot kDistBad{24, 8};          // pa_check_distance_matrices (pa_nj, pa_gower_center, pa_mantel): per matrix, of up to two, two 64-bit words: [0] cells that break the rule, [1] the first of them
 constexpr ScalarSlot kDerepProgress{14, 2};    // pa_derep_select: [0] nodes settled, [1] rounds that had work; zeroed as one, read once per batch of rounds
-static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow, kNjPick, kDistBad, kDerepProgress}),
+constexpr ScalarSlot kSubstUndefined{32, 16};  // pa_subst_distances: per matrix, of up to four a launch, two 64-bit words: the pairs without a shared nucleotide column, the saturated pairs; zeroed and read per launch
+static_assert(slots_apart(kCtxScalarBytes, {kCandCount, kSketchTotal, kDenseIds, kCompactTotal, kRegionOverflow, kNjPick, kDistBad, kDerepProgress, kSubstUndefined}),
               "two slots of pa_ctx::counters overlap or leave the block");
 
 // The words of pa_ctx::dict_scalars (pa_ctx::dict_slot), the hash dictionary's own block, touched by no other phase
@@ -188,7 +189,7 @@ constexpr uint32_t kPinnedBytes = 64;  // pa_ctx::h_pinned, the landing place of
 //   mantel-run-comp (mantel.hip): mantel_work, the moments, the cross sums, a batch's permutations,
 //   inverses and row sums
 //   dereplicate-run (derep.hip): derep_work, the nodes still open as bits, then a round's new representatives or candidates
-//   bootstrap-run (msa_boot.hip): boot_work, a launch's weights as bytes and as bit planes
+//   bootstrap-run (msa_boot.hip) and phylo-run (subst.hip): boot_work, a launch's weights as bytes and as bit planes (msa_boot_dev.h)
 #define PA_CTX_BUFFERS(ONE, PAIR)                                                                                   \
   PAIR(cand_keys) PAIR(cand_vals) ONE(genome_blk) ONE(counters) ONE(hist) ONE(flags) ONE(scan_tmp) ONE(region_off) \
   ONE(region_cursor) ONE(dirty) PAIR(dict_keys) PAIR(dict_vals) ONE(ids) ONE(post_genome) ONE(bitrows)             \

@@ -598,10 +598,11 @@ class HipEngine:
         self._check(self.lib.pa_fragani_set_workspace_cap(self.ctx, int(cap_bytes)), "pa_fragani_set_workspace_cap")
 
     # -- external alignment
-    def msa_upload(self, msa: "LoadedMSA", *, chunk_bytes: int = 1 << 29) -> "DeviceMSA":
-        """Rows -> bit planes on the device (``pa_msa_pack``), the rows uploaded in chunks of at most ``chunk_bytes``."""
+    def msa_upload(self, msa: "LoadedMSA", *, chunk_bytes: int = 1 << 29, table=None) -> "DeviceMSA":
+        """Rows -> bit planes on the device (``pa_msa_pack``), the rows uploaded in chunks of at most ``chunk_bytes``.
+        ``table``: ``(code, bits)`` to pack with (default: ``msa_code_table`` of the alignment's bytes)."""
         t = self.torch
-        code, bits = msa_code_table(msa.histogram)
+        code, bits = table if table is not None else msa_code_table(msa.histogram)
         n, stride = msa.n_rows, msa.rows.shape[1]
         words = int(self.lib.pa_msa_plane_words(n, msa.n_cols, bits))
         planes = t.empty(max(words, 1), dtype=t.int32, device=self.device)
@@ -664,6 +665,47 @@ class HipEngine:
             self._check(self.lib.pa_msa_boot_distances(self.ctx, match.data_ptr(), both.data_ptr(), n, reps, float(missing), d.data_ptr()),
                         "pa_msa_boot_distances")
         return d
+
+    # -- phylo-run
+    def msa_subst_upload(self, msa: "LoadedMSA", *, chunk_bytes: int = 1 << 29) -> "DeviceMSA":
+        """``msa_upload`` with the nucleotide code of ``pa_subst_code`` at ``PA_SUBST_BITS``: the planes
+        ``msa_subst_counts`` reads."""
+        return self.msa_upload(msa, chunk_bytes=chunk_bytes, table=(subst_code_table(), _capi.PA_SUBST_BITS))
+
+    def msa_subst_counts(self, dm: "DeviceMSA", weights=None):
+        """``pa_msa_subst_counts``: ``(V, S, T)`` of every pair of rows of ``dm`` (from ``msa_subst_upload``) as
+        torch.int32 ``[R, n, n]`` on the device (uint32 values): without ``weights`` R = 1 and every column counts once,
+        with them (uint8, R x ``dm.n_cols`` on the host, each row adding up to the columns) a matrix per row.  The same
+        integers as ``msa_subst_counts_host``."""
+        t = self.torch
+        if dm.bits != _capi.PA_SUBST_BITS:
+            raise ValueError(f"planes of {dm.bits} bits: msa_subst_counts reads what msa_subst_upload packs ({_capi.PA_SUBST_BITS} bits)")
+        w = None if weights is None else _boot_weights(weights, dm.n_cols)
+        reps, n = 1 if w is None else len(w), dm.n_rows
+        out = tuple(t.empty((reps, n, n), dtype=t.int32, device=self.device) for _ in range(3))
+        if out[0].numel():
+            self._check(
+                self.lib.pa_msa_subst_counts(self.ctx, dm.planes.data_ptr(), n, dm.n_cols, None if w is None else w.ctypes.data, reps,
+                                             *(x.data_ptr() for x in out)),
+                "pa_msa_subst_counts",
+            )  # fmt: skip
+        return out
+
+    def subst_distances(self, valid, ts, tv, model: str = "k80", missing: float = 3.0):
+        """``pa_subst_distances``: ``(D, undefined)`` -- the distance matrices of ``model`` (``SUBST_MODELS``), float64
+        ``[R, n, n]`` on the device, each ``D[r]`` ready for ``nj_tree_inplace``, and per matrix the unordered pairs
+        without a shared nucleotide column and the saturated ones (uint64 ``[R, 2]``, host).  The same bits as
+        ``subst_distances_host``."""
+        t = self.torch
+        reps, n = int(valid.shape[0]), int(valid.shape[1])
+        d = t.empty((reps, n, n), dtype=t.float64, device=self.device)
+        undefined = np.zeros((reps, 2), dtype=np.uint64)
+        self._check(
+            self.lib.pa_subst_distances(self.ctx, valid.data_ptr(), ts.data_ptr(), tv.data_ptr(), n, reps, _subst_model(model), float(missing), d.data_ptr(),
+                                        undefined.ctypes.data),
+            "pa_subst_distances",
+        )  # fmt: skip
+        return d, undefined
 
     def nj_tree_inplace(self, d) -> tuple[np.ndarray, np.ndarray, np.ndarray, float]:
         """``nj_tree`` of a contiguous n x n float64 tensor on this device, which the call overwrites: no copy is made."""
@@ -1219,6 +1261,63 @@ def tree_support(n: int, ref_child, rep_child) -> np.ndarray:
     out = np.zeros(joins, dtype=np.uint32)
     check(_capi.load_library().pa_tree_support(int(n), ref.ctypes.data, len(rep), rep.ctypes.data, out.ctypes.data), "pa_tree_support")
     return out
+
+
+# ------------------------------------------------------------------ phylo-run: the host forms (no GPU needed)
+SUBST_MODELS = {"p": _capi.PA_SUBST_MODEL_P, "jc69": _capi.PA_SUBST_MODEL_JC69, "k80": _capi.PA_SUBST_MODEL_K80}
+
+
+def _subst_model(model: str) -> int:
+    if model not in SUBST_MODELS:
+        raise ValueError(f"unknown substitution model {model!r}: expected one of {', '.join(SUBST_MODELS)}")
+    return SUBST_MODELS[model]
+
+
+def subst_code_table() -> np.ndarray:
+    """``pa_subst_code``: byte -> nucleotide code (A 4, G 5, C 6, T and U 7, either case; every other byte 0), uint8[256]."""
+    code = np.zeros(256, dtype=np.uint8)
+    check(_capi.load_library().pa_subst_code(code.ctypes.data), "pa_subst_code")
+    return code
+
+
+def subst_log_host(x) -> np.ndarray:
+    """``pa_subst_log_host``: the rule's own natural logarithm of every element."""
+    v = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    out = np.empty_like(v)
+    check(_capi.load_library().pa_subst_log_host(v.ctypes.data, v.size, out.ctypes.data), "pa_subst_log_host")
+    return out
+
+
+def msa_subst_counts_host(rows, n_cols: int, weights=None, threads: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``pa_msa_subst_counts_host``: what ``HipEngine.msa_subst_counts`` returns (uint32 ``[R, n, n]`` each) from the rows
+    as bytes (uint8, n x stride with stride >= ``n_cols``)."""
+    r = np.ascontiguousarray(rows, dtype=np.uint8)
+    if r.ndim != 2 or r.shape[1] < int(n_cols):
+        raise ValueError(f"rows of shape {r.shape} for {n_cols} columns")
+    w = None if weights is None else _boot_weights(weights, n_cols)
+    reps, n = 1 if w is None else len(w), r.shape[0]
+    out = tuple(np.zeros((reps, n, n), dtype=np.uint32) for _ in range(3))
+    check(
+        _capi.load_library().pa_msa_subst_counts_host(r.ctypes.data, r.shape[1], n, int(n_cols), None if w is None else w.ctypes.data, reps,
+                                                      *(x.ctypes.data for x in out), int(threads)),
+        "pa_msa_subst_counts_host",
+    )  # fmt: skip
+    return out
+
+
+def subst_distances_host(valid, ts, tv, model: str = "k80", missing: float = 3.0, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """``pa_subst_distances_host``: what ``HipEngine.subst_distances`` returns, bit for bit (float64 ``[R, n, n]``, uint64 ``[R, 2]``)."""
+    v, s, t = (np.ascontiguousarray(x, dtype=np.uint32) for x in (valid, ts, tv))
+    if v.ndim != 3 or v.shape[1] != v.shape[2] or s.shape != v.shape or t.shape != v.shape:
+        raise ValueError(f"counts of shapes {v.shape}, {s.shape} and {t.shape}, expected the same (R, n, n)")
+    d = np.zeros(v.shape, dtype=np.float64)
+    undefined = np.zeros((v.shape[0], 2), dtype=np.uint64)
+    check(
+        _capi.load_library().pa_subst_distances_host(v.ctypes.data, s.ctypes.data, t.ctypes.data, v.shape[1], v.shape[0], _subst_model(model), float(missing),
+                                                     d.ctypes.data, undefined.ctypes.data, int(threads)),
+        "pa_subst_distances_host",
+    )  # fmt: skip
+    return d, undefined
 
 
 # ------------------------------------------------------------------ dereplicate-run: the host forms (no GPU needed)

@@ -1,7 +1,7 @@
 """The reports of a recorded run: the build's own counterpart of ``export-run``, ``plot-run`` and ``plot-run-comp``
 (their tables; pyani_plus/plot_run.py) and ``classify`` (pyani_plus/public_cli.py:974-1091, 1095-1208, 1211-1331), and
-this project's ``tree-run``, ``bootstrap-run``, ``ordinate-run``, ``mantel-run-comp`` and ``dereplicate-run``.  They read the database through ``run_store`` and compute in the
-report modules (``classify``, ``cluster``, ``distribution``, ``scatter``, ``run_comp``, ``tree``, ``ordination``, ``mantel``,
+this project's ``tree-run``, ``bootstrap-run``, ``phylo-run``, ``ordinate-run``, ``mantel-run-comp`` and ``dereplicate-run``.  They read the database through ``run_store`` and compute in the
+report modules (``classify``, ``cluster``, ``distribution``, ``scatter``, ``run_comp``, ``tree``, ``substitution``, ``ordination``, ``mantel``,
 ``dereplicate`` and the figure modules); ``rundb`` re-exports them and is their command line, and nothing here imports it.
 
 Every command opens the same way -- the database is there, the image formats can be drawn, the output directory is
@@ -29,6 +29,7 @@ from . import mantel as mantel_mod
 from . import ordination as ordination_mod
 from . import run_comp as run_comp_mod
 from . import scatter as scatter_mod
+from . import substitution as substitution_mod
 from . import tree as tree_mod
 from ._capi import HipBackendError
 from .methods import external_alignment_hip, sourmash_hip
@@ -283,7 +284,7 @@ def tree_run(database: Path | str, outdir: Path, *, run_id: int | None = None, l
 
 
 # ------------------------------------------------------------------ bootstrap-run (this project's own: the reference writes no support)
-def _bootstrap_alignment(logger, run: Run, conn, alignment: Path | None, hashes: list[str]):
+def _bootstrap_alignment(logger, run: Run, conn, alignment: Path | None, hashes: list[str], who: str = "bootstrap-run"):
     """The run's alignment as ``engine.LoadedMSA`` with one row per genome, in the order of ``hashes``: found and checked
     as the column worker does (``external_alignment_hip.check_configuration``: next to the database unless ``alignment``
     says where; the md5 is the configuration's either way), a genome's row being its first record."""
@@ -299,7 +300,7 @@ def _bootstrap_alignment(logger, run: Run, conn, alignment: Path | None, hashes:
     try:
         msa = engine_mod.load_msa(path)
     except HipBackendError as err:
-        sourmash_hip.backend_failure(logger, "bootstrap-run alignment loading", err)
+        sourmash_hip.backend_failure(logger, f"{who} alignment loading", err)
     if md5 != msa.md5:
         sourmash_hip.log_sys_exit(logger, f"MD5 checksum of {path} didn't match.")
     cols = external_alignment_hip.MsaColumns(logger, msa, external_alignment_hip.label_mapping(run, msa_label), msa_label, path)
@@ -314,6 +315,23 @@ def _bootstrap_alignment(logger, run: Run, conn, alignment: Path | None, hashes:
         sourmash_hip.log_sys_exit(logger, f"Bad external-alignment, different lengths {cols.rec_len[short]} and {msa.n_cols} from {cols.names[short]} in {path.name}")
     rows = np.ascontiguousarray(msa.rows[records])
     return engine_mod.LoadedMSA(msa.md5, [msa.titles[r] for r in records], msa.lengths[records], msa.histogram, rows, msa.n_cols)
+
+
+def _labelled_alignment(logger, conn, run: Run, n: int, done: int, label: str, alignment: Path | None, who: str):  # noqa: PLR0913
+    """``(identity, labels, msa)`` of a complete external-alignment-hip run: its identity frame relabelled and sorted by
+    label as ``tree-run`` reads it, the labels in that order, and the run's alignment (``_bootstrap_alignment``) with a
+    row per genome in the same order.  Closes ``conn``."""
+    try:
+        frames = _score_frames(logger, conn, run)
+        logger.info("Run %d has %d comparisons across %d genomes.", run.run_id, done, n)
+        mapping = _label_mapping(logger, run, label)
+        identity = _relabelled(logger, run, frames, label)[0]
+        labels = [str(x) for x in identity.columns]
+        hash_of = {str(shown): genome_hash for genome_hash, shown in mapping.items()}
+        msa = _bootstrap_alignment(logger, run, conn, alignment, [hash_of[x] for x in labels], who)
+    finally:
+        conn.close()
+    return identity, labels, msa
 
 
 def bootstrap_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", replicates: int = 100, seed: int = 0,  # noqa: PLR0913
@@ -350,16 +368,7 @@ def bootstrap_run(database: Path | str, outdir: Path, *, run_id: int | None = No
             logger, f"Run-id {run.run_id} is a {method} run: it has no columns to resample (bootstrap-run needs an {external_alignment_hip.METHOD} run)")
     if n < 4:  # noqa: PLR2004
         sourmash_hip.log_sys_exit(logger, f"Run-id {run.run_id} has {n} genomes: a tree of fewer than 4 has no internal edge to support")
-    frames = _score_frames(logger, conn, run)
-    logger.info("Run %d has %d comparisons across %d genomes.", run.run_id, done, n)
-    mapping = _label_mapping(logger, run, label)
-    identity = _relabelled(logger, run, frames, label)[0]
-    labels = [str(x) for x in identity.columns]
-    hash_of = {str(shown): genome_hash for genome_hash, shown in mapping.items()}
-    try:
-        msa = _bootstrap_alignment(logger, run, conn, alignment, [hash_of[x] for x in labels])
-    finally:
-        conn.close()
+    identity, labels, msa = _labelled_alignment(logger, conn, run, n, done, label, alignment, "bootstrap-run")
     distances = tree_mod.run_distances(identity, missing, logger)
     _require_no_negative_distance(logger, distances, "tree")
     try:
@@ -376,6 +385,67 @@ def bootstrap_run(database: Path | str, outdir: Path, *, run_id: int | None = No
         written.append(outdir / f"{stem}_replicates.nwk")
         written[-1].write_text("".join(tree_mod.newick(t, labels) + "\n" for t in result.trees))
     logger.info("Wrote the support of %d edges among %d replicates to %s", max(n - 3, 0), replicates, written[0])
+    return written
+
+
+# ------------------------------------------------------------------ phylo-run (this project's own: the reference has no substitution distance)
+def phylo_run(database: Path | str, outdir: Path, *, run_id: int | None = None, label: str = "stem", model: str = substitution_mod.DEFAULT_MODEL,  # noqa: PLR0913
+              missing: float = substitution_mod.DEFAULT_MISSING, replicates: int = 0, seed: int = 0, alignment: Path | None = None,
+              keep_trees: bool = False, engine=None, logger: logging.Logger | None = None) -> list[Path]:
+    """Substitution distances of the genomes of a complete ``external-alignment-hip`` run from its alignment, their
+    neighbour-joining tree and, with ``replicates`` (0 to 100 000), its column bootstrap (``substitution.phylo``;
+    DESIGN.md section 7m).  ``model`` is "p" (the share of differing columns among those with a nucleotide in both
+    rows), "jc69" or "k80"; a pair without such a column, or one too diverged for the model's logarithm, gets the
+    distance ``missing``, and both kinds are counted in the log.  The genomes are in the order of ``tree-run``'s matrix
+    under the same ``label``; the alignment is found and checked as ``bootstrap-run`` does, and ``seed`` draws the
+    columns ``bootstrap-run`` draws.  A run of another method has no columns, and fewer than 4 genomes have no internal
+    edge to support: each ends with ``bootstrap-run``'s message.
+
+    * ``<method>_<model>_distances.tsv``: the labelled square matrix, values as ``repr``;
+    * ``<method>_<model>_nj.nwk``: its neighbour-joining tree;
+    * with replicates, ``<method>_<model>_nj_bootstrap.nwk`` and ``<method>_<model>_nj_bootstrap.tsv`` as
+      ``bootstrap-run`` writes them, and with ``keep_trees`` ``<method>_<model>_nj_replicates.nwk``.
+
+    ``engine``: a ``HipEngine`` makes the counts, the distances and the joins on the GPU; None makes them on the host,
+    with the same bytes.  Returns the written paths."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    _require_database(logger, database)
+    if model not in substitution_mod.MODELS:
+        sourmash_hip.log_sys_exit(logger, f"Unknown substitution model {model!r}: expected one of {', '.join(substitution_mod.MODELS)}")
+    if isinstance(replicates, bool) or not isinstance(replicates, int) or not 0 <= replicates <= bootstrap_mod.MAX_REPLICATES:
+        sourmash_hip.log_sys_exit(logger, f"Expected 0 to {bootstrap_mod.MAX_REPLICATES} replicates, not {replicates!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        sourmash_hip.log_sys_exit(logger, f"Expected a seed from 0 to 2^64 - 1, not {seed!r}")
+    _require_missing_distance(logger, missing)
+    outdir = _make_outdir(logger, outdir)
+    conn, run, n, done = _open_complete_run(logger, database, run_id, "Exporting")
+    method = run.configuration.method
+    if method != external_alignment_hip.METHOD:
+        sourmash_hip.log_sys_exit(
+            logger, f"Run-id {run.run_id} is a {method} run: it has no columns to resample (phylo-run needs an {external_alignment_hip.METHOD} run)")
+    if replicates and n < 4:  # noqa: PLR2004
+        sourmash_hip.log_sys_exit(logger, f"Run-id {run.run_id} has {n} genomes: a tree of fewer than 4 has no internal edge to support")
+    _identity, labels, msa = _labelled_alignment(logger, conn, run, n, done, label, alignment, "phylo-run")
+    try:
+        device_msa = engine.msa_subst_upload(msa) if engine is not None else None
+        result = substitution_mod.phylo(msa.rows, msa.n_cols, model, missing, replicates, seed, engine=engine, device_msa=device_msa)
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, "phylo-run", err)
+    logger.info("%s distances of %d genomes: %d pairs without a shared nucleotide column, %d saturated pairs (distance %r)", model, n,
+                result.no_columns, result.saturated, float(missing))
+    stem = f"{method}_{model}"
+    written = [outdir / f"{stem}_distances.tsv", outdir / f"{stem}_nj.nwk"]
+    written[0].write_text(substitution_mod.distances_tsv(result.distances, labels))
+    written[1].write_text(tree_mod.newick(result.table, labels) + "\n")
+    if result.bootstrap is not None:
+        written += [outdir / f"{stem}_nj_bootstrap.nwk", outdir / f"{stem}_nj_bootstrap.tsv"]
+        written[2].write_text(bootstrap_mod.support_newick(result.bootstrap, labels) + "\n")
+        written[3].write_text(bootstrap_mod.support_tsv(result.bootstrap))
+        if keep_trees:
+            written.append(outdir / f"{stem}_nj_replicates.nwk")
+            written[-1].write_text("".join(tree_mod.newick(t, labels) + "\n" for t in result.bootstrap.trees))
+        logger.info("Wrote the support of %d edges among %d replicates to %s", max(n - 3, 0), replicates, written[2])
+    logger.info("Wrote %s distances and their tree to %s", model, outdir)
     return written
 
 

@@ -11,7 +11,7 @@ Every run takes the same steps: register the genomes, record the run, find what 
 (``_finish_run``); ``_RunState`` carries what the steps share.
 
 The database layer is ``run_store`` and the eight reports of a recorded run (``export_run``, ``classify``, ``plot_run``,
-``plot_run_comp``, ``tree_run``, ``bootstrap_run``, ``ordinate_run``, ``mantel_run_comp``, ``dereplicate_run``) are ``reports``.  This module imports ``reports``, which
+``plot_run_comp``, ``tree_run``, ``bootstrap_run``, ``phylo_run``, ``ordinate_run``, ``mantel_run_comp``, ``dereplicate_run``) are ``reports``.  This module imports ``reports``, which
 imports ``run_store``, never the other way round, and re-exports both: ``rundb.<name>`` is the public face of all three.
 """
 
@@ -39,13 +39,14 @@ from . import launch, wire
 from . import classify as classify_mod
 from . import dereplicate as dereplicate_mod
 from . import scatter as scatter_mod
+from . import substitution as substitution_mod
 from . import tree as tree_mod
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
 from .engine import HipEngine, load_fasta_files
 from .methods import external_alignment_hip, fastani_hip, sourmash_hip, tetra_hip
 from .methods.external_alignment_hip import filename_stem  # noqa: F401  (reached as ``rundb.filename_stem``)
-from .reports import _require_database, bootstrap_run, classify, dereplicate_run, export_run, mantel_run_comp, ordinate_run, plot_run, plot_run_comp, tree_run  # noqa: F401
+from .reports import _require_database, bootstrap_run, classify, dereplicate_run, export_run, mantel_run_comp, ordinate_run, phylo_run, plot_run, plot_run_comp, tree_run  # noqa: F401
 from .run_store import (FASTA_EXTENSIONS, INSERT_COMPARISON, SCHEMA, Configuration, Run, RunGenomeAssociation, Session, _load_tile,  # noqa: F401
                         _open_run, _select_run_comparisons, _store_matrix_cache, add_run, cache_comparisons, cache_matrices, check_fasta,
                         connect_to_db, count_run_comparisons, db_configuration, db_genome, fasta_length_and_description,
@@ -902,6 +903,8 @@ _COMMANDS = {  # subcommand -> its call from (the parsed arguments, the engine o
                                                    logger=logger),
     "bootstrap-run": lambda a, engine, logger: bootstrap_run(a.database, a.outdir, run_id=a.run_id, label=a.label, replicates=a.replicates, seed=a.seed,
                                                              missing=a.missing, alignment=a.alignment, keep_trees=a.keep_trees, engine=engine, logger=logger),
+    "phylo-run": lambda a, engine, logger: phylo_run(a.database, a.outdir, run_id=a.run_id, label=a.label, model=a.model, missing=a.missing, replicates=a.replicates,
+                                                     seed=a.seed, alignment=a.alignment, keep_trees=a.keep_trees, engine=engine, logger=logger),
     "ordinate-run": lambda a, engine, logger: ordinate_run(a.database, a.outdir, run_id=a.run_id, label=a.label, dimensions=a.dimensions, missing=a.missing,
                                                            formats=a.formats, engine=engine, logger=logger),
     "mantel-run-comp": lambda a, engine, logger: mantel_run_comp(a.database, a.outdir, a.run_ids, permutations=a.permutations, seed=a.seed, missing=a.missing,
@@ -913,7 +916,7 @@ _COMMANDS = {  # subcommand -> its call from (the parsed arguments, the engine o
 
 
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run,bootstrap-run,ordinate-run,mantel-run-comp,dereplicate-run} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run,bootstrap-run,phylo-run,ordinate-run,mantel-run-comp,dereplicate-run} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -980,6 +983,16 @@ def main(argv: list[str] | None = None) -> int:
         ("--replicates", {"type": int, "default": 100, "help": "bootstrap replicates, 1 to 100000 (default 100)"}),
         ("--seed", {"type": int, "default": 0, "help": "seed of the column draws, 0 to 2^64 - 1 (default 0)"}),
         _MISSING_OPTION,
+        ("--alignment", {"type": Path, "default": None, "help": "the run's alignment (default: the configuration's file next to the database)"}),
+        ("--keep-trees", {"action": "store_true", "help": "also write the replicate trees, one per line"}),
+    ))  # fmt: skip
+    _report_parser(sub, "phylo-run", "p, JC69 or K80 distances of a complete external-alignment-hip run from its alignment, their neighbour-joining tree and its bootstrap",
+                   device="make the counts, the distances and the joins", own=(
+        ("--model", {"choices": substitution_mod.MODELS[::-1], "default": substitution_mod.DEFAULT_MODEL, "help": "the substitution model (default k80)"}),
+        ("--missing", {"type": float, "default": substitution_mod.DEFAULT_MISSING,
+                       "help": "distance of a pair without a shared nucleotide column or too diverged for the model (default 3.0)"}),
+        ("--replicates", {"type": int, "default": 0, "help": "bootstrap replicates, 0 to 100000 (default 0: no bootstrap)"}),
+        ("--seed", {"type": int, "default": 0, "help": "seed of the column draws, 0 to 2^64 - 1 (default 0)"}),
         ("--alignment", {"type": Path, "default": None, "help": "the run's alignment (default: the configuration's file next to the database)"}),
         ("--keep-trees", {"action": "store_true", "help": "also write the replicate trees, one per line"}),
     ))  # fmt: skip
