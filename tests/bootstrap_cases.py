@@ -16,6 +16,7 @@ weights the bootstrap tests share.  Written from the contract alone, without loo
 from __future__ import annotations
 
 import functools
+import re
 from typing import NamedTuple
 
 import numpy as np
@@ -121,6 +122,15 @@ def alignment(n: int, n_cols: int, seed: int, *, alphabet: bytes = b"ACGT", gaps
     return rows
 
 
+TIED_ROWS, TIED_COLUMNS, TIED_SEED, TIED_COPIES = 60, 64, 31, 3
+
+
+def tied_alignment(make=alignment) -> np.ndarray:
+    """60 rows of 64 columns stacked three times: 180 rows, more than one scan tile of the joins, whose distances -- ratios
+    of small integers, 0 between the copies of a row -- tie in every replicate."""
+    return np.tile(make(TIED_ROWS, TIED_COLUMNS, TIED_SEED), (TIED_COPIES, 1))
+
+
 # the three alignments of the support tests: (rows, columns, seed)
 SUPPORT_ALIGNMENTS = ((7, 97, 11), (12, 300, 12), (9, 64, 13))
 SUPPORT_REPLICATES = 50
@@ -203,6 +213,55 @@ def count_cases() -> tuple[CountCase, ...]:
 
 def count_case(name: str) -> CountCase:
     return next(c for c in count_cases() if c.name == name)
+
+
+# ---------------------------------------------------------------- hand-built counts past a launch's first trip
+def stride_cells() -> int:
+    """The cells a grid-stride launch covers before its lanes loop: kStrideThreads * kStrideMaxBlocks as
+    csrc/pa_launch_geom.h states them."""
+    text = (tree_cases.ROOT / "pyani_plus_amd" / "csrc" / "pa_launch_geom.h").read_text()
+    found = re.search(r"constexpr uint32_t kStrideThreads = (\d+), kStrideMaxBlocks = (\d+);", text)
+    assert found, "kStrideThreads and kStrideMaxBlocks not found in pa_launch_geom.h"
+    return int(found.group(1)) * int(found.group(2))
+
+
+def symmetric_integers(rng, n: int, low: int, high: int) -> np.ndarray:
+    """n x n int64 in [low, high], symmetric."""
+    upper = np.triu(rng.integers(low, high + 1, size=(n, n)))
+    return upper + np.triu(upper, 1).T
+
+
+class StridedCounts(NamedTuple):
+    match: np.ndarray  # R x n x n uint32
+    both: np.ndarray
+    all_gap: dict[int, tuple[int, int]]  # matrix -> its two rows without a residue
+
+
+STRIDED_ROWS, STRIDED_REPLICATES = 230, 5
+
+
+@functools.lru_cache(maxsize=None)
+def strided_counts(seed: int = 41) -> StridedCounts:
+    """Five 230 x 230 matrices of counts, 264 500 cells in one launch of the distances: the last rows of the last matrix
+    are written on the lanes' second trip.  Consistent with the rule: n_i on the diagonal of ``both`` and of ``match``,
+    ``both`` <= min(n_i, n_j), ``match`` <= ``both``.  Matrix 1 (first trip) and the last matrix (second trip) have two
+    rows without a residue each: their pair has no aligned column."""
+    rng = np.random.default_rng(seed)
+    n, reps = STRIDED_ROWS, STRIDED_REPLICATES
+    all_gap = {1: (3, 7), reps - 1: (n - 7, n - 2)}
+    match, both = np.zeros((reps, n, n), dtype=np.int64), np.zeros((reps, n, n), dtype=np.int64)
+    for r in range(reps):
+        residues = rng.integers(300, 401, size=n)
+        for row in all_gap.get(r, ()):
+            residues[row] = 0
+        both[r] = np.maximum(np.minimum(residues[:, None], residues[None, :]) - symmetric_integers(rng, n, 0, 50), 0)
+        match[r] = np.maximum(both[r] - symmetric_integers(rng, n, 0, 40), 0)
+        both[r][np.diag_indices(n)] = residues
+        match[r][np.diag_indices(n)] = residues
+    out = StridedCounts(match.astype(np.uint32), both.astype(np.uint32), all_gap)
+    out.match.setflags(write=False)
+    out.both.setflags(write=False)
+    return out
 
 
 @functools.lru_cache(maxsize=None)

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import functools
 import math
+import re
 from typing import NamedTuple
 
 import numpy as np
@@ -146,6 +147,11 @@ def alignment(n: int, n_cols: int, seed: int, *, alphabet: bytes = b"ACGT", gaps
     return bootstrap_cases.alignment(n, n_cols, seed, alphabet=alphabet, gaps=gaps, mutate=mutate)
 
 
+def tied_alignment() -> np.ndarray:
+    """``bootstrap_cases.tied_alignment`` with this module's rows: 180 rows, every row three times."""
+    return bootstrap_cases.tied_alignment(alignment)
+
+
 class CountCase(NamedTuple):
     name: str
     rows: np.ndarray  # n x L bytes
@@ -246,6 +252,100 @@ def edge_counts() -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     for i in range(n):
         S[i, i] = T[i, i] = 0
     return V[None], S[None], T[None]
+
+
+# ---------------------------------------------------------------- hand-built counts past a launch's first trip, and tiny matrices
+def distance_batch() -> int:
+    """The matrices a launch of the distances takes: two 64-bit words each of kSubstUndefined's, as csrc/pa_internal.h
+    states that slot."""
+    text = (tree_cases.ROOT / "pyani_plus_amd" / "csrc" / "pa_internal.h").read_text()
+    found = re.search(r"constexpr ScalarSlot kSubstUndefined\{(\d+), (\d+)\};", text)
+    assert found, "kSubstUndefined not found in pa_internal.h"
+    return int(found.group(2)) // 4
+
+
+NO_COLUMN_COUNTS = (0, 0, 0)  # (V, S, T) of a pair without a shared nucleotide column
+SATURATED_COUNTS = (1000, 0, 800)  # jc69: a = 1 - 3200 / 3000 < 0; k80: b = 1 - 1.6 < 0; p: 0.8, defined
+PLAIN_COUNTS = (1000, 30, 20)
+
+
+class PlantedCounts(NamedTuple):
+    valid: np.ndarray  # R x n x n uint32
+    ts: np.ndarray
+    tv: np.ndarray
+    planted: tuple  # per matrix, ((i, j), kind) with i < j and kind NO_COLUMNS or SATURATED
+
+    def undefined(self, model: str) -> list[list[int]]:
+        """Per matrix [pairs without a column, saturated pairs] as planted: nothing saturates under p."""
+        return [[sum(kind == NO_COLUMNS for _, kind in of), 0 if model == "p" else sum(kind == SATURATED for _, kind in of)] for of in self.planted]
+
+
+def _plant(counts, planted) -> PlantedCounts:
+    for r, of in enumerate(planted):
+        for (i, j), kind in of:
+            assert i < j
+            for x, value in zip(counts, NO_COLUMN_COUNTS if kind == NO_COLUMNS else SATURATED_COUNTS):
+                x[r, i, j] = x[r, j, i] = value
+    out = PlantedCounts(*(x.astype(np.uint32) for x in counts), tuple(tuple(of) for of in planted))
+    for x in out[:3]:
+        x.setflags(write=False)
+    return out
+
+
+STRIDED_ROWS, STRIDED_REPLICATES = 257, 5
+
+
+@functools.lru_cache(maxsize=None)
+def strided_counts(seed: int = 57) -> PlantedCounts:
+    """Five 257 x 257 matrices of counts: the first launch of the distances holds four, 264 196 cells, of which the last
+    2052 -- rows 249 and up of matrix 3 -- are written on the lanes' second trip, where the wave vote runs again (the last
+    wave with four lanes); the second launch holds one.  V in [200, 1000], S and T in [0, 20]: no pair is undefined but
+    the planted ones, of which every matrix has another number of each kind; those of matrix 3 in rows 250 and up are
+    counted on the second trip."""
+    rng = np.random.default_rng(seed)
+    n, reps = STRIDED_ROWS, STRIDED_REPLICATES
+    valid = np.stack([bootstrap_cases.symmetric_integers(rng, n, 200, 1000) for _ in range(reps)])
+    ts = np.stack([bootstrap_cases.symmetric_integers(rng, n, 0, 20) for _ in range(reps)])
+    tv = np.stack([bootstrap_cases.symmetric_integers(rng, n, 0, 20) for _ in range(reps)])
+    for x in (ts, tv):
+        x[:, np.arange(n), np.arange(n)] = 0
+    none_first, saturated_first = (1, 2, 3, 1, 5), (2, 4, 1, 3, 6)
+    planted = []
+    for r in range(reps):  # the first trip: row r and row 20 + r
+        of = [((r, 10 + k), NO_COLUMNS) for k in range(none_first[r])] + [((20 + r, 40 + k), SATURATED) for k in range(saturated_first[r])]
+        planted.append(of)
+    planted[3] += [((n - 7, n - 6), NO_COLUMNS), ((n - 7, n - 1), NO_COLUMNS), ((n - 2, n - 1), NO_COLUMNS)]
+    planted[3] += [((n - 6, n - 4), SATURATED), ((n - 3, n - 1), SATURATED)]
+    return _plant((valid, ts, tv), planted)
+
+
+def strided_cells_of(counts: PlantedCounts, first_row: int) -> list[int]:
+    """The index within its launch of the cells (i, j) and (j, i) of every pair planted at row ``first_row`` or below."""
+    n, batch = counts.valid.shape[1], distance_batch()
+    return [
+        (r % batch) * n * n + a * n + b
+        for r, of in enumerate(counts.planted)
+        for (i, j), _kind in of
+        if i >= first_row
+        for a, b in ((i, j), (j, i))
+    ]
+
+
+@functools.lru_cache(maxsize=None)
+def small_counts(n: int) -> PlantedCounts:
+    """Matrices so small that a wave spans a whole launch of them, undefined pairs in the matrices that do not lead the
+    wave.  n = 3: 27 matrices, every assignment of {defined, no column, saturated} to the pairs (0, 1), (0, 2), (1, 2), the
+    kinds of matrix r the digits of r in base 3.  n = 2: nine matrices of one pair, each kind next to each."""
+    pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
+    if n == 3:  # noqa: PLR2004
+        kinds = [[(r // 3**k) % 3 for k in range(3)] for r in range(27)]
+    else:
+        assert n == 2  # noqa: PLR2004
+        kinds = [[kind] for kind in (DEFINED, DEFINED, NO_COLUMNS, NO_COLUMNS, SATURATED, SATURATED, DEFINED, SATURATED, NO_COLUMNS)]
+    counts = [np.full((len(kinds), n, n), value, dtype=np.int64) for value in PLAIN_COUNTS]
+    for x in counts[1:]:
+        x[:, np.arange(n), np.arange(n)] = 0
+    return _plant(counts, [[(pair, kind) for pair, kind in zip(pairs, of) if kind != DEFINED] for of in kinds])
 
 
 # ---------------------------------------------------------------- the whole pipeline

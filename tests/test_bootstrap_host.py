@@ -108,6 +108,42 @@ def test_host_distances_equal_the_restatement(name):
         assert D[0, 1, 4] == 0.75 and D[0, 4, 1] == 0.75 and D[0, 1, 1] == 0.0  # no aligned column: `missing`
 
 
+def test_the_strided_counts_reach_the_second_trip():
+    """The conditions on the hand-built counts of ``tests/test_gpu_bootstrap.py``, from the constants of the sources, and
+    the twin against the restatement on the matrices with rows without a residue."""
+    counts, trip = cases.strided_counts(), cases.stride_cells()
+    reps, n, _ = counts.match.shape
+    assert (reps, n) == (cases.STRIDED_REPLICATES, cases.STRIDED_ROWS) == (5, 230)
+    assert (reps - 1) * n * n < trip < reps * n * n < 2 * trip  # one launch, whose lanes loop once
+    a, b = counts.all_gap[reps - 1]
+    assert min((reps - 1) * n * n + i * n + j for i, j in ((a, b), (b, a), (a, 0), (b, 0))) >= trip  # both rows, whole
+    assert max(1 * n * n + i * n + j for i, j in ((3, 7), (7, 3))) < trip and counts.all_gap[1] == (3, 7)
+    residues = counts.both.diagonal(axis1=1, axis2=2).astype(np.int64)
+    assert (counts.both <= np.minimum(residues[:, :, None], residues[:, None, :])).all() and (counts.match <= counts.both).all()
+    np.testing.assert_array_equal(counts.match, counts.match.transpose(0, 2, 1))
+    np.testing.assert_array_equal(counts.both, counts.both.transpose(0, 2, 1))
+    assert sorted(np.argwhere(residues == 0).tolist()) == [[1, 3], [1, 7], [reps - 1, a], [reps - 1, b]]
+    D = engine_mod.msa_boot_distances_host(counts.match, counts.both, 0.75)
+    assert np.argwhere(D == 0.75).tolist() == [[1, 3, 7], [1, 7, 3], [reps - 1, a, b], [reps - 1, b, a]]
+    for r in (1, reps - 1):
+        np.testing.assert_array_equal(D[r].view(np.uint64), cases.distances(counts.match[r], counts.both[r], 0.75).view(np.uint64))
+
+
+def test_the_tied_alignment_ties_on_more_than_one_tile():
+    """The condition of ``tests/test_tree_host.py`` on the matrices the device pipeline test joins: of the joins made
+    while more than kTile nodes are live, at least a third are tied.  Counted here: 23 or 24 of 52 in each."""
+    rows = cases.tied_alignment()
+    n, n_cols = rows.shape
+    k_tile = tree_cases.kernel_constants()["kTile"]
+    assert n == 180 > k_tile
+    w = np.concatenate([np.ones((1, n_cols), dtype=np.uint8), engine_mod.msa_boot_weights(0, n_cols, 0, 3)])
+    D = engine_mod.msa_boot_distances_host(*engine_mod.msa_boot_counts_host(rows, n_cols, w))
+    for what, d in zip(("unweighted", "replicate 0", "replicate 1", "replicate 2"), D):
+        tied, joins = tree_cases.tied_share(tree_cases.tied_pairs_per_join(d), n)
+        print(f"identity, {what}: {tied} of {joins} joins on more than one tile are tied")
+        assert joins == n - k_tile and 3 * tied >= joins, what
+
+
 # ------------------------------------------------------------------ support
 def _tables(trees) -> np.ndarray:
     return np.stack([np.asarray(t.child, dtype=np.uint32) for t in trees])

@@ -97,6 +97,20 @@ def test_device_distances_have_the_twins_bits(engine, name):
         assert D[0, 1, 4] == 0.75 and D[1, 4, 1] == 0.75  # two rows without residues: `missing`
 
 
+def test_the_distances_past_the_first_trip_of_the_launch(engine):
+    """Five matrices of 230 x 230 are more cells than the launch has lanes: the last rows of the fifth, two of them
+    without a residue, are written on the second trip (tests/test_bootstrap_host.py holds the conditions on the counts)."""
+    t = engine.torch
+    counts = cases.strided_counts()
+    reps = len(counts.match)
+    match, both = (t.from_numpy(np.array(x).view(np.int32)).to(engine.device) for x in (counts.match, counts.both))
+    D = engine.msa_boot_distances(match, both, 0.75).cpu().numpy()
+    twin = engine_mod.msa_boot_distances_host(counts.match, counts.both, 0.75)
+    np.testing.assert_array_equal(D.view(np.uint64), twin.view(np.uint64))
+    a, b = counts.all_gap[reps - 1]
+    assert np.argwhere(D == 0.75).tolist() == [[1, 3, 7], [1, 7, 3], [reps - 1, a, b], [reps - 1, b, a]]  # `missing`, there alone
+
+
 def test_the_refusals_of_the_device_entry_points(engine):
     case = cases.count_case("cols33")
     dm = engine.msa_upload(loaded(case.rows))
@@ -134,6 +148,23 @@ def test_the_trees_of_the_device_are_the_hosts(engine):
     dm = engine.msa_upload(loaded(r.rows))
     trees = bootstrap_mod.replicate_trees(r.rows, n_cols, cases.SUPPORT_REPLICATES, 0, engine=engine, device_msa=dm)
     for got, want in zip(trees, r.trees):
+        np.testing.assert_array_equal(got.child, want.child)
+        np.testing.assert_array_equal(got.length.view(np.uint64), want.length.view(np.uint64))
+        assert got.last == want.last and got.last_len == want.last_len
+
+
+def test_the_trees_of_the_device_are_the_hosts_where_ties_decide_on_two_tiles(engine):
+    """180 rows, every row three times: device-made matrices with ties go into the joins in place, on more than one scan
+    tile (tests/test_bootstrap_host.py counts the tied joins)."""
+    from pyani_plus_amd import bootstrap as bootstrap_mod
+
+    rows = cases.tied_alignment()
+    n_cols = rows.shape[1]
+    dm = engine.msa_upload(loaded(rows))
+    device = bootstrap_mod.replicate_trees(rows, n_cols, cases.BATCH + 2, 0, engine=engine, device_msa=dm)
+    host = bootstrap_mod.replicate_trees(rows, n_cols, cases.BATCH + 2, 0)
+    assert len(device) == len(host) == cases.BATCH + 2
+    for got, want in zip(device, host):
         np.testing.assert_array_equal(got.child, want.child)
         np.testing.assert_array_equal(got.length.view(np.uint64), want.length.view(np.uint64))
         assert got.last == want.last and got.last_len == want.last_len

@@ -112,6 +112,30 @@ def test_the_edges_of_the_rule_on_the_device(engine, model):
     cases.assert_distances(twin[0], twin_undefined[0], cases.distances(counts[0][0], counts[1][0], counts[2][0], model, 7.0), model)
 
 
+def planted_distances_on_the_device(engine, counts, model):
+    """Hand-built counts uploaded as they are: the twin's bits, the twin's undefined pairs, and the planted numbers."""
+    t = engine.torch
+    host = [np.array(x) for x in (counts.valid, counts.ts, counts.tv)]
+    D, undefined = engine.subst_distances(*(t.from_numpy(x.view(np.int32)).to(engine.device) for x in host), model, 0.75)
+    twin, twin_undefined = engine_mod.subst_distances_host(*host, model, 0.75)
+    np.testing.assert_array_equal(D.cpu().numpy().view(np.uint64), twin.view(np.uint64))
+    np.testing.assert_array_equal(undefined, twin_undefined)
+    assert undefined.tolist() == counts.undefined(model)
+
+
+@pytest.mark.parametrize("model", list(cases.MODELS))
+def test_the_distances_past_the_first_trip_of_a_launch(engine, model):
+    """Four matrices of 257 x 257 are more cells than a launch has lanes: the last rows of the fourth are written, and
+    their undefined pairs voted on, on the second trip (tests/test_subst_host.py holds the conditions on the counts)."""
+    planted_distances_on_the_device(engine, cases.strided_counts(), model)
+
+
+@pytest.mark.parametrize("model", list(cases.MODELS))
+@pytest.mark.parametrize("n", [3, 2])
+def test_the_vote_of_a_wave_that_spans_four_matrices(engine, n, model):
+    planted_distances_on_the_device(engine, cases.small_counts(n), model)
+
+
 def test_a_matrix_goes_straight_into_the_joins(engine):
     case = cases.count_case("rows65_weighted")
     dm = engine.msa_subst_upload(loaded(case.rows))
@@ -195,6 +219,25 @@ def test_the_trees_of_the_device_are_the_hosts(engine):
     device = bootstrap_mod.replicate_trees(rows, 300, cases.BATCH + 2, 0, 3.0, engine=engine, device_msa=dm, step=step)
     host = bootstrap_mod.replicate_trees(rows, 300, cases.BATCH + 2, 0, 3.0, step=step)
     assert len(device) == cases.BATCH + 2
+    for got, want in zip(device, host):
+        np.testing.assert_array_equal(got.child, want.child)
+        np.testing.assert_array_equal(got.length.view(np.uint64), want.length.view(np.uint64))
+        assert got.last == want.last and got.last_len == want.last_len
+
+
+def test_the_trees_of_the_device_are_the_hosts_where_ties_decide_on_two_tiles(engine):
+    """180 rows, every row three times: device-made matrices with ties go into the joins in place, on more than one scan
+    tile (tests/test_subst_host.py counts the tied joins)."""
+    from pyani_plus_amd import bootstrap as bootstrap_mod
+    from pyani_plus_amd import substitution
+
+    rows = cases.tied_alignment()
+    n_cols = rows.shape[1]
+    dm = engine.msa_subst_upload(loaded(rows))
+    step = substitution.replicate_step("k80")
+    device = bootstrap_mod.replicate_trees(rows, n_cols, cases.BATCH + 2, 0, 3.0, engine=engine, device_msa=dm, step=step)
+    host = bootstrap_mod.replicate_trees(rows, n_cols, cases.BATCH + 2, 0, 3.0, step=step)
+    assert len(device) == len(host) == cases.BATCH + 2
     for got, want in zip(device, host):
         np.testing.assert_array_equal(got.child, want.child)
         np.testing.assert_array_equal(got.length.view(np.uint64), want.length.view(np.uint64))

@@ -1,6 +1,8 @@
 """tree-run on the MI355X: ``pa_nj`` against ``pa_nj_host`` bit for bit on every case of tests/tree_cases.py (children,
 lengths and the last edge), twice on one case, its refusals, and ``rundb.tree_run`` with the engine against the host
-run.  The largest case is 511 joins of three small launches each; no step is tried twice."""
+run.  The largest of those cases is 511 joins of three small launches each.  Then the cases of their own: ties on more
+than one scan tile, and 2048 joins whose first two are found past the join kernel's first trip over the candidates.  No
+step is tried twice."""
 
 from __future__ import annotations
 
@@ -42,6 +44,26 @@ def test_device_equals_the_twin(engine, name):
     same_table(got, nj_tree_host(case.D))
     if case.edges is not None and n >= 2:
         assert tc.joins_bipartitions(n, *got) == case.edges
+
+
+@pytest.mark.parametrize("name", [c.name for c in tc.tie_cases()])
+def test_ties_across_tiles_go_by_node_id(engine, name):
+    """Equal scores in different tiles and in slots that swap-remove has shuffled (tests/test_tree_host.py holds the
+    condition on the inputs): the per-tile candidates and their reduction must pick the smallest lo, then hi."""
+    D = tc.tie_case(name).D
+    want = nj_tree_host(D)
+    same_table(engine.nj_tree(D), want)
+    if name == "copies258x86":  # and as the pipelines call it: on a device tensor, overwritten
+        d = engine.torch.from_numpy(np.array(D)).to(engine.device)
+        same_table(engine.nj_tree_inplace(d), want)
+
+
+def test_a_join_found_past_the_first_trip_over_the_candidates(engine):
+    """17 x 17 tiles in the first two joins, 289 candidates for the 256 lanes of the join kernel, the winners at 270."""
+    far = tc.far_tile_case()
+    got = engine.nj_tree(far.D)
+    assert tuple(got[0][0]) == far.first[0] and tuple(got[0][1]) == far.first[1]
+    same_table(got, tc.far_tile_twin())
 
 
 def test_two_runs_give_the_same_table_and_a_tensor_is_left_alone(engine):

@@ -174,6 +174,62 @@ def test_the_undefined_pairs_are_counted_per_matrix():
     assert (D[1][~np.eye(10, dtype=bool)] == 1.0).all() and not D[2][valid[2] > 0].any()
 
 
+def test_the_strided_counts_reach_the_second_trip_and_the_second_launch():
+    """The conditions on the hand-built counts of ``tests/test_gpu_subst.py``, from the constants of the sources."""
+    counts, trip, batch = cases.strided_counts(), bootstrap_cases.stride_cells(), cases.distance_batch()
+    reps, n, _ = counts.valid.shape
+    assert (reps, n) == (cases.STRIDED_REPLICATES, cases.STRIDED_ROWS) == (5, 257) and batch == 4  # noqa: PLR2004
+    assert batch < reps < 2 * batch and (batch - 1) * n * n < trip < batch * n * n < 2 * trip  # one launch loops, once; one follows
+    first_row = (trip - (batch - 1) * n * n) // n + 1  # the first row of matrix 3 that is on the second trip whole
+    assert first_row == 250 and batch * n * n - trip == 2052 and (batch * n * n - trip) % 64 == 4  # the last wave: four lanes  # noqa: PLR2004
+    strided = cases.strided_cells_of(counts, first_row)
+    assert len(strided) == 2 * 5 and min(strided) >= trip and max(strided) < batch * n * n  # noqa: PLR2004
+    late = [kind for (i, _j), kind in counts.planted[batch - 1] if i >= first_row]
+    assert late.count(cases.NO_COLUMNS) == 3 and late.count(cases.SATURATED) == 2  # noqa: PLR2004
+    assert all(any(i < first_row for (i, _j), _kind in of) for of in counts.planted)  # and the first trip of every matrix
+    for kind in (0, 1):
+        assert len({row[kind] for row in counts.undefined("k80")}) == reps  # every matrix another number of each kind
+    for x in (counts.valid, counts.ts, counts.tv):
+        np.testing.assert_array_equal(x, x.transpose(0, 2, 1))
+
+
+@pytest.mark.parametrize("model", list(cases.MODELS))
+def test_the_planted_pairs_are_the_undefined_pairs_of_the_twin(model):
+    counts = cases.strided_counts()
+    D, undefined = engine_mod.subst_distances_host(counts.valid, counts.ts, counts.tv, model, 0.75)
+    assert undefined.tolist() == counts.undefined(model)
+    for r, of in enumerate(counts.planted):
+        for (i, j), kind in of:
+            assert (D[r, i, j] == 0.75) == (model != "p" or kind == cases.NO_COLUMNS) and D[r, j, i] == D[r, i, j]  # noqa: PLR2004
+    assert (D == 0.75).sum() == 2 * int(undefined.sum())  # noqa: PLR2004
+    for n, reps in ((3, 27), (2, 9)):
+        small = cases.small_counts(n)
+        assert len(small.valid) == reps and n * n * cases.distance_batch() <= 64  # a wave spans a whole launch  # noqa: PLR2004
+        D, undefined = engine_mod.subst_distances_host(small.valid, small.ts, small.tv, model, 0.75)
+        assert undefined.tolist() == small.undefined(model)
+        for r in range(reps):
+            cases.assert_distances(D[r], undefined[r], cases.distances(small.valid[r], small.ts[r], small.tv[r], model, 0.75), f"{model}, {n}, {r}")
+    three = cases.small_counts(3).undefined("k80")
+    assert len({tuple(x) for x in three}) == 10 and three[0] == [0, 0] and three[13] == [3, 0] and three[26] == [0, 3]  # noqa: PLR2004
+    assert sum(x != [0, 0] for x in three[1:4]) == 3  # undefined pairs in the matrices that do not lead the first wave  # noqa: PLR2004
+
+
+def test_the_tied_alignment_ties_on_more_than_one_tile():
+    """The condition of ``tests/test_tree_host.py`` on the matrices the device pipeline test joins: of the joins made
+    while more than kTile nodes are live, at least a third are tied.  Counted here: 23 to 27 of 52 in each."""
+    rows = cases.tied_alignment()
+    n, n_cols = rows.shape
+    assert n == 180 > tree_cases.kernel_constants()["kTile"]  # noqa: PLR2004
+    w = engine_mod.msa_boot_weights(0, n_cols, 0, 3)
+    for model in ("p", "k80"):
+        plain, _ = engine_mod.subst_distances_host(*engine_mod.msa_subst_counts_host(rows, n_cols), model, 3.0)
+        drawn, _ = engine_mod.subst_distances_host(*engine_mod.msa_subst_counts_host(rows, n_cols, w), model, 3.0)
+        for what, D in (("unweighted", plain[0]), *((f"replicate {r}", drawn[r]) for r in range(3))):
+            tied, joins = tree_cases.tied_share(tree_cases.tied_pairs_per_join(D), n)
+            print(f"{model}, {what}: {tied} of {joins} joins on more than one tile are tied")
+            assert joins == n - tree_cases.kernel_constants()["kTile"] and 3 * tied >= joins, (model, what)
+
+
 def test_the_tree_of_the_host_distances_is_the_restatements():
     rows = cases.alignment(9, 130, 21)
     for model in cases.MODELS:

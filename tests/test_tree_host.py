@@ -88,6 +88,55 @@ def test_ties_go_by_node_id():
     assert int(last[1]) == 2 * 33 - 3  # the last node made is one end of the last edge
 
 
+TIE_NAMES = [c.name for c in tc.tie_cases()]
+
+
+def test_the_tie_counter_counts_the_pairs_at_the_smallest_score():
+    assert tc.tied_pairs_per_join(tc.all_equal(5)) == [10, 6, 3]  # every live pair, join after join: 5, 4 and 3 nodes
+    # random distances do not tie on more than one tile (with four nodes left or three, scores are equal but for rounding)
+    assert tc.tied_share(tc.tied_pairs_per_join(tc.case("random257").D), 257) == (0, 257 - tc.kernel_constants()["kTile"])
+    tied: list[int] = []
+    joins = tc.neighbour_joining(tc.case("duplicated9").D, tied)
+    assert len(tied) == len(joins.child) and np.array_equal(joins.child, tc.restated("duplicated9").child)
+
+
+@pytest.mark.parametrize("threads", [1, 3, 16])
+@pytest.mark.parametrize("name", TIE_NAMES)
+def test_twin_equals_the_restatement_where_ties_decide(name, threads):
+    same_table(nj_tree_host(tc.tie_case(name).D, threads), tc.tie_restated(name)[0])
+
+
+@pytest.mark.parametrize("name", TIE_NAMES)
+def test_the_tie_cases_tie_on_more_than_one_tile(name):
+    """A condition on the inputs, counted by the restatement alone: of the joins made while more than kTile nodes are
+    live, at least a third have more than one pair at the smallest score; every one of them where all distances are equal.
+    Counted here: all_equal257 129 of 129, copies258x86 65 of 130 (114 of 256 overall), copies130x65 1 of 2."""
+    n = len(tc.tie_case(name).D)
+    tied, joins = tc.tied_share(tc.tie_restated(name)[1], n)
+    print(f"{name}: {tied} of {joins} joins on more than one tile are tied")
+    assert joins == n - tc.kernel_constants()["kTile"] > 0
+    assert 3 * tied >= joins
+    if name.startswith("all_equal"):
+        assert tied == joins
+    else:
+        assert (tc.tie_case(name).D == 0.0).sum() > n  # d = 0 between the copies of a genome
+
+
+def test_the_far_tile_case_is_won_past_the_first_trip_over_the_candidates():
+    k = tc.kernel_constants()
+    far = tc.far_tile_case()
+    n = len(far.D)
+    assert (far.nt - 1) ** 2 <= k["kThreads"] < far.nt**2
+    tiles = [(n - t + k["kTile"] - 1) // k["kTile"] for t in range(n - 2)]  # a side, join by join
+    assert tiles[:3] == [far.nt, far.nt, far.nt - 1]  # exactly two joins with candidates past the workgroup's lanes
+    child = tc.far_tile_twin()[0]
+    assert tuple(child[0]) == far.first[0] == (2040, 2045) and tuple(child[1]) == far.first[1] == (2030, 2035)
+    for t, (lo, hi) in enumerate(far.first):
+        # join 0 puts its node into slot 2040 and the last slot's into 2045: the leaves of join 1 are where they were
+        ti, tj = lo // k["kTile"], hi // k["kTile"]
+        assert ti * tiles[t] + tj == far.candidate >= k["kThreads"], t
+
+
 def test_small_n():
     child, length, last, last_len = nj_tree_host(np.zeros((1, 1)))
     assert child.shape == (0, 2) and length.shape == (0, 2)

@@ -51,8 +51,9 @@ class Joins(NamedTuple):
     last_len: float
 
 
-def neighbour_joining(D: np.ndarray) -> Joins:
-    """The contract above, one join at a time."""
+def neighbour_joining(D: np.ndarray, tied: list[int] | None = None) -> Joins:
+    """The contract above, one join at a time.  ``tied``, if given, receives per join the number of live pairs whose
+    score equals the smallest: more than 1 where the tie rule decided."""
     D = np.asarray(D, dtype=np.float64)
     n = D.shape[0]
     joins = max(n - 2, 0)
@@ -74,6 +75,8 @@ def neighbour_joining(D: np.ndarray) -> Joins:
         q[np.tril_indices(m)] = np.inf
         at = int(np.argmin(q))  # the first of the smallest in row-major order
         assert q.flat[at] < np.inf
+        if tied is not None:
+            tied.append(int((q == q.flat[at]).sum()))
         lo, hi = int(live[at // m]), int(live[at % m])
         d = M[lo, hi]
         len_lo = np.float64(0.5) * d + (r[lo] - r[hi]) / (np.float64(2.0) * np.float64(m - 2))
@@ -90,6 +93,13 @@ def neighbour_joining(D: np.ndarray) -> Joins:
         live = np.append(others, u)  # u is the largest id so far: still ascending
     a, b = int(live[0]), int(live[1])
     return Joins(child, length, (a, b), float(M[a, b]))
+
+
+def tied_pairs_per_join(D: np.ndarray) -> list[int]:
+    """Per join of the restatement, the live pairs at the smallest score (join t is made with ``len(D) - t`` nodes live)."""
+    tied: list[int] = []
+    neighbour_joining(D, tied)
+    return tied
 
 
 # ---------------------------------------------------------------- trees as sets of leaf bipartitions
@@ -235,6 +245,93 @@ def case(name: str) -> Case:
 def restated(name: str) -> Joins:
     """The restatement's table of a case, computed once."""
     return neighbour_joining(case(name).D)
+
+
+# ---------------------------------------------------------------- ties on more than one tile, and candidates past a workgroup
+# Kept out of cases(): these are larger than LARGEST and have references of their own.
+def copies(genomes: int, times: int, seed: int) -> np.ndarray:
+    """``times`` copies of each of ``genomes`` genomes, copy c of genome g at g + c * genomes: d = 0 between the copies and
+    every other distance ``times`` squared times in the matrix."""
+    src = np.arange(genomes * times) % genomes
+    D = random_symmetric(genomes, seed)[np.ix_(src, src)].copy()
+    np.fill_diagonal(D, 0.0)
+    return D
+
+
+# The seeds are chosen for the condition test_tree_host.py states on these inputs (a third of the joins made on more than
+# one tile are tied).  With three copies the three pairs of a genome's copies share one score and any seed does; with two
+# copies only two joins are made above kTile nodes, the copies of a genome are one pair, and a tie needs a pair of
+# different genomes in front: of the seeds 0 .. 11 only 9 has one.
+COPIES_SEEDS = {"copies258x86": 4, "copies130x65": 9}
+
+
+@functools.lru_cache(maxsize=None)
+def tie_cases() -> tuple[Case, ...]:
+    """Matrices whose joins are decided by the tie rule while more than one scan tile is live: equal scores in different
+    tiles, in slots that swap-remove has shuffled."""
+    out = (
+        Case("all_equal257", all_equal(257), None),
+        Case("copies258x86", copies(86, 3, COPIES_SEEDS["copies258x86"]), None),  # three-way ties between the copies of a genome
+        Case("copies130x65", copies(65, 2, COPIES_SEEDS["copies130x65"]), None),  # the tile's edge: two tiles, the second two slots wide
+    )
+    for c in out:
+        c.D.setflags(write=False)
+    return out
+
+
+def tie_case(name: str) -> Case:
+    return next(c for c in tie_cases() if c.name == name)
+
+
+@functools.lru_cache(maxsize=None)
+def tie_restated(name: str) -> tuple[Joins, tuple[int, ...]]:
+    """The restatement's table of a tie case and its tied pairs per join, computed once."""
+    tied: list[int] = []
+    joins = neighbour_joining(tie_case(name).D, tied)
+    return joins, tuple(tied)
+
+
+def tied_share(tied, n: int) -> tuple[int, int]:
+    """``(joins with more than one pair at the smallest score, joins)`` among those made while more than kTile nodes are
+    live: join t has n - t."""
+    wide = [count for t, count in enumerate(tied) if n - t > kernel_constants()["kTile"]]
+    return sum(count > 1 for count in wide), len(wide)
+
+
+class FarTile(NamedTuple):
+    D: np.ndarray
+    nt: int  # tiles a side in the first joins: the smallest with nt * nt > kThreads
+    first: tuple[tuple[int, int], tuple[int, int]]  # the pairs of joins 0 and 1
+    candidate: int  # the index of their tile among the nt * nt candidates the join kernel reduces
+
+
+@functools.lru_cache(maxsize=None)
+def far_tile_case(seed: int = 17) -> FarTile:
+    """The smallest matrix at which the join kernel's loop over the candidates takes a second trip, for exactly two
+    joins, and whose first two joins are found in a tile that only the second trip reads: four leaves at distance 1.0
+    from everything (the largest row sums by far), paired at 2^-20 and 2^-19, all in the diagonal tile nt - 2."""
+    k = kernel_constants()
+    nt = next(x for x in range(1, 1 << 16) if x * x > k["kThreads"])
+    n = (nt - 1) * k["kTile"] + 2
+    D = random_symmetric(n, seed)
+    top = (nt - 1) * k["kTile"]  # the first slot of the last tile
+    first = ((top - 8, top - 3), (top - 18, top - 13))
+    for leaf in (*first[0], *first[1]):
+        D[leaf, :] = 1.0
+        D[:, leaf] = 1.0
+    for (a, b), d in zip(first, (2.0**-20, 2.0**-19)):
+        D[a, b] = D[b, a] = d
+    np.fill_diagonal(D, 0.0)
+    D.setflags(write=False)
+    return FarTile(D, nt, first, (nt - 2) * nt + (nt - 2))
+
+
+@functools.lru_cache(maxsize=None)
+def far_tile_twin():
+    """``pa_nj_host`` of the far-tile case, computed once: the restatement would take a minute at this size."""
+    from pyani_plus_amd.engine import nj_tree_host
+
+    return nj_tree_host(far_tile_case().D)
 
 
 def invalid_matrices() -> list[tuple[str, np.ndarray, tuple[int, int]]]:
