@@ -987,6 +987,42 @@ PA_API int pa_derep_assign(pa_ctx *ctx, const double *d_S, uint32_t n, int agg_s
 PA_API int pa_derep_assign_host(const double *h_S, uint32_t n, int agg_score, const uint64_t *h_bits, const uint8_t *h_is_rep, uint32_t *h_rep,
                                 double *h_rep_score, uint32_t n_threads);
 
+/* ---- search-run: for new genomes, the nearest genomes of a run ----
+ * Replaces nothing in the reference, which has no such command.  The definitions below are this project's own contract,
+ * pinned by an independent restatement in tests/search_cases.py.  DESIGN.md section 7n.  Integer work only: the device
+ * entry point gives the same bits run to run and the same bits as its _host twin, whose result does not depend on
+ * n_threads (0: as many as the process may use).  hits_rule.h states the order once for both.
+ *
+ *   Input.  counts[q * ld + c] = I = |S_q n S_s| of query q < nq and column c < ns of this tile of subjects, the layout
+ *        pa_pair_counts writes (ld = the tile's width there, ld >= ns); q_size[nq] and s_size[ns] the sketch sizes,
+ *        1 to 2^32 - 1 each (the twin refuses a 0, the device call does not look).  Column c is subject s_base + c;
+ *        s_base + ns < PA_HITS_NONE.  Nothing of the input is modified.
+ *   Hit.  A column with I > 0 (I = 0 is the reference's NULL, no hit), with the denominator m = min(|Q|, |S|) under
+ *        PA_HITS_RANK_IDENTITY -- (I / m)^(1/k) is the larger of the two containments, the sourmash identity -- and
+ *        m = |Q| under PA_HITS_RANK_CONTAINMENT.
+ *   Order.  Hit a comes before hit b when I_a m_b > I_b m_a as exact 64-bit products; when these are equal, I_a > I_b;
+ *        then the lower subject index.  A strict total order: a query's `top` best hits are unique and do not depend on
+ *        how the subjects are cut into tiles.
+ *   Output.  Three arrays of nq x top, best first: the subject's index, I and m; a missing rank holds PA_HITS_NONE, 0, 0.
+ *        With accumulate != 0 the three arrays are inputs as well: the lists so far compete with this tile's columns under
+ *        the same order (the stored m is what makes that possible without the earlier tiles' sizes).  The tiles of one
+ *        accumulation must not overlap; this is not checked.  nq == 0 or ns == 0 is a valid call: without accumulate it
+ *        writes the empty lists.
+ *   Checks, the same code and messages for both forms, PA_E_INVALID: top outside 1 .. PA_HITS_MAX_TOP; an unknown rank;
+ *        ld < ns; index overflow (s_base + ns, or nq * ld * 4 bytes past 64 bits); a null pointer to an array that has
+ *        elements, named in the message.
+ *   Device: every pointer is device memory; one launch on the context's stream, no synchronisation, no workspace. */
+#define PA_HITS_MAX_TOP 64
+#define PA_HITS_NONE 0xFFFFFFFFu
+#define PA_HITS_RANK_IDENTITY 0
+#define PA_HITS_RANK_CONTAINMENT 1
+PA_API int pa_best_hits(pa_ctx *ctx, const uint32_t *d_counts, uint32_t nq, uint32_t ns, uint64_t ld, const uint32_t *d_q_size,
+                        const uint32_t *d_s_size, uint32_t s_base, int rank, uint32_t top, int accumulate, uint32_t *d_hit_subject,
+                        uint32_t *d_hit_shared, uint32_t *d_hit_denom);
+PA_API int pa_best_hits_host(const uint32_t *h_counts, uint32_t nq, uint32_t ns, uint64_t ld, const uint32_t *h_q_size,
+                             const uint32_t *h_s_size, uint32_t s_base, int rank, uint32_t top, int accumulate, uint32_t *h_hit_subject,
+                             uint32_t *h_hit_shared, uint32_t *h_hit_denom, uint32_t n_threads);
+
 /* ---- in-library HIP-event timing of the kernels (bench.py roofline) ----
  * Phases are timed with hipEvents on the context's stream when enabled. */
 #define PA_PROF_KMER_HASH 0   /* k-mer hash + threshold filter kernel */

@@ -125,6 +125,7 @@ try:
         raise HipBackendError(f"{HEADER_PATH}: {len(PROF_PHASES)} PA_PROF_ phases, but PA_PROF_NPHASES is {_constants['PA_PROF_NPHASES']}")
     PA_AGG = {name: _constants[f"PA_AGG_{name.upper()}"] for name in ("min", "max", "mean")}
     PA_DEREP_MODE = {name: _constants[f"PA_DEREP_{name.upper()}"] for name in ("greedy", "cover")}
+    PA_HITS_RANK = {name: _constants[f"PA_HITS_RANK_{name.upper()}"] for name in ("identity", "containment")}
 except (OSError, KeyError) as err:
     raise HipBackendError(f"cannot bind {HEADER_PATH}: {err!r} (a missing file or a missing constant)") from err
 

@@ -1095,6 +1095,43 @@ class HipEngine:
         rep, rep_score = self.derep_assign_device(s, bits, is_rep, score_edges=score_edges)
         return Dereplication(is_rep.cpu().numpy().astype(bool), rep.cpu().numpy().view(np.uint32), rep_score.cpu().numpy(), n_reps, n_rounds)
 
+    # -- search-run
+    def _u32_words_on_device(self, values, n: int, what: str):
+        """``n`` uint32 words (a host array, or an int32 tensor with the same bits) on this device."""
+        t = self.torch
+        v = values if isinstance(values, t.Tensor) else t.from_numpy(_hit_sizes(values, what).view(np.int32).copy())
+        v = v.to(self.device).contiguous()
+        if v.dtype != t.int32 or v.numel() != n:
+            raise ValueError(f"{what}: {v.numel()} words of {v.dtype}, expected {n} of 32 bits")
+        return v
+
+    def best_hits_device(self, counts, q_size, s_size, s_base: int, rank: str, top: int, state=None):  # noqa: PLR0913
+        """``pa_best_hits``: ``(subject, shared, denom)``, three device tensors of nq x ``top`` int32 (views of uint32), the
+        best ``top`` columns of every row of ``counts`` (a device tensor of nq x ns int32 as ``pair_counts`` returns it;
+        a row stride above ns is taken as it is) under ``rank`` ("identity" or "containment"), best first, a missing rank
+        ``PA_HITS_NONE``, 0, 0; column c is subject ``s_base`` + c.  ``q_size`` and ``s_size``: the sketch sizes, host
+        arrays (checked: 1 to 2^32 - 1) or int32 tensors on this device (not checked).  ``state``: the three tensors an
+        earlier call returned for other columns; they take part, are overwritten and returned."""
+        t = self.torch
+        if not isinstance(counts, t.Tensor) or counts.dtype != t.int32 or counts.dim() != 2 or counts.device != self.device:  # noqa: PLR2004
+            raise ValueError("counts: expected an nq x ns int32 tensor on this device")
+        nq, ns = counts.shape
+        if ns and counts.stride(1) != 1:
+            counts = counts.contiguous()
+        ld = counts.stride(0) if nq > 1 and ns else ns
+        q = self._u32_words_on_device(q_size, nq, "query sizes")
+        s = self._u32_words_on_device(s_size, ns, "subject sizes")
+        if state is None:
+            out = tuple(t.empty((nq, max(int(top), 1)), dtype=t.int32, device=self.device) for _ in range(3))
+        else:
+            out = tuple(state)
+            if len(out) != 3 or any(not isinstance(x, t.Tensor) or x.dtype != t.int32 or x.shape != (nq, int(top)) or not x.is_contiguous()  # noqa: PLR2004
+                                    or x.device != self.device for x in out):
+                raise ValueError(f"state: expected three contiguous {nq} x {top} int32 tensors on this device")
+        self._check(self.lib.pa_best_hits(self.ctx, counts.data_ptr(), nq, ns, ld, q.data_ptr(), s.data_ptr(), int(s_base), _hits_rank(rank), int(top),
+                                          int(state is not None), *(x.data_ptr() for x in out)), "pa_best_hits")  # fmt: skip
+        return out
+
     def prof_enable(self, on: bool = True) -> None:
         self._check(self.lib.pa_prof_enable(self.ctx, int(on)), "pa_prof_enable")
 
@@ -1135,6 +1172,50 @@ def ani_host(counts: np.ndarray, q_sizes, s_sizes, k: int, *, symmetric: bool = 
         "pa_ani_host",
     )
     return ident, cov, null.view(np.bool_) if null.dtype == np.uint8 else null
+
+
+# ------------------------------------------------------------------ search-run: the host form (no GPU needed)
+def _hits_rank(rank) -> int:
+    """``PA_HITS_RANK_*`` of a rank's name; an integer is handed to the library as it is (which refuses an unknown one)."""
+    if isinstance(rank, (int, np.integer)) and not isinstance(rank, bool):
+        return int(rank)
+    if rank not in _capi.PA_HITS_RANK:
+        raise ValueError(f"Unknown rank {rank!r}: expected one of {', '.join(_capi.PA_HITS_RANK)}")
+    return _capi.PA_HITS_RANK[rank]
+
+
+def _hit_sizes(sizes, what: str) -> np.ndarray:
+    """Sketch sizes as contiguous uint32, each checked to be 1 to 2^32 - 1: the library's order needs both."""
+    wide = np.asarray(sizes).astype(np.int64 if np.asarray(sizes).dtype.kind == "i" else np.uint64, copy=False).reshape(-1)
+    if wide.size and (int(wide.min()) < 1 or int(wide.max()) >= 1 << 32):
+        raise ValueError(f"{what}: sketch sizes must be 1 to 2^32 - 1, found {int(wide.min())} to {int(wide.max())}")
+    return np.ascontiguousarray(wide, dtype=np.uint32)
+
+
+def best_hits_host(counts, q_size, s_size, s_base: int, rank, top: int, state=None, *, ld: int | None = None, threads: int = 0):  # noqa: PLR0913
+    """``pa_best_hits_host``: what ``HipEngine.best_hits_device`` returns, from numpy arrays into three nq x ``top``
+    uint32 arrays, with the same bits.  ``counts`` is nq x ns, or -- with ``ld`` -- a flat array of rows ``ld`` apart.
+    ``state``: the three arrays of an earlier call on other columns; they take part, are overwritten and returned."""
+    lib = _capi.load_library()
+    q = _hit_sizes(q_size, "query sizes")
+    s = _hit_sizes(s_size, "subject sizes")
+    nq, ns = len(q), len(s)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if ld is None:
+        if counts.shape != (nq, ns):
+            raise ValueError(f"counts of shape {counts.shape} for {nq} queries and {ns} subjects")
+        ld = ns
+    elif ld >= ns and counts.size < (nq - 1) * int(ld) + ns and nq:
+        raise ValueError(f"{counts.size} counts for {nq} rows of {ns} columns, {ld} apart")
+    if state is None:
+        out = tuple(np.empty((nq, max(int(top), 1)), dtype=np.uint32) for _ in range(3))
+    else:
+        out = tuple(state)
+        if len(out) != 3 or any(not isinstance(x, np.ndarray) or x.dtype != np.uint32 or x.shape != (nq, int(top)) or not x.flags.c_contiguous for x in out):  # noqa: PLR2004
+            raise ValueError(f"state: expected three contiguous {nq} x {top} uint32 arrays")
+    check(lib.pa_best_hits_host(counts.ctypes.data, nq, ns, int(ld), q.ctypes.data, s.ctypes.data, int(s_base), _hits_rank(rank), int(top),
+                                int(state is not None), *(x.ctypes.data for x in out), int(threads)), "pa_best_hits_host")  # fmt: skip
+    return out
 
 
 # ------------------------------------------------------------------ TETRA-hip: the host forms (no GPU needed)

@@ -1,5 +1,6 @@
 """Run drivers for the four methods ``sourmash-hip``, ``fastANI-hip``, ``external-alignment-hip`` and ``TETRA-hip``,
-``resume``, and the command line of the drivers and of the run reports.
+``resume``, ``search_run`` (new genomes looked up in a ``sourmash-hip`` run: it sketches, so it lives with the
+drivers), and the command line of the drivers and of the run reports.
 
 The reference's Python (Typer CLI, SQLAlchemy ORM, snakemake) does not travel to the GPU box, so this module is the
 build's own counterpart of ``cli_sourmash`` / ``fastani`` / ``external_alignment`` + ``start_and_run_method`` +
@@ -35,15 +36,16 @@ from pathlib import Path
 
 import numpy as np
 
-from . import launch, wire
+from . import launch, reports, wire
 from . import classify as classify_mod
 from . import dereplicate as dereplicate_mod
 from . import scatter as scatter_mod
+from . import search as search_mod
 from . import substitution as substitution_mod
 from . import tree as tree_mod
 from ._capi import HipBackendError
 from .distributed import shard_bounds_by_cost
-from .engine import HipEngine, load_fasta_files
+from .engine import HipEngine, load_fasta_files, max_hash_for_scaled
 from .methods import external_alignment_hip, fastani_hip, sourmash_hip, tetra_hip
 from .methods.external_alignment_hip import filename_stem  # noqa: F401  (reached as ``rundb.filename_stem``)
 from .reports import _require_database, bootstrap_run, classify, dereplicate_run, export_run, mantel_run_comp, ordinate_run, phylo_run, plot_run, plot_run_comp, tree_run  # noqa: F401
@@ -840,6 +842,73 @@ def resume(database: Path | str, *, run_id: int | None = None, cache: Path | Non
     return _finish_run(state, compute_missing(state))
 
 
+# ------------------------------------------------------------------ search-run (this project's own: the reference answers no such question)
+def search_run(query_fasta: Path, database: Path | str, outdir: Path, *, run_id: int | None = None, cache: Path | None = None,  # noqa: PLR0913
+               label: str = "stem", top: int = search_mod.TOP, rank: str = "identity", min_identity: float = 0.0, cov_min: float = 0.0,
+               temp: Path | None = None, engine=None, engine_factory: str | None = None, logger: logging.Logger | None = None) -> list[Path]:
+    """For every genome of the directory ``query_fasta``, the ``top`` (1 to 64) nearest genomes of a ``sourmash-hip``
+    run (``search.search``), without adding it to the run: nothing is written to the database.
+    The run (``run_id``; None: the last one) need not be complete: only its genomes, k-mer size and ``scaled`` are used.
+    Its sketches come from the ``.sig`` cache ``cache`` (``prepare_genomes`` writes what it lacks from the run's FASTA
+    directory; None: a temporary one under ``temp``, so every subject is sketched again); the queries are sketched with
+    the run's parameters, in file-name order, and are neither recorded nor cached.  ``rank`` "identity" orders a query's
+    subjects by the sourmash identity the run stores, the larger of the two containments; "containment" by how much of
+    the query is contained, the right key for an incomplete or contaminated query.  Equal values go to the subject that
+    shares more hashes, then to the one whose md5 sorts first.
+
+    * ``<method>_search_hits.tsv``: ``#query subject rank identity query_cov shared_hashes query_hashes subject_hashes``,
+      a row per hit among a query's ``top`` with identity >= ``min_identity`` and query_cov >= ``cov_min`` (the
+      thresholds filter the top hits; they do not look further down the ranking); ``rank`` is the hit's rank before that;
+    * ``<method>_search_queries.tsv``: ``#query md5 length hashes best_subject best_identity best_query_cov hits``, a row
+      per query; ``best_*`` is rank 1 whatever the thresholds say, ``NA`` when the query shares no hash with any subject.
+
+    Subjects are labelled by ``label``, queries by their file stem; floats as ``repr``.  Like ``run_sourmash_hip`` this
+    needs the device for sketching (``engine``, or ``engine_factory`` "module:callable", else the process's own).
+    Returns the written paths."""
+    logger = logger or logging.getLogger("pyani_plus_amd")
+    _require_database(logger, database)
+    if isinstance(top, bool) or not isinstance(top, int) or not 1 <= top <= search_mod.MAX_TOP:
+        sourmash_hip.log_sys_exit(logger, f"Expected 1 to {search_mod.MAX_TOP} hits a query, not {top!r}")
+    if rank not in search_mod.RANKS:
+        sourmash_hip.log_sys_exit(logger, f"Unknown rank {rank!r}: expected one of {', '.join(search_mod.RANKS)}")
+    for value, what in ((min_identity, "identity"), (cov_min, "query coverage")):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0 <= value <= 1:  # a NaN fails the comparison
+            sourmash_hip.log_sys_exit(logger, f"The minimum {what} must be a number from 0 to 1, not {value!r}")
+    query_names = check_fasta(logger, query_fasta)
+    outdir = reports._make_outdir(logger, outdir)
+    conn, run = _open_run(logger, database, run_id, "Searching")
+    config = run.configuration
+    if config.method != sourmash_hip.METHOD:
+        sourmash_hip.log_sys_exit(logger, f"Run-id {run.run_id} is a {config.method} run: search-run needs the sketches of a {sourmash_hip.METHOD} run")
+    reports._require_genomes(logger, run)
+    mapping = reports._label_mapping(logger, run, label)
+    reports._require_distinct_stems(logger, label, mapping)
+    conn.close()
+    if engine is None and engine_factory:
+        module, _, attr = engine_factory.partition(":")
+        engine = getattr(importlib.import_module(module), attr)()
+    cache_dir = _work_dir(Path(tempfile.mkdtemp(prefix="pyani_hip_cache_", dir=_work_dir(temp))) if temp and not cache else cache, "pyani_hip_cache_")
+    for _ in sourmash_hip.prepare_genomes(logger, run, cache_dir, engine=engine):
+        pass
+    kmersize, scaled = int(config.kmersize), sourmash_hip.parse_scaled(config.extra)
+    subjects = sorted(a.genome_hash for a in run.fasta_hashes)  # a subject's index: its place among the run's md5, as in the run's matrices
+    sig_dir = sourmash_hip.sig_cache_dir(cache_dir, config.kmersize, config.extra)
+    subject_sketches = sourmash_hip.read_cached_sketches(logger, [sig_dir / f"{h}.sig" for h in subjects], kmersize, max_hash_for_scaled(scaled))
+    queries: list[tuple[str, str, int, np.ndarray]] = []  # stem, md5, length, sketch
+    try:
+        for batch_paths, infos, sketches in sourmash_hip.sketch_fasta_batches(logger, query_names, kmersize=kmersize, scaled=scaled, engine=engine):
+            queries += [(filename_stem(path.name), info.md5, info.length, mins) for path, info, mins in zip(batch_paths, infos, sketches)]
+        hits = search_mod.search(subject_sketches, [q[3] for q in queries], kmersize, top=top, rank=rank, engine=engine)
+    except HipBackendError as err:
+        sourmash_hip.backend_failure(logger, "search-run", err)
+    except ValueError as err:  # a genome too short for a single hash
+        sourmash_hip.log_sys_exit(logger, f"search-run: {err}")
+    written = search_mod.write_tables(outdir, config.method, hits, [q[0] for q in queries], [q[1] for q in queries], [q[2] for q in queries],
+                                      [mapping[h] for h in subjects], min_identity=float(min_identity), cov_min=float(cov_min))  # fmt: skip
+    logger.info("Wrote the hits of %d queries among %d genomes of run-id %d to %s", len(queries), len(subjects), run.run_id, outdir)
+    return written
+
+
 # ------------------------------------------------------------------ the driver as a process
 _LABEL_OPTION = dict(choices=("md5", "filename", "stem"), default="stem")  # noqa: C408  every ``--label``
 _MISSING_OPTION = ("--missing", {"type": float, "default": 1.0, "help": "distance of a pair with no identity in either direction (default 1.0)"})
@@ -912,11 +981,13 @@ _COMMANDS = {  # subcommand -> its call from (the parsed arguments, the engine o
     "dereplicate-run": lambda a, engine, logger: dereplicate_run(a.database, a.outdir, run_id=a.run_id, label=a.label, min_identity=a.min_identity,
                                                                  cov_min=a.cov_min, score_edges=a.score_edges, coverage_edges=a.coverage_edges, mode=a.mode,
                                                                  prefer=a.prefer, engine=engine, logger=logger),
+    "search-run": lambda a, _engine, logger: search_run(a.query_fasta, a.database, a.outdir, run_id=a.run_id, cache=a.cache, label=a.label, top=a.top, rank=a.rank,
+                                                        min_identity=a.min_identity, cov_min=a.cov_min, temp=a.temp, engine_factory=a.engine_factory, logger=logger),
 }  # fmt: skip
 
 
 def main(argv: list[str] | None = None) -> int:
-    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run,bootstrap-run,phylo-run,ordinate-run,mantel-run-comp,dereplicate-run} ...``: the run driver as a process of its own,
+    """``python -m pyani_plus_amd.rundb {sourmash,fastani,external-alignment,tetra,resume,export-run,classify,plot-run,plot-run-comp,tree-run,bootstrap-run,phylo-run,ordinate-run,mantel-run-comp,dereplicate-run,search-run} ...``: the run driver as a process of its own,
     with SIGINT and SIGTERM arriving as ``KeyboardInterrupt`` the way the reference's worker command arranges it
     (pyani_plus/private_cli.py:816-823), so that ``scancel`` / ``kill`` leave the finished batches recorded and the run
     marked "Worker interrupted" exactly as Ctrl-C does.  Only what the drivers above take as arguments; the reference's
@@ -1014,6 +1085,17 @@ def main(argv: list[str] | None = None) -> int:
         ("--coverage-edges", {"choices": classify_mod.AGG_NAMES, "default": "min"}),
         ("--mode", {"choices": dereplicate_mod.MODES, "default": "greedy", "help": "greedy: keep a genome that no kept genome is adjacent to; cover: greedy dominating set"}),
         ("--prefer", {"choices": dereplicate_mod.PREFERENCES, "default": "length", "help": "the order of preference: the longer genome first (ties by label), or label order"}),
+    ))  # fmt: skip
+    _report_parser(sub, "search-run", "the nearest genomes of a sourmash-hip run for the genomes of a FASTA directory as <method>_search_hits.tsv and <method>_search_queries.tsv", own=(
+        ("query_fasta", {"type": Path, "metavar": "QUERY_FASTA", "help": "directory of the genomes to look up; they are not added to the run"}),
+        ("--cache", {"type": Path, "default": None, "help": "the run's .sig cache (default: a temporary one, so every genome of the run is sketched again)"}),
+        ("--top", {"type": int, "default": search_mod.TOP, "help": "hits kept per query, 1 to 64 (default 5)"}),
+        ("--rank", {"choices": search_mod.RANKS, "default": "identity",
+                    "help": "identity: the larger of the two containments, the run's own identity; containment: how much of the query is contained"}),
+        ("--min-identity", {"type": float, "default": 0.0, "help": "write a hit only from this identity on (default 0.0); this filters the top hits and does not look further down the ranking"}),
+        ("--cov-min", {"type": float, "default": 0.0, "help": "... and from this query coverage on (default 0.0), in the same way"}),
+        ("--temp", {"type": Path, "default": None}),
+        ("--engine-factory", {"default": None, "help": "module:callable that makes the engine (tests)"}),
     ))  # fmt: skip
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")

@@ -124,6 +124,38 @@ def synth_arena_torch(engine, n_genomes: int, length, n_species: int = 40, seed:
     return DeviceArena(packed, mask, starts)
 
 
+def synth_sketches_torch(engine, n_genomes: int, size: int = 5000, n_species: int = 40, seed: int = SEED, *, spread: int = 500,
+                         chunk: int = 10000):
+    """Sketches without genomes, made on the GPU (torch RNG): ``DeviceSketches`` of ``n_genomes`` ascending
+    duplicate-free rows of ``size`` - ``spread`` to ``size`` + ``spread`` hashes.  Genome g keeps a hash of its species'
+    root with probability (1 - rate)^31 -- what a substitution rate leaves of the root's 31-mers, species and rate as
+    ``species_and_rate`` -- and has a hash of its own otherwise, so that related genomes share hashes the way the
+    synthetic genomes above do.  For the benchmarks of what comes after sketching, at sizes whose genomes nobody wants to hash."""
+    from .engine import DeviceSketches
+
+    t, dev = engine.torch, engine.device
+    gen = t.Generator(device=dev)
+    gen.manual_seed(seed)
+    width = size + spread
+    roots = t.randint(0, 2**54, (n_species, width), generator=gen, device=dev, dtype=t.int64)
+    rates = t.tensor(RATES, device=dev, dtype=t.float64)
+    column = t.arange(width, device=dev)[None, :]
+    parts, sizes = [], []
+    for g0 in range(0, n_genomes, chunk):
+        idx = t.arange(g0, min(g0 + chunk, n_genomes), device=dev)
+        keep = t.rand((len(idx), width), generator=gen, device=dev) < ((1.0 - rates[(idx // n_species) % len(RATES)]) ** 31)[:, None]
+        own = t.randint(2**54, 2**62, (len(idx), width), generator=gen, device=dev, dtype=t.int64)
+        rows = t.sort(t.where(keep, roots[idx % n_species], own), dim=1).values
+        n_kept = size - spread + (idx * 7919) % (2 * spread + 1)  # a subset of a sorted row is sorted
+        parts.append(rows[column < n_kept[:, None]])
+        sizes.append(n_kept)
+    sizes = t.cat(sizes)
+    off = t.zeros(n_genomes + 1, dtype=t.int64, device=dev)
+    off[1:] = t.cumsum(sizes, 0)
+    hashes = t.cat(parts).contiguous()
+    return DeviceSketches(hashes, off, n_genomes, int(hashes.numel()))
+
+
 # ---- a second generator mode: genomes that differ from their species' root by more than substitutions -----------------
 # (fragment ANI, BASELINE configs[3]).  The substitution-only sets above are the friendliest input a fragment mapper can
 # get: every fragment of a genome has ONE locus in every genome of its species, on one contig, at the same offset.  Real
