@@ -159,6 +159,7 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane) {
 }
 
 // The kernels, in pipeline order (one translation unit: the files are included here, inside the anonymous namespace)
+#include "fragani_rules.inc"   // the key of a seed hit; the rules of the mapping that its two kernels share
 #include "fragani_index.inc"   // 1. minimizers, 2. dictionary of minimizer hashes, postings, frequency cut
 #include "fragani_seed.inc"    // 3. fragment sketches, 4. seed hits bucketed by reference genome, segment lists
 #include "fragani_map.inc"     // 4. (continued) map_segments_kernel: L1, the exact slide, bounds
@@ -945,7 +946,7 @@ int list_segments_bucketed(pa_ctx *c, FragWork &W, const FragCall &a, const Frag
     const uint32_t sort_lds = np2_max * 12u;
     // (contig, window id) to the top, the rank below
     PA_TRY(PA_LAUNCH_RAISE_LDS(c, frag_sort_kernel, n_big, kFragSortThreads, sort_lds, S.hk[0], S.hv[0], big_a0, big_nh, np2_max,
-                               64u - kHitRankShift + 11u));
+                               kHitRankRotation));
   }
   return PA_OK;
 }

@@ -566,7 +566,7 @@ __global__ __launch_bounds__(kThreads) void postings_kernel(const uint64_t *__re
   // the posting as the low 44 bits of a hit key, its genome on top so that bucketing needs no second lookup
   const uint32_t pg = contig_genome[mc];
   const uint64_t key = keys[i];
-  post_cw[i] = ((uint64_t)pg << 44) | ((uint64_t)mc << 24) | (uint32_t)(key >> 32);  // the window id rode along in the sort key
+  post_cw[i] = posting_of(pg, place_of(mc, (uint32_t)(key >> 32)));  // the window id rode along in the sort key
   post_genome[i] = (uint16_t)pg;  // (the bucketed seeding and the frequency cut read this; at most 65 535 genomes)
   if (flags[i]) { post_start[id] = i; uniq_hash[id] = (uint32_t)key; }
   if (i == m - 1) post_start[n_ids] = m;

@@ -24,6 +24,7 @@ struct EvalShared {
   uint16_t *qt;        // [kQtBuckets] the fragment's sketch bucketed by the top bits of the hash: first rank (10 bits) | hashes in the bucket (6 bits)
 };
 constexpr uint32_t kLmaskWords = (uint32_t)kHitCap / 32u + 2u;  // a word per 32 staged hits, one more for "all of them", even
+__device__ __forceinline__ uint32_t staged_hit(uint32_t window, uint32_t rank) { return (window << 8) | (rank >> 1); }  // EvalShared::hw
 // Bit tables of the windowed evaluation: one row per query rank r = the stretch positions (one bit each, kRefCap / 32
 // words) whose minimizer has rank <= r among the fragment's hashes.  Coarse rows stand at every kCoarse-th rank; the
 // fine rows cover kFineGroups coarse groups at a time, every rank of them.
@@ -77,18 +78,18 @@ __global__ __launch_bounds__(kThreads) void segment_records_kernel(
   if (i >= n_segs) return;
   const uint32_t a0 = seg_a0[i], nh = seg_nh[i];
   const uint64_t key = keys[a0];
-  const uint32_t f = seg_f ? seg_f[i] : (uint32_t)(key >> 44);
+  const uint32_t f = seg_f ? seg_f[i] : hit_fragment(key);
   uint32_t s = q_s[f];
   const uint32_t mh = s ? tab_min_hits[s] : 0u, ms = s ? tab_min_shared[s] : 0u;
   if (nh < mh) s = 0;  // chance matches with unrelated genomes: fewer seed hits than any L1 run needs
-  const uint32_t hc_base = genome_first_contig[contig_genome[(uint32_t)(key >> 24) & 0xfffffu]];
+  const uint32_t hc_base = genome_first_contig[contig_genome[hit_contig(key)]];
   rec[3 * (uint64_t)i] = make_uint4(a0, nh, f, s);
   rec[3 * (uint64_t)i + 1] = make_uint4(mh, hc_base, q_cut[f], ms);
   rec[3 * (uint64_t)i + 2] = make_uint4(contig_mini_off[hc_base + 1u], contig_bucket_off[hc_base], contig_bucket_off[hc_base + 1u], frag_genome_local[f]);
 }
 
 // the segment's hits from the hit array into LDS, in order: window id and rank (see EvalShared::hw), contig relative to
-// the genome's first.  The hits come as the bucketing pass left them: rank << kHitRankShift | contig << 24 | window id.
+// the genome's first.  The hits come as the bucketing pass left them: the rank on top of the place (hit_key_of_rank).
 // `loaded(nearest, widest)`: called once the hits are there, before they are ordered, with the smallest window id and the
 // largest relative contig of the segment -- what the caller wants to ask the memory for while the ordering goes on.
 // What a fragment leaves in a genome of its species is, nearly always, ONE cluster of hits -- its own locus: one contig, a
@@ -120,12 +121,11 @@ __device__ __forceinline__ void stage_hits_sorted(const uint64_t *__restrict__ s
   for (int q = 0; q < E; ++q) {
     const uint32_t e = lane * (uint32_t)E + (uint32_t)q;
     const uint64_t raw = raws[q];
-    // sort key: (contig, window id) on top of the rank -- a (contig, window id) occurs once, the rank decides nothing
-    k[q] = e < nh ? ((raw & 0xfffffffffffULL) << 9) | (raw >> kHitRankShift) : ~0ULL;
+    k[q] = e < nh ? hit_sort_key(raw) : ~0ULL;
     if (e < nh) {
-      widest = max(widest, ((uint32_t)(raw >> 24) & 0xfffffu) - hc_base);
-      furthest = max(furthest, (uint32_t)raw & 0xffffffu);
-      nearest = min(nearest, (uint32_t)raw & 0xffffffu);
+      widest = max(widest, hit_contig(raw) - hc_base);
+      furthest = max(furthest, hit_window(raw));
+      nearest = min(nearest, hit_window(raw));
     }
   }
   widest = pa_dev::wave_max_dpp(widest);
@@ -133,17 +133,16 @@ __device__ __forceinline__ void stage_hits_sorted(const uint64_t *__restrict__ s
   nearest = pa_dev::wave_min_dpp(nearest);
   loaded(nearest, widest);
   if (PA_MAP_COUNT_SORT) {
-    constexpr uint64_t kKeyMask = 0xfffffffffffULL;  // contig << 24 | window id
     for (uint32_t attempt = 0; attempt < 2u; ++attempt) {
-      const uint64_t pivot = readlane_u64(raws[0], attempt) & kKeyMask;  // hit 0, then hit E (past the segment's end: its last hit)
-      const uint32_t pw = (uint32_t)pivot & 0xffffffu, base = pw > kCountSpan / 2u ? pw - kCountSpan / 2u : 0u;
-      const uint64_t lo_key = (pivot & ~0xffffffULL) | base;  // the window: this contig, window ids [base, base + kCountSpan)
+      const uint64_t pivot = hit_place(readlane_u64(raws[0], attempt));  // hit 0, then hit E (past the segment's end: its last hit)
+      const uint32_t pw = hit_window(pivot), base = pw > kCountSpan / 2u ? pw - kCountSpan / 2u : 0u;
+      const uint64_t lo_key = place_of(hit_contig(pivot), base);  // the window: this contig, window ids [base, base + kCountSpan)
       uint32_t out_q = 0, n_out = 0;  // bit q: the lane's hit q lies outside the window
 #pragma unroll
       for (int q = 0; q < E; ++q) {
         const uint32_t e = lane * (uint32_t)E + (uint32_t)q;
-        const uint64_t mine = raws[q] & kKeyMask;
-        const bool inside = (mine >> 24) == (pivot >> 24) && ((uint32_t)mine & 0xffffffu) - base < kCountSpan;  // (below the base: the difference wraps)
+        const uint64_t mine = hit_place(raws[q]);
+        const bool inside = hit_contig(mine) == hit_contig(pivot) && hit_window(mine) - base < kCountSpan;  // (below the base: the difference wraps)
         const bool out = e < nh && !inside;
         out_q |= (out ? 1u : 0u) << q;
         n_out += (uint32_t)__popcll(__ballot(out));
@@ -154,7 +153,7 @@ __device__ __forceinline__ void stage_hits_sorted(const uint64_t *__restrict__ s
 #pragma unroll
         for (int q = 0; q < E; ++q) {
           for (uint64_t m = __ballot((out_q >> q) & 1u); m; m &= m - 1) {
-            const uint64_t key = readlane_u64(raws[q], (uint32_t)__builtin_ctzll(m)) & kKeyMask;
+            const uint64_t key = hit_place(readlane_u64(raws[q], (uint32_t)__builtin_ctzll(m)));
             if (o1 == ~0ULL) o1 = key; else o2 = key;
           }
         }
@@ -166,7 +165,7 @@ __device__ __forceinline__ void stage_hits_sorted(const uint64_t *__restrict__ s
 #pragma unroll
       for (int q = 0; q < E; ++q) {
         const uint32_t e = lane * (uint32_t)E + (uint32_t)q;
-        const uint32_t rel = ((uint32_t)raws[q] & 0xffffffu) - base;
+        const uint32_t rel = hit_window(raws[q]) - base;
         if (e < nh && !((out_q >> q) & 1u)) atomicOr(&bits[rel >> 5], 1u << (rel & 31u));
       }
       __builtin_amdgcn_wave_barrier();
@@ -181,13 +180,13 @@ __device__ __forceinline__ void stage_hits_sorted(const uint64_t *__restrict__ s
       for (int q = 0; q < E; ++q) {
         const uint32_t e = lane * (uint32_t)E + (uint32_t)q;
         if (e < nh) {
-          const uint64_t mine = raws[q] & kKeyMask;
-          const uint32_t wpos = (uint32_t)mine & 0xffffffu, rel = wpos - base;
+          const uint64_t mine = hit_place(raws[q]);
+          const uint32_t wpos = hit_window(mine), rel = wpos - base;
           uint32_t at;
           if ((out_q >> q) & 1u) at = (mine < lo_key ? 0u : n_cluster) + (o1 < mine ? 1u : 0u) + (o2 < mine ? 1u : 0u);
           else at = before[rel >> 5] + (uint32_t)__popc(bits[rel >> 5] & ((1u << (rel & 31u)) - 1u));
-          hw[at] = (wpos << 8) | (((uint32_t)(raws[q] >> kHitRankShift) & 0x1ffu) >> 1);
-          hc[at] = (uint16_t)(((uint32_t)(mine >> 24) & 0xfffffu) - hc_base);
+          hw[at] = staged_hit(wpos, hit_rank(raws[q]));
+          hc[at] = (uint16_t)(hit_contig(mine) - hc_base);
         }
       }
       return;
@@ -203,8 +202,8 @@ __device__ __forceinline__ void stage_hits_sorted(const uint64_t *__restrict__ s
       const uint32_t e = lane * (uint32_t)E + (uint32_t)q;
       k32[q] = 0xffffffffu;
       if (e < nh) {
-        const uint32_t c_rel = ((uint32_t)(k[q] >> 33) & 0xfffffu) - hc_base, wpos = (uint32_t)(k[q] >> 9) & 0xffffffu;
-        k32[q] = ((((c_rel << w_bits) | wpos)) << 9) | ((uint32_t)k[q] & 0x1ffu);
+        const uint32_t c_rel = sort_key_contig(k[q]) - hc_base, wpos = sort_key_window(k[q]);
+        k32[q] = (((c_rel << w_bits) | wpos) << kHitRankBits) | sort_key_rank(k[q]);
       }
     }
     bitonic_sort_lanes<E, uint32_t>(k32, lane);
@@ -212,8 +211,8 @@ __device__ __forceinline__ void stage_hits_sorted(const uint64_t *__restrict__ s
     for (int q = 0; q < E; ++q) {
       const uint32_t e = lane * (uint32_t)E + (uint32_t)q;
       if (e < nh) {
-        const uint32_t cw = k32[q] >> 9;
-        hw[e] = ((cw & ((1u << w_bits) - 1u)) << 8) | ((k32[q] & 0x1ffu) >> 1);
+        const uint32_t cw = k32[q] >> kHitRankBits;
+        hw[e] = staged_hit(cw & ((1u << w_bits) - 1u), sort_key_rank(k32[q]));
         hc[e] = (uint16_t)(cw >> w_bits);
       }
     }
@@ -224,8 +223,8 @@ __device__ __forceinline__ void stage_hits_sorted(const uint64_t *__restrict__ s
   for (int q = 0; q < E; ++q) {
     const uint32_t e = lane * (uint32_t)E + (uint32_t)q;
     if (e < nh) {
-      hw[e] = (((uint32_t)(k[q] >> 9) & 0xffffffu) << 8) | (((uint32_t)k[q] & 0x1ffu) >> 1);
-      hc[e] = (uint16_t)(((uint32_t)(k[q] >> 33) & 0xfffffu) - hc_base);
+      hw[e] = staged_hit(sort_key_window(k[q]), sort_key_rank(k[q]));
+      hc[e] = (uint16_t)(sort_key_contig(k[q]) - hc_base);
     }
   }
 }
@@ -287,8 +286,13 @@ constexpr bool kL1OneRun = PA_MAP_L1_ONE_RUN != 0;
 #endif
 constexpr bool kL1Strays = PA_MAP_L1_STRAYS != 0;
 #ifndef PA_MAP_WAVES
-#define PA_MAP_WAVES 4  // waves per SIMD the register allocation aims at: 128 VGPRs, the kernel needs 117 without spilling (80 registers / 6 waves: 0.64 s instead of 0.48 s for the 1 000-genome run)
+#define PA_MAP_WAVES 4  // waves per SIMD the register allocation aims at: 128 VGPRs, the kernel takes 126 and spills none (80 registers / 6 waves: 0.64 s instead of 0.48 s for the 1 000-genome run)
 #endif
+// a segment's seed hits by their bit length, for the event counters that come in seven slots: <= 7, 8-15, 16-31, ..., 256 and more
+__device__ __forceinline__ uint32_t seed_hits_slot(uint32_t nh) {
+  const uint32_t bits = 32u - (uint32_t)__builtin_clz(nh | 1u);
+  return min(6u, bits > 3u ? bits - 3u : 0u);
+}
 // kAllStaged: the launch holds only segments of at most hit_cap hits (the bucketed path's list of short segments), so
 // every access to a hit is an LDS read and the choice is not made per access.
 template <uint32_t kRefCap, bool kAllStaged>
@@ -321,7 +325,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
   const int32_t unseeded = (int32_t)rec1.z;  // hashes of the sketch whose reference occurrences are not all seed hits (frequency cut)
   if (s == 0) return;  // no sketch, or fewer seed hits than any L1 run needs
   PA_STAT(0, 1);   // segments that reach L1
-  PA_STAT(25 + min(6u, (uint32_t)(32 - __builtin_clz(nh | 1u)) > 3u ? (uint32_t)(32 - __builtin_clz(nh | 1u)) - 3u : 0u), 1);  // ... by their seed hits
+  PA_STAT(25 + seed_hits_slot(nh), 1);  // ... by their seed hits
   PA_STAT(1, nh);  // their seed hits
   // segments of up to kHitCap hits are staged in LDS; larger ones (repeats: rRNA operons, IS elements)
   // are read in place from the sorted hit arrays
@@ -330,14 +334,14 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
   const uint32_t hc_base = rec1.y;
   const bool staged = kAllStaged || nh <= kStageCap;
   (void)hit_cap;
-  auto HW = [&](uint32_t i) -> uint32_t { return staged ? sh.hw[i] >> 8 : (uint32_t)(keys[a0 + i] & 0xffffffu); };
+  auto HW = [&](uint32_t i) -> uint32_t { return staged ? sh.hw[i] >> 8 : hit_window(keys[a0 + i]); };
   // "the window id of hit i is below w" without the shift (the searches of the bounds ask nothing else)
   // (window ids stay below 2^24 - 1: contigs are shorter than 2^24)
   auto HW_below = [&](uint32_t i, uint32_t w) -> bool {
-    return staged ? sh.hw[i] < ((w < 0xffffffu ? w : 0xffffffu) << 8) : (uint32_t)(keys[a0 + i] & 0xffffffu) < w;
+    return staged ? sh.hw[i] < ((w < kHitWindowMax ? w : kHitWindowMax) << 8) : hit_window(keys[a0 + i]) < w;
   };
   auto HC = [&](uint32_t i) -> uint32_t {
-    return staged ? hc_base + sh.hc[i] : (uint32_t)(keys[a0 + i] >> 24) & 0xfffffu;
+    return staged ? hc_base + sh.hc[i] : hit_contig(keys[a0 + i]);
   };
   // The fragment's sketch, 16 bytes per lane and turn (s_cap is a multiple of 64; a row of q_hash holds kQMax hashes).  The
   // It waits in registers (two turns per lane at most) while the hits are loaded and ordered: the loads are in flight together
@@ -364,16 +368,15 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
   auto ask_buckets = [&](uint32_t nearest, uint32_t widest) {
     if (widest != 0u) return;  // hits on other contigs than the first
     const uint32_t nb0 = c0_b1 - c0_bb - 1u;
-    const uint32_t start = nearest + 1u > frag_len ? nearest + 1u - frag_len : 0u;
-    spec_bk0 = min(start >> kBucketShift, nb0);
+    spec_bk0 = min(l1_range_start(nearest, frag_len) >> kBucketShift, nb0);
     spec_first = bucket_first[c0_bb + min(spec_bk0 + (lane & 3u), nb0)];
   };
   if (staged) {
     if (presorted) {
       for (uint32_t i = lane; i < nh; i += 64) {  // hits ordered as a whole: the fragment on top of the key, the rank in the payload
         const uint64_t key = keys[a0 + i];
-        sh.hw[i] = ((uint32_t)(key & 0xffffffu) << 8) | ((vals[a0 + i] & 0x1ffu) >> 1);
-        sh.hc[i] = (uint16_t)(((uint32_t)(key >> 24) & 0xfffffu) - hc_base);
+        sh.hw[i] = staged_hit(hit_window(key), vals[a0 + i] & ((1u << kHitRankBits) - 1u));
+        sh.hc[i] = (uint16_t)(hit_contig(key) - hc_base);
       }
     } else {
       // the bucketing pass leaves a segment's hits in no particular order: ordered in registers on their way to LDS
@@ -530,12 +533,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
     const bool on_first = c == hc_base;
     const uint32_t m1 = on_first ? c0_m1 : contig_mini_off[c + 1];
     const uint32_t bb = on_first ? c0_bb : contig_bucket_off[c], nb = (on_first ? c0_b1 : contig_bucket_off[c + 1]) - bb - 1;
-    // Window ids of 512 minimizers from the start of the range's bucket on, in ONE batch of loads: the first begin is the
-    // first of them at or past the range's start (a bucket holds ~20: it lies among the first 64), and the rest say where
-    // the slide ends, where the range of begins ends and where the first seed hit sits -- the search for the first begin and
-    // the batch were two memory round trips, one waiting for the other.  (The groups re-read their own 64 window ids
-    // later: they are in L2 by then, and eight registers are free.)
-    constexpr int kStartBatch = 8;
+    // the first begin and the batch of window ids after it (slide_first_begin), from the start of the range's bucket
     uint32_t b_lo, origin;
     uint32_t wpv[kStartBatch];
     {
@@ -549,37 +547,14 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
         lo = bucket_first[bb + bk];
         hi = bk < nb ? bucket_first[bb + bk + 1] : lo;
       }
-      origin = lo;
-#pragma unroll
-      for (int q = 0; q < kStartBatch; ++q) {
-        const uint32_t t = origin + (uint32_t)q * 64u + lane;
-        wpv[q] = t < m1 ? mini_wpos[t] : 0xffffffffu;
-      }
-      const uint64_t ge = __ballot(lo + lane < hi && wpv[0] >= cs);
-      if (ge) {
-        b_lo = lo + (uint32_t)__builtin_ctzll(ge);
-      } else if (hi - lo <= 64u) {
-        b_lo = hi;  // the first minimizer of the next bucket (still in the batch)
-      } else {  // a bucket of more than 64 minimizers (low-complexity sequence): searched on, the batch loaded again from the begin found
-        b_lo = hi;
-        for (uint32_t base = lo + 64u; base < hi; base += 64) {
-          const uint32_t t = base + lane;
-          const uint64_t ge2 = __ballot(t < hi && mini_wpos[t] >= cs);
-          if (ge2) { b_lo = base + (uint32_t)__builtin_ctzll(ge2); break; }
-        }
-        origin = b_lo;
-#pragma unroll
-        for (int q = 0; q < kStartBatch; ++q) {
-          const uint32_t t = origin + (uint32_t)q * 64u + lane;
-          wpv[q] = t < m1 ? mini_wpos[t] : 0xffffffffu;
-        }
-      }
+      slide_first_begin(mini_wpos, m1, lo, hi, cs, lane, b_lo, origin, wpv);
     }
     if (b_lo >= m1) return;
     uint32_t b_hi = 0xffffffffu, at = 0xffffffffu, i_max;
     uint32_t h_lo, h_hi;  // the seed hits any window of this candidate can hold: hits on contig c with window id in [cs, i_max + count_windows)
     uint32_t est = first_hit_w;  // where the optimum is expected
     {
+      // (map_sparse_kernel has a copy of this block up to b_hi: a change here is a change there)
       // where the slide ends: the window's end may not reach the first minimizer at or past rangeEnd + fragLen (or the
       // contig's end); z = the window id of the minimizer before that one -- the largest of the batch below the limit when
       // the batch reaches the limit (it nearly always does: a candidate range spans at most two fragment lengths)
@@ -664,14 +639,11 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
       const uint32_t sb = tile0 + g * 64u;
       const uint32_t b = sb + lane;
       const bool has = b >= b_lo && b < b_hi;
-      const uint32_t wp = has ? mini_wpos[b] : 0u;
-      const uint32_t wp_next = (has && b + 1u < m1) ? mini_wpos[b + 1u] : 0xffffffffu;
-      const uint32_t w_end = min(wp_next - 1u, i_max) + count_windows;  // window ids below this: the begin's widest window
+      const WidestWindow ww = begin_widest_window(mini_wpos, m1, b, has, i_max, count_windows);
+      const uint32_t wp = ww.wp, wp_next = ww.wp_next, w_end = ww.w_end;
       // what a window must reach to matter (ties matter) -- in SEED HITS: a window shares no more than the seed hits it holds
       // plus the sketch's hashes that the frequency cut took out of the seeds (nearly always none)
-      int32_t bar = c_best > best_shared ? c_best : best_shared;
-      if (bar < floor_bar) bar = floor_bar;
-      bar -= unseeded;
+      const int32_t bar = shared_bar(c_best, best_shared, floor_bar) - unseeded;
       // A window with `bar` of the candidate's hits ends after the bar-th hit and does not begin after the bar-th hit
       // from the end: groups without such a begin are passed over before any counting
       if (bar > 0) {
@@ -694,7 +666,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
       uint32_t e_next = 0;  // end (minimizer index) of the begin's next state; 0: none of its states has been evaluated yet
       while (__any(pending)) {
         PA_STAT(5, 1);  // rounds
-        PA_STAT(18 + min(6u, (uint32_t)(32 - __builtin_clz(nh | 1u)) > 3u ? (uint32_t)(32 - __builtin_clz(nh | 1u)) - 3u : 0u), 1);  // ... by the segment's seed hits: <= 7, 8-15, 16-31, ..., 256 and more
+        PA_STAT(18 + seed_hits_slot(nh), 1);  // ... by the segment's seed hits
         const uint32_t first_lane = (uint32_t)__builtin_ctzll(__ballot(pending));
         const uint32_t base = sb + first_lane;  // stretch = minimizers [base, base + n)
         const uint32_t n = min(m1 - base, kRefCap);
@@ -832,8 +804,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
             const uint32_t w = i >> 5;
             return sh.lpre[w] + (uint32_t)__popc(sh.lmask[w] & ((1u << (i & 31u)) - 1u));
           };
-          int32_t bar_full = c_best > best_shared ? c_best : best_shared;
-          if (bar_full < floor_bar) bar_full = floor_bar;
+          const int32_t bar_full = shared_bar(c_best, best_shared, floor_bar);
           bool fails = false;
           if (who) {
             const uint32_t cb = below_upto(min(xe_lo, n)) - below_upto(min(b - base, n));
@@ -865,8 +836,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
               continue;
             }
 #ifdef PA_MAP_STATS
-            stat_bar = c_best > best_shared ? c_best : best_shared;  // this round goes on past the tight bound: how many of its windows reach the bar it was asked with?
-            if (stat_bar < floor_bar) stat_bar = floor_bar;
+            stat_bar = shared_bar(c_best, best_shared, floor_bar);  // this round goes on past the tight bound: how many of its windows reach the bar it was asked with?
             PA_STAT(39, __popcll(__ballot(lane_on && pending)));  // begins that pass the tight bound
             PA_STAT(40, 1);                                       // rounds that go on past it
 #endif
@@ -881,8 +851,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
         bool counted = false;  // the lane holds the exact value of a state (a window found out of reach of the bar is done, but not counted)
         uint32_t taken = 0;
         bool complete = false;  // the begin's last state is behind it
-        // fold the evaluated states into the candidate's optimum: most shared; position of the first and of the last
-        // state that has it (the lanes hold the states in slide order; the groups of a candidate do not come in that order).
+        // fold the evaluated states into the candidate's optimum (fold_ties; the lanes hold the states in slide order).
         // The states that are not evaluated -- reached by taking in a minimizer the fragment does not hold -- share as many
         // as the state before them or fewer and have that state's begin, hence its position: they change neither.
 #ifdef PA_MAP_STATS
@@ -893,10 +862,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
           const int32_t group_best = (int32_t)pa_dev::wave_max_dpp(counted ? f_shared + 1u : 0u) - 1;
           if (dm && group_best >= c_best) {
             const uint64_t top_items = __ballot(counted && (int32_t)f_shared == group_best);
-            const uint32_t w_first = __shfl(p_state, __builtin_ctzll(top_items), 64), w_last = __shfl(p_state, 63 - __builtin_clzll(top_items), 64);
-            c_last = group_best > c_best ? w_last : max(c_last, w_last);
-            c_first = group_best > c_best ? w_first : min(c_first, w_first);
-            c_best = group_best;
+            fold_ties(group_best, top_items, p_state, c_best, c_first, c_last);
             const uint32_t tt = (uint32_t)__builtin_amdgcn_readlane((int)t_state, __builtin_ctzll(top_items));
             if (tt != kNoT) pivot_T = tt;
 #ifdef PA_MAP_STATS
@@ -1162,8 +1128,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
               // group's last rank bound it from above (by the matches of at most 15 more ranks): windows that cannot reach
               // the bar any more -- most of a candidate's windows away from its optimum -- are done here, without the fine
               // tables, and are left out of the fold below (their exact value is below the bar, which is all that matters).
-              int32_t bar_now = c_best > best_shared ? c_best : best_shared;
-              if (bar_now < floor_bar) bar_now = floor_bar;
+              const int32_t bar_now = shared_bar(c_best, best_shared, floor_bar);
               const bool in_reach = (int32_t)count_in(bc + g_lo * kRow + kW) >= bar_now;
               counted = it_on && in_reach;
               bool unresolved = counted && !PA_CUT_IS(kCutNoFinePass);
@@ -1210,7 +1175,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
                 PA_STAT(38, __popcll(__ballot(counted && (int32_t)f_shared >= stat_bar_round)));     // ... that reach the bar
               }
 #endif
-              PA_STAT(15, __popcll(__ballot(counted && (int32_t)f_shared >= max(max(c_best, best_shared), floor_bar))));  // ... at or above the bar
+              PA_STAT(15, __popcll(__ballot(counted && (int32_t)f_shared >= shared_bar(c_best, best_shared, floor_bar))));  // ... at or above the bar
               fold_items();
             }
             PA_CUT(kCutFirstRound);  // first round only, complete: fine passes and fold included
@@ -1239,9 +1204,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
         pending = pending && !complete;
         // whoever can no longer reach the bar drops out
         {
-          int32_t bar2 = c_best > best_shared ? c_best : best_shared;
-          if (bar2 < floor_bar) bar2 = floor_bar;
-          bar2 -= unseeded;
+          const int32_t bar2 = shared_bar(c_best, best_shared, floor_bar) - unseeded;
           pending = pending && (bar2 > 0 ? holds_hits(bar2) : true);
         }
       }
@@ -1250,20 +1213,15 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
     PA_STAT(33, stat_ties ? stat_ties : 1u);  // states tying the candidate's optimum (one probe where nothing was evaluated)
 #endif
     if (c_best < 0) return;
-    // fastANI keeps every candidate as a mapping, orders a fragment's mappings by identity and lets each overwrite the one
-    // before: of several candidates that share equally many minimizers the LAST one -- the candidates come in (contig,
-    // position) order -- is the fragment's mapping.
     __syncthreads();
-    if (c_best >= best_shared && lane == 0) {
+    if (candidate_is_the_mapping(c_best, best_shared) && lane == 0) {  // (of equals, the last)
       sh.scan[kBestShared] = (uint32_t)c_best; sh.scan[kBestC] = c; sh.scan[kBestFirst] = c_first; sh.scan[kBestLast] = c_last;
       sh.scan[kBestT] = pivot_T;
     }
     __syncthreads();
   };
 
-  // ---- L1: run a is valid when hits a .. a+mh-1 share a contig and span < frag_len window ids; its candidate range
-  // of window starts is [y.w - fragLen + 1, x.w]; ranges that touch on one contig merge (hits are in (contig, window)
-  // order, so both ends only grow and "touches the merged range" is "touches the previous run's")
+  // ---- L1 (the rule: l1_run_valid, l1_range_start, l1_opens_candidate), sixty-four runs at a time.
   // The candidates a chunk of 64 runs closes are first listed (LDS, kListCap at a time), then evaluated: the evaluation
   // is in the code once and none of the scan's per-lane state is alive across it.  A chunk that closes more than
   // kListCap candidates is scanned again for the rest (`handled` = its breaks already listed).
@@ -1293,15 +1251,16 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
     const uint32_t e_w = sh.hw[idx] >> 8, e_c = sh.hc[idx];
     auto W = [&](uint32_t i) { return (uint32_t)__builtin_amdgcn_readlane((int)e_w, (int)(i < kEnd ? i : i + 2u * kEnd - nh)); };  // i < 8 or i >= nh - 8
     auto C = [&](uint32_t i) { return (uint32_t)__builtin_amdgcn_readlane((int)e_c, (int)(i < kEnd ? i : i + 2u * kEnd - nh)); };
+    // (l1_run_valid written out, the window ids read only where the contigs agree: as a call it changed the kernel's scalar spills)
     auto run_valid = [&](uint32_t i) { return C(i) == C(i + mh - 1u) && W(i + mh - 1u) - W(i) < frag_len; };  // (i and i + mh - 1 at the same end)
     uint32_t lo = 0xffffffffu, hi = 0;
     if (!enough) {
       const uint32_t w_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)e_w), w_last = (uint32_t)__builtin_amdgcn_readlane((int)e_w, 1);
-      if ((uint32_t)__builtin_amdgcn_readfirstlane((int)e_c) == (uint32_t)__builtin_amdgcn_readlane((int)e_c, 1) && w_last - w_first < frag_len) {
+      if (l1_run_valid((uint32_t)__builtin_amdgcn_readfirstlane((int)e_c), w_first, (uint32_t)__builtin_amdgcn_readlane((int)e_c, 1), w_last, frag_len)) {
         lo = 0;
         const uint32_t yw = (uint32_t)__builtin_amdgcn_readfirstlane((int)(sh.hw[mh - 1u] >> 8));
         cur_c = hc_base + (uint32_t)__builtin_amdgcn_readfirstlane((int)e_c);
-        cur_cs = yw + 1u > frag_len ? yw + 1u - frag_len : 0u;
+        cur_cs = l1_range_start(yw, frag_len);
         cur_ce = (uint32_t)__builtin_amdgcn_readfirstlane((int)(sh.hw[nh - mh] >> 8));
         cur_fw = w_first;
       }
@@ -1321,7 +1280,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
       if (lo != 0xffffffffu) {
         const uint32_t yw = W(lo + mh - 1u);
         cur_c = hc_base + C(lo);
-        cur_cs = yw + 1u > frag_len ? yw + 1u - frag_len : 0u;
+        cur_cs = l1_range_start(yw, frag_len);
         cur_ce = W(nh - hi - mh);
         cur_fw = W(lo);
       }
@@ -1354,8 +1313,8 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
         c_i = HC(i);
         ce_i = HW(i);
         const uint32_t yw = HW(i + mh - 1);
-        v = HC(i + mh - 1) == c_i && yw - ce_i < frag_len;
-        cs_i = yw + 1u > frag_len ? yw + 1u - frag_len : 0u;
+        v = l1_run_valid(c_i, ce_i, HC(i + mh - 1), yw, frag_len);
+        cs_i = l1_range_start(yw, frag_len);
       }
       const uint64_t vm = __ballot(v);
       if (!vm) { chunk += 64; continue; }
@@ -1365,7 +1324,7 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
       const uint32_t sc = __shfl(c_i, pl, 64), se = __shfl(ce_i, pl, 64);
       const bool hp = below ? true : have_prev;
       const uint32_t pc = below ? sc : prev_c, pe = below ? se : prev_ce;
-      const bool brk = v && (!hp || pc != c_i || cs_i > pe);
+      const bool brk = v && l1_opens_candidate(hp, pc, pe, c_i, cs_i);
       const uint64_t bm_all = __ballot(brk);
       uint64_t bm = bm_all & ~handled;
       if (!handled) {
@@ -1430,11 +1389,9 @@ __global__ __launch_bounds__(64, PA_MAP_WAVES) void map_segments_kernel(
 
   __syncthreads();
   const int32_t best_shared = (int32_t)sh.scan[kBestShared];
-  if (lane == 0 && best_shared >= 0 && (uint32_t)best_shared >= rec1.w) {
-    // fastANI buckets the reference by fragLen - 20
-    const uint64_t jq = ((uint64_t)best_shared << 30) / s;
-    const unsigned long long packed = ((unsigned long long)jq << 32) | ((unsigned long long)best_shared << 16) | s;
-    const uint64_t bin = contig_bin_off[sh.scan[kBestC]] + (sh.scan[kBestFirst] + sh.scan[kBestLast]) / 2u / (frag_len - 20u);
-    atomicMax(&table[(uint64_t)rec2.w * table_stride + bin], packed);  // (rec2.w: frag_genome_local[f])
+  if (lane == 0 && best_shared >= 0 && (uint32_t)best_shared >= rec1.w) {  // (rec1.w: tab_min_shared[s]; rec2.w: frag_genome_local[f])
+    const unsigned long long packed = mapping_packed(best_shared, s);
+    const uint64_t bin = mapping_bin(contig_bin_off[sh.scan[kBestC]], sh.scan[kBestFirst], sh.scan[kBestLast], frag_len);
+    atomicMax(&table[(uint64_t)rec2.w * table_stride + bin], packed);
   }
 }

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(kThreads) void fill_hits_kernel(
     const uint32_t ex = wave_excl_scan(n, lane);
     for (uint32_t t = 0; t < n; ++t) {
       const uint32_t g = sorted_idx[lo + t];
-      keys[base + ex + t] = ((uint64_t)f << 44) | ((uint64_t)mini_contig[g] << 24) | mini_wpos[g];
+      keys[base + ex + t] = hit_key_of_fragment(f, place_of(mini_contig[g], mini_wpos[g]));
       vals[base + ex + t] = i;  // the rank of the hit's hash among the fragment's (the sketch is in hash order)
     }
     base += wave_sum(n);
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(kThreads) void segment_heads_kernel(const uint64_t 
   bool head = i == 0;
   if (!head) {
     const uint64_t a = keys[i - 1], b = keys[i];
-    head = (a >> 44) != (b >> 44) || contig_genome[(a >> 24) & 0xfffffu] != contig_genome[(b >> 24) & 0xfffffu];
+    head = hit_fragment(a) != hit_fragment(b) || contig_genome[hit_contig(a)] != contig_genome[hit_contig(b)];
   }
   flags[i] = head ? 1u : 0u;
 }
@@ -285,7 +285,6 @@ __global__ __launch_bounds__(kThreads) void segment_starts_kernel(const uint32_t
 // segment in LDS, longer segments (repeats) are listed for segment_sort.  Eight lanes walk one posting
 // list, so a wave reads 8 lists at a time in 64-byte pieces.
 constexpr int kBucketWaves = 4;
-constexpr uint32_t kHitRankShift = 55;  // a bucketed hit: rank of its hash in the fragment's sketch (9 bits) << 55 | contig << 24 | window id
 __global__ __launch_bounds__(kBucketWaves * 64) void bucket_hits_kernel(
     uint32_t n_frags, const uint32_t *__restrict__ q_pos, const uint32_t *__restrict__ q_id,
     const uint32_t *__restrict__ q_s, const uint32_t *__restrict__ hit_off, const uint16_t *__restrict__ post_genome,
@@ -427,13 +426,12 @@ __global__ __launch_bounds__(kBucketWaves * 64) void bucket_hits_kernel(
   // the (fragment, genome) slices in place only when every slot holds its own key with the fragment on top; the rank
   // then rides in the sort's payload.
   for_each_posting(post_cw, [&](uint32_t i, uint64_t cw) {
-    const uint32_t at = atomicAdd(&hist[(uint32_t)(cw >> 44)], 1u);
-    const uint64_t cw44 = cw & ((1ULL << 44) - 1ULL);
+    const uint32_t at = atomicAdd(&hist[posting_genome(cw)], 1u);
     if (write_all) {
-      keys[base + (at & 0x7fffffffu)] = ((uint64_t)f << 44) | cw44;
+      keys[base + (at & 0x7fffffffu)] = hit_key_of_fragment(f, hit_place(cw));
       vals[base + (at & 0x7fffffffu)] = i;
     } else if (!(at & 0x80000000u)) {
-      keys[base + at] = ((uint64_t)i << kHitRankShift) | cw44;
+      keys[base + at] = hit_key_of_rank(i, hit_place(cw));
     }
   });
 }
@@ -583,8 +581,8 @@ __global__ __launch_bounds__(kStageWaves * 64) void bucket_hits_staged_kernel(
   // in the hit range stay as they are: the copy below reads them); else from the genome's offset, which moves.
   if (staged) {
     for_each_posting(post_cw, [&](uint32_t i, uint64_t cw) {
-      const uint32_t g = (uint32_t)(cw >> 44);
-      if (!(hist[g] & 0x80000000u)) stage[atomicAdd(&coff[g], 1u)] = ((uint64_t)i << kHitRankShift) | (cw & ((1ULL << 44) - 1ULL));
+      const uint32_t g = posting_genome(cw);
+      if (!(hist[g] & 0x80000000u)) stage[atomicAdd(&coff[g], 1u)] = hit_key_of_rank(i, hit_place(cw));
     });
     __syncthreads();
     // the listed slices, from LDS to the hit array: a wave per genome, consecutive lanes consecutive hits.  A genome's
@@ -610,8 +608,8 @@ __global__ __launch_bounds__(kStageWaves * 64) void bucket_hits_staged_kernel(
   } else {
     __syncthreads();  // every offset has been read before the scatter pass moves it
     for_each_posting(post_cw, [&](uint32_t i, uint64_t cw) {
-      const uint32_t at = atomicAdd(&hist[(uint32_t)(cw >> 44)], 1u);
-      if (!(at & 0x80000000u)) keys[base + at] = ((uint64_t)i << kHitRankShift) | (cw & ((1ULL << 44) - 1ULL));
+      const uint32_t at = atomicAdd(&hist[posting_genome(cw)], 1u);
+      if (!(at & 0x80000000u)) keys[base + at] = hit_key_of_rank(i, hit_place(cw));
     });
   }
 }
@@ -643,7 +641,7 @@ __global__ __launch_bounds__(kThreads) void prefilter_segments_kernel(
 #pragma unroll
       for (uint32_t j = 0; j < kTinySegment; ++j) k[j] = keys[a0 + min(j, nh - 1u)];  // (loads without a branch: all in flight together; nh >= 1)
 #pragma unroll
-      for (uint32_t j = 0; j < kTinySegment; ++j) k[j] = j < nh ? (k[j] & ((1ULL << 44) - 1ULL)) : ~0ULL;  // (contig, window id)
+      for (uint32_t j = 0; j < kTinySegment; ++j) k[j] = j < nh ? hit_place(k[j]) : ~0ULL;  // (contig, window id)
 #pragma unroll
       for (uint32_t pass = 0; pass < kTinySegment; ++pass)  // odd-even transposition sort: 8 passes sort 8 keys
 #pragma unroll
@@ -658,8 +656,7 @@ __global__ __launch_bounds__(kThreads) void prefilter_segments_kernel(
       for (uint32_t a = 0; a < kTinySegment; ++a) {
 #pragma unroll
         for (uint32_t z = a; z < kTinySegment; ++z) {  // z = a + mh - 1
-          if (z + 1 == a + mh && z < nh && ((k[a] >> 24) & 0xfffffu) == ((k[z] >> 24) & 0xfffffu) &&
-              (uint32_t)(k[z] & 0xffffffu) - (uint32_t)(k[a] & 0xffffffu) < frag_len)
+          if (z + 1 == a + mh && z < nh && l1_run_valid(hit_contig(k[a]), hit_window(k[a]), hit_contig(k[z]), hit_window(k[z]), frag_len))
             keep = true;
         }
       }
@@ -772,8 +769,8 @@ __global__ __launch_bounds__(kThreads) void segment_keep_kernel(const uint64_t *
   if (seg >= n_segs) return;
   const uint32_t a0 = seg_start[seg], nh = seg_start[seg + 1] - a0;
   const uint64_t key = keys[a0];
-  const uint32_t s = q_s[(uint32_t)(key >> 44)];
-  const uint32_t g = contig_genome[(key >> 24) & 0xfffffu];
+  const uint32_t s = q_s[hit_fragment(key)];
+  const uint32_t g = contig_genome[hit_contig(key)];
   keep[seg] = (s != 0 && nh >= tab_min_hits[s] && g >= ref0 && g < ref1) ? 1u : 0u;
 }
 

@@ -11,7 +11,7 @@
 // rank, no table; per group of 64 begins the stretch's hashes are compared with the (at most eight) hit hashes, one bit
 // mask and its prefix counts per hit go to LDS, and every begin that can still matter evaluates all its states (which begins
 // those are, and in which order the groups are taken: at the group loop below).  Same candidates, same slide, same
-// positions and ties as map_segments_kernel (of which this is the small-segment form); whatever does not fit the
+// positions and ties as map_segments_kernel (the rules both call: fragani_rules.inc); whatever does not fit the
 // simple form -- a hash met twice in a stretch, windows longer than the stretch -- sends the segment to
 // map_segments_kernel through the overflow list.
 constexpr uint32_t kSparseHits = kTinySegment;  // (16: 426 ms of mapping per 1 000-genome run against 419)
@@ -58,27 +58,27 @@ __global__ __launch_bounds__(64) void map_sparse_kernel(
   {  // the hits in (contig, window id) order, with the rank and the hash of each
     uint64_t k1[1];
     const uint64_t raw = lane < nh ? keys[a0 + lane] : 0ULL;
-    k1[0] = lane < nh ? ((raw & 0xfffffffffffULL) << 9) | (raw >> kHitRankShift) : ~0ULL;
+    k1[0] = lane < nh ? hit_sort_key(raw) : ~0ULL;
     bitonic_sort_lanes<1, uint64_t>(k1, lane);
     if (lane < nh) {
-      const uint32_t r = (uint32_t)k1[0] & 0x1ffu;
-      s_hw[lane] = (uint32_t)(k1[0] >> 9) & 0xffffffu;
-      s_hc[lane] = (uint32_t)(k1[0] >> 33) & 0xfffffu;
+      const uint32_t r = sort_key_rank(k1[0]);
+      s_hw[lane] = sort_key_window(k1[0]);
+      s_hc[lane] = sort_key_contig(k1[0]);
       s_hr[lane] = r;
       s_ph[lane] = q_hash[(uint64_t)f * kQMax + r];
     }
   }
   __syncthreads();
-  // ---- L1 (map_segments_kernel's rule, one after the other: at most eight hits)
+  // ---- L1, one run after the other: at most eight hits
   uint32_t n_cand = 0;
   {
     bool have = false, have_prev = false;
     uint32_t cur_c = 0, cur_cs = 0, cur_ce = 0, cur_fw = 0, prev_c = 0, prev_ce = 0;
     for (uint32_t i = 0; i + mh <= nh; ++i) {
       const uint32_t c_i = s_hc[i], ce_i = s_hw[i], yw = s_hw[i + mh - 1u];
-      if (!(s_hc[i + mh - 1u] == c_i && yw - ce_i < frag_len)) continue;
-      const uint32_t cs_i = yw + 1u > frag_len ? yw + 1u - frag_len : 0u;
-      if (!have_prev || prev_c != c_i || cs_i > prev_ce) {
+      if (!l1_run_valid(c_i, ce_i, s_hc[i + mh - 1u], yw, frag_len)) continue;
+      const uint32_t cs_i = l1_range_start(yw, frag_len);
+      if (l1_opens_candidate(have_prev, prev_c, prev_ce, c_i, cs_i)) {
         if (have) { if (lane == 0) { s_cand[n_cand][0] = cur_c; s_cand[n_cand][1] = cur_cs; s_cand[n_cand][2] = cur_ce; s_cand[n_cand][3] = cur_fw; } ++n_cand; }
         cur_c = c_i; cur_cs = cs_i; cur_ce = ce_i; cur_fw = ce_i; have = true;
       } else {
@@ -100,8 +100,6 @@ __global__ __launch_bounds__(64) void map_sparse_kernel(
     const uint32_t ce = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cand[ci][2]);
     const uint32_t m1 = contig_mini_off[c + 1];
     const uint32_t bb = contig_bucket_off[c], nb = contig_bucket_off[c + 1] - bb - 1;
-    // (the first begin and the window ids after it in one batch of loads from the start of the range's bucket, as in map_segments_kernel)
-    constexpr int kStartBatch = 8;
     uint32_t b_lo, origin;
     uint32_t wpv[kStartBatch];
     {
@@ -109,34 +107,12 @@ __global__ __launch_bounds__(64) void map_sparse_kernel(
       if (bk >= nb) bk = nb;
       const uint32_t lo = bucket_first[bb + bk];
       const uint32_t hi = bk < nb ? bucket_first[bb + bk + 1] : lo;
-      origin = lo;
-#pragma unroll
-      for (int q = 0; q < kStartBatch; ++q) {
-        const uint32_t t = origin + (uint32_t)q * 64u + lane;
-        wpv[q] = t < m1 ? mini_wpos[t] : 0xffffffffu;
-      }
-      const uint64_t ge = __ballot(lo + lane < hi && wpv[0] >= cs);
-      if (ge) {
-        b_lo = lo + (uint32_t)__builtin_ctzll(ge);
-      } else if (hi - lo <= 64u) {
-        b_lo = hi;
-      } else {
-        b_lo = hi;
-        for (uint32_t base = lo + 64u; base < hi; base += 64) {
-          const uint32_t t = base + lane;
-          const uint64_t ge2 = __ballot(t < hi && mini_wpos[t] >= cs);
-          if (ge2) { b_lo = base + (uint32_t)__builtin_ctzll(ge2); break; }
-        }
-        origin = b_lo;
-#pragma unroll
-        for (int q = 0; q < kStartBatch; ++q) {
-          const uint32_t t = origin + (uint32_t)q * 64u + lane;
-          wpv[q] = t < m1 ? mini_wpos[t] : 0xffffffffu;
-        }
-      }
+      slide_first_begin(mini_wpos, m1, lo, hi, cs, lane, b_lo, origin, wpv);
     }
     if (b_lo >= m1) continue;
     uint32_t b_hi, i_max;
+    // where the slide ends: a copy of the block in process_candidate of map_segments_kernel (fragani_map.inc) -- a change
+    // here is a change there; as a shared function it changed both kernels' scalar spills
     {
       const uint32_t limit = ce + frag_len;
       uint32_t z = 0;
@@ -202,11 +178,9 @@ __global__ __launch_bounds__(64) void map_sparse_kernel(
       const uint32_t sb = b_lo + g * 64u, b = sb + lane;
       const bool has = b < b_hi;
       if (kSparseEnds && c_best >= 0 && (uint32_t)c_best >= n_all && sb > tie_lo && sb + 63u < tie_hi) { PA_SSTAT(59, 1); break; }  // between the ties, and nothing shares more
-      const uint32_t wp = has ? mini_wpos[b] : 0u;
-      const uint32_t wp_next = (has && b + 1u < m1) ? mini_wpos[b + 1u] : 0xffffffffu;
-      const uint32_t w_end = min(wp_next - 1u, i_max) + count_windows;  // window ids below this: the begin's widest window
-      int32_t bar = c_best > best_shared ? c_best : best_shared;
-      if (bar < floor_bar) bar = floor_bar;
+      const WidestWindow ww = begin_widest_window(mini_wpos, m1, b, has, i_max, count_windows);
+      const uint32_t wp = ww.wp, wp_next = ww.wp_next, w_end = ww.w_end;
+      const int32_t bar = shared_bar(c_best, best_shared, floor_bar);
       uint32_t held = 0;  // seed hits inside the begin's widest window: no window of the begin shares more
       for (uint32_t i = 0; i < nh; ++i) held += (s_hc[i] == c && s_hw[i] >= wp && s_hw[i] < w_end) ? 1u : 0u;
       const bool between = kSparseEnds && c_best >= 0 && b > tie_lo && b < tie_hi;  // a tie here changes nothing
@@ -364,24 +338,20 @@ __global__ __launch_bounds__(64) void map_sparse_kernel(
       }
       PA_SSTAT(51, __popcll(__ballot(lane_on)));                                  // begins evaluated
       PA_SSTAT(52, wave_sum(lane_on ? xe_hi - xe_lo + 1u : 0u));                  // states evaluated
-      // fold: most shared; window ids of the first and of the last begin that has it (a state's position is its begin's)
       const int32_t group_best = (int32_t)pa_dev::wave_max_dpp(lane_on ? (uint32_t)(lane_best + 1) : 0u) - 1;
       if (__any(lane_on) && group_best >= c_best) {
         const uint64_t top = __ballot(lane_on && lane_best == group_best);
         PA_SSTAT(53, __popcll(top));  // begins tying the best so far of their candidate when their group is folded (an upper count of the ties)
-        const uint32_t w_first = __shfl(wp, __builtin_ctzll(top), 64), w_last = __shfl(wp, 63 - __builtin_clzll(top), 64);
-        c_last = group_best > c_best ? w_last : max(c_last, w_last);
-        c_first = group_best > c_best ? w_first : min(c_first, w_first);
+        const bool better = fold_ties(group_best, top, wp, c_best, c_first, c_last);
         const uint32_t b_first = sb + (uint32_t)__builtin_ctzll(top), b_last = sb + 63u - (uint32_t)__builtin_clzll(top);
-        tie_hi = group_best > c_best ? b_last : max(tie_hi, b_last);
-        tie_lo = group_best > c_best ? b_first : min(tie_lo, b_first);
-        c_best = group_best;
+        tie_hi = better ? b_last : max(tie_hi, b_last);
+        tie_lo = better ? b_first : min(tie_lo, b_first);
       }
       } while (false);
     }
     if (overflow) break;
     PA_SSTAT(54, c_best >= 0 ? 1u + ((tie_lo - b_lo) / 64u != (tie_hi - b_lo) / 64u ? 1u : 0u) : 0u);  // groups that hold the candidate's first or last tying begin: what any order has to evaluate
-    if (c_best >= 0 && c_best >= best_shared) { best_shared = c_best; best_c = c; best_first = c_first; best_last = c_last; }  // of equals, the last
+    if (candidate_is_the_mapping(c_best, best_shared)) { best_shared = c_best; best_c = c; best_first = c_first; best_last = c_last; }  // (of equals, the last)
   }
   if (overflow) {  // (rare: one draw per such segment)
     if (lane == 0) {
@@ -391,9 +361,8 @@ __global__ __launch_bounds__(64) void map_sparse_kernel(
     return;
   }
   if (lane == 0 && best_shared >= 0 && (uint32_t)best_shared >= tab_min_shared[s]) {
-    const uint64_t jq = ((uint64_t)best_shared << 30) / s;
-    const unsigned long long packed = ((unsigned long long)jq << 32) | ((unsigned long long)best_shared << 16) | s;
-    const uint64_t bin = contig_bin_off[best_c] + (best_first + best_last) / 2u / (frag_len - 20u);
+    const unsigned long long packed = mapping_packed(best_shared, s);
+    const uint64_t bin = mapping_bin(contig_bin_off[best_c], best_first, best_last, frag_len);
     atomicMax(&table[(uint64_t)frag_genome_local[f] * table_stride + bin], packed);
   }
 }
